@@ -6,16 +6,20 @@ region.  Two workloads:
 
   streams   (default at --gpus 1)  S independent TUM-shaped camera streams per GPU (BASELINE.json configs[1] shape: 640x480, TUM3
             intrinsics, depth factor 5000, FAST 15/5, 1500 features; the real TUM frames are not available offline); W untimed warm-up
-            steps, K timed steps, weak scaling.  On one GPU the line also carries `sequence`: the fixed-length job below, run after
-            the timed region, i.e. the N = 1 point of the curve that --gpus N > 1 reports.
+            steps, K timed steps, weak scaling.  With --full, on one GPU the line also carries `sequence`: the fixed-length job below, run
+            after the timed region, i.e. the N = 1 point of the curve that --gpus N > 1 reports.
   sequence  (default at --gpus N > 1; BASELINE.json configs[3]) ONE synthetic RGB-D sequence of --sequence-frames (4000) frames sharded by
             frame into N*S lock-step chunks (sindslam_amd.sequence.plan_lockstep): every chunk processes K*T frames, chunk 0 from the first
             frame on, chunk g > 0 starts 24 frames before its first owned frame to rebuild the tail state.  The W warm-up steps are
             untimed and their state is dropped (all streams are primed again); the K timed steps are the WHOLE job, chunk warm-up
             frames included, software-pipelined, and after every step the per-frame dynamic masks of all ranks are gathered with one
             RCCL all_gather over xGMI into the sequence-ordered mask array every rank holds.  value = sequence frames / wall time:
-            strong scaling (the sequence length does not grow with N).  Rank 0 then re-runs the first frames in the in-order
+            strong scaling (the sequence length does not grow with N).  With --full, rank 0 then re-runs the first frames in the in-order
             ("exact") mode and reports the chunk-seam IoU and the exact mode's own rate.
+
+A plain run sets up, warms up, times the K steps and prints the line; everything else it can measure or check (CPU baseline and parity sample,
+the one-GPU sequence / TUM-length / drop-in / small-step legs, the in-order re-run, the N = 1 leg of --gpus N) runs only with --full.
+--dump-outputs DIR writes the last timed step's results (streams workload; the inputs are the same from run to run for the same arguments).
 
 --gpus N without a launcher (WORLD_SIZE unset): this process starts N rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set)
 BEFORE anything touches torch or the GPU and only waits for them; under torch.distributed.run the ranks are already there.
@@ -92,7 +96,14 @@ def parse_args(argv=None):
                                                                                     "(sind_pipe_gather_masks on RCCL; torch.distributed then only hands the 128-byte id to the ranks)")
     ap.add_argument("--collective-at-1", action="store_true", help="with one rank, still create the process group and run the per-step mask gather (RCCL calls at world size 1)")
     ap.add_argument("--rendezvous-only", action="store_true", help="ranks only meet, count themselves and exit (launcher test, needs no GPU)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the CPU baseline and parity sample, the sequence / TUM-length / drop-in / "
+                                                        "small-step legs of one GPU, the in-order re-run and the N = 1 leg of the sequence workload (the --no-* flags still apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="streams workload: write the last timed step's results to DIR/<name>.npy (float32 / float64, "
+                                                                         "at most 64 MB: per-frame counts of every frame, full outputs of a fixed sample of frames)")
+    args = ap.parse_args(argv)
+    if not args.full:           # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_sequence_leg = args.no_tum_leg = args.no_dropin_leg = args.no_small_step_leg = args.no_exact_leg = args.no_n1_leg = True
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------ launcher
@@ -173,6 +184,65 @@ def stream_variants(base_b, base_d, S):
         bgr[s0] = np.clip(b.astype(np.float32) * g, 0, 255).astype(np.uint8) if g != 1.0 else b
         depth[s0] = d
     return bgr, depth
+
+
+def gain_lut(k):
+    """what stream_variants' gain 1 - 0.04 k makes of each of the 256 u8 values (numpy's own float32 products, clipped and truncated)"""
+    import numpy as np
+    return np.clip(np.arange(256, dtype=np.uint8).astype(np.float32) * (1.0 - 0.04 * k), 0, 255).astype(np.uint8)
+
+
+def device_step_inputs(base_b, base_d, S, T, nsteps, device):
+    """inputs of steps 0 .. nsteps-1 on `device`: dev_b[i] / dev_d[i] = stream_variants(base_b, base_d, S)[0 / 1][:, 2 + i * T: 2 + (i + 1) * T] (depth as int16),
+    the same bytes built from the base frames on the device instead of S x frames host copies (flips are copies, the gain goes through gain_lut)"""
+    import numpy as np
+    import torch
+    if base_b.ndim == 4: base_b, base_d = base_b[None], base_d[None]
+    scenes = base_b.shape[0]
+    bb = torch.from_numpy(base_b).to(device); bd = torch.from_numpy(base_d.view(np.int16)).to(device)
+    luts = torch.from_numpy(np.stack([gain_lut(k) for k in range(4)])).to(device)
+    dev_b, dev_d = [], []
+    for i in range(nsteps):
+        f0 = 2 + i * T
+        ob = torch.empty((S, T) + base_b.shape[2:], dtype=torch.uint8, device=device); od = torch.empty((S, T) + base_d.shape[2:], dtype=torch.int16, device=device)
+        for s0 in range(S):
+            b, d = bb[s0 % scenes, f0:f0 + T], bd[s0 % scenes, f0:f0 + T]; s = s0 // scenes
+            flip = ([2] if s & 1 else []) + ([1] if s & 2 else [])
+            if flip: b, d = b.flip(flip), d.flip(flip)
+            k = (s >> 2) % 4
+            ob[s0] = luts[k][b.long()] if k else b
+            od[s0] = d
+        dev_b.append(ob); dev_d.append(od)
+    return dev_b, dev_d
+
+
+def dump_outputs(pipe, out_dir, budget=64 << 20):
+    """the results of the last step that went through `pipe`, as out_dir/<name>.npy (float32 / float64, at most `budget` bytes): per frame of the step the keypoint count,
+    the dynamic and dilated-mask pixel counts and the label sum; for a fixed, seeded sample of the step's frames (index s * T + t) the full outputs a caller of Pipeline
+    receives -- imgDyna, imgLabel, the dilated mask, the keypoints (KP_DTYPE fields in order, rows past the frame's count zero) and the descriptors (one byte per value)"""
+    import numpy as np
+    from sindslam_amd.orb import KP_DTYPE
+    os.makedirs(out_dir, exist_ok=True)
+    S, T, H, W = pipe.dyna.shape; B = S * T; cap = pipe.kps.shape[1]
+    dyna, label, mask = (a.reshape(B, H, W) for a in (pipe.dyna, pipe.label, pipe.mask))
+    nkp = np.asarray(pipe.nkp[:B])
+    per_frame = (3 * H * W + cap * (len(KP_DTYPE.names) + 32)) * 4
+    n = max(1, min(8, B, (48 << 20) // per_frame))
+    pick = np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    kps = np.zeros((n, cap, len(KP_DTYPE.names)), np.float32); desc = np.zeros((n, cap, 32), np.float32)
+    for j, k in enumerate(pick):
+        m = int(nkp[k])
+        kps[j, :m] = np.stack([pipe.kps[k, :m][f].astype(np.float32) for f in KP_DTYPE.names], 1)
+        desc[j, :m] = pipe.desc[k, :m]
+    arrays = {"frame_keypoints": nkp.astype(np.float64), "frame_dynamic_pixels": (dyna == 255).sum((1, 2)).astype(np.float64),
+              "frame_mask_pixels": (mask != 0).sum((1, 2)).astype(np.float64), "frame_label_sum": label.sum((1, 2), dtype=np.int64).astype(np.float64),
+              "sample_frames": pick.astype(np.float64), "sample_dyna": dyna[pick].astype(np.float32), "sample_label": label[pick].astype(np.float32),
+              "sample_mask": mask[pick].astype(np.float32), "sample_keypoints": kps, "sample_descriptors": desc}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= budget, f"--dump-outputs: {total} bytes over the {budget}-byte budget"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def pingpong(f, P):
@@ -836,6 +906,8 @@ def main():
     T, K, Wm = args.frames_per_step, args.steps, args.warmup
     S = args.streams or (cfg["streams"] if workload == "streams" else sequence_streams(world, args.sequence_frames, cfg["streams"], K, args.seq_warmup_frames))
     seq_leg = workload == "streams" and world == 1 and not args.no_sequence_leg and not args.host_input       # N = 1 point of the sequence curve next to the streams headline
+    if args.dump_outputs and workload != "streams":
+        raise SystemExit("--dump-outputs: the streams workload only")
     import sindslam_amd.synth as SY
     intr0 = getattr(SY, cfg["intr"]); sc = cfg["width"] / 640.0
     intr = dict(intr0, fx=intr0["fx"] * sc, fy=intr0["fy"] * sc, cx=intr0["cx"] * sc, cy=intr0["cy"] * sc)
@@ -847,7 +919,11 @@ def main():
         nsteps = K + Wm
         ndata = min(nsteps, 12)             # distinct steps of input kept in host + device memory; longer runs cycle through them (the jump at the wrap is just another large-motion pair)
         base_b, base_d = base_frames(cfg, T * ndata + 2, 12345 + rank, nseeds=3)      # three scenes; the first eight streams (the parity sample) cover all of them
-        bgr, depth = stream_variants(base_b, base_d, S)
+        # per-stream frames on the host: the two priming frames of every stream, and all frames of the first streams for the one-GPU legs and the CPU baseline
+        # (stream s of stream_variants does not depend on how many streams are made); the timed steps' inputs are built on the GPU (device_step_inputs)
+        prime_b, _ = stream_variants(base_b[:, :2], base_d[:, :2], S)
+        host_legs = world == 1 and (not args.no_cpu_baseline or (not args.host_input and not (args.no_small_step_leg and args.no_dropin_leg)))
+        bgr, depth = stream_variants(base_b, base_d, min(S, max(16, args.cpu_threads))) if host_legs else (None, None)
 
         def frames_of_stream(s, count):
             return bgr[s, :count], depth[s, :count]
@@ -900,9 +976,8 @@ def main():
         pipe = make_pipeline(cfg, intr, S, T, local, args.host_threads, parts)
         # inputs resident in HBM before the timed region, laid out [step][S][T]...
         for s in range(S):
-            pipe.prime(s, bgr[s, 1], bgr[s, 0])
-        dev_b = [torch.from_numpy(np.ascontiguousarray(bgr[:, 2 + i * T: 2 + (i + 1) * T])).cuda() for i in range(ndata)]
-        dev_d = [torch.from_numpy(np.ascontiguousarray(depth[:, 2 + i * T: 2 + (i + 1) * T]).view(np.int16)).cuda() for i in range(ndata)]
+            pipe.prime(s, prime_b[s, 1], prime_b[s, 0])
+        dev_b, dev_d = device_step_inputs(base_b, base_d, S, T, ndata, "cuda")
         torch.cuda.synchronize()
         gbuf = {}
 
@@ -965,6 +1040,8 @@ def main():
             tt = torch.tensor([dt], device=comm_dev); dist.all_reduce(tt, op=dist.ReduceOp.MAX); dt = float(tt.item())
             rs = torch.ones(1, device=comm_dev); dist.all_reduce(rs); ranks_seen = int(rs.item())
         loads = gather_host_load(load, pg, comm_dev)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(pipe, args.dump_outputs)
         pairs = S * T * K * world
         if args.thread_cpu and rank == 0:       # short-lived threads (flow slices, ORB, octree) that ended before the second sample are not listed
             cpu_s = load[0] * (time.perf_counter() - t0)

@@ -7,14 +7,14 @@ set -o pipefail
 tag=${1:-r03}; part=${2:-all}; R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/$tag; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 if [ "$part" = all ] || [ "$part" = 1 ]; then
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-sequence-leg > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err || exit 1
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-sequence-leg > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err || exit 1
   cp $O/prof/*/*kernel_stats.csv $O/kernel_stats.csv
   python3 $R/profiles/sor_by_grid.py $O/prof k_sor_ > $O/sor_by_level.txt; python3 $R/profiles/kernel_duration_dist.py $O/prof > $O/tail_kernel_durations.txt; python3 $R/profiles/tail_gpu_busy.py $O/prof 4 > $O/tail_gpu_busy.txt
   rm -rf $O/prof
 fi
 if [ "$part" = all ] || [ "$part" = 1b ]; then
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout -k 10 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-sequence-leg > $O/pmc_$c.json 2> $O/pmc_$c.err || exit 1
+    timeout -k 10 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-sequence-leg > $O/pmc_$c.json 2> $O/pmc_$c.err || exit 1
     python3 $R/profiles/pmc_sum.py k_sor_stream $O/pmc_$c > $O/pmc_$c.txt; python3 $R/profiles/pmc_sum.py k_sor_fused $O/pmc_$c >> $O/pmc_$c.txt; python3 $R/profiles/pmc_sum.py k_peac_grow $O/pmc_$c >> $O/pmc_$c.txt; rm -rf $O/pmc_$c
   done
   i=0
@@ -26,11 +26,11 @@ if [ "$part" = all ] || [ "$part" = 1b ]; then
 fi
 cd $R
 if [ "$part" = all ] || [ "$part" = 2 ]; then
-  timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $O/bench_default_driver_args.json 2> $O/bench_default_driver_args.err || exit 1
-  timeout -k 10 300 python3 bench.py --sync --no-cpu-baseline --no-sequence-leg > $O/bench_sync.json 2> $O/bench_sync.err || exit 1
-  timeout -k 10 300 python3 bench.py --config bonn --no-sequence-leg > $O/bench_bonn.json 2> $O/bench_bonn.err || exit 1
-  timeout -k 10 400 python3 bench.py --config d455_720p --no-sequence-leg > $O/bench_d455_720p.json 2> $O/bench_d455_720p.err || exit 1
-  timeout -k 10 600 python3 bench.py --workload sequence --steps 20 --warmup 5 --no-cpu-baseline --collective-at-1 > $O/bench_sequence_driver_args.json 2> $O/bench_sequence_driver_args.err || exit 1
+  timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_default_driver_args.json 2> $O/bench_default_driver_args.err || exit 1
+  timeout -k 10 300 python3 bench.py --full --sync --no-cpu-baseline --no-sequence-leg > $O/bench_sync.json 2> $O/bench_sync.err || exit 1
+  timeout -k 10 300 python3 bench.py --full --config bonn --no-sequence-leg > $O/bench_bonn.json 2> $O/bench_bonn.err || exit 1
+  timeout -k 10 400 python3 bench.py --full --config d455_720p --no-sequence-leg > $O/bench_d455_720p.json 2> $O/bench_d455_720p.err || exit 1
+  timeout -k 10 600 python3 bench.py --full --workload sequence --steps 20 --warmup 5 --no-cpu-baseline --collective-at-1 > $O/bench_sequence_driver_args.json 2> $O/bench_sequence_driver_args.err || exit 1
   timeout -k 10 600 python3 bench.py --workload sequence --steps 20 --warmup 5 --no-cpu-baseline --collective-at-1 --collective cabi --no-exact-leg > $O/bench_sequence_cabi.json 2> $O/bench_sequence_cabi.err || exit 1
   SIND_TAIL_TIMING=1 timeout -k 10 300 python3 profiles/tools/exact_mode_timing.py 641 32 > $O/exact_mode_timing.txt 2>&1 || exit 1
 fi

@@ -30,10 +30,10 @@ if [ "$part" = all ] || [ "$part" = 1b ]; then
 fi
 cd $R
 if [ "$part" = all ] || [ "$part" = 2 ]; then
-  timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > $O/bench_default_driver_args.json 2> $O/bench_default_driver_args.err || exit 1
-  timeout -k 10 300 python3 bench.py --config bonn --no-sequence-leg --no-dropin-leg --no-small-step-leg > $O/bench_bonn.json 2> $O/bench_bonn.err || exit 1
-  timeout -k 10 400 python3 bench.py --config d455_720p --no-sequence-leg --no-small-step-leg > $O/bench_d455_720p.json 2> $O/bench_d455_720p.err || exit 1
-  timeout -k 10 600 python3 bench.py --workload sequence --steps 20 --warmup 5 --no-cpu-baseline --collective-at-1 > $O/bench_sequence_driver_args.json 2> $O/bench_sequence_driver_args.err || exit 1
+  timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_default_driver_args.json 2> $O/bench_default_driver_args.err || exit 1
+  timeout -k 10 300 python3 bench.py --full --config bonn --no-sequence-leg --no-dropin-leg --no-small-step-leg > $O/bench_bonn.json 2> $O/bench_bonn.err || exit 1
+  timeout -k 10 400 python3 bench.py --full --config d455_720p --no-sequence-leg --no-small-step-leg > $O/bench_d455_720p.json 2> $O/bench_d455_720p.err || exit 1
+  timeout -k 10 600 python3 bench.py --full --workload sequence --steps 20 --warmup 5 --no-cpu-baseline --collective-at-1 > $O/bench_sequence_driver_args.json 2> $O/bench_sequence_driver_args.err || exit 1
   timeout -k 10 600 python3 bench.py --workload sequence --steps 20 --warmup 5 --no-cpu-baseline --seq-driver python --no-exact-leg > $O/bench_sequence_python_driver.json 2> $O/bench_sequence_python_driver.err || exit 1
 fi
 if [ "$part" = all ] || [ "$part" = 3 ]; then

@@ -1,9 +1,9 @@
-"""Secondary cross-check of oracle primitives against scikit-image (run by tests/test_oracle_crosscheck_cpu.py under the image's
-conda interpreter, which has scikit-image 0.18 but none of this repo's dependencies).  NOT the parity reference: scikit-image is an
+"""Secondary cross-check of oracle primitives against scikit-image (run under an interpreter with scikit-image 0.18, which needs none
+of this repo's dependencies, by tests/test_oracle_crosscheck_cpu.py's make_skimage_golden; its outputs are tests/golden/skimage_crosscheck.npz).  NOT the parity reference: scikit-image is an
 independent implementation whose semantics coincide with OpenCV's for these cases, so agreement is evidence that the
 oracle restates the OpenCV primitive correctly.
 
-usage: python3.9 crosscheck_skimage.py <in.npz> <out.npz>
+usage: python crosscheck_skimage.py <in.npz> <out.npz>
 in : fast_img (u8, the padded ORB level image), otsu_imgs (k, h, w) u8, resize_src (f32), resize_shape (2,),
      brief_img (u8, blurred level image), brief_rc (n, 2) keypoint rows / columns, brief_angle (n,) radians,
      angle_img (u8, padded unblurred level image), angle_rc (n, 2)

@@ -79,3 +79,52 @@ def test_sequence_chunk_count_heuristic():
         assert p.processed_total <= 1.3 * 4000 and sum(c.last - c.first for c in p.chunks) == 4000
         if n == 8:
             assert p.T <= 4 and s * p.T <= 40          # a rank's ~30 pairs per step as at least eight short chains (the tails of a chunk's frames run one after the other)
+
+
+def test_device_step_inputs_equal_the_host_stream_variants():
+    """the timed steps' inputs are built from the base frames on the device: the same bytes as stream_variants (every flip and gain; torch on the CPU here)"""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    b = rng.integers(0, 256, (3, 10, 8, 16, 3), dtype=np.uint8); d = rng.integers(0, 65536, (3, 10, 8, 16), dtype=np.uint16)
+    S, T = 50, 2                                                            # streams 0..49: all four flips and all four gains of the three scenes
+    vb, vd = bench.stream_variants(b, d, S)
+    db, dd = bench.device_step_inputs(b, d, S, T, 4, "cpu")
+    for i in range(4):
+        assert np.array_equal(db[i].numpy(), vb[:, 2 + i * T: 2 + (i + 1) * T]) and np.array_equal(dd[i].numpy(), vd[:, 2 + i * T: 2 + (i + 1) * T].view(np.int16))
+    # the host frames the bench keeps: stream s does not depend on the number of streams made, frame f not on the frames made
+    hb, hd = bench.stream_variants(b, d, 16)
+    pb, pd = bench.stream_variants(b[:, :2], d[:, :2], S)
+    assert np.array_equal(hb, vb[:16]) and np.array_equal(hd, vd[:16]) and np.array_equal(pb, vb[:, :2]) and np.array_equal(pd, vd[:, :2])
+    sb, sd = b[0], d[0]                                                     # one scene
+    db1, dd1 = bench.device_step_inputs(sb, sd, 20, T, 2, "cpu"); vb1, vd1 = bench.stream_variants(sb, sd, 20)
+    assert np.array_equal(db1[1].numpy(), vb1[:, 4:6]) and np.array_equal(dd1[0].numpy(), vd1[:, 2:4].view(np.int16))
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    from types import SimpleNamespace
+    from sindslam_amd.orb import KP_DTYPE
+    rng = np.random.default_rng(5)
+    S, T, H, W, cap = 6, 3, 8, 16, 10
+    kps = np.zeros((S * T, cap), KP_DTYPE)
+    for f in KP_DTYPE.names:
+        kps[f] = rng.integers(1, 100, kps.shape)
+    pipe = SimpleNamespace(dyna=rng.choice([0, 255], (S, T, H, W)).astype(np.uint8), label=rng.integers(0, 9, (S, T, H, W), dtype=np.uint8),
+                           mask=rng.choice([0, 255], (S, T, H, W)).astype(np.uint8), kps=kps, nkp=rng.integers(0, cap + 1, S * T).astype(np.int32),
+                           desc=rng.integers(0, 256, (S * T, cap, 32), dtype=np.uint8))
+    total = bench.dump_outputs(pipe, str(tmp_path / "a")); bench.dump_outputs(pipe, str(tmp_path / "b"))
+    a = {f.name[:-4]: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert sum(v.nbytes for v in a.values()) == total <= 64 << 20 and all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy"))) for k, v in a.items())       # the sample is fixed
+    pick = a["sample_frames"].astype(int); B = S * T
+    assert len(pick) == 8 and len(set(pick.tolist())) == 8 and pick.max() < B
+    assert np.array_equal(a["frame_keypoints"], pipe.nkp) and np.array_equal(a["frame_dynamic_pixels"], (pipe.dyna.reshape(B, -1) == 255).sum(1))
+    assert np.array_equal(a["frame_mask_pixels"], (pipe.mask.reshape(B, -1) != 0).sum(1)) and np.array_equal(a["frame_label_sum"], pipe.label.reshape(B, -1).sum(1))
+    assert np.array_equal(a["sample_dyna"], pipe.dyna.reshape(B, H, W)[pick]) and np.array_equal(a["sample_label"], pipe.label.reshape(B, H, W)[pick])
+    assert np.array_equal(a["sample_mask"], pipe.mask.reshape(B, H, W)[pick])
+    for j, k in enumerate(pick):
+        n = pipe.nkp[k]
+        assert np.array_equal(a["sample_keypoints"][j, :n, 0], kps[k, :n]["x"]) and np.array_equal(a["sample_keypoints"][j, :n, 5], kps[k, :n]["octave"])
+        assert not a["sample_keypoints"][j, n:].any() and np.array_equal(a["sample_descriptors"][j, :n], pipe.desc[k, :n]) and not a["sample_descriptors"][j, n:].any()

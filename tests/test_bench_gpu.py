@@ -18,7 +18,7 @@ def test_two_ranks_frame_sharded_sequence_line():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     env["MASTER_PORT"] = str(29400 + os.getpid() % 1500)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4", "--warmup", "1", "--streams", "2",
-                        "--sequence-frames", "200", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=800)
+                        "--sequence-frames", "200", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "spawned 2 ranks" in r.stderr and "torch imported in the launcher: False" in r.stderr
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -50,7 +50,7 @@ def test_one_gpu_line_carries_the_sequence_leg():
     """--gpus 1: streams headline (weak) plus the fixed-length sequence job as `sequence` (the N = 1 point of the strong-scaling curve)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--streams", "8", "--sequence-frames", "300", "--no-cpu-baseline",
-                        "--no-exact-leg"], env=env, capture_output=True, text=True, timeout=800)
+                        "--no-exact-leg", "--full"], env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0]); s = d["sequence"]
     assert d["config"]["mode"] == "streams" and d["scaling"] == "weak" and d["warmup"] == 1 and d["steps"] == 2 and d["config"]["frame_pairs_per_step"] == 32
@@ -70,7 +70,7 @@ def test_sequence_at_the_drivers_chunk_count_every_seam_equal():
     sequence: all 25 seams are covered, every owned frame of every later chunk is byte-identical to the in-order run"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "sequence", "--steps", "20", "--warmup", "1", "--streams", "26", "--sequence-frames", "1000",
-                        "--exact-leg-frames", "1000", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=1100)
+                        "--exact-leg-frames", "1000", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=1100)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0]); s = d["sequence"]; v = s["verify"]
     print({k: s[k] for k in ("value", "value_excl_warmup", "chunks", "frames_per_step_per_chunk", "seam_frames_compared", "seam_masks_equal", "seam_iou_min")}, v)
@@ -87,10 +87,39 @@ def test_three_ranks_short_warmup_repairs_across_rank_seams():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     env["MASTER_PORT"] = str(27400 + os.getpid() % 1500)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--streams", "2",
-                        "--sequence-frames", "150", "--seq-warmup-frames", "2", "--exact-leg-frames", "150", "--no-n1-leg", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=800)
+                        "--sequence-frames", "150", "--seq-warmup-frames", "2", "--exact-leg-frames", "150", "--no-n1-leg", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0]); s = d["sequence"]; v = s["verify"]
     print({k: s[k] for k in ("value", "chunks", "frames_per_step_per_chunk", "seam_frames_compared", "seam_masks_equal")}, v)
     assert d["n_gpus"] == 3 and d["ranks_seen"] == 3 and s["chunks"] == 6 and s["exact"] is True and len(d["host_by_rank"]) == 3
     assert all(h["sizing"]["ranks_on_node"] == 3 and h["sizing"]["cpu_share"] >= 4 for h in d["host_by_rank"])
     assert s["seam_masks_equal"] == s["seam_frames_compared"] >= 100 and s["seam_iou_min"] == 1.0
+
+
+@pytest.mark.timeout(900)
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """a plain run is the headline alone (no legs, no CPU baseline), `ms_per_step` is one of the K timed steps, and --dump-outputs writes the last step's results:
+    float arrays within 64 MB, the same bytes from run to run"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
+    runs = []
+    for k in range(2):
+        out_dir = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--streams", "8", "--dump-outputs", str(out_dir)],
+                           env=env, capture_output=True, text=True, timeout=400)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frame-pairs/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["config"]["frame_pairs_per_step"] == 32 and abs(d["value"] * d["ms_per_step"] * 1e-3 - 32) < 1e-6 * 32
+        assert d["cpu_baseline"] is None and not any(leg in d for leg in ("dropin", "small_step", "sequence", "sequence_tum_length", "parity"))
+        a = {f.name[:-4]: np.load(f) for f in out_dir.iterdir()}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+        assert a["frame_keypoints"].shape == (32,) and a["frame_keypoints"].min() > 0 and a["sample_dyna"].shape == (8, 480, 640)
+        pick = a["sample_frames"].astype(int)
+        assert np.array_equal(a["frame_dynamic_pixels"][pick], (a["sample_dyna"] == 255).sum((1, 2)))
+        runs.append(a)
+    assert runs[0].keys() == runs[1].keys()
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name

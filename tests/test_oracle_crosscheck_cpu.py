@@ -1,9 +1,12 @@
 """CPU: the oracle's OpenCV restatements against INDEPENDENT implementations of the same primitive (scipy in this interpreter,
-scikit-image 0.18 in the image's conda interpreter through tests/crosscheck_skimage.py).  The reference ships no golden vectors and
+scikit-image 0.18 through tests/crosscheck_skimage.py, whose outputs are stored in tests/golden/skimage_crosscheck.npz).  The reference ships no golden vectors and
 OpenCV is not installed ("parity unpinned"), so these are secondary evidence only: where scipy / scikit-image define
 the operation exactly like OpenCV, the oracle must agree with them."""
+import hashlib
 import os
 import subprocess
+import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -11,8 +14,8 @@ from scipy import ndimage
 
 import oracle_lib as O
 
-CONDA_PY = "/opt/conda/bin/python3.9"
 HERE = os.path.dirname(os.path.abspath(__file__))
+SKIMAGE_GOLDEN = os.path.join(HERE, "golden", "skimage_crosscheck.npz")
 
 
 def _blobs(seed, h=120, w=160):
@@ -109,8 +112,8 @@ def test_external_contours_are_the_8_connected_components():
         assert np.array_equal(traced, inner)
 
 
-@pytest.mark.skipif(not os.path.exists(CONDA_PY), reason="the image's conda interpreter (scikit-image) is not present")
-def test_fast_scores_otsu_and_resize_against_scikit_image(frames, tmp_path):
+def _skimage_inputs(frames):
+    """the inputs of tests/crosscheck_skimage.py (in.npz) and what the test compares its outputs with"""
     bgr, _ = frames
     gray = O.bgr2gray(bgr[2])
     orb = O.ORBextractor(1500, 1.2, 8, 15, 5); orb.extract(gray)
@@ -125,13 +128,36 @@ def test_fast_scores_otsu_and_resize_against_scikit_image(frames, tmp_path):
     kps, desc = orb.extract(gray)
     l0 = kps["octave"] == 0; k0 = kps[l0]; d0 = desc[l0]
     blurred = O.gaussian_blur_u8(gray, 7, 2.0)             # ORBextractor.cc:1145: the level image is cloned, then blurred
-    fin, fout = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
-    np.savez(fin, fast_img=pad, otsu_imgs=otsu_imgs, resize_src=src, resize_shape=np.array([57, 76]), brief_img=blurred,
-             brief_rc=np.stack([np.rint(k0["y"]), np.rint(k0["x"])], 1).astype(np.int64), brief_angle=np.deg2rad(k0["angle"].astype(np.float64)),
-             angle_img=orb.level_padded(0), angle_rc=np.stack([np.rint(k0["y"]) + 19, np.rint(k0["x"]) + 19], 1).astype(np.int64))
-    env = {k: v for k, v in os.environ.items() if not k.startswith("PYTHON")}
-    subprocess.check_call([CONDA_PY, os.path.join(HERE, "crosscheck_skimage.py"), fin, fout], env=env, timeout=600)
-    r = np.load(fout)
+    inp = dict(fast_img=pad, otsu_imgs=otsu_imgs, resize_src=src, resize_shape=np.array([57, 76]), brief_img=blurred,
+               brief_rc=np.stack([np.rint(k0["y"]), np.rint(k0["x"])], 1).astype(np.int64), brief_angle=np.deg2rad(k0["angle"].astype(np.float64)),
+               angle_img=orb.level_padded(0), angle_rc=np.stack([np.rint(k0["y"]) + 19, np.rint(k0["x"]) + 19], 1).astype(np.int64))
+    return inp, fk, otsu_imgs, src, k0, d0
+
+
+def _digest(arrays):
+    h = hashlib.sha256()
+    for k in sorted(arrays):
+        a = np.ascontiguousarray(arrays[k]); h.update(f"{k}:{a.dtype.str}:{a.shape}".encode()); h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def make_skimage_golden(python, path=SKIMAGE_GOLDEN):
+    """runs tests/crosscheck_skimage.py under `python` (an interpreter with scikit-image 0.18) and stores its outputs with the digest of their inputs"""
+    from sindslam_amd.synth import SyntheticStream
+    inp = _skimage_inputs(SyntheticStream().frames(0, 6))[0]
+    with tempfile.TemporaryDirectory() as tmp:
+        fin, fout = os.path.join(tmp, "in.npz"), os.path.join(tmp, "out.npz")
+        np.savez(fin, **inp)
+        env = {k: v for k, v in os.environ.items() if not k.startswith("PYTHON")}
+        subprocess.check_call([python, os.path.join(HERE, "crosscheck_skimage.py"), fin, fout], env=env, timeout=600)
+        out = dict(np.load(fout))
+    np.savez_compressed(path, inputs_sha256=np.array(_digest(inp)), **out)
+
+
+def test_fast_scores_otsu_and_resize_against_scikit_image(frames):
+    inp, fk, otsu_imgs, src, k0, d0 = _skimage_inputs(frames)
+    r = np.load(SKIMAGE_GOLDEN)
+    assert str(r["inputs_sha256"]) == _digest(inp), "the stored scikit-image outputs were made from other inputs: regenerate tests/golden/skimage_crosscheck.npz"
     # FAST: every cell-wise keypoint of the oracle (position relative to the 16-px border, image padded by 19) is a FAST-9 corner whose
     # OpenCV score (largest threshold at which it is still a corner) equals scikit-image's segment test evaluated threshold by threshold
     assert len(fk) > 200
@@ -162,3 +188,9 @@ def test_fast_scores_otsu_and_resize_against_scikit_image(frames, tmp_path):
     # IC_Angle: atan2 of the first-order moments over the radius-15 disc; the oracle goes through cv::fastAtan2 (about 0.3 degrees accurate)
     da = np.abs((np.rad2deg(r["angle"]) % 360.0) - k0["angle"]); da = np.minimum(da, 360.0 - da)
     assert da.max() < 0.5, float(da.max())
+
+
+if __name__ == "__main__":
+    # regenerate the stored scikit-image outputs:  python tests/test_oracle_crosscheck_cpu.py <python with scikit-image 0.18>
+    sys.path.insert(0, os.path.dirname(HERE))
+    make_skimage_golden(sys.argv[1])
