@@ -59,12 +59,10 @@ int sind_flow_set_latency_tiles(sind_flow* f, int on);
 /* per handle: on != 0 (default) makes the transition between two pyramid levels -- W += dW, the bilinear up-sampling / 0.95 and the next level's warp, average and temporal
  * difference -- one launch (k_level_up) instead of three; 0 = the three kernels (cross-check).  Same bits either way. */
 int sind_flow_set_level_up(sind_flow* f, int on);
-/* solver variant of THIS handle (every variant returns the same bits; nothing here is process-wide).  Fused register-resident SOR with 1x8 pixel strips: mode 4 = divisions
+/* solver variant of THIS handle (every variant returns the same bits; nothing here is process-wide).  mode 4 = fused register-resident SOR with 1x8 pixel strips, divisions
  * through a reciprocal formed on the fly (hardware estimate + one Newton step, then Markstein's correction; default: 5 iterations per launch on 64 x 64 tiles), 5 = the
- * streaming kernel on every level it fits, 6 = the one-wave pipeline on every level beyond one workgroup, 0 = one launch per colour (cross-check); lab builds also: 1 = IEEE division, 3 = reciprocals of A11 / A22 read from planes and
- * held in registers (three waves per SIMD; tiles of 256, 384 and 768 threads), 2 = 1x4 strips + reciprocal division.  fuse = iterations per launch on tiled levels
- * (default 5), 0 = a plan per level (lab builds); tile_w x tile_h = extended tile (tile_w * tile_h / 8 threads).  sind_flow_set_sor keeps the round-1 argument list
- * (tile height 48 for mode 3, 64 otherwise). */
+ * streaming kernel on every level it fits, 6 = the one-wave pipeline on every level beyond one workgroup, 0 = one launch per colour (cross-check).  fuse = iterations per
+ * launch on tiled levels (1 .. 12, default 5); tile_w x tile_h = extended tile (tile_w * tile_h / 8 threads).  sind_flow_set_sor keeps the round-1 argument list (tile height 64). */
 int sind_flow_set_sor(sind_flow* f, int mode, int fuse, int tile_w);
 int sind_flow_set_sor_tiled(sind_flow* f, int mode, int fuse, int tile_w, int tile_h);
 /* streaming solver: at most `cap` workgroups per launch, each taking several (column strip, image) items in turn (persistent workgroups); 0 = one workgroup per item.
@@ -81,7 +79,6 @@ int sind_flow_wave_layout(int w, int h, int B, int target_items, int bands, int 
 /* coefficient kernel: 1 = k_coef_lanes (neighbours from lanes, short correctly rounded sqrt / quotient forms; default), 2 = k_coef_lanes with the compiler's IEEE forms,
  * 0 = k_coef (neighbours from memory), 3 = variant 1 with its tiles in plain grid order over the XCDs (A/B timing: by default the tiles of a pair share an XCD's L2).  Same results. */
 int sind_flow_set_coef_kernel(sind_flow* f, int variant);
-int sind_lab_build(void);        /* 1: built with -DSIND_LAB (dormant solver variants and the SIND_* experiment switches of the measurement rounds), 0: the shipped drop-in */
 /* HIP-event timing of everything enqueued on the handle's stream between begin and end (bench.py roofline leg) */
 int sind_flow_timer_begin(sind_flow* f);
 int sind_flow_timer_end(sind_flow* f, float* milliseconds);

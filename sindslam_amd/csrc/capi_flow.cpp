@@ -8,10 +8,6 @@ struct sind_flow {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
-#ifdef SIND_LAB
-namespace sind { int debug_ss_profile(unsigned long long* out, int reset); }
-#endif
-
 extern "C" {
 
 int sind_flow_set_max_levels(sind_flow* f, int n) { if (!f || n < 0) return SIND_E_ARG; f->eng.max_levels = n; return SIND_OK; }
@@ -122,9 +118,6 @@ int sind_debug_coef_math_scan(int device, int exp_lo, int exp_hi, const float nu
     HIP_TRY(hipMemcpy(out, d.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return SIND_OK;
 }
-#ifdef SIND_LAB
-int sind_lab_ss_profile(unsigned long long* out96, int reset) { return sind::debug_ss_profile(out96, reset); }      // lab builds only: k_sor_stream's per-wave step cycles
-#endif
 
 int sind_debug_flow_thresholds(const int* hist, int n, int width, int height, int variant, int device, int* res, double* mu1) {
     if (!hist || !res || n < 1 || variant < 0 || variant > 2 || width < 1 || height < 1) { sind_set_error("sind_debug_flow_thresholds: bad arguments"); return SIND_E_ARG; }
@@ -144,15 +137,10 @@ int sind_debug_flow_thresholds(const int* hist, int n, int width, int height, in
 int sind_flow_set_sor_tiled(sind_flow* f, int mode, int fuse, int tile_w, int tile_h) {
     if (!f) { sind_set_error("sind_flow_set_sor_tiled: null handle"); return SIND_E_ARG; }
     const int nt = tile_w * tile_h / 8;
-    if (mode < 0 || mode > 6 || fuse < 0 || fuse > 12 || tile_w < 16 || tile_w % 8 || tile_h < 8 || tile_h % 2 || nt % 128 || nt > 1024 || 4 * fuse >= tile_w || 4 * fuse >= tile_h ||
-        (mode == 3 && nt != 256 && nt != 384 && nt != 768)) {
+    if ((mode != 0 && mode != 4 && mode != 5 && mode != 6) || fuse < 1 || fuse > 12 || tile_w < 16 || tile_w % 8 || tile_h < 8 || tile_h % 2 || nt % 128 || nt > 1024 ||
+        4 * fuse >= tile_w || 4 * fuse >= tile_h) {
         sind_set_error("sind_flow_set_sor_tiled: bad arguments (mode %d, fuse %d, tile %d x %d)", mode, fuse, tile_w, tile_h); return SIND_E_ARG;
     }
-#ifndef SIND_LAB
-    // the shipped library carries the per-colour reference (0), the tiled kernel with the reciprocal formed on the fly (4, fixed fuse depth) and the streaming
-    // kernel (5); IEEE-division, reciprocal-plane and 1 x 4-strip variants and the per-level fuse plans are lab builds (make -C sindslam_amd/csrc lab)
-    if ((mode != 0 && mode != 4 && mode != 5 && mode != 6) || fuse == 0) { sind_set_error("sind_flow_set_sor_tiled: solver variant (mode %d, fuse %d) exists in lab builds only", mode, fuse); return SIND_E_ARG; }
-#endif
     sind::SolverCfg& C = f->eng.solver; C.mode = mode; C.fuse = fuse; C.tile_w = tile_w; C.tile_h = tile_h; return SIND_OK;
 }
 int sind_flow_set_solver_workgroups(sind_flow* f, int cap) { if (!f || cap < 0) return SIND_E_ARG; f->eng.solver.stream_wg_cap = cap; return SIND_OK; }
@@ -168,14 +156,7 @@ int sind_flow_wave_layout(int w, int h, int B, int target_items, int bands, int 
 int sind_flow_set_coef_kernel(sind_flow* f, int variant) { if (!f || variant < 0 || variant > 3) return SIND_E_ARG; f->eng.solver.coef_kernel = variant == 3 ? 1 : variant; f->eng.solver.coef_xcd = variant == 3 ? 0 : 1; return SIND_OK; }
 int sind_flow_set_sor(sind_flow* f, int mode, int fuse, int tile_w) {
     if (tile_w != 64 && tile_w != 128) { sind_set_error("sind_flow_set_sor: bad arguments"); return SIND_E_ARG; }
-    return sind_flow_set_sor_tiled(f, mode, fuse, tile_w, mode == 3 ? (tile_w == 64 ? 48 : 48) : 64);
-}
-int sind_lab_build(void) {
-#ifdef SIND_LAB
-    return 1;
-#else
-    return 0;
-#endif
+    return sind_flow_set_sor_tiled(f, mode, fuse, tile_w, 64);
 }
 int sind_flow_sync(sind_flow* f) { if (!f) return SIND_E_ARG; HIP_TRY(hipStreamSynchronize(f->stream)); return SIND_OK; }
 int sind_flow_timer_begin(sind_flow* f) { if (!f) return SIND_E_ARG; HIP_TRY(hipEventRecord(f->ev0, f->stream)); return SIND_OK; }

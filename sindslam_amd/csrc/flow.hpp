@@ -16,7 +16,6 @@ struct FlowPlanes {
     float *A11, *A12, *A22, *b1, *b2, *wgt;                   // linear system + smoothness weights
     float *Wu, *Wv, *dWu, *dWv, *tWu, *tWv;                    // level flow, increment, W + dW
     float *dWu2, *dWv2;                                       // ping-pong partner of the increment (tiled fused SOR)
-    float *r11, *r22;                                         // RN(1 / A11), RN(1 / A22): the tiled solver divides through them (Markstein)
 };
 
 // HIP-event brackets around the SOR launch groups of the flow solver (bench.py's roofline leg): events are recorded on the
@@ -55,15 +54,13 @@ int sor_iterations(hipStream_t s, FlowPlanes& P, int w, int h, int B, int total,
 #define FLOW_OPT_LEVEL_UP 4          /* W += dW, the up-sampling and the next level's warp in one launch (k_level_up) instead of three */     /* tiled levels with a compute unit per tile (few images): 1024-thread tiles, up to 13 iterations per launch (k_sor_tile) */
 // Solver settings of ONE flow handle (every variant returns the same bits; sind_flow_set_sor_tiled / _solver_workgroups / _coef_kernel / _coarse_chain / _latency_tiles).
 struct SolverCfg {
-    int mode = 4;              // fused register-resident SOR with 1x8 strips: 4 = divisions through a reciprocal formed on the fly (hardware estimate + Newton step, then Markstein's
-                               // correction; default), 5 = the streaming kernel on every level it fits, 6 = the one-wave pipeline (k_sor_wave) on every level beyond one workgroup, 0 = one launch per colour (cross-check); lab builds: 1 = IEEE division, 3 = reciprocal
-                               // planes held in registers (three waves per SIMD), 2 = 1x4 strips + reciprocal division
-    int fuse = 5;              // iterations per launch on the tiled levels; 0 = per-level plan (sor_fuse_plan: measured 1-2 % faster, 10 % more launches; lab builds)
+    int mode = 4;              // 4 = fused register-resident SOR with 1x8 strips, divisions through a reciprocal formed on the fly (hardware estimate + Newton step, then
+                               // Markstein's correction; default), 5 = the streaming kernel on every level it fits, 6 = the one-wave pipeline (k_sor_wave) on every level beyond
+                               // one workgroup, 0 = one launch per colour (cross-check)
+    int fuse = 5;              // iterations per launch on the tiled levels (>= 1)
     int tile_w = 64, tile_h = 64;      // extended tile (multiple of 8 wide, even height, tile_w * tile_h / 8 threads)
-    int xcd = 1;               // XCD-aware tile order of the fused kernel (0 = plain blockIdx order, for A/B timing)
     int stream_min_b = 80;     // mode 4: tiled levels go to the streaming kernel (one workgroup per image and column strip) from this many images per launch on
                                // (profiles/r05/stream_min_batch.txt: 48 images per launch 907 pairs/s streamed vs 1093-1110 tiled; 112 images 1356 vs 1237; 170 images 1514 vs 1296)
-    int stream_min_px = 0;     // ... and only for levels of at least this many pixels
     int stream_wg_cap = 0;     // k_sor_stream: at most this many (persistent) workgroups per launch (0 = one per item)
     int wave = 1;              // mode 4: levels that would go to the streaming kernel go to the one-wave pipeline instead (k_sor_wave, flow_wave.hip); 0 = k_sor_stream (cross-check, A/B timing)
     int wave_items = 1024;     // k_sor_wave: row bands are cut while a launch has fewer waves than this (2048 fill the chip; every cut recomputes 20 rows, and the slices of a step run side by side:
@@ -72,7 +69,6 @@ struct SolverCfg {
     int wave_prefetch = 2;     // k_sor_wave: steps between a row's request and its take-over (1 .. 3; 16 registers per row in flight)
     int coef_kernel = 1;       // 1: k_coef_lanes (neighbours from lanes; short forms of sqrt and c / sqrt), 2: k_coef_lanes with the IEEE forms, 0: k_coef (neighbours from memory)
     int coef_xcd = 1;          // k_coef_lanes: the tiles of a pair go to one XCD (1) or round-robin over the eight in grid order (0: A/B timing)
-    double plan_cost = 14;     // prologue of a tile in iterations (sor_fuse_plan)
     int opts = FLOW_OPT_COARSE_CHAIN | FLOW_OPT_LATENCY_TILES | FLOW_OPT_LEVEL_UP;
 };
 int varref_level(hipStream_t s, FlowPlanes& P, const float* I0, const float* I1, int w, int h, int B, const VarParams& V, SorTimer* timer, const SolverCfg& C,

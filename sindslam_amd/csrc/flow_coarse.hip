@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(CL_NT) k_coarse_chain(const float* __restrict_
                 const int ty = item / tiles_x, tx = item - ty * tiles_x;
                 const int c0 = tx * KL_COLS - 2, y0 = ty * KL_ROWS, col = c0 + lane;
                 const bool store_lane = lane >= 2 && lane < 2 + KL_COLS && col < w;
-                kc_lanes<true, true>(C.V, w, h, col, y0, 0, avg, Iz, Wu, Wv, dWu, dWv, A11, A12, A22, B1, B2, Wg, nullptr, nullptr, store_lane);
+                kc_lanes<true, true>(C.V, w, h, col, y0, 0, avg, Iz, Wu, Wv, dWu, dWv, A11, A12, A22, B1, B2, Wg, store_lane);
             }
             cl_sync_global();
             // ---- RedBlackSOR

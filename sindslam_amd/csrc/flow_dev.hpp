@@ -80,7 +80,7 @@ __device__ __forceinline__ float lane_prev(float v) { return __int_as_float(__bu
 template <bool BORDER, bool FASTM>
 __device__ __forceinline__ void kc_lanes(const VarParams& P, int w, int h, int col, int y0, size_t base, const float* __restrict__ gAvg, const float* __restrict__ gIz, const float* __restrict__ gWu,
                        const float* __restrict__ gWv, const float* __restrict__ gdWu, const float* __restrict__ gdWv, float* __restrict__ A11, float* __restrict__ A12,
-                       float* __restrict__ A22, float* __restrict__ B1, float* __restrict__ B2, float* __restrict__ Wgt, float* __restrict__ R11, float* __restrict__ R22, bool store_lane) {
+                       float* __restrict__ A22, float* __restrict__ B1, float* __restrict__ B2, float* __restrict__ Wgt, bool store_lane) {
     const float zeta2 = P.zeta * P.zeta, eps2 = P.epsilon * P.epsilon, gamma2 = P.gamma / 2, delta2 = P.delta / 2, alpha2 = P.alpha / 2;
     const unsigned xc = BORDER ? (unsigned)min(max(col, 0), w - 1) : (unsigned)col;          // the column this lane loads (replicated outside the image)
     auto row_of = [&](int yy) { return (unsigned)(BORDER ? min(max(yy, 0), h - 1) : yy) * (unsigned)w * 4u; };   // byte offset of a row in its plane; wave-uniform: scalar arithmetic
@@ -171,7 +171,6 @@ __device__ __forceinline__ void kc_lanes(const VarParams& P, int w, int h, int c
             const unsigned ro = (unsigned)y * (unsigned)w * 4u;
             auto st = [&](const __amdgpu_buffer_rsrc_t& r, float val) { __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(val), r, xoff, ro, 0); };
             st(oA11, a11); st(oA12, a12); st(oA22, a22); st(oB1, b1); st(oB2, b2); st(oW, wp);
-            if (R11) { st(rs(R11), 1.f / a11); st(rs(R22), 1.f / a22); }
         }
         w_up = wp;
     }

@@ -20,24 +20,15 @@ static std::vector<std::pair<int, int>> deepflow_sizes(int w, int h) {
 
 int FlowEngine::init(int fw_, int fh_, int maxB_, hipStream_t s) {
     fw = fw_; fh = fh_; maxB = maxB_; stream = s;
-    if (const char* e = sind_lab_env("SIND_SOR_MODE")) solver.mode = atoi(e);       // see SolverCfg (flow.hpp); the tile / fuse variables are for A/B timing
-    if (const char* e = sind_lab_env("SIND_SOR_TILEW")) solver.tile_w = atoi(e);
-    if (const char* e = sind_lab_env("SIND_SOR_FUSE")) solver.fuse = std::max(0, std::min(atoi(e), 12));
-    if (const char* e = sind_lab_env("SIND_SOR_PLAN_COST")) solver.plan_cost = std::max(0.0, atof(e));
-    if (const char* e = sind_lab_env("SIND_SOR_XCD")) solver.xcd = atoi(e) != 0;
-    if (const char* e = sind_lab_env("SIND_SOR_TILEH")) solver.tile_h = atoi(e);
-    if (const char* e = sind_lab_env("SIND_SOR_STREAM_MINB")) solver.stream_min_b = atoi(e);
-    if (const char* e = sind_lab_env("SIND_SOR_STREAM_MINPX")) solver.stream_min_px = atoi(e);       // images per launch from which the tiled levels take the streaming kernel
-    if (const char* e = sind_lab_env("SIND_LAUNCH_AHEAD")) launch_ahead = std::max(0, atoi(e));       // 0: unbounded
     levels = deepflow_sizes(fw, fh);
     level_off.clear(); pyr_pixels = 0;
     for (auto& l : levels) { level_off.push_back(pyr_pixels); pyr_pixels += (size_t)l.first * l.second; }
     const size_t n0 = (size_t)fw * fh * maxB;
-    static_assert(sizeof(FlowPlanes) == 18 * sizeof(float*), "FlowPlanes is filled as an array of 18 plane pointers");
-    SIND_TRY(plane_store.alloc(n0 * 18 + 16));           // + 16: the streaming solver's row loader reads whole 16-byte chunks (up to 3 floats past a row's end)
-    if (hipMemsetAsync(plane_store.p, 0, (n0 * 18 + 16) * sizeof(float), stream) != hipSuccess) { sind_set_error("hipMemset(plane store) failed"); return SIND_E_HIP; }     // (the loader's over-reads must find finite values)
+    static_assert(sizeof(FlowPlanes) == 16 * sizeof(float*), "FlowPlanes is filled as an array of 16 plane pointers");
+    SIND_TRY(plane_store.alloc(n0 * 16 + 16));           // + 16: the streaming solver's row loader reads whole 16-byte chunks (up to 3 floats past a row's end)
+    if (hipMemsetAsync(plane_store.p, 0, (n0 * 16 + 16) * sizeof(float), stream) != hipSuccess) { sind_set_error("hipMemset(plane store) failed"); return SIND_E_HIP; }     // (the loader's over-reads must find finite values)
     float** f = reinterpret_cast<float**>(&planes);
-    for (int i = 0; i < 18; i++) f[i] = plane_store.p + n0 * i;
+    for (int i = 0; i < 16; i++) f[i] = plane_store.p + n0 * i;
     SIND_TRY(pyr0.alloc(pyr_pixels * maxB));
     SIND_TRY(pyr1.alloc(pyr_pixels * maxB));
     return SIND_OK;

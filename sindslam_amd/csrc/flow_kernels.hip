@@ -8,13 +8,9 @@
 // imgwarp.cpp remap); the parity tests compare these kernels with the CPU oracle bit for bit.
 //
 // Roofline: all kernels here are HBM/L2-bound stencil passes (no MFMA: nothing is a contraction).
-#include <mutex>
 #include "common.hpp"
 #include "flow.hpp"
 #include "flow_dev.hpp"
-#include <functional>
-#include <array>
-#include <map>
 
 namespace sind {
 
@@ -148,8 +144,7 @@ template <bool IN>
 __device__ __forceinline__ void kc_rows(const VarParams& P, int w, int h, int x, int y0, size_t base, const float* __restrict__ gAvg, const float* __restrict__ gIz, const float* __restrict__ gWu,
                        const float* __restrict__ gWv,
                        const float* __restrict__ gdWu, const float* __restrict__ gdWv, float* __restrict__ A11, float* __restrict__ A12,
-                       float* __restrict__ A22, float* __restrict__ B1, float* __restrict__ B2, float* __restrict__ Wgt, float* __restrict__ R11,
-                       float* __restrict__ R22) {
+                       float* __restrict__ A22, float* __restrict__ B1, float* __restrict__ B2, float* __restrict__ Wgt) {
     const float zeta2 = P.zeta * P.zeta, eps2 = P.epsilon * P.epsilon, gamma2 = P.gamma / 2, delta2 = P.delta / 2, alpha2 = P.alpha / 2;
     // The seven Sobel(ksize = 1, BORDER_REPLICATE) derivative images of prepareBuffers are formed here from the warped average and
     // the temporal difference (the float operations k_derivs used to store, evaluated at the same replicated positions): two planes
@@ -226,27 +221,25 @@ __device__ __forceinline__ void kc_rows(const VarParams& P, int w, int h, int x,
         #undef OWN_V
         #undef UP_V
         A11[base + i] = a11; A12[base + i] = a12; A22[base + i] = a22; B1[base + i] = b1; B2[base + i] = b2; Wgt[base + i] = wp;
-        if (R11) { R11[base + i] = 1.f / a11; R22[base + i] = 1.f / a22; }     // solver mode 3 only: correctly rounded (Markstein's division needs exactly RN(1 / a))
         w_up = wp;
     }
 }
 __global__ void k_coef(VarParams P, int w, int h, const float* __restrict__ gAvg, const float* __restrict__ gIz, const float* __restrict__ gWu,
                        const float* __restrict__ gWv,
                        const float* __restrict__ gdWu, const float* __restrict__ gdWv, float* __restrict__ A11, float* __restrict__ A12,
-                       float* __restrict__ A22, float* __restrict__ B1, float* __restrict__ B2, float* __restrict__ Wgt, float* __restrict__ R11,
-                       float* __restrict__ R22) {
+                       float* __restrict__ A22, float* __restrict__ B1, float* __restrict__ B2, float* __restrict__ Wgt) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.z, y0 = blockIdx.y * KC_ROWS;
     if (x >= w) return;
     const size_t base = (size_t)b * w * h;
     // interior: rows y0 - 2 .. y0 + KC_ROWS + 1 and, for every lane of the wave, columns x - 2 .. x + 2 exist (wave-uniform: a ballot over the wave's live lanes)
     const bool in = y0 >= 2 && y0 + KC_ROWS + 1 < h && __builtin_amdgcn_ballot_w64(x < 2 || x + 2 >= w) == 0ull;
-    if (in) kc_rows<true>(P, w, h, x, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt, R11, R22);
-    else kc_rows<false>(P, w, h, x, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt, R11, R22);
+    if (in) kc_rows<true>(P, w, h, x, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt);
+    else kc_rows<false>(P, w, h, x, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt);
 }
 // grid (tiles of KL_COLS columns, groups of 4 x KL_ROWS rows, pairs), 256 threads: wave k of a workgroup takes the rows (4 * blockIdx.y + k) * KL_ROWS ...
 __global__ __launch_bounds__(256) void k_coef_lanes(VarParams P, int w, int h, const float* __restrict__ gAvg, const float* __restrict__ gIz, const float* __restrict__ gWu,
                        const float* __restrict__ gWv, const float* __restrict__ gdWu, const float* __restrict__ gdWv, float* __restrict__ A11, float* __restrict__ A12,
-                       float* __restrict__ A22, float* __restrict__ B1, float* __restrict__ B2, float* __restrict__ Wgt, float* __restrict__ R11, float* __restrict__ R22, int fast_math,
+                       float* __restrict__ A22, float* __restrict__ B1, float* __restrict__ B2, float* __restrict__ Wgt, int fast_math,
                        int tiles_x, int tiles_y, int n_tiles, int xcd) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // 1-D grid (a multiple of 8): tile = x + tiles_x * (y + tiles_y * pair).  xcd: consecutive tiles -- the tiles of one pair, which share their halo rows and columns -- go to the
@@ -262,11 +255,11 @@ __global__ __launch_bounds__(256) void k_coef_lanes(VarParams P, int w, int h, c
     // the short forms of sqrt and c / sqrt need arguments >= 2^-96: every argument carries epsilon^2 (1e-6 with the reference's parameters); any other epsilon takes the IEEE forms
     const bool interior = c0 >= 0 && c0 + 63 < w && y0 >= 2 && y0 + KL_ROWS + 1 < h, fastm = P.epsilon >= 1e-12f && fast_math != 0;
     if (fastm) {
-        if (interior) kc_lanes<false, true>(P, w, h, col, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt, R11, R22, store_lane);
-        else kc_lanes<true, true>(P, w, h, col, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt, R11, R22, store_lane);
+        if (interior) kc_lanes<false, true>(P, w, h, col, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt, store_lane);
+        else kc_lanes<true, true>(P, w, h, col, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt, store_lane);
     } else {
-        if (interior) kc_lanes<false, false>(P, w, h, col, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt, R11, R22, store_lane);
-        else kc_lanes<true, false>(P, w, h, col, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt, R11, R22, store_lane);
+        if (interior) kc_lanes<false, false>(P, w, h, col, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt, store_lane);
+        else kc_lanes<true, false>(P, w, h, col, y0, base, gAvg, gIz, gWu, gWv, gdWu, gdWv, A11, A12, A22, B1, B2, Wgt, store_lane);
     }
 }
 
@@ -364,20 +357,16 @@ int debug_rcp_scan(hipStream_t s, int exp_lo, int exp_hi, unsigned long long* ou
     hipLaunchKernelGGL(k_debug_rcp_scan, dim3((1u << 23) / 256), dim3(256), 0, s, exp_lo, exp_hi, out_dev);
     HIP_TRY(hipGetLastError()); return SIND_OK;
 }
-// RCP: the two IEEE divisions of a pixel update (ten VALU instructions each, one of them quarter rate) become Markstein's three-operation
-// sequence on the reciprocals of A11 / A22, formed once per launch and held in registers (see sor_div / k_sor_fused4 below); a pixel outside the
-// image gets the reciprocal 0, which makes its update return exactly 0 and removes the per-pixel validity select from the loop.
-// The ten persistent values per pixel (80 registers per strip) do not fit the 128-register budget of four waves per SIMD, so the RCP instance runs
-// three waves per SIMD (<= 168 registers): MAXT threads per workgroup, WPE waves per SIMD.
+// Fused register-resident SOR over one extended tile: the two divisions of a pixel update are Markstein's three-operation sequence on a reciprocal formed
+// on the fly (sor_rcp / sor_div: the correctly rounded quotient).  MAXT threads per workgroup, WPE waves per SIMD.
 // CEW x CNR: extended tile known at compile time (0 = run-time sizes, the one-workgroup levels): every LDS address then is one base register plus an
 // immediate offset instead of a dozen address registers held across the loop.
-template <int DIV, int MAXT, int WPE, int CEW, int CNR>        // DIV: 0 = IEEE division, 1 = reciprocal planes in registers (RCP), 2 = reciprocal formed on the fly (sor_rcp)
+template <int MAXT, int WPE, int CEW, int CNR>
 __global__ void __attribute__((amdgpu_flat_work_group_size(64, MAXT), amdgpu_waves_per_eu(WPE, WPE)))
 k_sor_fused(int w, int h, int EW, int EH, int IW, int IH, int halo_x, int halo, int ntx, int iters, int xcd_remap, float omega,
             const float* __restrict__ gA11, const float* __restrict__ gA12, const float* __restrict__ gA22, const float* __restrict__ gB1,
-            const float* __restrict__ gB2, const float* __restrict__ gW, const float* __restrict__ gR11, const float* __restrict__ gR22,
-            const float* __restrict__ gUin, const float* __restrict__ gVin, float* __restrict__ gUout, float* __restrict__ gVout) {
-    constexpr bool RCP = DIV == 1;
+            const float* __restrict__ gB2, const float* __restrict__ gW, const float* __restrict__ gUin, const float* __restrict__ gVin,
+            float* __restrict__ gUout, float* __restrict__ gVout) {
     extern __shared__ float4 lds4[];             // float4-indexed so that every strip access is one ds_read/write_b128
     float* lds = reinterpret_cast<float*>(lds4);
     const int SW = (CEW ? CEW : EW) / SOR_PX;    // strips per row
@@ -404,21 +393,15 @@ k_sor_fused(int w, int h, int EW, int EH, int IW, int IH, int halo_x, int halo, 
 
     float a11[SOR_PX], a12[SOR_PX], a22[SOR_PX], b1[SOR_PX], b2[SOR_PX], wp[SOR_PX], du[SOR_PX], dv[SOR_PX];
     float wtop[SOR_PX];                          // weights of the image row above the tile, loaded by the tile's first row only
-    float r11[RCP ? SOR_PX : 1], r22[RCP ? SOR_PX : 1];
     float wl0 = 0.f;
-    unsigned valid = 0;      // a pixel outside the image keeps the reciprocal 0 (RCP): its update returns exactly 0, with no select in the loop
+    unsigned valid = 0;
     const bool row_ok = ly < EH && gy >= 0 && gy < h;
     #pragma unroll
     for (int i = 0; i < SOR_PX; i++) { a11[i] = 1.f; a12[i] = 0.f; a22[i] = 1.f; b1[i] = 0.f; b2[i] = 0.f; wp[i] = 0.f; wtop[i] = 0.f; du[i] = 0.f; dv[i] = 0.f; }
-    if constexpr (RCP) {
-        #pragma unroll
-        for (int i = 0; i < SOR_PX; i++) { r11[i] = 0.f; r22[i] = 0.f; }
-    }
     if (row_ok && gx0 >= 0 && gx0 + SOR_PX <= w) {        // whole strip inside the image: 16-byte loads
         const size_t g = base + (size_t)gy * w + gx0;
         valid = 0xffu;
         ld8(gA11 + g, a11); ld8(gA12 + g, a12); ld8(gA22 + g, a22); ld8(gB1 + g, b1); ld8(gB2 + g, b2); ld8(gW + g, wp); ld8(gUin + g, du); ld8(gVin + g, dv);
-        if constexpr (RCP) { ld8(gR11 + g, r11); ld8(gR22 + g, r22); }
         if (ly == 0 && gy > 0) ld8(gW + g - w, wtop);
     } else if (row_ok) {
         #pragma unroll
@@ -430,7 +413,6 @@ k_sor_fused(int w, int h, int EW, int EH, int IW, int IH, int halo_x, int halo, 
                 a11[i] = gA11[g]; a12[i] = gA12[g]; a22[i] = gA22[g]; b1[i] = gB1[g]; b2[i] = gB2[g]; wp[i] = gW[g];
                 if (ly == 0 && gy > 0) wtop[i] = gW[g - w];
                 du[i] = gUin[g]; dv[i] = gVin[g];
-                if constexpr (RCP) { r11[i] = gR11[g]; r22[i] = gR22[g]; }
             }
         }
     }
@@ -492,21 +474,10 @@ k_sor_fused(int w, int h, int EW, int EH, int IW, int IH, int halo_x, int halo, 
                 const float sigmaU = wl * ul + wp[i] * ur + wu[k] * uu[k] + wp[i] * ud[k];                                        \
                 const float sigmaV = wl * vl + wp[i] * vr + wu[k] * vu[k] + wp[i] * vd[k];                                        \
                 float nu = du[i], nv = dv[i];                                                                                     \
-                if constexpr (RCP) {                                                                                              \
-                    nu += omega * (sor_div(sigmaU + b1[i] - nv * a12[i], a11[i], r11[i]) - nu);                                   \
-                    nv += omega * (sor_div(sigmaV + b2[i] - nu * a12[i], a22[i], r22[i]) - nv);                                   \
-                    du[i] = nu; dv[i] = nv;                                                                                       \
-                } else if constexpr (DIV == 2) {                                                                                  \
-                    nu += omega * (sor_div(sigmaU + b1[i] - nv * a12[i], a11[i], sor_rcp(a11[i])) - nu);                          \
-                    nv += omega * (sor_div(sigmaV + b2[i] - nu * a12[i], a22[i], sor_rcp(a22[i])) - nv);                          \
-                    const bool ok = (valid >> i) & 1u;                                                                            \
-                    du[i] = ok ? nu : 0.f; dv[i] = ok ? nv : 0.f;                                                                 \
-                } else {                                                                                                          \
-                    nu += omega * ((sigmaU + b1[i] - nv * a12[i]) / a11[i] - nu);                                                 \
-                    nv += omega * ((sigmaV + b2[i] - nu * a12[i]) / a22[i] - nv);                                                 \
-                    const bool ok = (valid >> i) & 1u;                                                                            \
-                    du[i] = ok ? nu : 0.f; dv[i] = ok ? nv : 0.f;                                                                 \
-                }                                                                                                                 \
+                nu += omega * (sor_div(sigmaU + b1[i] - nv * a12[i], a11[i], sor_rcp(a11[i])) - nu);                              \
+                nv += omega * (sor_div(sigmaV + b2[i] - nu * a12[i], a22[i], sor_rcp(a22[i])) - nv);                              \
+                const bool ok = (valid >> i) & 1u;                                                                                \
+                du[i] = ok ? nu : 0.f; dv[i] = ok ? nv : 0.f;                                                                     \
             }                                                                                                                     \
             lds4[((Q) * 2 + 0) * PL4 + ro4] = make_float4(du[START], du[(START) + 2], du[(START) + 4], du[(START) + 6]);         \
             lds4[((Q) * 2 + 1) * PL4 + ro4] = make_float4(dv[START], dv[(START) + 2], dv[(START) + 4], dv[(START) + 6]);         \
@@ -543,130 +514,6 @@ k_sor_fused(int w, int h, int EW, int EH, int IW, int IH, int halo_x, int halo, 
     }
 }
 
-#ifdef SIND_LAB      /* dormant variant of the measurement rounds (make lab): kept for A/B timing, bit-identical to the shipped kernels */
-// ---------------------------------------------------------------------------------------------------------
-// Second generation of the fused kernel for the tiled levels: 1x4 pixel strips (1024 threads per 64x64 tile) leave room in the
-// 128-VGPR budget for the RECIPROCALS of A11 / A22, so the two IEEE divisions of a pixel update (~14 VALU operations each, and the
-// kernel is VALU-bound once the coefficients come from L2) become Markstein's three-operation sequence
-//     q0 = n * r;  e = fma(-a, q0, n);  q = fma(e, r, q0)        with r = RN(1 / a)
-// which returns the correctly rounded quotient RN(n / a) for a correctly rounded reciprocal (Markstein 1990; no overflow /
-// underflow: the system is O(1)).  Same LDS scheme as above with float2 instead of float4 (two pixels per colour and strip).
-// tests/test_flow_gpu.py::test_sor_variants_agree_bitwise holds this kernel to the per-colour reference kernel bit for bit.
-#define SOR4_PX 4
-__global__ void __launch_bounds__(1024) k_sor_fused4(int w, int h, int EW, int EH, int IW, int IH, int halo_x, int halo, int ntx, int iters, int xcd_remap, float omega,
-                                                     const float* __restrict__ gA11, const float* __restrict__ gA12, const float* __restrict__ gA22,
-                                                     const float* __restrict__ gB1, const float* __restrict__ gB2, const float* __restrict__ gW,
-                                                     const float* __restrict__ gUin, const float* __restrict__ gVin, float* __restrict__ gUout,
-                                                     float* __restrict__ gVout) {
-    extern __shared__ float4 lds4[];
-    float2* lds2 = reinterpret_cast<float2*>(lds4);
-    float* lds = reinterpret_cast<float*>(lds4);
-    const int SW = EW / SOR4_PX;                 // strips per row
-    const int RS2 = EW / 4 + 2;                  // LDS row stride in float2 (one guard float2 on each side)
-    const int half = blockDim.x >> 1;
-    const int NR = 2 * (half / SW);
-    const int PL2 = (NR + 2) * RS2;
-    const int tid = threadIdx.x;
-    const int idx = tid < half ? tid : tid - half;
-    const int j = idx % SW, ly = 2 * (idx / SW) + (tid < half ? 0 : 1);
-    int tile = blockIdx.x, b = blockIdx.y;
-    {
-        const long long ntile = gridDim.x, lin = blockIdx.x + (long long)blockIdx.y * ntile, per = ntile * gridDim.y / 8;
-        if (xcd_remap && lin < per * 8) { const long long logical = (lin & 7) * per + (lin >> 3); b = (int)(logical / ntile); tile = (int)(logical - (long long)b * ntile); }
-    }
-    const int tx = tile % ntx, ty = tile / ntx;
-    const int ex0 = tx * IW - halo_x, ey0 = ty * IH - halo;
-    const int gy = ey0 + ly, gx0 = ex0 + SOR4_PX * j;
-    const size_t base = (size_t)b * w * h;
-    const int off = (ex0 + ey0) & 1;
-
-    for (int i = tid; i < 4 * PL2; i += blockDim.x) lds2[i] = make_float2(0.f, 0.f);
-    float a11[4], a12[4], a22[4], b1[4], b2[4], wp[4], wu[4], du[4], dv[4], r11[4], r22[4];
-    float wl0 = 0.f;
-    unsigned valid = 0;
-    const bool row_ok = ly < EH && gy >= 0 && gy < h;
-    #pragma unroll
-    for (int i = 0; i < 4; i++) { a11[i] = 1.f; a12[i] = 0.f; a22[i] = 1.f; b1[i] = 0.f; b2[i] = 0.f; wp[i] = 0.f; wu[i] = 0.f; du[i] = 0.f; dv[i] = 0.f; }
-    #define LD4(P, D) { const F4u t_ = *reinterpret_cast<const F4u*>(P); D[0] = t_.x; D[1] = t_.y; D[2] = t_.z; D[3] = t_.w; }
-    if (row_ok && gx0 >= 0 && gx0 + 4 <= w) {
-        const size_t g = base + (size_t)gy * w + gx0;
-        valid = 0xfu;
-        LD4(gA11 + g, a11) LD4(gA12 + g, a12) LD4(gA22 + g, a22) LD4(gB1 + g, b1) LD4(gB2 + g, b2) LD4(gW + g, wp) LD4(gUin + g, du) LD4(gVin + g, dv)
-        if (gy > 0) LD4(gW + g - w, wu)
-    } else if (row_ok) {
-        #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int gx = gx0 + i;
-            if (gx >= 0 && gx < w) {
-                const size_t g = base + (size_t)gy * w + gx;
-                valid |= 1u << i;
-                a11[i] = gA11[g]; a12[i] = gA12[g]; a22[i] = gA22[g]; b1[i] = gB1[g]; b2[i] = gB2[g]; wp[i] = gW[g];
-                wu[i] = gy > 0 ? gW[g - w] : 0.f;
-                du[i] = gUin[g]; dv[i] = gVin[g];
-            }
-        }
-    }
-    #undef LD4
-    if (row_ok && gx0 - 1 >= 0 && gx0 - 1 < w) wl0 = gW[base + (size_t)gy * w + gx0 - 1];
-    #pragma unroll
-    for (int i = 0; i < 4; i++) { r11[i] = 1.0f / a11[i]; r22[i] = 1.0f / a22[i]; }          // correctly rounded (IEEE divide flag of the build)
-    __syncthreads();
-    const int ro2 = (ly + 1) * RS2 + 1 + j;
-    const int s0 = ly & 1;
-    {
-        const int pe = s0 == 0 ? 0 : 2, po = s0 == 0 ? 2 : 0;
-        lds2[(pe + 0) * PL2 + ro2] = make_float2(du[0], du[2]); lds2[(pe + 1) * PL2 + ro2] = make_float2(dv[0], dv[2]);
-        lds2[(po + 0) * PL2 + ro2] = make_float2(du[1], du[3]); lds2[(po + 1) * PL2 + ro2] = make_float2(dv[1], dv[3]);
-    }
-    __syncthreads();
-
-    #define SOR4_HALF(START, Q)                                                                                                   \
-        {                                                                                                                         \
-            const int oq = (Q) ^ 1;                                                                                               \
-            const float2 t0 = lds2[(oq * 2 + 0) * PL2 + ro2 - RS2], t1 = lds2[(oq * 2 + 1) * PL2 + ro2 - RS2];                    \
-            const float2 t2 = lds2[(oq * 2 + 0) * PL2 + ro2 + RS2], t3 = lds2[(oq * 2 + 1) * PL2 + ro2 + RS2];                    \
-            const float uu[2] = {t0.x, t0.y}, vu[2] = {t1.x, t1.y}, ud[2] = {t2.x, t2.y}, vd[2] = {t3.x, t3.y};                   \
-            const float eu = lds[2 * ((oq * 2 + 0) * PL2 + ro2) + ((START) == 0 ? -1 : 2)];                                       \
-            const float ev = lds[2 * ((oq * 2 + 1) * PL2 + ro2) + ((START) == 0 ? -1 : 2)];                                       \
-            _Pragma("unroll")                                                                                                     \
-            for (int k = 0; k < 2; k++) {                                                                                         \
-                const int i = (START) + 2 * k;                                                                                    \
-                const float wl = i == 0 ? wl0 : wp[i == 0 ? 0 : i - 1];                                                           \
-                const float ul = i == 0 ? eu : du[i == 0 ? 0 : i - 1], vl = i == 0 ? ev : dv[i == 0 ? 0 : i - 1];                \
-                const float ur = i == 3 ? eu : du[i == 3 ? 3 : i + 1], vr = i == 3 ? ev : dv[i == 3 ? 3 : i + 1];                \
-                const float sigmaU = wl * ul + wp[i] * ur + wu[i] * uu[k] + wp[i] * ud[k];                                        \
-                const float sigmaV = wl * vl + wp[i] * vr + wu[i] * vu[k] + wp[i] * vd[k];                                        \
-                float nu = du[i], nv = dv[i];                                                                                     \
-                nu += omega * (sor_div(sigmaU + b1[i] - nv * a12[i], a11[i], r11[i]) - nu);                                       \
-                nv += omega * (sor_div(sigmaV + b2[i] - nu * a12[i], a22[i], r22[i]) - nv);                                       \
-                const bool ok = (valid >> i) & 1u;                                                                                \
-                du[i] = ok ? nu : 0.f; dv[i] = ok ? nv : 0.f;                                                                     \
-            }                                                                                                                     \
-            lds2[((Q) * 2 + 0) * PL2 + ro2] = make_float2(du[START], du[(START) + 2]);                                            \
-            lds2[((Q) * 2 + 1) * PL2 + ro2] = make_float2(dv[START], dv[(START) + 2]);                                            \
-        }
-    if ((off ^ s0) == 0) {
-        for (int it = 0; it < iters; it++) { SOR4_HALF(0, off) __syncthreads(); SOR4_HALF(1, off ^ 1) __syncthreads(); }
-    } else {
-        for (int it = 0; it < iters; it++) { SOR4_HALF(1, off) __syncthreads(); SOR4_HALF(0, off ^ 1) __syncthreads(); }
-    }
-    #undef SOR4_HALF
-    if (row_ok) {
-        const int ix0 = tx * IW, iy0 = ty * IH;
-        if (gy >= iy0 && gy < iy0 + IH) {
-            #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int gx = gx0 + i;
-                if (((valid >> i) & 1u) && gx >= ix0 && gx < ix0 + IW) { const size_t g = base + (size_t)gy * w + gx; gUout[g] = du[i]; gVout[g] = dv[i]; }
-            }
-        }
-    }
-}
-
-// tempW = W + dW (end of a fixed-point iteration); with commit != 0 also W = tempW (end of the level)
-
-#endif  // SIND_LAB
-
 // ---------------------------------------------------------------------------------------------------------
 // Third generation for the large levels: the solver STREAMS down the image instead of tiling it.
 // The tiled kernel above pays for its halo twice: a 64 x 64 tile with a 10-pixel halo computes (64 / 44)^2 = 2.1 x the pixel updates it keeps, and a
@@ -697,25 +544,6 @@ typedef float ss_f4 __attribute__((ext_vector_type(4)));
 typedef float ss_f2 __attribute__((ext_vector_type(2)));
 typedef float ss_f2a __attribute__((ext_vector_type(2), aligned(4)));      // two neighbouring floats at any 4-byte address (ds_read2_b32)
 __device__ __forceinline__ void ss_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#ifdef SIND_LAB
-// lab builds: where a step's cycles go, per wave of the workgroups (0, y): [wave][0] cycles from the step's start to its barrier, [1] cycles in the barrier,
-// [2] steps, [3] / [4] the same two sums over the steps in which the wave holds threads changing row pairs; waves 14 / 15 = the loaders
-// ([3] there: the wait for the loads of two steps ago)
-__device__ unsigned long long g_ss_prof[16][6];
-#define SS_PROF_BEGIN unsigned long long pr_b = 0, pr_w = 0, pr_n = 0, pr_hb = 0, pr_hn = 0;
-#define SS_PROF_T0 const unsigned long long pr_t0 = __builtin_amdgcn_s_memtime();
-#define SS_PROF_MARK { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); pr_hb += __builtin_amdgcn_s_memtime() - pr_t0; pr_hn++; }     /* (loader: the wait for the loads of two steps ago) */
-#define SS_PROF_BARRIER(HEAVY) { const unsigned long long pr_t1 = __builtin_amdgcn_s_memtime(); ss_lds_barrier(); const unsigned long long pr_t2 = __builtin_amdgcn_s_memtime(); \
-        pr_b += pr_t1 - pr_t0; pr_w += pr_t2 - pr_t1; pr_n++; if (HEAVY) { pr_hb += pr_t1 - pr_t0; pr_hn++; } }
-#define SS_PROF_END(WAVE) if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) { atomicAdd(&g_ss_prof[WAVE][0], pr_b); atomicAdd(&g_ss_prof[WAVE][1], pr_w); atomicAdd(&g_ss_prof[WAVE][2], pr_n); \
-        atomicAdd(&g_ss_prof[WAVE][3], pr_hb); atomicAdd(&g_ss_prof[WAVE][4], pr_hn); }
-#else
-#define SS_PROF_BEGIN
-#define SS_PROF_T0
-#define SS_PROF_MARK
-#define SS_PROF_BARRIER(HEAVY) ss_lds_barrier();
-#define SS_PROF_END(WAVE)
-#endif
 struct SsRow { float a11[4], a12[4], a22[4], b1[4], b2[4], wp[4], r11[4], r22[4], du[4], dv[4]; float wl0; };      // du / dv: the owner's copy (the rings hold the same values for the neighbours and the write-back); r = RN(1 / a), formed once per row by the loader wave (0 for a pixel outside the image: its update returns exactly 0)
 // MAXSW: widest column strip (in 4-pixel strips) the instance is laid out for.  The LDS layout is fixed at compile time (every plane at a constant offset:
 // an access is one base register per ring row plus an immediate); 38 strips = 152 columns need 69 KB and 512 threads (6 compute waves + 2 loaders):
@@ -739,7 +567,7 @@ __device__ __forceinline__ void ss_item(float* lds, const int strip, const int i
     // roles: threads [0, 10 SW) compute -- slot group g (parity of the pair index: first 5 SW threads even slots, next 5 SW odd), slot within the group, strip;
     // the LAST TWO waves of the block are the loaders, one for the even and one for the odd row of every pair (their own registers hold two rows of 16-byte
     // pieces in flight each; the compute waves hold none).  One loader wave for both rows ran ~3500 cycles a step against ~1900 of a compute wave and was
-    // the step time (s_memtime probes of the lab build, profiles/tools/ss_step_profile.py)
+    // the step time (in-kernel clock probes, profiles/r03/v2_step_probes.txt)
     const int CT = (int)blockDim.x - 128;                         // compute threads (padded to whole waves)
     const int lw = (tid - CT) >> 6;                               // loader index (0, 1) if this wave loads
     const bool is_loader = tid >= CT;
@@ -847,7 +675,6 @@ __device__ __forceinline__ void ss_item(float* lds, const int strip, const int i
 
     // The loader wave and the compute waves run their own copy of the step loop (same number of steps, one barrier each): the register allocation of one
     // role does not see the other's live values (two rows of pieces in flight there, two rows of coefficients here)
-    SS_PROF_BEGIN
     if (is_loader) {
         // per piece, fixed for the launch: source pointer of row 0, LDS offset without the row part, kind (0 staging, 1 ring, -1 none), in-image mask of the 4 pixels
         // an A11 / A22 piece also leaves its reciprocals in the staging planes 5 / 6 (prd: distance to that plane, 0 = none): the step's one heavy job of
@@ -885,9 +712,7 @@ __device__ __forceinline__ void ss_item(float* lds, const int strip, const int i
                 // "the loads of two steps ago have landed".  The loads are inline assembly: the compiler's own s_waitcnt would be vmcnt(0) at every use of a
                 // loaded register in this loop (it cannot count across the back edge), i.e. one full memory latency per piece instead of per step.
                 const int T = T0 + tt;
-                SS_PROF_T0
                 asm volatile("s_waitcnt vmcnt(%0)" :: "n"(SS_NC) : "memory");
-                SS_PROF_MARK
                 {
                     const int ys = 2 * (T + 1) + srow;
                     const bool park = ys >= 0 && ys <= h + 1, rowin = ys < h;       // the two rows below the image read as zero
@@ -924,11 +749,10 @@ __device__ __forceinline__ void ss_item(float* lds, const int strip, const int i
                     #pragma unroll
                     for (int c = 0; c < SS_NC; c++) { const float* a = psrc[c] + src_off; asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(pf[tt][c]) : "v"(a) : "memory"); }
                 }
-                SS_PROF_BARRIER(false)
+                ss_lds_barrier();
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        SS_PROF_END(14 + lrow)
         return;
     }
     // Per-thread pipeline state, touched only when the thread changes pairs (every SS_NQ steps): the ring rows of its pair (pA, pB), of the row above (pU)
@@ -950,7 +774,6 @@ __device__ __forceinline__ void ss_item(float* lds, const int strip, const int i
             const int par = (tt + sgrp) & 1;
             // step T of this thread's row pair p: s = T - p.  First its odd row's half-sweep s - 1, then its even row's half-sweep s (the even row's vertical
             // neighbours in the odd row are of the colour just updated -- same thread, same columns).  Both update the column parity s & 1 = (T + g) & 1.
-            SS_PROF_T0
             if (sg == 1 && stS) SS_STORE(yS, pS)               // the odd row of the pair left in the last step (the ring keeps a finished row for two steps)
             if (sg >= 1 && okB) { if (par == 0) SS_HALF_B(0) else SS_HALF_B(1) }
             if (sg == SS_NQ) {                                  // the pair is through: the thread takes the pair SS_NQ further down (same parity)
@@ -965,12 +788,11 @@ __device__ __forceinline__ void ss_item(float* lds, const int strip, const int i
             }
             if (sg >= 0 && okA) { if (par == 0) SS_HALF_A(0) else SS_HALF_A(1) }
             if (sg == SS_NQ - 1 && okA) SS_STORE(2 * p, pA)
-            SS_PROF_BARRIER(__builtin_amdgcn_ballot_w64(sg == 0 && okA) != 0ull)
+            ss_lds_barrier();
             sg++;
         }
     }
     #undef SS_PAIR
-    SS_PROF_END(ct >> 6)
     #undef SS_LOAD
     #undef SS_HALF_A
     #undef SS_HALF_B
@@ -992,14 +814,6 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64, 512), amdgpu_wave
         __syncthreads();                                          // every wave is through with the item's LDS before the next item clears it
     }
 }
-
-#ifdef SIND_LAB
-int debug_ss_profile(unsigned long long* out, int reset) {
-    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ss_prof), sizeof(g_ss_prof)) != hipSuccess) return SIND_E_HIP;
-    if (reset) { static const unsigned long long z[16][6] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_ss_prof), z, sizeof(z)) != hipSuccess) return SIND_E_HIP; }
-    return SIND_OK;
-}
-#endif
 
 // ---------------------------------------------------------------------------------------------------------
 // Level transition of the DeepFlow loop in ONE launch instead of three (k_add_flow, k_resize_f32_pair, k_warp_avg_iz of the next level; deepflow.cpp: W += dW; resize(W) / 0.95;
@@ -1526,40 +1340,9 @@ int launch_bgr2gray(hipStream_t s, const uint8_t* bgr, uint8_t* gray, size_t npi
 }
 
 // `total` red-black SOR iterations on the level's system.  Small levels: the whole image is one tile and all iterations run
-// in one launch; larger levels: 64 x 64 tiles, SOR_FUSE iterations per launch with a 2*SOR_FUSE halo, ping-pong between the
+// in one launch; larger levels: 64 x 64 tiles, C.fuse iterations per launch with a 2 * C.fuse halo, ping-pong between the
 // two increment buffers (a tile reads its halo from neighbours that another workgroup of the same launch rewrites).
 // (the solver settings -- variant, iterations per launch, tile, streaming threshold -- are a SolverCfg per flow handle: flow.hpp)
-// How the `total` iterations of a level are cut into launches.  A launch of f iterations needs a halo of 2 f pixels, so it covers the level with
-// ceil(w / (EW - 4 f)) x ceil(h / (EH - 4 f)) tiles, and a tile costs its prologue (coefficient loads, LDS set-up, write-back: C.plan_cost iterations'
-// worth, fitted to the measured 4 / 5 / 6-iteration runs) plus f iterations.  With a fixed f = 5 the 26 tiled levels of the 384 x 288 pyramid compute
-// 2.5 x their pixels (levels just above a multiple of the 44-pixel interior up to 3.5 x); the cheapest partition per level (dynamic programme over
-// the remaining iterations) picks e.g. 1 + 6 x 4 iterations for 178 x 133: 12 tiles per launch instead of 20.  Measured (bench --sync, solver busy per step):
-// 370 ms with f = 5 everywhere, 364-369 ms with the plans for a prologue cost of 7-20 iterations, 392 ms for 4 -- the model's 6 % shrink to 1-2 %, so the plan
-// is an option (C.fuse = 0), not the default.
-static std::vector<int> sor_fuse_plan(const SolverCfg& C, int w, int h, int EW, int EH, int total) {
-    if (C.fuse > 0) return std::vector<int>((size_t)divup(total, C.fuse), C.fuse);
-    static std::mutex mu; static std::map<std::array<int, 6>, std::vector<int>> cache;
-    const std::array<int, 6> key{w, h, EW, EH, total, (int)std::lrint(C.plan_cost * 16)};
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    const int fmax = std::min(10, (std::min(EW, EH) - 1) / 4);
-    std::vector<double> cost((size_t)total + 1, 0.0); std::vector<int> pick((size_t)total + 1, 1);
-    for (int rem = 1; rem <= total; rem++) {
-        double best = -1; int bf = 1;
-        for (int f = 1; f <= std::min(fmax, rem); f++) {
-            const int IW = EW - 4 * f, IH = EH - 4 * f;
-            const double c = (double)divup(w, IW) * divup(h, IH) * (C.plan_cost + f) + cost[(size_t)rem - f];
-            if (best < 0 || c < best) { best = c; bf = f; }
-        }
-        cost[(size_t)rem] = best; pick[(size_t)rem] = bf;
-    }
-    std::vector<int> plan;
-    for (int rem = total; rem > 0; rem -= pick[(size_t)rem]) plan.push_back(pick[(size_t)rem]);
-    std::sort(plan.begin(), plan.end(), std::greater<int>());            // the order of the launches is free: same iterations, same bits
-    cache[key] = plan;
-    return plan;
-}
 // Few images: the launch is latency-bound (a tile per compute unit, most of the chip idle).  Then 1024-thread tiles (k_sor_tile) run MORE iterations per launch on deeper
 // halos: the fewest launches whose tiles all still find a compute unit of their own (a launch costs ~6 us before its first iteration; an iteration ~0.8 us).
 // Returns the iterations of each launch, or nothing if the level at this batch size is throughput-bound (the kernels below).
@@ -1590,12 +1373,7 @@ int sor_iterations(hipStream_t s, FlowPlanes& P, int w, int h, int B, int total,
     static SindPerDeviceInit attr_init;
     HIP_TRY(attr_init.run([] {
         hipError_t attr_rc = hipSuccess;
-        const void* fs[] = {(const void*)k_sor_fused<2, 1024, 4, 0, 0>, (const void*)k_sor_fused<2, 512, 2, 0, 0>, (const void*)k_sor_fused<2, 512, 4, 64, 64>, (const void*)k_sor_stream<SS_MAXSW>,
-#ifdef SIND_LAB
-                            (const void*)k_sor_fused<0, 1024, 4, 0, 0>, (const void*)k_sor_fused<0, 512, 4, 64, 64>, (const void*)k_sor_fused<1, 384, 3, 0, 0>, (const void*)k_sor_fused<1, 768, 3, 0, 0>,
-                            (const void*)k_sor_fused<1, 256, 3, 0, 0>,
-#endif
-        };
+        const void* fs[] = {(const void*)k_sor_fused<1024, 4, 0, 0>, (const void*)k_sor_fused<512, 2, 0, 0>, (const void*)k_sor_fused<512, 4, 64, 64>, (const void*)k_sor_stream<SS_MAXSW>};
         for (const void* f : fs) if (attr_rc == hipSuccess) attr_rc = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         return attr_rc;
     }));
@@ -1614,18 +1392,14 @@ int sor_iterations(hipStream_t s, FlowPlanes& P, int w, int h, int B, int total,
         const size_t shm = sor_lds_bytes(EW, nt);
         if (shm > 150 * 1024) { sind_set_error("sor_iterations: a %d x %d level needs %zu bytes of LDS", w, h, shm); return SIND_E_ARG; }
         // <= 512 threads: two waves per SIMD, i.e. up to 256 registers -- room for the run-time tile sizes AND the reciprocal division without spills
-        // (all 25 iterations run in this launch, so here the loop is the cost); larger blocks keep the four-waves-per-SIMD IEEE instance
-#ifdef SIND_LAB
-        auto kern1 = (nt <= 512 && (C.mode == 4 || C.mode == 5)) ? k_sor_fused<2, 512, 2, 0, 0> : (C.mode == 4 || C.mode == 5) ? k_sor_fused<2, 1024, 4, 0, 0> : k_sor_fused<0, 1024, 4, 0, 0>;
-#else
-        auto kern1 = nt <= 512 ? k_sor_fused<2, 512, 2, 0, 0> : k_sor_fused<2, 1024, 4, 0, 0>;
-#endif
+        // (all 25 iterations run in this launch, so here the loop is the cost); larger blocks run four waves per SIMD
+        auto kern1 = nt <= 512 ? k_sor_fused<512, 2, 0, 0> : k_sor_fused<1024, 4, 0, 0>;
         hipLaunchKernelGGL(kern1, dim3(1, B), dim3(nt), shm, s, w, h, EW, EH, EW, EH, 0, 0, 1, total, 0, omega, P.A11, P.A12, P.A22, P.b1, P.b2, P.wgt,
-                           P.r11, P.r22, P.dWu, P.dWv, P.dWu, P.dWv);
+                           P.dWu, P.dWv, P.dWu, P.dWv);
         *nlaunch += 1; return SIND_OK;
     }
     // large levels, many images: one-wave row pipelines (flow_wave.hip) -- no workgroup barrier anywhere
-    if (total % 5 == 0 && (C.mode == 6 || (C.mode == 4 && C.wave && B >= C.stream_min_b && w * h >= C.stream_min_px))) {
+    if (total % 5 == 0 && (C.mode == 6 || (C.mode == 4 && C.wave && B >= C.stream_min_b))) {
         for (int done = 0; done < total; done += 5) { SIND_TRY(launch_sor_wave(s, P, w, h, B, omega, C.wave_items, C.wave_bands, C.wave_prefetch)); *nlaunch += 1; }
         if (streamed) *streamed = 1;
         return SIND_OK;
@@ -1637,7 +1411,7 @@ int sor_iterations(hipStream_t s, FlowPlanes& P, int w, int h, int B, int total,
         while (SW > SS_MAXSW) { n++; IW = divup(divup(w, n), 4) * 4; SW = (IW + 24) / 4; }
         const int HT = divup(5 * SW, 64) * 64, CT = 2 * HT;       // threads of one slot group (whole waves: a wave holding both groups would run both colours' code every step), compute threads; + two loader waves
         const bool fits = h >= 4 && total % (SS_NQ / 2) == 0;
-        if (fits && (C.mode == 5 || (C.mode == 4 && B >= C.stream_min_b && w * h >= C.stream_min_px))) {
+        if (fits && (C.mode == 5 || (C.mode == 4 && B >= C.stream_min_b))) {
             const size_t shm = ((size_t)6 * SS_RING * (2 * SS_MAXSW + 4) + (size_t)SS_NST * SS_STG * 4 * SS_MAXSW) * sizeof(float);
             for (int done = 0; done < total; done += SS_NQ / 2) {
                 const int items = n * B, wgs = (C.stream_wg_cap > 0 && items > C.stream_wg_cap) ? divup(items, divup(items, C.stream_wg_cap)) : items;      // persistent: every workgroup the same number of items (+- 1)
@@ -1650,45 +1424,18 @@ int sor_iterations(hipStream_t s, FlowPlanes& P, int w, int h, int B, int total,
         }
         if (C.mode == 5 && !fits) { /* wider than one workgroup's strip: the tiled kernel below */ }
     }
-#ifdef SIND_LAB
-    if (C.mode == 2) {                             // 1x4 strips + reciprocal division (k_sor_fused4), 64 x 64 tiles, 1024 threads
-        static SindPerDeviceInit attr4_init;
-        HIP_TRY(attr4_init.run([] { return hipFuncSetAttribute((const void*)k_sor_fused4, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); }));
-        const int EW = 64, EH = 64, nt = 1024;
-        const size_t shm = (size_t)4 * (EH + 2) * (EW / 4 + 2) * sizeof(float2);
-        for (int done = 0; done < total;) {
-            const int k = std::min(C.fuse > 0 ? C.fuse : 5, total - done), halo = 2 * k, halo_x = halo, IW = EW - 2 * halo_x, IH = EH - 2 * halo;
-            const int ntx = divup(w, IW), nty = divup(h, IH);
-            hipLaunchKernelGGL(k_sor_fused4, dim3(ntx * nty, B), dim3(nt), shm, s, w, h, EW, EH, IW, IH, halo_x, halo, ntx, k, C.xcd, omega, P.A11, P.A12, P.A22, P.b1, P.b2,
-                               P.wgt, P.dWu, P.dWv, P.dWu2, P.dWv2);
-            std::swap(P.dWu, P.dWu2); std::swap(P.dWv, P.dWv2);
-            done += k; *nlaunch += 1;
-        }
-        return SIND_OK;
-    }
-#endif
-    // tiled levels.  Reciprocal instance (default): EW x EH tiles of EW * EH / 8 threads at three waves per SIMD; IEEE-division instance: four waves per SIMD
+    // tiled levels: EW x EH tiles of EW * EH / 8 threads, four waves per SIMD, C.fuse iterations per launch (the last launch of a level takes the rest)
     const int EW = C.tile_w, EH = C.tile_h, nt = threads_for(EW, EH);
-    const bool rcp = C.mode == 3;
-    if (rcp && nt != 256 && nt != 384 && nt != 768) { sind_set_error("sor_iterations: %d x %d tiles (%d threads) have no reciprocal-solver instance", EW, EH, nt); return SIND_E_ARG; }
-    if (nt > SOR_NT || (C.fuse > 0 && 2 * 2 * C.fuse >= std::min(EW, EH))) { sind_set_error("sor_iterations: tile %d x %d / %d fused iterations not supported", EW, EH, C.fuse); return SIND_E_ARG; }
+    if (nt > SOR_NT || 2 * 2 * C.fuse >= std::min(EW, EH)) { sind_set_error("sor_iterations: tile %d x %d / %d fused iterations not supported", EW, EH, C.fuse); return SIND_E_ARG; }
     const size_t shm = sor_lds_bytes(EW, nt);
     if (shm > 150 * 1024) { sind_set_error("sor_iterations: %d x %d tiles need %zu bytes of LDS", EW, EH, shm); return SIND_E_ARG; }
-    const std::vector<int> plan = sor_fuse_plan(C, w, h, EW, EH, total);
-    size_t step = 0;
+    const bool t64 = EW == 64 && EH == 64 && nt == 512;               // the default tile has an instance with compile-time sizes
+    auto kern = t64 ? k_sor_fused<512, 4, 64, 64> : k_sor_fused<1024, 4, 0, 0>;
     for (int done = 0; done < total;) {
-        const int k = std::min(plan[step++], total - done), halo = 2 * k, halo_x = halo, IW = EW - 2 * halo_x, IH = EH - 2 * halo;
+        const int k = std::min(C.fuse, total - done), halo = 2 * k, halo_x = halo, IW = EW - 2 * halo_x, IH = EH - 2 * halo;
         const int ntx = divup(w, IW), nty = divup(h, IH);
-        const bool t64 = EW == 64 && EH == 64 && nt == 512;           // the default tile has instances with compile-time sizes
-#ifdef SIND_LAB
-        auto kern = (C.mode == 4 || C.mode == 5) ? (t64 ? k_sor_fused<2, 512, 4, 64, 64> : k_sor_fused<2, 1024, 4, 0, 0>) : !rcp ? (t64 ? k_sor_fused<0, 512, 4, 64, 64> : k_sor_fused<0, 1024, 4, 0, 0>)
-                    : nt == 384 ? k_sor_fused<1, 384, 3, 0, 0> : nt == 768 ? k_sor_fused<1, 768, 3, 0, 0> : k_sor_fused<1, 256, 3, 0, 0>;
-#else
-        auto kern = t64 ? k_sor_fused<2, 512, 4, 64, 64> : k_sor_fused<2, 1024, 4, 0, 0>;
-#endif
-        static const int dry = sind_lab_env("SIND_SOR_DRY") ? atoi(sind_lab_env("SIND_SOR_DRY")) : 0;       // timing experiment: 1 = no iterations (prologue + write-back only; results are wrong)
-        hipLaunchKernelGGL(kern, dim3(ntx * nty, B), dim3(nt), shm, s, w, h, EW, EH, IW, IH, halo_x, halo, ntx, dry ? 0 : k, C.xcd, omega, P.A11, P.A12, P.A22, P.b1, P.b2,
-                           P.wgt, P.r11, P.r22, P.dWu, P.dWv, P.dWu2, P.dWv2);
+        hipLaunchKernelGGL(kern, dim3(ntx * nty, B), dim3(nt), shm, s, w, h, EW, EH, IW, IH, halo_x, halo, ntx, k, 1, omega, P.A11, P.A12, P.A22, P.b1, P.b2,
+                           P.wgt, P.dWu, P.dWv, P.dWu2, P.dWv2);
         std::swap(P.dWu, P.dWu2); std::swap(P.dWv, P.dWv2);
         done += k; *nlaunch += 1;
     }
@@ -1710,11 +1457,11 @@ int varref_level(hipStream_t s, FlowPlanes& P, const float* I0, const float* I1,
         if (C.coef_kernel) {
             const int tx = divup(w, KL_COLS), ty = divup(h, 4 * KL_ROWS), nt = tx * ty * B;
             hipLaunchKernelGGL(k_coef_lanes, dim3(divup(nt, 8) * 8), dim3(256), 0, s, V, w, h, P.avg, P.Iz, P.Wu, P.Wv,
-                               P.dWu, P.dWv, P.A11, P.A12, P.A22, P.b1, P.b2, P.wgt, C.mode == 3 ? P.r11 : nullptr, C.mode == 3 ? P.r22 : nullptr, C.coef_kernel == 2 ? 0 : 1, tx, ty, nt, C.coef_xcd);
+                               P.dWu, P.dWv, P.A11, P.A12, P.A22, P.b1, P.b2, P.wgt, C.coef_kernel == 2 ? 0 : 1, tx, ty, nt, C.coef_xcd);
         }
         else
             hipLaunchKernelGGL(k_coef, dim3(divup(w, 128), divup(h, KC_ROWS), B), blk, 0, s, V, w, h, P.avg, P.Iz, P.Wu, P.Wv,
-                               P.dWu, P.dWv, P.A11, P.A12, P.A22, P.b1, P.b2, P.wgt, C.mode == 3 ? P.r11 : nullptr, C.mode == 3 ? P.r22 : nullptr);
+                               P.dWu, P.dWv, P.A11, P.A12, P.A22, P.b1, P.b2, P.wgt);
         if (timer) timer->begin(s);
         long long nlaunch = 0; int streamed = 0;
         SIND_TRY(sor_iterations(s, P, w, h, B, V.sorIterations, V.omega, &nlaunch, C, &streamed));

@@ -6,18 +6,17 @@ extern "C" int sind_pipe_destroy(sind_pipe* p);
 int pipe_build(sind_pipe* p, const sind_pipe_config* cfg) {
     p->c = *cfg; p->S = cfg->streams; p->T = cfg->frames_per_step;
     p->dc.W = cfg->width; p->dc.H = cfg->height; p->dc.fx = cfg->fx; p->dc.fy = cfg->fy; p->dc.cx = cfg->cx; p->dc.cy = cfg->cy; p->dc.depthScale = cfg->depth_scale; p->dc.device = cfg->device;
-    const bool flow_hi = sind_lab_env("SIND_FLOW_PRIORITY") && atoi(sind_lab_env("SIND_FLOW_PRIORITY")) != 0;
-    SIND_TRY(make_stream(&p->stream, flow_hi)); SIND_TRY(make_stream(&p->orb_stream, false)); HIP_TRY(hipEventCreateWithFlags(&p->ev_gray, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&p->ev_depth, hipEventDisableTiming));
+    SIND_TRY(make_stream(&p->stream, false)); SIND_TRY(make_stream(&p->orb_stream, false)); HIP_TRY(hipEventCreateWithFlags(&p->ev_gray, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&p->ev_depth, hipEventDisableTiming));
     const int B = p->S * p->T; const size_t np = (size_t)cfg->width * cfg->height;
     // dense-flow slices: concurrent streams keep the GPU busy through the launch tails and the small pyramid levels of each other; small batches stay in one piece.
     // Measured (profiles/r04/split_sweep.txt, lab build): 512 pairs per step: 3 slices 1382-1417 pairs/s, 2: 1377, 4: 1354; 224 pairs (the one-GPU sequence job's step): 2 slices
     // 1192, 1: 1164, 3: 1150, 4: 1120.  Round 5 (k_coarse_chain, k_sor_tile; profiles/r05/small_step_slices.txt): slices of 12 - 50 pairs keep each other's latency-bound launches
     // company -- 24 pairs: 2 slices 750 pairs/s (1: 671), 48: 2 -> 935 (1: 607), 64: 2 -> 1042 (1: 741), 96: 3 -> 1130 (2: 991); slices of 80 and more take the streaming solver
-    const int nsplit = std::max(1, std::min(sind_lab_env("SIND_FLOW_SPLIT") ? atoi(sind_lab_env("SIND_FLOW_SPLIT")) : (cfg->flow_slices > 0 ? cfg->flow_slices : B >= 320 ? 3 : B >= 160 ? 2 : B >= 80 ? 3 : B >= 24 ? 2 : 1), std::min(4, B))), Bs = (B + nsplit - 1) / nsplit;
+    const int nsplit = std::max(1, std::min(cfg->flow_slices > 0 ? cfg->flow_slices : B >= 320 ? 3 : B >= 160 ? 2 : B >= 80 ? 3 : B >= 24 ? 2 : 1, std::min(4, B))), Bs = (B + nsplit - 1) / nsplit;
     SIND_TRY(p->front.init(p->dc, nsplit > 1 ? std::max(Bs, 2) : B, p->stream));
     HIP_TRY(hipEventCreate(&p->ev_pool));                   // with timing: also the time base of the solver intervals
     for (int i = 1; i < nsplit; i++) {
-        hipStream_t st = nullptr; SIND_TRY(make_stream(&st, flow_hi)); p->extra_streams.push_back(st);
+        hipStream_t st = nullptr; SIND_TRY(make_stream(&st, false)); p->extra_streams.push_back(st);
         p->extra_fronts.emplace_back(new DynaFront()); SIND_TRY(p->extra_fronts.back()->init(p->dc, Bs, st));
     }
     p->front.flow.max_levels = std::max(0, cfg->flow_max_levels); for (auto& f : p->extra_fronts) f->flow.max_levels = p->front.flow.max_levels;
@@ -41,21 +40,19 @@ int pipe_build(sind_pipe* p, const sind_pipe_config* cfg) {
     p->host_info[0] = cpu_share; p->host_info[3] = nproc; p->host_info[4] = quota; p->host_info[5] = lw;
     p->cpu_share = cpu_share;
     if (const char* e = getenv("SIND_GROW_GPU")) { p->grow_q_fixed = std::max(0, std::min(4, atoi(e))); p->grow_q = p->grow_q_fixed; }
-    const int nworkers = sind_lab_env("SIND_WORKERS") ? std::max(2, atoi(sind_lab_env("SIND_WORKERS"))) : cfg->host_threads > 0 ? cfg->host_threads : std::max(2, cpu_share * 3);         // default: 3x the CPU share (workers sleep while they wait for the GPU: a tail waits ~6 ms of its ~11; 48 against 32 workers:
-                                                                                                                                                                                        // 1280 x 720 790 - 818 -> 813 - 866 pairs/s, headline 1530 - 1577 -> 1548 - 1593, small steps unchanged, profiles/r05/pool_workers.txt)
+    const int nworkers = cfg->host_threads > 0 ? cfg->host_threads : std::max(2, cpu_share * 3);         // default: 3x the CPU share (workers sleep while they wait for the GPU: a tail waits ~6 ms of its ~11; 48 against 32 workers:
+                                                                                                         // 1280 x 720 790 - 818 -> 813 - 866 pairs/s, headline 1530 - 1577 -> 1548 - 1593, small steps unchanged, profiles/r05/pool_workers.txt)
     // A task leaves its stream idle (every GPU section ends in a wait), so the HIP streams belong to the workers, not to the camera
     // streams: their number does not grow with S.
     p->worker_streams.resize(nworkers); p->occ_tails.resize(nworkers); p->tails.resize(p->S);
-    // Two streams per worker: phase-B tasks use a high-priority stream; phase-A tasks (CalOccluded, optional depth stages) have their own
-    // stream, high priority by default as well.  Measured on MI355X: at normal priority these small kernels starve behind the solver's
-    // workgroups (dense flow 230 -> 221 ms, but 65-90 ms of CalOccluded / depth-stage work is then left over when the flow ends); at high
-    // priority they cost the solver about what they would cost alone.  Either way the small kernels of a step are worth ~90 ms of GPU time.
+    // One high-priority stream per worker, for its phase-B tasks and its phase-A tasks (CalOccluded, optional depth stages) alike.  Measured on MI355X: at
+    // normal priority the small phase-A kernels starve behind the solver's workgroups (dense flow 230 -> 221 ms, but 65-90 ms of CalOccluded / depth-stage
+    // work is then left over when the flow ends); at high priority they cost the solver about what they would cost alone.  Either way the small kernels of
+    // a step are worth ~90 ms of GPU time.
     p->worker_streams_lo.resize(nworkers);
-    const bool phase_a_hi = !(sind_lab_env("SIND_PHASEA_PRIORITY") && atoi(sind_lab_env("SIND_PHASEA_PRIORITY")) == 0);
     for (int w = 0; w < nworkers; w++) {
-        SIND_TRY(make_stream(&p->worker_streams[w], !(sind_lab_env("SIND_TAIL_PRIORITY") && atoi(sind_lab_env("SIND_TAIL_PRIORITY")) == 0)));
-        if (phase_a_hi) p->worker_streams_lo[w] = p->worker_streams[w];      // same stream (extra streams would also change how the runtime spreads the workers' streams over its hardware queues)
-        else SIND_TRY(make_stream(&p->worker_streams_lo[w], false));
+        SIND_TRY(make_stream(&p->worker_streams[w], true));
+        p->worker_streams_lo[w] = p->worker_streams[w];      // same stream (extra streams would also change how the runtime spreads the workers' streams over its hardware queues)
         p->occ_tails[w].reset(new DynaTail()); SIND_TRY(p->occ_tails[w]->init(p->dc, p->worker_streams_lo[w]));
     }
     for (int s = 0; s < p->S; s++) { p->tails[s].reset(new DynaTail()); SIND_TRY(p->tails[s]->init(p->dc, p->worker_streams[s % nworkers]));
@@ -65,13 +62,9 @@ int pipe_build(sind_pipe* p, const sind_pipe_config* cfg) {
     // host-bound configuration wants every core it can get.  The controller below moves between the two on the same signal as the region grow's share.
     p->cpu_tokens_max = std::max(2, cpu_share + 2);      // (the controller only goes there while steps wait for the host: 1280 x 720, host-bound, 798 - 809 pairs/s with 15 tokens, 822 - 855 with 17, 836 - 857 with 20 -- a token is held
                                                               // through short waits too, so a few more tokens than cores keep the 16 cores of the quota busy: 13.6 -> 14.5 - 14.8; profiles/r05/cpu_tokens_720p.txt) p->cpu_tokens_min = std::max(2, cpu_share - 3); p->cpu_tokens = p->cpu_tokens_min;
-    if (sind_lab_env("SIND_CPU_TOKENS")) { p->cpu_tokens = std::max(1, atoi(sind_lab_env("SIND_CPU_TOKENS"))); p->cpu_tokens_fixed = true; }
     p->host_info[1] = nworkers; p->host_info[2] = p->cpu_tokens_max;
     p->occ_workers = std::max(1, std::min(nworkers, cpu_share - 2));             // CalOccluded runners: leave two cores of the share to the flow's launch threads
-    if (const char* e = sind_lab_env("SIND_OCC_WORKERS")) p->occ_workers = std::max(1, std::min(atoi(e), nworkers));
-    p->depth_ahead = sind_lab_env("SIND_DEPTH_AHEAD") && atoi(sind_lab_env("SIND_DEPTH_AHEAD")) != 0;
-    if (p->depth_ahead) SIND_TRY(ensure_dtails(p));
-    p->batch_km = p->S >= 2 && !(sind_lab_env("SIND_KM_BATCH") && atoi(sind_lab_env("SIND_KM_BATCH")) == 0);
+    p->batch_km = p->S >= 2;
     if (p->batch_km) {
         // Two to four groups of streams, each with its own batched k-means chain, HIP stream and round thread: a round is ~60 dependent launches and takes
         // ~20 ms next to the flow solver whatever the batch (24 or 128 frames), and while ONE batch for all streams ran, every tail worker was idle --
@@ -83,12 +76,12 @@ int pipe_build(sind_pipe* p, const sind_pipe_config* cfg) {
         for (int g = 0; g < p->km_groups_max; g++) {                          // group 0 may hold all streams, the others at most half of them
             SIND_TRY(make_stream(&p->km_streams[g], true)); SIND_TRY(p->kmb[g].init(p->dc, g == 0 ? p->S : (p->S + 1) / 2, p->km_streams[g])); }
     }
-    p->batch_occ = B >= 4 && !(sind_lab_env("SIND_OCC_BATCH") && atoi(sind_lab_env("SIND_OCC_BATCH")) == 0);
+    p->batch_occ = B >= 4;
     if (p->batch_occ) {
         // frames per launch of CalOccluded's GPU half and of the region grow: 128 (profiles/r04/lab_settings_sweep.txt, 512 frames per step: 32: 1295, 64: 1438-1468, 128: 1474-1510,
         // 192: 1506, 256: 1492, 512: 1499 pairs/s)
-        p->occ_chunk = std::min(B, std::max(1, sind_lab_env("SIND_OCC_CHUNK") ? atoi(sind_lab_env("SIND_OCC_CHUNK")) : 128));
-        SIND_TRY(make_stream(&p->occ_stream, !(sind_lab_env("SIND_OCC_PRIORITY") && atoi(sind_lab_env("SIND_OCC_PRIORITY")) == 0))); SIND_TRY(p->occb.init(p->dc, p->occ_chunk));
+        p->occ_chunk = std::min(B, 128);
+        SIND_TRY(make_stream(&p->occ_stream, true)); SIND_TRY(p->occb.init(p->dc, p->occ_chunk));
         const size_t nblk = (size_t)(cfg->width / 16) * (cfg->height / 16); const int nch = (B + p->occ_chunk - 1) / p->occ_chunk;
         for (int k = 0; k < 2; k++) {
             SIND_TRY(p->sb[k].occ_edge_h.alloc(np * B)); SIND_TRY(p->sb[k].occ_total_h.alloc(np * B)); SIND_TRY(p->sb[k].occ_blocks_h.alloc(nblk * B));
@@ -101,7 +94,7 @@ int pipe_build(sind_pipe* p, const sind_pipe_config* cfg) {
             p->sb[k].grow_ev.assign(nch, nullptr); p->sb[k].grow_left.reset(new std::atomic<int>[nch]); p->sb[k].grow_state.reset(new std::atomic<int>[nch]);
             for (int c = 0; c < nch; c++) HIP_TRY(hipEventCreateWithFlags(&p->sb[k].grow_ev[c], hipEventDisableTiming));
         }
-        SIND_TRY(make_stream(&p->grow_stream, !(sind_lab_env("SIND_OCC_PRIORITY") && atoi(sind_lab_env("SIND_OCC_PRIORITY")) == 0)));
+        SIND_TRY(make_stream(&p->grow_stream, true));
         p->grow_ok = PeacGrowBatch::supports(cfg->width, cfg->height);
         if (p->grow_ok) SIND_TRY(p->grow.init(cfg->width, cfg->height, cfg->fx, cfg->fy, cfg->cx, cfg->cy, cfg->depth_scale, p->occ_chunk));
     }

@@ -114,7 +114,7 @@ struct sind_pipe {
     int cur = 0; int occ_workers = 24;
     // CPU tokens (common.hpp) for the software-pipelined steps, where CalOccluded runners and tails compete for the quota (measured: throttled periods 7 -> 2
     // of 22, +1 %); synchronous steps run ungated -- there the hand-over of tokens at every GPU wait costs more than the throttling (tails 145 -> 173 ms)
-    int cpu_tokens = 15, cpu_tokens_min = 13, cpu_tokens_max = 15; bool cpu_tokens_fixed = false;
+    int cpu_tokens = 15, cpu_tokens_min = 13, cpu_tokens_max = 15;
     // Optional schedule of the synchronous step: run the depth half of the tails (k-means, SegAndMerge) underneath the dense flow.
     // Parity-tested, off by default: the tails phase shrinks from ~75 to ~23 ms, but the solver loses as much to the ~13 k extra small
     // launches it then shares the GPU with (dense flow 232 -> 287 ms at high stream priority; at normal priority the chains starve).
@@ -140,9 +140,9 @@ static inline void grow_adapt(sind_pipe* p, double host_wait_ms, double step_ms)
         if ((p->grow_q >= 4 || host_wait_ms > 0.15 * step_ms) && p->batch_km && p->km_groups_fixed < 0) p->km_groups = std::min(p->km_groups_max, p->km_groups + 1);      // every grow is on the GPU already (or the wait is long): one more k-means chain
         p->grow_q = std::min(4, p->grow_q + 1); p->grow_idle_steps = 0;
         // clearly host-bound (the step waits for the tails for > 10 % of its time): a few more tokens than cores (a token is held through short waits too: 1280 x 720 + 3 - 6 %); else one more, up to share - 1
-        if (!p->cpu_tokens_fixed) p->cpu_tokens = host_wait_ms > 0.10 * step_ms ? p->cpu_tokens_max : std::max(p->cpu_tokens, std::min(p->cpu_tokens_max - 3, p->cpu_tokens + 1));
+        p->cpu_tokens = host_wait_ms > 0.10 * step_ms ? p->cpu_tokens_max : std::max(p->cpu_tokens, std::min(p->cpu_tokens_max - 3, p->cpu_tokens + 1));
     } else if (host_wait_ms < 0.005 * step_ms) {
-        if (!p->cpu_tokens_fixed) p->cpu_tokens = std::max(p->cpu_tokens_min, p->cpu_tokens - 1);
+        p->cpu_tokens = std::max(p->cpu_tokens_min, p->cpu_tokens - 1);
         if (++p->grow_idle_steps >= 3) {
             if (p->batch_km && p->km_groups > 1 && p->km_groups_fixed < 0) p->km_groups--; else p->grow_q = std::max(0, p->grow_q - 1);
             p->grow_idle_steps = 0;

@@ -19,13 +19,10 @@ class FlowStage:
         """finest n levels of the 0.95 pyramid only (BASELINE.json config 5, "3-level flow pyramid"); 0 = the full pyramid of OpenCV's DeepFlow"""
         check(lib().sind_flow_set_max_levels(self._h, int(n)), "sind_flow_set_max_levels")
 
-    def set_sor_variant(self, mode: int = 4, fuse: int = 5, tile_w: int = 64, tile_h: int | None = None):
-        """solver variant of this handle (all return the same bits).  Fused register-resident SOR with 1x8 strips: mode 4 = divisions through a reciprocal formed on the fly
-        (default), 5 = the streaming kernel wherever it fits, 6 = the one-wave pipeline on every level beyond one workgroup, 0 = one launch per colour (cross-check); lab builds: 1 = IEEE division, 3 = reciprocal planes held in registers
-        (three waves per SIMD; 256/384/768-thread tiles), 2 = 1x4 strips and reciprocal division.  fuse = iterations per launch on the tiled levels, 0 = a per-level plan
-        (lab builds).  tile_h defaults to 48 (mode 3) / 64."""
-        if tile_h is None:
-            tile_h = 48 if mode == 3 else 64
+    def set_sor_variant(self, mode: int = 4, fuse: int = 5, tile_w: int = 64, tile_h: int = 64):
+        """solver variant of this handle (all return the same bits).  mode 4 = fused register-resident SOR with 1x8 strips, divisions through a reciprocal formed on the
+        fly (default), 5 = the streaming kernel wherever it fits, 6 = the one-wave pipeline on every level beyond one workgroup, 0 = one launch per colour (cross-check).
+        fuse = iterations per launch on the tiled levels (1 .. 12); tile_w x tile_h = extended tile."""
         check(lib().sind_flow_set_sor_tiled(self._h, mode, fuse, tile_w, tile_h), "sind_flow_set_sor_tiled")
 
     def set_solver_workgroups(self, cap: int):

@@ -147,30 +147,35 @@ def test_pipelined_depth_ahead_equals_sync(frames):
     ref.close(); pip.close()
 
 
-def test_batched_caloccluded_stage_equals_the_per_frame_chain(frames, monkeypatch):
-    """the GPU half of CalOccluded run once per chunk of frames at the start of a step (default for >= 4 frames per step; here in chunks of 3, so that
-    a ragged last chunk is covered) returns what the per-frame launches of the worker tasks return (SIND_OCC_BATCH=0), output for output"""
+def test_batched_caloccluded_stage_equals_the_per_frame_chain(frames):
+    """the GPU half of CalOccluded run once per chunk of frames at the start of a step (batch_occ: steps of >= 4 frames; here S = 2, T = 2) returns what the
+    per-frame launches of the worker tasks return (steps of 2 frames: S = 2, T = 1, two steps for every batched one), frame for frame.  A ragged last chunk
+    (144 frames per step: chunks of 128 + 16) is covered against the oracle by test_pipeline_in_the_shape_the_bench_runs_streaming_solver_and_ragged_step."""
     from sindslam_amd.pipeline import Pipeline
     bgr, depth = frames
-    S, T = 2, 2
+    S = 2
     K = (TUM3["fx"], TUM3["fy"], TUM3["cx"], TUM3["cy"], TUM3["depth_factor"])
     sb = np.stack([bgr, bgr[:, :, ::-1]]); sd = np.stack([depth, depth[:, :, ::-1]])
     out = {}
-    for batch in ("1", "0"):
-        monkeypatch.setenv("SIND_OCC_BATCH", batch); monkeypatch.setenv("SIND_OCC_CHUNK", "3")
+    for T in (2, 1):
         pipe = Pipeline(S, T, 640, 480, *K, 1500, 1.2, 8, 15, 5)
         for s in range(S):
             pipe.prime(s, sb[s, 1], sb[s, 0])
-        res = []
-        for step in range(2):
+        res = {}                                  # frame index -> per stream (dyna, label, mask, nkp)
+        for step in range(4 // T):
             lo = 2 + step * T
             pipe.process(sb[:, lo:lo + T], sd[:, lo:lo + T])
-            res.append((pipe.dyna.copy(), pipe.label.copy(), pipe.mask.copy(), pipe.nkp.copy()))
-        out[batch] = res; pipe.close()
-    for a, b in zip(out["1"], out["0"]):
-        for x, y in zip(a, b):
-            assert np.array_equal(x, y)
-    assert (out["1"][1][0] == 255).any()
+            for t in range(T):
+                res[lo + t] = [(pipe.dyna[s, t].copy(), pipe.label[s, t].copy(), pipe.mask[s, t].copy(), int(pipe.nkp[s * T + t])) for s in range(S)]
+        out[T] = res; pipe.close()
+    assert sorted(out[2]) == sorted(out[1]) == [2, 3, 4, 5]
+    for f in out[2]:
+        for s in range(S):
+            batched, per_frame = out[2][f][s], out[1][f][s]
+            for x, y in zip(batched[:3], per_frame[:3]):
+                assert np.array_equal(x, y), (f, s)
+            assert batched[3] == per_frame[3], (f, s)
+    assert any((out[2][f][s][0] == 255).any() for f in (4, 5) for s in range(S))
 
 
 def test_region_grow_share_does_not_change_the_results(frames):
