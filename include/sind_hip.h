@@ -354,6 +354,58 @@ int sind_match_destroy(sind_match* m);
 int sind_match_by_projection(sind_match* m, const sind_match_pair* pairs, int B, float th, int mono, int check_orientation);
 int sind_match_last_rounds(sind_match* m);      /* resolution rounds the last call needed (see csrc/match_kernels.hip) */
 
+/* Local-map search.  Replaces, for B frames at once, the body of Tracking::SearchLocalPoints from its second loop on (src/Tracking.cc:1203-1229):
+ *   bool Frame::isInFrustum(MapPoint* pMP, float viewingCosLimit)                                     src/Frame.cc:340-396
+ *   int MapPoint::PredictScale(const float& currentDist, Frame* pF)                                   src/MapPoint.cc:402-418
+ *   int ORBmatcher::SearchByProjection(Frame& F, const vector<MapPoint*>& vpMapPoints, const float th)  src/ORBmatcher.cc:45-129, RadiusByViewingCos :131-137
+ * The frame's intrinsics, bounds and scale factors are the handle's (sind_match_config); the capacity for map points per frame is set by
+ * sind_match_reserve_map_points (once, or again to grow), which must precede the first sind_match_local_map (SIND_E_STATE otherwise).
+ *   Tcw = F.mTcw (4x4 row-major, rows 0..2 are read; mRcw, mtcw and mOw are derived from it as Frame::UpdatePoseMatrices does)
+ *   map points, per entry i of mvpLocalMapPoints:  x3Dw = pMP->GetWorldPos(), normal = pMP->GetNormal(), max_dist / min_dist = the members mfMaxDistance /
+ *       mfMinDistance (not the Get...Invariance() values), flags bit0 = !pMP->isBad() && pMP->mnLastFrameSeen != F.mnId, bit1 = pMP->Observations() > 0,
+ *       desc = pMP->GetDescriptor() (32 B)
+ *   current frame, per keypoint: cur_un_xy / cur_octave = mvKeysUn, cur_u_right = mvuRight, cur_desc = mDescriptors rows, grid_start / grid_idx = mGrid (as
+ *       sind_frame_post_orb returns it), cur_taken = mvpMapPoints[idx] && mvpMapPoints[idx]->Observations() > 0 on entry (NULL = all free)
+ * Outputs (host): in_view = pMP->mbTrackInView, proj_xyr = {mTrackProjX, mTrackProjY, mTrackProjXR} (3 floats per point), level = mnTrackScaleLevel,
+ * view_cos = mTrackViewCos (all zero where in_view is 0), *n_to_match = nToMatch; each of the five may be NULL.  match_of_cur[idx] = index i of the map
+ * point the reference leaves in F.mvpMapPoints[idx] (-1: the search wrote nothing there), *nmatches = the function's return value (it counts every
+ * assignment, overwritten ones included).  The caller still does IncreaseVisible() for the points in view and the mnLastFrameSeen bookkeeping.
+ * th: 1 / 3 / 5 of the tracker; nnratio: ORBmatcher::mfNNratio (0.8 there); viewing_cos_limit: 0.5 there.
+ * std::log in PredictScale and in Frame::mfLogScaleFactor is evaluated as the FP64 logarithm rounded to FP32 (see csrc/match_local.hip).
+ * Errors: a frame over capacity -> SIND_E_CAPACITY, a NULL array with a non-zero count or a malformed grid -> SIND_E_ARG; nothing is launched.
+ */
+int sind_match_reserve_map_points(sind_match* m, int cap_points);
+typedef struct sind_match_local {
+    const float* Tcw;
+    int n_points; const float* x3Dw; const float* normal; const float* max_dist; const float* min_dist; const uint8_t* flags; const uint8_t* desc;
+    int n_cur; const float* cur_un_xy; const int* cur_octave; const float* cur_u_right; const uint8_t* cur_desc;
+    const int* grid_start; const int* grid_idx; const uint8_t* cur_taken;
+    uint8_t* in_view; float* proj_xyr; int* level; float* view_cos; int* n_to_match;      /* outputs (host), may be NULL */
+    int* match_of_cur; int* nmatches;                                                     /* outputs (host) */
+} sind_match_local;
+int sind_match_local_map(sind_match* m, const sind_match_local* frames, int B, float th, float nnratio, float viewing_cos_limit);
+
+/* Relocalisation search.  Replaces, for B (CurrentFrame, KeyFrame) pairs at once,
+ *   int ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, const float th, const int ORBdist)
+ *                                                                                                      src/ORBmatcher.cc:1472-1599
+ * (Tracking::Relocalization calls it with th 10 / ORBdist 100 and th 3 / ORBdist 64).  At most cap_last key-frame slots and cap_cur keypoints per pair.
+ *   Tcw = CurrentFrame.mTcw
+ *   key frame, per slot i of pKF->GetMapPointMatches():  valid = pMP && !pMP->isBad() && !sAlreadyFound.count(pMP), x3Dw = pMP->GetWorldPos(),
+ *       max_dist / min_dist = mfMaxDistance / mfMinDistance, kf_angle = pKF->mvKeysUn[i].angle, desc = pMP->GetDescriptor() (32 B)
+ *   current frame, per keypoint: cur_un_xy / cur_octave / cur_angle = mvKeysUn, cur_desc = mDescriptors rows, grid_start / grid_idx = mGrid,
+ *       cur_taken = CurrentFrame.mvpMapPoints[i2] != NULL on entry (NULL = all free)
+ * Output: match_of_cur[i2] = slot i whose MapPoint the reference stores in CurrentFrame.mvpMapPoints[i2] (-1: none or removed by the orientation check);
+ * *nmatches = the function's return value.  check_orientation = ORBmatcher::mbCheckOrientation.  Errors as above.
+ */
+typedef struct sind_match_reloc {
+    const float* Tcw;
+    int n_points; const float* x3Dw; const float* max_dist; const float* min_dist; const uint8_t* valid; const float* kf_angle; const uint8_t* desc;
+    int n_cur; const float* cur_un_xy; const int* cur_octave; const float* cur_angle; const uint8_t* cur_desc;
+    const int* grid_start; const int* grid_idx; const uint8_t* cur_taken;
+    int* match_of_cur; int* nmatches;                                                     /* outputs (host) */
+} sind_match_reloc;
+int sind_match_by_projection_kf(sind_match* m, const sind_match_reloc* frames, int B, float th, int orb_dist, int check_orientation);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of
  *   generatePointCloud(imgRGB, imgDepth, imgDepthLast, imgDynaMask, imgDynaMaskLast, imgLabel, poseRelative, Twc)

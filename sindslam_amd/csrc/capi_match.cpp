@@ -1,5 +1,7 @@
 // C ABI: projection matcher (include/sind_hip.h, "sind_match_*").
+#include <cmath>
 #include <cstring>
+#include <vector>
 #include "../../include/sind_hip.h"
 #include "match.hpp"
 
@@ -11,6 +13,24 @@ struct sind_match {
     std::vector<sind::MatchPose> h_pose; std::vector<int> h_nLast, h_nCur, h_lastOct, h_curOct, h_gstart, h_gidx, h_match, h_nm, h_rounds;
     std::vector<float> h_x3Dw, h_lastAng, h_curXY, h_curAng, h_curUR; std::vector<uint8_t> h_lastFlags, h_curTaken, h_lastDesc, h_curDesc;
     int last_rounds = 0;
+    DevBuf<float4> curPack;                                        // keypoint records of match_local.hip, on first use
+    // map-point side of sind_match_local_map (capacity from sind_match_reserve_map_points) and of sind_match_by_projection_kf (cap_last, on first use)
+    struct PointSide {
+        int cap = 0;
+        DevBuf<sind::LocalPose> pose; DevBuf<int> nPts, level, choice, nToMatch; DevBuf<float> x3Dw, normal, maxDist, minDist, angle, projXYR, viewCos;
+        DevBuf<uint8_t> flags, inView; DevBuf<uint32_t> desc;
+        std::vector<sind::LocalPose> h_pose; std::vector<int> h_nPts, h_level, h_nToMatch; std::vector<float> h_x3Dw, h_normal, h_maxDist, h_minDist, h_angle, h_projXYR, h_viewCos;
+        std::vector<uint8_t> h_flags, h_inView, h_desc;
+        int reserve(size_t B, int c) {
+            const size_t n = B * (size_t)c; int r = SIND_OK;
+            if ((r = pose.alloc(B)) || (r = nPts.alloc(B)) || (r = nToMatch.alloc(B)) || (r = level.alloc(n)) || (r = choice.alloc(n)) || (r = x3Dw.alloc(n * 3)) || (r = normal.alloc(n * 3)) ||
+                (r = maxDist.alloc(n)) || (r = minDist.alloc(n)) || (r = angle.alloc(n)) || (r = projXYR.alloc(n * 3)) || (r = viewCos.alloc(n)) || (r = flags.alloc(n)) || (r = inView.alloc(n)) ||
+                (r = desc.alloc(n * 8))) return r;
+            h_pose.resize(B); h_nPts.resize(B); h_nToMatch.resize(B); h_level.resize(n); h_x3Dw.resize(n * 3); h_normal.resize(n * 3); h_maxDist.resize(n); h_minDist.resize(n); h_angle.resize(n);
+            h_projXYR.resize(n * 3); h_viewCos.resize(n); h_flags.resize(n); h_inView.resize(n); h_desc.resize(n * 32);
+            cap = c; return SIND_OK;
+        }
+    } local, reloc;
 };
 
 // CurrentFrame / LastFrame pose algebra of ORBmatcher.cc:1338-1349 (cv::gemm semantics: A*b+c without transposition = FP32 row
@@ -102,5 +122,125 @@ int sind_match_by_projection(sind_match* m, const sind_match_pair* pairs, int B,
     return SIND_OK;
 }
 int sind_match_last_rounds(sind_match* m) { return m ? m->last_rounds : SIND_E_ARG; }
+
+}  // extern "C"
+
+// ---- local-map search and relocalisation search (match_local.hip) ----
+namespace {
+struct PointsFrame {                                               // one frame of either call, the public structs flattened to one shape
+    const float* Tcw; int n_points; const float* x3Dw; const float* normal; const float* max_dist; const float* min_dist; const uint8_t* flags; const float* angle; const uint8_t* desc;
+    int n_cur; const float* cur_un_xy; const int* cur_octave; const float* cur_angle; const float* cur_u_right; const uint8_t* cur_desc; const int* grid_start; const int* grid_idx;
+    const uint8_t* cur_taken;
+    uint8_t* in_view; float* proj_xyr; int* level; float* view_cos; int* n_to_match; int* match_of_cur; int* nmatches;
+};
+}
+
+static void cpy(void* d, const void* s, size_t n) { if (n) std::memcpy(d, s, n); }                  // empty frames may pass NULL arrays
+
+static int run_points(sind_match* m, sind_match::PointSide& ps, const std::vector<PointsFrame>& fr, sind::LocalParams p, int reloc, const char* who) {
+    const int B = (int)fr.size(), cp = ps.cap, cc = p.capCur;
+    p.capPts = cp;
+    p.logScaleFactor = (float)std::log((double)p.scale[1]);       // Frame.cc:71 with log as match_local.hip defines it
+    bool wantFrustum = false;
+    for (int b = 0; b < B; b++) {
+        const PointsFrame& q = fr[b];
+        if (q.n_points < 0 || q.n_points > cp || q.n_cur < 0 || q.n_cur > cc) { sind_set_error("%s: frame %d has %d points / %d keypoints, capacity %d / %d", who, b, q.n_points, q.n_cur, cp, cc); return SIND_E_CAPACITY; }
+        if (!q.Tcw || !q.match_of_cur || !q.nmatches || !q.grid_start || (q.n_points && (!q.x3Dw || !q.max_dist || !q.min_dist || !q.flags || !q.desc || (reloc ? !q.angle : !q.normal))) ||
+            (q.n_cur && (!q.cur_un_xy || !q.cur_octave || !q.cur_desc || !q.grid_idx || (reloc ? !q.cur_angle : !q.cur_u_right)))) { sind_set_error("%s: null array in frame %d", who, b); return SIND_E_ARG; }
+        if (q.grid_start[0] != 0 || q.grid_start[3072] < 0 || q.grid_start[3072] > q.n_cur) { sind_set_error("%s: malformed grid of frame %d", who, b); return SIND_E_ARG; }
+        for (int c = 0; c < 3072; c++) if (q.grid_start[c + 1] < q.grid_start[c]) { sind_set_error("%s: malformed grid of frame %d", who, b); return SIND_E_ARG; }
+        for (int j = 0; j < q.grid_start[3072]; j++) if (q.grid_idx[j] < 0 || q.grid_idx[j] >= q.n_cur) { sind_set_error("%s: grid index outside the keypoints (frame %d)", who, b); return SIND_E_ARG; }
+        wantFrustum = wantFrustum || q.in_view || q.proj_xyr || q.level || q.view_cos;
+        sind::LocalPose& po = ps.h_pose[b]; cpy(po.Tcw, q.Tcw, sizeof(po.Tcw));
+        for (int r = 0; r < 3; r++) { double s = 0; for (int k = 0; k < 3; k++) s += (double)q.Tcw[4 * k + r] * (double)q.Tcw[4 * k + 3]; po.Ow[r] = (float)(s * -1.0); }   // -Rcw^T * tcw
+        ps.h_nPts[b] = q.n_points; m->h_nCur[b] = q.n_cur;
+        const size_t o = (size_t)b * cp, c0 = (size_t)b * cc, np = (size_t)q.n_points, nc = (size_t)q.n_cur;
+        cpy(&ps.h_x3Dw[o * 3], q.x3Dw, np * 12); cpy(&ps.h_maxDist[o], q.max_dist, np * 4); cpy(&ps.h_minDist[o], q.min_dist, np * 4);
+        cpy(&ps.h_desc[o * 32], q.desc, np * 32);
+        if (reloc) { cpy(&ps.h_angle[o], q.angle, np * 4); for (size_t i = 0; i < np; i++) ps.h_flags[o + i] = q.flags[i] ? 3 : 0; }     // every assignment closes its keypoint (:1541)
+        else { cpy(&ps.h_normal[o * 3], q.normal, np * 12); for (size_t i = 0; i < np; i++) ps.h_flags[o + i] = q.flags[i] & 3; }
+        cpy(&m->h_curXY[c0 * 2], q.cur_un_xy, nc * 8); cpy(&m->h_curOct[c0], q.cur_octave, nc * 4); cpy(&m->h_curDesc[c0 * 32], q.cur_desc, nc * 32);
+        if (reloc) cpy(&m->h_curAng[c0], q.cur_angle, nc * 4); else cpy(&m->h_curUR[c0], q.cur_u_right, nc * 4);
+        cpy(&m->h_gstart[(size_t)b * 3073], q.grid_start, 3073 * 4); cpy(&m->h_gidx[c0], q.grid_idx, (size_t)q.grid_start[3072] * 4);
+        if (q.cur_taken) cpy(&m->h_curTaken[c0], q.cur_taken, nc); else std::memset(&m->h_curTaken[c0], 0, nc);
+    }
+    SIND_TRY(m->curPack.alloc((size_t)m->maxB * cc));
+    hipStream_t s = m->stream; const size_t np = (size_t)B * cp, nc = (size_t)B * cc;
+    SIND_TRY(up(ps.pose, ps.h_pose, B, s)); SIND_TRY(up(ps.nPts, ps.h_nPts, B, s)); SIND_TRY(up(m->nCur, m->h_nCur, B, s)); SIND_TRY(up(ps.x3Dw, ps.h_x3Dw, np * 3, s));
+    SIND_TRY(up(ps.maxDist, ps.h_maxDist, np, s)); SIND_TRY(up(ps.minDist, ps.h_minDist, np, s)); SIND_TRY(up(ps.flags, ps.h_flags, np, s));
+    HIP_TRY(hipMemcpyAsync(ps.desc.p, ps.h_desc.data(), np * 32, hipMemcpyHostToDevice, s)); HIP_TRY(hipMemcpyAsync(m->curDesc.p, m->h_curDesc.data(), nc * 32, hipMemcpyHostToDevice, s));
+    if (reloc) { SIND_TRY(up(ps.angle, ps.h_angle, np, s)); SIND_TRY(up(m->curAng, m->h_curAng, nc, s)); } else { SIND_TRY(up(ps.normal, ps.h_normal, np * 3, s)); SIND_TRY(up(m->curUR, m->h_curUR, nc, s)); }
+    SIND_TRY(up(m->curXY, m->h_curXY, nc * 2, s)); SIND_TRY(up(m->curOct, m->h_curOct, nc, s));
+    SIND_TRY(up(m->gstart, m->h_gstart, (size_t)B * 3073, s)); SIND_TRY(up(m->gidx, m->h_gidx, nc, s)); SIND_TRY(up(m->curTaken, m->h_curTaken, nc, s));
+    HIP_TRY(hipMemsetAsync(ps.nToMatch.p, 0, (size_t)B * 4, s));
+    sind::LocalArrays a{ps.pose.p, ps.nPts.p, m->nCur.p, ps.x3Dw.p, ps.normal.p, ps.maxDist.p, ps.minDist.p, ps.flags.p, ps.angle.p, ps.desc.p, m->curXY.p, m->curOct.p, m->curAng.p, m->curUR.p,
+                        m->curDesc.p, m->gstart.p, m->gidx.p, m->curTaken.p, ps.inView.p, ps.projXYR.p, ps.level.p, ps.viewCos.p, ps.nToMatch.p, ps.choice.p, m->minOwner.p, m->curPack.p, m->matchOfCur.p,
+                        m->nmatches.p, m->rounds.p};
+    SIND_TRY(sind::launch_project_points(p, a, B, reloc, s));
+    SIND_TRY(sind::launch_search_points(p, a, B, reloc, s));
+    if (wantFrustum) {
+        HIP_TRY(hipMemcpyAsync(ps.h_inView.data(), ps.inView.p, np, hipMemcpyDeviceToHost, s)); HIP_TRY(hipMemcpyAsync(ps.h_projXYR.data(), ps.projXYR.p, np * 12, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ps.h_level.data(), ps.level.p, np * 4, hipMemcpyDeviceToHost, s)); HIP_TRY(hipMemcpyAsync(ps.h_viewCos.data(), ps.viewCos.p, np * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipMemcpyAsync(ps.h_nToMatch.data(), ps.nToMatch.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(m->h_match.data(), m->matchOfCur.p, nc * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(m->h_nm.data(), m->nmatches.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(m->h_rounds.data(), m->rounds.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    m->last_rounds = 0;
+    for (int b = 0; b < B; b++) {
+        const PointsFrame& q = fr[b]; const size_t o = (size_t)b * cp, n = (size_t)q.n_points;
+        if (q.in_view) cpy(q.in_view, &ps.h_inView[o], n); if (q.proj_xyr) cpy(q.proj_xyr, &ps.h_projXYR[o * 3], n * 12);
+        if (q.level) cpy(q.level, &ps.h_level[o], n * 4); if (q.view_cos) cpy(q.view_cos, &ps.h_viewCos[o], n * 4);
+        if (q.n_to_match) *q.n_to_match = ps.h_nToMatch[b];
+        cpy(q.match_of_cur, &m->h_match[(size_t)b * cc], (size_t)q.n_cur * 4); *q.nmatches = m->h_nm[b];
+        m->last_rounds = std::max(m->last_rounds, m->h_rounds[b]);
+    }
+    return SIND_OK;
+}
+
+static sind::LocalParams local_params(const sind_match* m, float th) {
+    sind::LocalParams p{}; const sind::MatchParams& c = m->prm;
+    p.fx = c.fx; p.fy = c.fy; p.cx = c.cx; p.cy = c.cy; p.bf = c.bf; std::memcpy(p.bounds, c.bounds, sizeof(p.bounds)); std::memcpy(p.scale, c.scale, sizeof(p.scale));
+    p.nlevels = c.nlevels; p.capCur = c.capCur; p.th = th;
+    return p;
+}
+
+extern "C" {
+
+int sind_match_reserve_map_points(sind_match* m, int cap_points) {
+    if (!m || cap_points < 1) { sind_set_error("sind_match_reserve_map_points: bad arguments"); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return m->local.reserve((size_t)m->maxB, cap_points);
+}
+
+int sind_match_local_map(sind_match* m, const sind_match_local* frames, int B, float th, float nnratio, float viewing_cos_limit) {
+    if (!m || !frames || B < 1 || B > m->maxB || !(th > 0)) { sind_set_error("sind_match_local_map: bad arguments (B=%d, max %d)", B, m ? m->maxB : 0); return SIND_E_ARG; }
+    if (!m->local.cap) { sind_set_error("sind_match_local_map: call sind_match_reserve_map_points first"); return SIND_E_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    sind::LocalParams p = local_params(m, th); p.nnratio = nnratio; p.viewCosLimit = viewing_cos_limit;
+    std::vector<PointsFrame> fr(B);
+    for (int b = 0; b < B; b++) {
+        const sind_match_local& q = frames[b];
+        fr[b] = PointsFrame{q.Tcw, q.n_points, q.x3Dw, q.normal, q.max_dist, q.min_dist, q.flags, nullptr, q.desc, q.n_cur, q.cur_un_xy, q.cur_octave, nullptr, q.cur_u_right, q.cur_desc,
+                            q.grid_start, q.grid_idx, q.cur_taken, q.in_view, q.proj_xyr, q.level, q.view_cos, q.n_to_match, q.match_of_cur, q.nmatches};
+    }
+    return run_points(m, m->local, fr, p, 0, "sind_match_local_map");
+}
+
+int sind_match_by_projection_kf(sind_match* m, const sind_match_reloc* frames, int B, float th, int orb_dist, int check_orientation) {
+    if (!m || !frames || B < 1 || B > m->maxB || !(th > 0)) { sind_set_error("sind_match_by_projection_kf: bad arguments (B=%d, max %d)", B, m ? m->maxB : 0); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(m->device));
+    if (!m->reloc.cap) SIND_TRY(m->reloc.reserve((size_t)m->maxB, m->prm.capLast));
+    sind::LocalParams p = local_params(m, th); p.orbDist = orb_dist; p.checkOrientation = check_orientation ? 1 : 0;
+    std::vector<PointsFrame> fr(B);
+    for (int b = 0; b < B; b++) {
+        const sind_match_reloc& q = frames[b];
+        fr[b] = PointsFrame{q.Tcw, q.n_points, q.x3Dw, nullptr, q.max_dist, q.min_dist, q.valid, q.kf_angle, q.desc, q.n_cur, q.cur_un_xy, q.cur_octave, q.cur_angle, nullptr, q.cur_desc,
+                            q.grid_start, q.grid_idx, q.cur_taken, nullptr, nullptr, nullptr, nullptr, nullptr, q.match_of_cur, q.nmatches};
+    }
+    return run_points(m, m->reloc, fr, p, 1, "sind_match_by_projection_kf");
+}
 
 }  // extern "C"

@@ -1,0 +1,66 @@
+// Device functions shared by the projection searches (match_kernels.hip, match_local.hip): DescriptorDistance
+// (reference src/ORBmatcher.cc:1647-1665), and the tail every search with an orientation check ends on -- assignments ->
+// CurrentFrame.mvpMapPoints (the later point wins), rotation histogram, ComputeThreeMaxima (:1601-1642), removal.
+#pragma once
+#include "common.hpp"
+
+namespace sind {
+
+#define MT_NT 1024
+#define HISTO_LENGTH 30
+
+struct MatchTailShared { int hist[HISTO_LENGTH], keep[HISTO_LENGTH], nmatch; };
+
+// x3Dc = Rcw * x3Dw + tcw, Tcw = rows 0..2 of the 4x4 pose.  cv::gemm small-matrix path: FP32 row product, FP64 alpha/beta.
+__device__ __forceinline__ void d_to_camera(const float* Tcw, const float* X, float* xc) {
+    for (int k = 0; k < 3; k++) {
+        const float t = Tcw[4 * k] * X[0] + Tcw[4 * k + 1] * X[1] + Tcw[4 * k + 2] * X[2];
+        xc[k] = (float)((double)t * 1.0 + (double)Tcw[4 * k + 3] * 1.0);
+    }
+}
+
+__device__ __forceinline__ int d_hamming(const uint32_t* a, const uint4 b0, const uint4 b1) {
+    const uint4 a0 = *(const uint4*)a, a1 = *(const uint4*)(a + 4);
+    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+
+// choice[i] = current keypoint chosen by point i (-1: none), final.  Called by all MT_NT threads of the workgroup; returns with
+// matchOfCur[0..nC) written and sh.nmatch = the function's return value (valid for every thread after the call).
+__device__ __forceinline__ void d_assign_and_check_orientation(MatchTailShared& sh, int t, int nL, int nC, const int* choice, int* matchOfCur, const float* lang, const float* cang,
+                                                               int checkOrientation) {
+    for (int c = t; c < nC; c += MT_NT) matchOfCur[c] = -1;
+    if (t < HISTO_LENGTH) sh.hist[t] = 0;
+    if (t == 0) sh.nmatch = 0;
+    __syncthreads();
+    const float factor = 1.0f / HISTO_LENGTH;
+    for (int i = t; i < nL; i += MT_NT) {
+        const int c = choice[i]; if (c < 0) continue;
+        atomicMax(&matchOfCur[c], i); atomicAdd(&sh.nmatch, 1);
+        if (checkOrientation) { float rot = lang[i] - cang[c]; if (rot < 0.0f) rot += 360.0f; int bin = (int)roundf(rot * factor); if (bin == HISTO_LENGTH) bin = 0; atomicAdd(&sh.hist[bin], 1); }
+    }
+    __syncthreads();
+    if (checkOrientation) {
+        if (t == 0) {
+            int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
+            for (int i = 0; i < HISTO_LENGTH; i++) {
+                const int s = sh.hist[i];
+                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+                else if (s > max3) { max3 = s; ind3 = i; }
+            }
+            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; } else if (max3 < 0.1f * (float)max1) ind3 = -1;
+            for (int i = 0; i < HISTO_LENGTH; i++) sh.keep[i] = (i == ind1 || i == ind2 || i == ind3);
+        }
+        __syncthreads();
+        for (int i = t; i < nL; i += MT_NT) {
+            const int c = choice[i]; if (c < 0) continue;
+            float rot = lang[i] - cang[c]; if (rot < 0.0f) rot += 360.0f; int bin = (int)roundf(rot * factor); if (bin == HISTO_LENGTH) bin = 0;
+            if (!sh.keep[bin]) { matchOfCur[c] = -2; atomicAdd(&sh.nmatch, -1); }           // -2 < every index: a removal always wins
+        }
+        __syncthreads();
+        for (int c = t; c < nC; c += MT_NT) if (matchOfCur[c] == -2) matchOfCur[c] = -1;
+    }
+    __syncthreads();
+}
+
+}  // namespace sind

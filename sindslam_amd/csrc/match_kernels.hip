@@ -9,11 +9,10 @@
 // result.  Real frames need 2-3 rounds.  The window search keeps the reference's traversal order (cells x-major, push_back order
 // inside a cell, strict '<' on the distance), so ties resolve identically.  Integer / bit work: v_bcnt popcounts, L2-resident.
 #include "match.hpp"
+#include "match_device.hpp"
 
 namespace sind {
 
-#define MT_NT 1024
-#define HISTO_LENGTH 30
 #define TH_HIGH 100
 
 struct Proj { float u, v, invzc, radius; int minL, maxL, ok; };
@@ -21,10 +20,7 @@ struct Proj { float u, v, invzc, radius; int minL, maxL, ok; };
 __device__ __forceinline__ Proj d_project(const MatchParams& p, const MatchPose& ps, const float* X, int oct) {
     Proj r; r.ok = 0;
     float xc[3];
-    for (int k = 0; k < 3; k++) {                                      // cv::gemm small-matrix path: FP32 row product, FP64 alpha/beta
-        const float t = ps.Tcw[4 * k] * X[0] + ps.Tcw[4 * k + 1] * X[1] + ps.Tcw[4 * k + 2] * X[2];
-        xc[k] = (float)((double)t * 1.0 + (double)ps.Tcw[4 * k + 3] * 1.0);
-    }
+    d_to_camera(ps.Tcw, X, xc);
     r.invzc = (float)(1.0 / xc[2]);
     if (r.invzc < 0) return r;
     r.u = p.fx * xc[0] * r.invzc + p.cx; r.v = p.fy * xc[1] * r.invzc + p.cy;
@@ -35,13 +31,8 @@ __device__ __forceinline__ Proj d_project(const MatchParams& p, const MatchPose&
     r.ok = 1; return r;
 }
 
-__device__ __forceinline__ int d_hamming(const uint32_t* a, const uint4 b0, const uint4 b1) {
-    const uint4 a0 = *(const uint4*)a, a1 = *(const uint4*)(a + 4);
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
 __global__ __launch_bounds__(MT_NT) void k_search_by_projection(MatchParams p, MatchArrays a) {
-    __shared__ int changed, hist[HISTO_LENGTH], keep[HISTO_LENGTH], nmatch;
+    __shared__ int changed; __shared__ MatchTailShared tail;
     const int b = blockIdx.x, t = threadIdx.x, nL = min(a.nLast[b], p.capLast), nC = min(a.nCur[b], p.capCur);
     const MatchPose ps = a.pose[b];
     const float* x3Dw = a.x3Dw + (size_t)b * p.capLast * 3; const uint8_t* lflags = a.lastFlags + (size_t)b * p.capLast; const int* loct = a.lastOctave + (size_t)b * p.capLast;
@@ -102,40 +93,8 @@ __global__ __launch_bounds__(MT_NT) void k_search_by_projection(MatchParams p, M
         if (!ch || round > nL) break;
     }
     // assignments -> CurrentFrame.mvpMapPoints (the later point wins), rotation histogram, three maxima, removal
-    for (int c = t; c < nC; c += MT_NT) matchOfCur[c] = -1;
-    if (t < HISTO_LENGTH) hist[t] = 0;
-    if (t == 0) nmatch = 0;
-    __syncthreads();
-    const float factor = 1.0f / HISTO_LENGTH;
-    for (int i = t; i < nL; i += MT_NT) {
-        const int c = choice[i]; if (c < 0) continue;
-        atomicMax(&matchOfCur[c], i); atomicAdd(&nmatch, 1);
-        if (p.checkOrientation) { float rot = lang[i] - cang[c]; if (rot < 0.0f) rot += 360.0f; int bin = (int)roundf(rot * factor); if (bin == HISTO_LENGTH) bin = 0; atomicAdd(&hist[bin], 1); }
-    }
-    __syncthreads();
-    if (p.checkOrientation) {
-        if (t == 0) {
-            int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < HISTO_LENGTH; i++) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; } else if (max3 < 0.1f * (float)max1) ind3 = -1;
-            for (int i = 0; i < HISTO_LENGTH; i++) keep[i] = (i == ind1 || i == ind2 || i == ind3);
-        }
-        __syncthreads();
-        for (int i = t; i < nL; i += MT_NT) {
-            const int c = choice[i]; if (c < 0) continue;
-            float rot = lang[i] - cang[c]; if (rot < 0.0f) rot += 360.0f; int bin = (int)roundf(rot * factor); if (bin == HISTO_LENGTH) bin = 0;
-            if (!keep[bin]) { matchOfCur[c] = -2; atomicAdd(&nmatch, -1); }              // -2 < every index: a removal always wins
-        }
-        __syncthreads();
-        for (int c = t; c < nC; c += MT_NT) if (matchOfCur[c] == -2) matchOfCur[c] = -1;
-    }
-    __syncthreads();
-    if (t == 0) { a.nmatches[b] = nmatch; a.rounds[b] = round; }
+    d_assign_and_check_orientation(tail, t, nL, nC, choice, matchOfCur, lang, cang, p.checkOrientation);
+    if (t == 0) { a.nmatches[b] = tail.nmatch; a.rounds[b] = round; }
 }
 
 int launch_search_by_projection(const MatchParams& p, const MatchArrays& a, int B, hipStream_t s) {
