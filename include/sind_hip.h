@@ -406,6 +406,82 @@ typedef struct sind_match_reloc {
 } sind_match_reloc;
 int sind_match_by_projection_kf(sind_match* m, const sind_match_reloc* frames, int B, float th, int orb_dist, int check_orientation);
 
+/* Vocabulary transform: the feature-vector half of Frame::ComputeBoW / KeyFrame::ComputeBoW, for B frames at once.  Replaces
+ *   void TemplatedVocabulary::transform(features, BowVector& v, FeatureVector& fv, int levelsup)        Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1194
+ *   void TemplatedVocabulary::transform(feature, WordId&, WordValue&, NodeId* nid, int levelsup)        :1218-1259, with FORB::distance (Hamming)
+ * sind_voc holds one vocabulary tree on the device; the caller flattens DBoW2's object graph once (sind_voc_tree):
+ *   n_nodes = m_nodes.size() (node 0 is the root), levels = m_L, child_start / child = CSR over m_nodes[i].children in the vector's own order,
+ *   desc = m_nodes[i].descriptor (32 B per node, row 0 is not read), word_id = m_nodes[i].word_id for a leaf and -1 for an inner node,
+ *   weight = m_nodes[i].weight (read for leaves only).
+ * sind_voc_create checks that this is a tree rooted at node 0 with at least one child under the root (indices in range, every other node the child of exactly
+ * one node and reachable from the root, every childless node with word_id >= 0) and returns SIND_E_ARG otherwise.
+ * sind_voc_transform, per descriptor: the descent from the root takes at every level the child of smallest Hamming distance, the first one on equal distance,
+ * and stops at a childless node.  word_id = that leaf's word.  node_id = the node the path passed at level (levels - levelsup), the reference's nid
+ * (ORB-SLAM2 passes levelsup = 4); 0 if levels - levelsup <= 0; the leaf's own id if the path ends above that level (the reference leaves nid uninitialised
+ * there); -1 if the word is stopped, !(weight > 0): such a feature is not in mFeatVec (:1157-1161).  DBoW2 fills mFeatVec in feature order
+ * (FeatureVector.cpp:31-45), so node_id per keypoint determines it: nodes ascend, indices ascend inside a node.  The BowVector (word weights, normalisation) is
+ * left to the caller, who gets word_id for it.
+ *   desc[b] = n[b] x 32 bytes (host); node_id[b], word_id[b] = n[b] ints (host); node_id, word_id and their entries may be NULL.
+ * Errors: n[b] > cap or B > max_batch -> SIND_E_CAPACITY, a NULL desc[b] with n[b] > 0 -> SIND_E_ARG; nothing is launched, the outputs are untouched.
+ */
+typedef struct sind_voc sind_voc;
+typedef struct sind_voc_tree {
+    int n_nodes, levels;
+    const int* child_start;       /* [n_nodes + 1] */
+    const int* child;             /* [n_nodes - 1] */
+    const uint8_t* desc;          /* [n_nodes][32] */
+    const int* word_id;           /* [n_nodes] */
+    const double* weight;         /* [n_nodes] */
+} sind_voc_tree;
+int sind_voc_create(const sind_voc_tree* tree, int cap, int max_batch, int device, sind_voc** out);
+int sind_voc_destroy(sind_voc* v);
+int sind_voc_transform(sind_voc* v, const uint8_t* const* desc, const int* n, int B, int levelsup, int* const* node_id, int* const* word_id);
+
+/* Search by vocabulary node.  Replaces, for B (KeyFrame, Frame) pairs at once,
+ *   int ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches)          src/ORBmatcher.cc:159-288
+ * (Tracking::TrackReferenceKeyFrame; Tracking::Relocalization runs it once per candidate key frame: one frame against many key frames is one call).
+ * Runs on the sind_match handle: at most min(cap_last, 4096) key-frame keypoints and min(cap_cur, 4096) frame keypoints per pair.
+ *   key frame, per keypoint i:  kf_node = node id of pKF->mFeatVec as sind_voc_transform returns it (-1: not in the feature vector),
+ *       kf_valid = pMP && !pMP->isBad() for pMP = pKF->GetMapPointMatches()[i], kf_angle = pKF->mvKeysUn[i].angle,
+ *       kf_desc = row i of pKF->mDescriptors (the key frame's own descriptor, not the map point's)
+ *   frame, per keypoint:  cur_node = node id of F.mFeatVec, cur_angle = F.mvKeys[i].angle, cur_desc = row i of F.mDescriptors
+ * Output: match_of_cur[iF] = index i of the key-frame keypoint whose MapPoint the reference leaves in vpMapPointMatches[iF] (-1: none, or removed by the
+ * orientation check); *nmatches = the function's return value.  nnratio = ORBmatcher::mfNNratio (0.7 in TrackReferenceKeyFrame, 0.75 in Relocalization),
+ * check_orientation = mbCheckOrientation.  TH_LOW = 50, the ratio test in FP32, 30 histogram bins: the reference's.
+ * The result is that of the reference's order (nodes ascending, key-frame entries ascending inside a node, frame keypoints already matched skipped).
+ * Errors: a pair over capacity -> SIND_E_CAPACITY, a NULL array with a non-zero count or a node id below -1 -> SIND_E_ARG; nothing is launched and the
+ * outputs are untouched.  A count of 0 is valid and gives *nmatches = 0.
+ */
+typedef struct sind_match_bow {
+    int n_kf;  const int* kf_node;  const uint8_t* kf_valid;  const float* kf_angle;  const uint8_t* kf_desc;
+    int n_cur; const int* cur_node; const float* cur_angle;   const uint8_t* cur_desc;
+    int* match_of_cur; int* nmatches;                                                     /* outputs (host) */
+} sind_match_bow;
+int sind_match_by_bow(sind_match* m, const sind_match_bow* pairs, int B, float nnratio, int check_orientation);
+
+/* Search for triangulation.  Replaces, for B (pKF1, pKF2) pairs at once (LocalMapping::CreateNewMapPoints, one key frame against its neighbours),
+ *   int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t, size_t>>& vMatchedPairs, bool bOnlyStereo)
+ *                                                                                                      src/ORBmatcher.cc:657-823
+ *   bool ORBmatcher::CheckDistEpipolarLine(kp1, kp2, F12, pKF2)                                        :140-157
+ * fx fy cx cy and scale_factors (mvScaleFactors; mvLevelSigma2[l] = scale[l] * scale[l] in FP32) are the handle's.  Capacities as for sind_match_by_bow
+ * (pKF1: cap_last, pKF2: cap_cur).
+ *   Tcw2 = pKF2's pose (4x4 row-major, rows 0..2 are read: GetRotation(), GetTranslation()), Cw1 = pKF1->GetCameraCenter() (3), F12 (3x3 row-major)
+ *   per keypoint of pKF1:  node1 = node id of mFeatVec, has_mp1 = pKF1->GetMapPoint(idx1) != NULL, un_xy1 / angle1 = mvKeysUn, u_right1 = mvuRight,
+ *       desc1 = mDescriptors rows
+ *   per keypoint of pKF2:  node2, has_mp2, un_xy2 / octave2 / angle2 = mvKeysUn, u_right2, desc2 likewise
+ * Output: match12[idx1] = vMatches12[idx1] after the orientation check (idx2 or -1), from which vMatchedPairs is the list of (idx1, match12[idx1]) with
+ * match12[idx1] >= 0 in ascending idx1; *nmatches = the function's return value.  only_stereo = bOnlyStereo, check_orientation = mbCheckOrientation.
+ * The epipole, the epipolar line and its distance are FP32 in the reference's order of operations; the last comparison is in FP64 (csrc/match_bow.hip).
+ * Errors as for sind_match_by_bow, and an octave2 outside [0, nlevels) -> SIND_E_ARG.
+ */
+typedef struct sind_match_tri {
+    const float* Tcw2; const float* Cw1; const float* F12;
+    int n1; const int* node1; const uint8_t* has_mp1; const float* un_xy1; const float* angle1; const float* u_right1; const uint8_t* desc1;
+    int n2; const int* node2; const uint8_t* has_mp2; const float* un_xy2; const int* octave2; const float* angle2; const float* u_right2; const uint8_t* desc2;
+    int* match12; int* nmatches;                                                          /* outputs (host): match12[idx1] = idx2 or -1 */
+} sind_match_tri;
+int sind_match_for_triangulation(sind_match* m, const sind_match_tri* pairs, int B, int only_stereo, int check_orientation);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of
  *   generatePointCloud(imgRGB, imgDepth, imgDepthLast, imgDynaMask, imgDynaMaskLast, imgLabel, poseRelative, Twc)

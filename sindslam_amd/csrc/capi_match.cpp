@@ -31,6 +31,20 @@ struct sind_match {
             cap = c; return SIND_OK;
         }
     } local, reloc;
+    // node ids, sort scratch and the extra key-frame arrays of sind_match_by_bow / sind_match_for_triangulation (match_bow.hip), on first use
+    struct BowSide {
+        bool ready = false;
+        DevBuf<int> nodeA, nodeB, segStart, nSeg, nValid; DevBuf<int2> sortedA, sortedB; DevBuf<float> lastXY, lastUR; DevBuf<sind::TriPose> pose;
+        std::vector<int> h_nodeA, h_nodeB, h_match12; std::vector<float> h_lastXY, h_lastUR; std::vector<sind::TriPose> h_pose;
+        int reserve(size_t B, size_t cl, size_t cc) {
+            if (ready) return SIND_OK;
+            int r = SIND_OK;
+            if ((r = nodeA.alloc(B * cl)) || (r = nodeB.alloc(B * cc)) || (r = segStart.alloc(B * cl)) || (r = nSeg.alloc(B)) || (r = nValid.alloc(2 * B)) || (r = sortedA.alloc(B * cl)) ||
+                (r = sortedB.alloc(B * cc)) || (r = lastXY.alloc(B * cl * 2)) || (r = lastUR.alloc(B * cl)) || (r = pose.alloc(B))) return r;
+            h_nodeA.resize(B * cl); h_nodeB.resize(B * cc); h_match12.resize(B * cl); h_lastXY.resize(B * cl * 2); h_lastUR.resize(B * cl); h_pose.resize(B);
+            ready = true; return SIND_OK;
+        }
+    } bow;
 };
 
 // CurrentFrame / LastFrame pose algebra of ORBmatcher.cc:1338-1349 (cv::gemm semantics: A*b+c without transposition = FP32 row
@@ -241,6 +255,108 @@ int sind_match_by_projection_kf(sind_match* m, const sind_match_reloc* frames, i
                             q.grid_start, q.grid_idx, q.cur_taken, nullptr, nullptr, nullptr, nullptr, nullptr, q.match_of_cur, q.nmatches};
     }
     return run_points(m, m->reloc, fr, p, 1, "sind_match_by_projection_kf");
+}
+
+}  // extern "C"
+
+// ---- vocabulary-guided searches (match_bow.hip) ----
+static int sort_length(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+
+static int check_nodes(const int* node, int n) { for (int i = 0; i < n; i++) if (node[i] < -1) return 0; return 1; }
+
+static sind::BowParams bow_params(const sind_match* m, int maxN) {
+    sind::BowParams p{}; const sind::MatchParams& c = m->prm;
+    p.fx = c.fx; p.fy = c.fy; p.cx = c.cx; p.cy = c.cy; std::memcpy(p.scale, c.scale, sizeof(p.scale)); p.capA = c.capLast; p.capB = c.capCur; p.sortLen = sort_length(maxN);
+    return p;
+}
+
+static sind::BowArrays bow_arrays(sind_match* m) {
+    sind_match::BowSide& w = m->bow;
+    return sind::BowArrays{m->nLast.p, m->nCur.p, w.nodeA.p, w.nodeB.p, m->lastFlags.p, m->lastAng.p, m->lastDesc.p, m->curAng.p, m->curDesc.p, w.pose.p, w.lastXY.p, w.lastUR.p, m->curTaken.p,
+                           m->curXY.p, m->curOct.p, m->curUR.p, w.sortedA.p, w.sortedB.p, w.segStart.p, w.nSeg.p, w.nValid.p, m->choice.p, m->matchOfCur.p, m->nmatches.p};
+}
+
+extern "C" {
+
+int sind_match_by_bow(sind_match* m, const sind_match_bow* pairs, int B, float nnratio, int check_orientation) {
+    const char* who = "sind_match_by_bow";
+    if (!m || !pairs || B < 1 || B > m->maxB) { sind_set_error("%s: bad arguments (B=%d, max %d)", who, B, m ? m->maxB : 0); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(m->device));
+    const int cl = std::min(m->prm.capLast, BOW_MAX_KEYS), cc = std::min(m->prm.capCur, BOW_MAX_KEYS);
+    int maxN = 1;
+    for (int b = 0; b < B; b++) {
+        const sind_match_bow& q = pairs[b];
+        if (q.n_kf < 0 || q.n_kf > cl || q.n_cur < 0 || q.n_cur > cc) { sind_set_error("%s: pair %d has %d / %d keypoints, capacity %d / %d", who, b, q.n_kf, q.n_cur, cl, cc); return SIND_E_CAPACITY; }
+        if (!q.nmatches || (q.n_kf && (!q.kf_node || !q.kf_valid || !q.kf_angle || !q.kf_desc)) || (q.n_cur && (!q.cur_node || !q.cur_angle || !q.cur_desc || !q.match_of_cur))) {
+            sind_set_error("%s: null array in pair %d", who, b); return SIND_E_ARG;
+        }
+        if (!check_nodes(q.kf_node, q.n_kf) || !check_nodes(q.cur_node, q.n_cur)) { sind_set_error("%s: node id below -1 in pair %d", who, b); return SIND_E_ARG; }
+        maxN = std::max(maxN, std::max(q.n_kf, q.n_cur));
+    }
+    const size_t sl = m->prm.capLast, sc = m->prm.capCur;
+    SIND_TRY(m->bow.reserve((size_t)m->maxB, sl, sc));
+    sind_match::BowSide& w = m->bow;
+    for (int b = 0; b < B; b++) {
+        const sind_match_bow& q = pairs[b]; const size_t oa = b * sl, ob = b * sc, na = (size_t)q.n_kf, nb = (size_t)q.n_cur;
+        m->h_nLast[b] = q.n_kf; m->h_nCur[b] = q.n_cur;
+        cpy(&w.h_nodeA[oa], q.kf_node, na * 4); for (size_t i = 0; i < na; i++) m->h_lastFlags[oa + i] = q.kf_valid[i] ? 1 : 0;
+        cpy(&m->h_lastAng[oa], q.kf_angle, na * 4); cpy(&m->h_lastDesc[oa * 32], q.kf_desc, na * 32);
+        cpy(&w.h_nodeB[ob], q.cur_node, nb * 4); cpy(&m->h_curAng[ob], q.cur_angle, nb * 4); cpy(&m->h_curDesc[ob * 32], q.cur_desc, nb * 32);
+    }
+    hipStream_t s = m->stream; const size_t nl = (size_t)B * sl, nc = (size_t)B * sc;
+    SIND_TRY(up(m->nLast, m->h_nLast, B, s)); SIND_TRY(up(m->nCur, m->h_nCur, B, s)); SIND_TRY(up(w.nodeA, w.h_nodeA, nl, s)); SIND_TRY(up(w.nodeB, w.h_nodeB, nc, s));
+    SIND_TRY(up(m->lastFlags, m->h_lastFlags, nl, s)); SIND_TRY(up(m->lastAng, m->h_lastAng, nl, s)); SIND_TRY(up(m->curAng, m->h_curAng, nc, s));
+    HIP_TRY(hipMemcpyAsync(m->lastDesc.p, m->h_lastDesc.data(), nl * 32, hipMemcpyHostToDevice, s)); HIP_TRY(hipMemcpyAsync(m->curDesc.p, m->h_curDesc.data(), nc * 32, hipMemcpyHostToDevice, s));
+    sind::BowParams p = bow_params(m, maxN); p.nnratio = nnratio; p.checkOrientation = check_orientation ? 1 : 0;
+    SIND_TRY(sind::launch_match_by_bow(p, bow_arrays(m), B, s));
+    HIP_TRY(hipMemcpyAsync(m->h_match.data(), m->matchOfCur.p, nc * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(m->h_nm.data(), m->nmatches.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) { cpy(pairs[b].match_of_cur, &m->h_match[b * sc], (size_t)pairs[b].n_cur * 4); *pairs[b].nmatches = m->h_nm[b]; }
+    return SIND_OK;
+}
+
+int sind_match_for_triangulation(sind_match* m, const sind_match_tri* pairs, int B, int only_stereo, int check_orientation) {
+    const char* who = "sind_match_for_triangulation";
+    if (!m || !pairs || B < 1 || B > m->maxB) { sind_set_error("%s: bad arguments (B=%d, max %d)", who, B, m ? m->maxB : 0); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(m->device));
+    const int cl = std::min(m->prm.capLast, BOW_MAX_KEYS), cc = std::min(m->prm.capCur, BOW_MAX_KEYS);
+    int maxN = 1;
+    for (int b = 0; b < B; b++) {
+        const sind_match_tri& q = pairs[b];
+        if (q.n1 < 0 || q.n1 > cl || q.n2 < 0 || q.n2 > cc) { sind_set_error("%s: pair %d has %d / %d keypoints, capacity %d / %d", who, b, q.n1, q.n2, cl, cc); return SIND_E_CAPACITY; }
+        if (!q.Tcw2 || !q.Cw1 || !q.F12 || !q.nmatches || (q.n1 && (!q.node1 || !q.has_mp1 || !q.un_xy1 || !q.angle1 || !q.u_right1 || !q.desc1 || !q.match12)) ||
+            (q.n2 && (!q.node2 || !q.has_mp2 || !q.un_xy2 || !q.octave2 || !q.angle2 || !q.u_right2 || !q.desc2))) { sind_set_error("%s: null array in pair %d", who, b); return SIND_E_ARG; }
+        if (!check_nodes(q.node1, q.n1) || !check_nodes(q.node2, q.n2)) { sind_set_error("%s: node id below -1 in pair %d", who, b); return SIND_E_ARG; }
+        for (int i = 0; i < q.n2; i++) if (q.octave2[i] < 0 || q.octave2[i] >= m->prm.nlevels) { sind_set_error("%s: octave %d outside [0,%d)", who, q.octave2[i], m->prm.nlevels); return SIND_E_ARG; }
+        maxN = std::max(maxN, std::max(q.n1, q.n2));
+    }
+    const size_t sl = m->prm.capLast, sc = m->prm.capCur;
+    SIND_TRY(m->bow.reserve((size_t)m->maxB, sl, sc));
+    sind_match::BowSide& w = m->bow;
+    for (int b = 0; b < B; b++) {
+        const sind_match_tri& q = pairs[b]; const size_t oa = b * sl, ob = b * sc, na = (size_t)q.n1, nb = (size_t)q.n2;
+        sind::TriPose& ps = w.h_pose[b]; cpy(ps.Tcw2, q.Tcw2, sizeof(ps.Tcw2)); cpy(ps.Cw1, q.Cw1, sizeof(ps.Cw1)); cpy(ps.F12, q.F12, sizeof(ps.F12));
+        m->h_nLast[b] = q.n1; m->h_nCur[b] = q.n2;
+        cpy(&w.h_nodeA[oa], q.node1, na * 4); for (size_t i = 0; i < na; i++) m->h_lastFlags[oa + i] = q.has_mp1[i] ? 1 : 0;
+        cpy(&w.h_lastXY[oa * 2], q.un_xy1, na * 8); cpy(&m->h_lastAng[oa], q.angle1, na * 4); cpy(&w.h_lastUR[oa], q.u_right1, na * 4); cpy(&m->h_lastDesc[oa * 32], q.desc1, na * 32);
+        cpy(&w.h_nodeB[ob], q.node2, nb * 4); for (size_t i = 0; i < nb; i++) m->h_curTaken[ob + i] = q.has_mp2[i] ? 1 : 0;
+        cpy(&m->h_curXY[ob * 2], q.un_xy2, nb * 8); cpy(&m->h_curOct[ob], q.octave2, nb * 4); cpy(&m->h_curAng[ob], q.angle2, nb * 4); cpy(&m->h_curUR[ob], q.u_right2, nb * 4);
+        cpy(&m->h_curDesc[ob * 32], q.desc2, nb * 32);
+    }
+    hipStream_t s = m->stream; const size_t nl = (size_t)B * sl, nc = (size_t)B * sc;
+    SIND_TRY(up(w.pose, w.h_pose, B, s)); SIND_TRY(up(m->nLast, m->h_nLast, B, s)); SIND_TRY(up(m->nCur, m->h_nCur, B, s)); SIND_TRY(up(w.nodeA, w.h_nodeA, nl, s)); SIND_TRY(up(w.nodeB, w.h_nodeB, nc, s));
+    SIND_TRY(up(m->lastFlags, m->h_lastFlags, nl, s)); SIND_TRY(up(w.lastXY, w.h_lastXY, nl * 2, s)); SIND_TRY(up(m->lastAng, m->h_lastAng, nl, s)); SIND_TRY(up(w.lastUR, w.h_lastUR, nl, s));
+    SIND_TRY(up(m->curTaken, m->h_curTaken, nc, s)); SIND_TRY(up(m->curXY, m->h_curXY, nc * 2, s)); SIND_TRY(up(m->curOct, m->h_curOct, nc, s)); SIND_TRY(up(m->curAng, m->h_curAng, nc, s));
+    SIND_TRY(up(m->curUR, m->h_curUR, nc, s));
+    HIP_TRY(hipMemcpyAsync(m->lastDesc.p, m->h_lastDesc.data(), nl * 32, hipMemcpyHostToDevice, s)); HIP_TRY(hipMemcpyAsync(m->curDesc.p, m->h_curDesc.data(), nc * 32, hipMemcpyHostToDevice, s));
+    sind::BowParams p = bow_params(m, maxN); p.onlyStereo = only_stereo ? 1 : 0; p.checkOrientation = check_orientation ? 1 : 0;
+    SIND_TRY(sind::launch_match_for_triangulation(p, bow_arrays(m), B, s));
+    HIP_TRY(hipMemcpyAsync(w.h_match12.data(), m->choice.p, nl * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(m->h_nm.data(), m->nmatches.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) { cpy(pairs[b].match12, &w.h_match12[b * sl], (size_t)pairs[b].n1 * 4); *pairs[b].nmatches = m->h_nm[b]; }
+    return SIND_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,97 @@
+// C ABI: vocabulary transform (include/sind_hip.h, "sind_voc_*").
+#include <algorithm>
+#include <cstring>
+#include <vector>
+#include "../../include/sind_hip.h"
+#include "match.hpp"
+
+struct sind_voc {
+    int device = 0, cap = 0, maxB = 0, levels = 0, nNodes = 0; hipStream_t stream = nullptr;
+    DevBuf<int> childStart, child, wordId, n, outNode, outWord; DevBuf<uint32_t> nodeDesc, desc; DevBuf<uint8_t> stopped;
+    std::vector<int> h_n, h_node, h_word; std::vector<uint8_t> h_desc;
+};
+
+// a tree rooted at node 0: CSR in range, every node but the root the child of exactly one node and reachable from the root, every leaf with a word
+static const char* tree_fault(const sind_voc_tree* t) {
+    const int n = t->n_nodes;
+    if (n < 2 || t->levels < 0) return "fewer than two nodes or negative levels";        // the reference's descent reads the root's first child unconditionally
+    if (!t->child_start || !t->child || !t->desc || !t->word_id || !t->weight) return "null array";
+    if (t->child_start[0] != 0 || t->child_start[n] != n - 1) return "child_start does not span n_nodes - 1 children";
+    for (int i = 0; i < n; i++) if (t->child_start[i + 1] < t->child_start[i]) return "child_start decreases";
+    std::vector<uint8_t> seen(n, 0);
+    for (int j = 0; j < n - 1; j++) {
+        const int c = t->child[j];
+        if (c < 1 || c >= n) return "child index out of range (the root is nobody's child)";
+        if (seen[c]) return "node with two parents";
+        seen[c] = 1;
+    }
+    std::vector<int> stack{0}; int reached = 0;
+    while (!stack.empty()) {
+        const int i = stack.back(); stack.pop_back(); reached++;
+        for (int j = t->child_start[i]; j < t->child_start[i + 1]; j++) stack.push_back(t->child[j]);
+    }
+    if (reached != n) return "nodes not reachable from the root";
+    for (int i = 0; i < n; i++) if (t->child_start[i] == t->child_start[i + 1] && t->word_id[i] < 0) return "leaf without a word";
+    return nullptr;
+}
+
+extern "C" {
+
+int sind_voc_create(const sind_voc_tree* tree, int cap, int max_batch, int device, sind_voc** out) {
+    if (!tree || !out || cap < 1 || max_batch < 1) { sind_set_error("sind_voc_create: bad arguments"); return SIND_E_ARG; }
+    if (const char* why = tree_fault(tree)) { sind_set_error("sind_voc_create: not a vocabulary tree: %s", why); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(device));
+    sind_voc* v = new sind_voc(); v->device = device; v->cap = cap; v->maxB = max_batch; v->levels = tree->levels; v->nNodes = tree->n_nodes;
+    const size_t n = tree->n_nodes, nd = (size_t)max_batch * cap;
+    std::vector<uint8_t> stopped(n);
+    for (size_t i = 0; i < n; i++) stopped[i] = !(tree->weight[i] > 0);                   // TemplatedVocabulary.h:1157 "if(w > 0) // not stopped"
+    int r = SIND_OK;
+    if ((r = v->childStart.alloc(n + 1)) || (r = v->child.alloc(n - 1)) || (r = v->wordId.alloc(n)) || (r = v->nodeDesc.alloc(n * 8)) || (r = v->stopped.alloc(n)) || (r = v->n.alloc(max_batch)) ||
+        (r = v->outNode.alloc(nd)) || (r = v->outWord.alloc(nd)) || (r = v->desc.alloc(nd * 8))) { delete v; return r; }
+    if (hipMemcpy(v->childStart.p, tree->child_start, (n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(v->child.p, tree->child, (n - 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v->wordId.p, tree->word_id, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(v->nodeDesc.p, tree->desc, n * 32, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v->stopped.p, stopped.data(), n, hipMemcpyHostToDevice) != hipSuccess || hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess) {
+        delete v; sind_set_error("sind_voc_create: uploading the tree failed"); return SIND_E_HIP;
+    }
+    v->h_n.resize(max_batch); v->h_node.resize(nd); v->h_word.resize(nd); v->h_desc.resize(nd * 32);
+    *out = v; return SIND_OK;
+}
+
+int sind_voc_destroy(sind_voc* v) {
+    if (!v) return SIND_OK;
+    (void)hipSetDevice(v->device);
+    if (v->stream) (void)hipStreamSynchronize(v->stream);
+    hipStream_t s = v->stream; delete v; if (s) (void)hipStreamDestroy(s);
+    return SIND_OK;
+}
+
+int sind_voc_transform(sind_voc* v, const uint8_t* const* desc, const int* n, int B, int levelsup, int* const* node_id, int* const* word_id) {
+    if (!v || !desc || !n || B < 1) { sind_set_error("sind_voc_transform: bad arguments"); return SIND_E_ARG; }
+    if (B > v->maxB) { sind_set_error("sind_voc_transform: B=%d, max_batch %d", B, v->maxB); return SIND_E_CAPACITY; }
+    int maxN = 0;
+    for (int b = 0; b < B; b++) {
+        if (n[b] < 0 || (n[b] && !desc[b])) { sind_set_error("sind_voc_transform: null array or negative count in frame %d", b); return SIND_E_ARG; }
+        if (n[b] > v->cap) { sind_set_error("sind_voc_transform: frame %d has %d descriptors, capacity %d", b, n[b], v->cap); return SIND_E_CAPACITY; }
+        maxN = std::max(maxN, n[b]);
+    }
+    if (!maxN) return SIND_OK;
+    HIP_TRY(hipSetDevice(v->device));
+    const size_t cap = v->cap, nd = (size_t)B * cap;
+    for (int b = 0; b < B; b++) { v->h_n[b] = n[b]; if (n[b]) std::memcpy(&v->h_desc[b * cap * 32], desc[b], (size_t)n[b] * 32); }
+    hipStream_t s = v->stream;
+    HIP_TRY(hipMemcpyAsync(v->n.p, v->h_n.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(v->desc.p, v->h_desc.data(), nd * 32, hipMemcpyHostToDevice, s));
+    const sind::VocTree tr{v->nNodes, v->childStart.p, v->child.p, v->nodeDesc.p, v->wordId.p, v->stopped.p};
+    SIND_TRY(sind::launch_voc_transform(tr, v->desc.p, v->n.p, v->cap, maxN, B, v->levels - levelsup, v->outNode.p, v->outWord.p, s));
+    HIP_TRY(hipMemcpyAsync(v->h_node.data(), v->outNode.p, nd * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(v->h_word.data(), v->outWord.p, nd * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) {
+        if (!n[b]) continue;
+        if (node_id && node_id[b]) std::memcpy(node_id[b], &v->h_node[b * cap], (size_t)n[b] * 4);
+        if (word_id && word_id[b]) std::memcpy(word_id[b], &v->h_word[b * cap], (size_t)n[b] * 4);
+    }
+    return SIND_OK;
+}
+
+}  // extern "C"

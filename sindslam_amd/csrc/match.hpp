@@ -1,4 +1,5 @@
-// Projection matcher interface (reference src/ORBmatcher.cc:45-129, :1328-1470, :1472-1599); kernels in match_kernels.hip, match_local.hip.
+// Matcher interface: projection searches (reference src/ORBmatcher.cc:45-129, :1328-1470, :1472-1599; kernels in match_kernels.hip, match_local.hip) and
+// vocabulary-guided searches (:159-288, :657-823; match_bow.hip, bow_kernels.hip).
 #pragma once
 #include "common.hpp"
 
@@ -42,5 +43,29 @@ struct LocalArrays {                                              // device poin
 // reloc = 0: Frame::isInFrustum + SearchByProjection(F, vpMapPoints, th); reloc = 1: SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)
 int launch_project_points(const LocalParams& p, const LocalArrays& a, int B, int reloc, hipStream_t s);
 int launch_search_points(const LocalParams& p, const LocalArrays& a, int B, int reloc, hipStream_t s);
+
+// Vocabulary-guided searches (match_bow.hip): SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation.  Side A is the one whose entries act
+// (the key frame / pKF1, capacity capLast), side B the one searched (the frame / pKF2, capacity capCur).
+#define BOW_MAX_KEYS 4096                                         // keypoints per side one workgroup sorts in LDS
+struct BowParams {
+    float fx, fy, cx, cy, nnratio; float scale[16];
+    int capA, capB, sortLen /* power of two >= every count of the call */, checkOrientation, onlyStereo;
+};
+struct TriPose { float Tcw2[12]; float Cw1[3]; float F12[9]; };    // per pair: rows 0..2 of pKF2's pose, pKF1's camera centre, F12 row-major
+
+struct BowArrays {                                                // device pointers, dense [B][cap...]
+    const int* nA; const int* nB; const int* nodeA; const int* nodeB;
+    const uint8_t* flagsA /* by_bow: kf_valid; triangulation: has_mp1 */; const float* angA; const uint32_t* descA; const float* angB; const uint32_t* descB;
+    const TriPose* pose; const float* xyA; const float* urA; const uint8_t* flagsB /* has_mp2 */; const float* xyB; const int* octB; const float* urB;      // triangulation only
+    int2* sortedA; int2* sortedB; int* segStart; int* nSeg; int* nValid;       // scratch: (node, index) ascending [B][cap], first entry of every node of side A [B][capA], [B], [2][B]
+    int* choice;                                                  // [B][capA]: by_bow: scratch, triangulation: match12 (output)
+    int* matchOfCur; int* nmatches;                               // outputs [B][capB] (by_bow), [B]
+};
+int launch_match_by_bow(const BowParams& p, const BowArrays& a, int B, hipStream_t s);
+int launch_match_for_triangulation(const BowParams& p, const BowArrays& a, int B, hipStream_t s);
+
+// Vocabulary transform (bow_kernels.hip): descriptor -> word and node at a level, TemplatedVocabulary::transform
+struct VocTree { int nNodes; const int* childStart; const int* child; const uint32_t* desc; const int* wordId; const uint8_t* stopped; };   // device pointers
+int launch_voc_transform(const VocTree& tree, const uint32_t* desc /* [B][cap][8] */, const int* n, int cap, int maxN /* >= 1 */, int B, int nidLevel, int* nodeId, int* wordId, hipStream_t s);
 
 }  // namespace sind

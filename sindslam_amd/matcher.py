@@ -39,6 +39,19 @@ class _Reloc(C.Structure):
                 ("match_of_cur", C.c_void_p), ("nmatches", C.c_void_p)]
 
 
+class _Bow(C.Structure):
+    _fields_ = [("n_kf", C.c_int), ("kf_node", C.c_void_p), ("kf_valid", C.c_void_p), ("kf_angle", C.c_void_p), ("kf_desc", C.c_void_p),
+                ("n_cur", C.c_int), ("cur_node", C.c_void_p), ("cur_angle", C.c_void_p), ("cur_desc", C.c_void_p),
+                ("match_of_cur", C.c_void_p), ("nmatches", C.c_void_p)]
+
+
+class _Tri(C.Structure):
+    _fields_ = [("Tcw2", C.c_void_p), ("Cw1", C.c_void_p), ("F12", C.c_void_p),
+                ("n1", C.c_int), ("node1", C.c_void_p), ("has_mp1", C.c_void_p), ("un_xy1", C.c_void_p), ("angle1", C.c_void_p), ("u_right1", C.c_void_p), ("desc1", C.c_void_p),
+                ("n2", C.c_int), ("node2", C.c_void_p), ("has_mp2", C.c_void_p), ("un_xy2", C.c_void_p), ("octave2", C.c_void_p), ("angle2", C.c_void_p), ("u_right2", C.c_void_p),
+                ("desc2", C.c_void_p), ("match12", C.c_void_p), ("nmatches", C.c_void_p)]
+
+
 _f32 = lambda a: np.ascontiguousarray(a, np.float32)
 _u8 = lambda a: np.ascontiguousarray(a, np.uint8)
 _i32 = lambda a: np.ascontiguousarray(a, np.int32)
@@ -48,7 +61,8 @@ class ORBmatcher:
     """ORBmatcher(nnratio, checkOri) of the reference.  Provided: SearchByProjection(CurrentFrame, LastFrame, th, bMono) (TrackWithMotionModel),
     SearchLocalPoints = Frame::isInFrustum over the local map + SearchByProjection(F, vpMapPoints, th) (TrackLocalMap), and SearchByProjectionKF =
     SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (Relocalization).  A frame / a set of map points is a dict of arrays
-    (see include/sind_hip.h: sind_match_pair, sind_match_local, sind_match_reloc)."""
+    (see include/sind_hip.h: sind_match_pair, sind_match_local, sind_match_reloc).  By vocabulary node: SearchByBoW(pKF, F) (TrackReferenceKeyFrame, Relocalization;
+    :159-288) and SearchForTriangulation (LocalMapping::CreateNewMapPoints; :657-823), on node ids from vocabulary.ORBVocabulary (sind_match_bow, sind_match_tri)."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
 
     def __init__(self, fx, fy, cx, cy, bf, bounds, scale_factors, nnratio=0.6, checkOri=True, cap=4096, max_batch=1, device=0, cap_points=0):
@@ -133,6 +147,39 @@ class ORBmatcher:
             keep.append(a); arr[b].n_points = n; arr[b].n_cur = nc; outs.append((a, nc))
         self._call(lib().sind_match_by_projection_kf, "sind_match_by_projection_kf", arr, keep, C.c_float(th), int(ORBdist), int(self.checkOri))
         return [(a["match_of_cur"][:nc].copy(), int(a["nmatches"][0])) for a, nc in outs]
+
+    def SearchByBoW(self, pairs, nnratio=None):
+        """pairs: list of (kf, cur); kf, per keypoint of the key frame: node (as ORBVocabulary.transform returns it), valid (pMP && !isBad), angle, desc (the key
+        frame's own descriptors); cur: node, angle, desc.  nnratio None = the constructor's.  -> list of (match_of_cur i32 [n_cur], nmatches)"""
+        keep, arr, outs = [], (_Bow * len(pairs))(), []
+        for b, (kf, cur) in enumerate(pairs):
+            a = dict(kf_node=_i32(kf["node"]), kf_valid=_u8(kf["valid"]), kf_angle=_f32(kf["angle"]), kf_desc=_u8(kf["desc"]),
+                     cur_node=_i32(cur["node"]), cur_angle=_f32(cur["angle"]), cur_desc=_u8(cur["desc"]))
+            n, nc = len(a["kf_node"]), len(a["cur_node"])
+            a.update(match_of_cur=np.full(max(nc, 1), -1, np.int32), nmatches=np.zeros(1, np.int32))
+            keep.append(a); arr[b].n_kf = n; arr[b].n_cur = nc; outs.append((a, nc))
+        self._call(lib().sind_match_by_bow, "sind_match_by_bow", arr, keep, C.c_float(self.nnratio if nnratio is None else nnratio), int(self.checkOri))
+        return [(a["match_of_cur"][:nc].copy(), int(a["nmatches"][0])) for a, nc in outs]
+
+    def SearchForTriangulation(self, pairs, bOnlyStereo=False):
+        """pairs: list of (Tcw2, Cw1, F12, kf1, kf2); kf1, per keypoint: node, has_mp, un_xy, angle, u_right, desc; kf2: the same and octave.
+        -> list of (match12 i32 [n1], nmatches, matched_pairs i64 [nmatches, 2] = vMatchedPairs, ascending idx1)"""
+        keep, arr, outs = [], (_Tri * len(pairs))(), []
+        for b, (T2, Cw1, F12, k1, k2) in enumerate(pairs):
+            a = dict(Tcw2=_f32(T2), Cw1=_f32(Cw1), F12=_f32(F12))
+            for s, k in (("1", k1), ("2", k2)):
+                a.update({"node" + s: _i32(k["node"]), "has_mp" + s: _u8(k["has_mp"]), "un_xy" + s: _f32(k["un_xy"]), "angle" + s: _f32(k["angle"]), "u_right" + s: _f32(k["u_right"]),
+                          "desc" + s: _u8(k["desc"])})
+            a["octave2"] = _i32(k2["octave"])
+            n1, n2 = len(a["node1"]), len(a["node2"])
+            a.update(match12=np.full(max(n1, 1), -1, np.int32), nmatches=np.zeros(1, np.int32))
+            keep.append(a); arr[b].n1 = n1; arr[b].n2 = n2; outs.append((a, n1))
+        self._call(lib().sind_match_for_triangulation, "sind_match_for_triangulation", arr, keep, int(bOnlyStereo), int(self.checkOri))
+        res = []
+        for a, n1 in outs:
+            m = a["match12"][:n1].copy(); i1 = np.nonzero(m >= 0)[0]
+            res.append((m, int(a["nmatches"][0]), np.stack([i1, m[i1]], 1).astype(np.int64)))
+        return res
 
     def last_rounds(self):
         return lib().sind_match_last_rounds(self._h)
