@@ -109,6 +109,8 @@ int sind_orb_pyramid(sind_orb* o, int frame, int level, uint8_t* out, int* w, in
  * coordinates relative to the 16-px min border) and the octree survivors with their orientation before mask erasure */
 int sind_orb_debug_fast(sind_orb* o, int frame, int level, float* xyr, int cap);
 int sind_orb_debug_selected(sind_orb* o, int frame, sind_keypoint* kps, int cap, uint8_t* desc);
+/* the 7x7 sigma-2 Gaussian-blurred level BRIEF reads, frame `frame` of the last call: copies the w*h interior, dense */
+int sind_orb_debug_blurred(sind_orb* o, int frame, int level, uint8_t* out, int* w, int* h);
 
 /* ------------------------------------------------------------------------------------------------------------
  * DynaDetect.  Replaces ORB_SLAM2::DynaDetect (include/DynaDetect.h:95-131):

@@ -99,6 +99,14 @@ int sind_orb_debug_selected(sind_orb* o, int frame, sind_keypoint* kps, int cap,
     if (desc) std::memcpy(desc, R.desc.data(), (size_t)n * 32);
     return (int)R.kps.size();
 }
+int sind_orb_debug_blurred(sind_orb* o, int frame, int level, uint8_t* out, int* w, int* h) {
+    if (!o || !o->ready || level < 0 || level >= o->eng.nlevels || frame < 0 || frame >= o->eng.maxB) { sind_set_error("sind_orb_debug_blurred: bad arguments"); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(o->device));
+    const sind::OrbLevel& L = o->eng.levels[level];
+    if (w) *w = L.w; if (h) *h = L.h;
+    if (out) HIP_TRY(hipMemcpy(out, o->eng.blurred_dev() + (size_t)frame * o->eng.blur_bytes + L.blur_off, (size_t)L.w * L.h, hipMemcpyDeviceToHost));
+    return SIND_OK;
+}
 
 // PNG scanline reconstruction (filters None / Sub / Up / Average / Paeth, PNG spec section 9) for the rgbd_tum_noros-shaped harness
 // (sindslam_amd/harness.py inflates with zlib and calls this for the byte-serial part).  raw: h rows of (1 + stride) bytes.

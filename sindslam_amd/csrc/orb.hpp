@@ -59,6 +59,7 @@ public:
     // reference operator() tail (ORBextractor.cc:1063-1163): dynamic-mask erasure, <250 fallback, level scaling.
     void finish(const OrbFrameResult& all, const uint8_t* mask_or_null, int mask_stride, std::vector<OrbKeyPoint>& kps, std::vector<uint8_t>& desc, int* fallback = nullptr) const;
     const uint8_t* slab_dev() const { return slab.p; }
+    const uint8_t* blurred_dev() const { return blurred.p; }
     // debug access for stage-level parity tests (valid after extract_all)
     std::vector<std::vector<std::vector<OctKp>>> dbg_fast;   // [frame][level] cell-wise FAST keypoints
 private:

@@ -51,6 +51,8 @@ int OrbEngine::init(int W_, int H_, int nf, float sf, int nl, int ini, int mn, i
         const float width = (float)(maxBX - minBX), height = (float)(maxBY - minBY), Wc = 30;
         const int nCols = (int)(width / Wc), nRows = (int)(height / Wc);
         if (nCols < 1 || nRows < 1) continue;
+        // the octree starts from round(width / height) nodes (ORBextractor.cc:543): a level that can hold keypoints must give at least one
+        if (std::round(width / height) < 1) { sind_set_error("OrbEngine: level %d (%d x %d) is less than half as wide as tall inside its border; the octree cannot take it", l, L.w, L.h); return SIND_E_ARG; }
         const int wCell = (int)std::ceil(width / nCols), hCell = (int)std::ceil(height / nRows);
         for (int i = 0; i < nRows; i++) {
             const float iniY = (float)(minBY + i * hCell); float maxY = iniY + hCell + 6;

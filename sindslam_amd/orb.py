@@ -76,3 +76,11 @@ class ORBextractor:
     def debug_selected(self, frame=0):
         kps = np.zeros(self.cap, KP_DTYPE); desc = np.zeros((self.cap, 32), np.uint8)
         n = check(lib().sind_orb_debug_selected(self._h, frame, ptr(kps), self.cap, ptr(desc))); return kps[:n].copy(), desc[:n].copy()
+
+    def debug_blurred(self, level: int, frame: int = 0):
+        """The 7x7 sigma-2 blur of one level's interior (what BRIEF samples), u8 [h, w]."""
+        w = C.c_int(); h = C.c_int()
+        check(lib().sind_orb_debug_blurred(self._h, frame, level, None, C.byref(w), C.byref(h)))
+        out = np.empty((h.value, w.value), np.uint8)
+        check(lib().sind_orb_debug_blurred(self._h, frame, level, ptr(out), C.byref(w), C.byref(h)))
+        return out
