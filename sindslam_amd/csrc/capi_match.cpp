@@ -1,63 +1,202 @@
 // C ABI: projection matcher (include/sind_hip.h, "sind_match_*").
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 #include "../../include/sind_hip.h"
 #include "match.hpp"
 
+namespace {
+const int GRID_CELLS = 3072;                                       // Frame's 64 x 48 grid; grid_start has one entry more
+const int DESC_WORDS = 8;                                          // a descriptor: 32 bytes from the caller, 8 words for the kernels; staged and counted in words
+
+// A frame's keypoints as the caller passes them, and which of the arrays a search reads besides n and desc.  flags is whatever the search takes for "closed":
+// cur_taken (NULL = all free), kf_valid, has_mp1, has_mp2; the kernels read it as zero or not.
+enum { K_XY = 1, K_OCTAVE = 2, K_ANGLE = 4, K_URIGHT = 8, K_FLAGS = 16, K_GRID = 32, K_NODE = 64 };
+struct Keys { int n; const float* xy; const int* octave; const float* angle; const float* uRight; const uint8_t* desc; const uint8_t* flags; const int* gridStart; const int* gridIdx; const int* node; };
+
+void cpy(void* d, const void* s, size_t n) { if (n) std::memcpy(d, s, n); }                          // empty frames may pass NULL arrays
+template <class T> void put(Staged<T>& a, size_t at, const void* src, size_t count) { cpy(&a.h[at], src, count * sizeof(T)); }    // at, count: elements of T
+
+// One side of a search, dense [maxB][cap]; stage and upload take the same `use`.  Node ids, and xy and uRight of the acting side, appear with the first vocabulary search.
+struct Side {
+    int cap = 0;
+    Staged<int> n, octave, gridStart, gridIdx, node; Staged<float> xy, angle, uRight; Staged<uint8_t> flags; Staged<uint32_t> desc;
+    void stage(int b, const Keys& q, int use) {
+        const size_t o = (size_t)b * cap, k = (size_t)q.n;
+        n.h[b] = q.n; put(desc, o * DESC_WORDS, q.desc, k * DESC_WORDS);
+        if (use & K_XY) put(xy, o * 2, q.xy, k * 2); if (use & K_OCTAVE) put(octave, o, q.octave, k); if (use & K_ANGLE) put(angle, o, q.angle, k); if (use & K_URIGHT) put(uRight, o, q.uRight, k);
+        if (use & K_FLAGS) { if (q.flags) put(flags, o, q.flags, k); else std::memset(&flags.h[o], 0, k); }      // never what an earlier call left there
+        if (use & K_GRID) { put(gridStart, (size_t)b * (GRID_CELLS + 1), q.gridStart, GRID_CELLS + 1); put(gridIdx, o, q.gridIdx, (size_t)q.gridStart[GRID_CELLS]); }
+        if (use & K_NODE) put(node, o, q.node, k);
+    }
+    int upload(int B, int use, hipStream_t s) {
+        const size_t k = (size_t)B * cap;
+        SIND_TRY(n.up(B, s)); SIND_TRY(desc.up(k * DESC_WORDS, s));
+        if (use & K_XY) SIND_TRY(xy.up(k * 2, s)); if (use & K_OCTAVE) SIND_TRY(octave.up(k, s)); if (use & K_ANGLE) SIND_TRY(angle.up(k, s)); if (use & K_URIGHT) SIND_TRY(uRight.up(k, s));
+        if (use & K_FLAGS) SIND_TRY(flags.up(k, s)); if (use & K_NODE) SIND_TRY(node.up(k, s));
+        if (use & K_GRID) { SIND_TRY(gridStart.up((size_t)B * (GRID_CELLS + 1), s)); SIND_TRY(gridIdx.up(k, s)); }
+        return SIND_OK;
+    }
+};
+
+// a NULL among the arrays the search reads (flags is for the caller to judge: the projection searches take NULL for "all free")
+bool has_null(const Keys& q, int use) {
+    return ((use & K_GRID) && !q.gridStart) || (q.n && (!q.desc || ((use & K_XY) && !q.xy) || ((use & K_OCTAVE) && !q.octave) || ((use & K_ANGLE) && !q.angle) || ((use & K_URIGHT) && !q.uRight) ||
+                                                        ((use & K_GRID) && !q.gridIdx) || ((use & K_NODE) && !q.node)));
+}
+
+// One element of a batch (who: "entry point: pair" or "...: frame"; a: its acting side, q: its searched side), in the order every entry point reports: capacity, then NULL
+// arrays (otherNull: one among those that are on neither side), then the contents that can send a kernel out of bounds
+int check(const char* who, int b, bool otherNull, const Keys& a, int capA, int useA, const Keys& q, int capQ, int useQ) {
+    if (a.n < 0 || a.n > capA || q.n < 0 || q.n > capQ) { sind_set_error("%s %d has %d / %d entries, capacity %d / %d", who, b, a.n, q.n, capA, capQ); return SIND_E_CAPACITY; }
+    if (otherNull || has_null(a, useA) || has_null(q, useQ)) { sind_set_error("%s %d: null array", who, b); return SIND_E_ARG; }
+    if (useQ & K_GRID) {
+        const int* g = q.gridStart; bool ok = g[0] == 0 && g[GRID_CELLS] >= 0 && g[GRID_CELLS] <= q.n;
+        for (int c = 0; ok && c < GRID_CELLS; c++) ok = g[c + 1] >= g[c];
+        if (!ok) { sind_set_error("%s %d: malformed grid", who, b); return SIND_E_ARG; }
+        for (int j = 0; j < g[GRID_CELLS]; j++) if (q.gridIdx[j] < 0 || q.gridIdx[j] >= q.n) { sind_set_error("%s %d: grid index outside the keypoints", who, b); return SIND_E_ARG; }
+    }
+    if (useQ & K_NODE) for (const Keys* k : {&a, &q}) for (int i = 0; i < k->n; i++) if (k->node[i] < -1) { sind_set_error("%s %d: node id below -1", who, b); return SIND_E_ARG; }
+    return SIND_OK;
+}
+}  // namespace
+
+// The kinds of call share the two sides and the results (last.flags holds valid|has_obs, kf_valid or has_mp1, cur.flags holds cur_taken or has_mp2), so a call stages
+// everything it reads.  What only some calls need appears on first use.
 struct sind_match {
-    int device = 0, maxB = 0; sind::MatchParams prm{}; float mb = 0; hipStream_t stream = nullptr;
-    DevBuf<sind::MatchPose> pose; DevBuf<int> nLast, nCur, lastOct, curOct, gstart, gidx, choice, minOwner, matchOfCur, nmatches, rounds;
-    DevBuf<float> x3Dw, lastAng, curXY, curAng, curUR; DevBuf<uint8_t> lastFlags, curTaken; DevBuf<uint32_t> lastDesc, curDesc;
-    // host staging (one H2D per array and call)
-    std::vector<sind::MatchPose> h_pose; std::vector<int> h_nLast, h_nCur, h_lastOct, h_curOct, h_gstart, h_gidx, h_match, h_nm, h_rounds;
-    std::vector<float> h_x3Dw, h_lastAng, h_curXY, h_curAng, h_curUR; std::vector<uint8_t> h_lastFlags, h_curTaken, h_lastDesc, h_curDesc;
-    int last_rounds = 0;
+    int device = 0, maxB = 0; sind::MatchParams prm{}; float mb = 0; hipStream_t stream = nullptr; int last_rounds = 0;
+    Side last, cur;                                                // acting side: the last frame's points, side A of the vocabulary searches; searched side: the frame, side B
+    Staged<sind::MatchPose> pose; Staged<float> x3Dw;              // of the last frame (sind_match_by_projection)
+    Staged<int> matchOfCur, nmatches, rounds;                      // results [maxB][capCur], [maxB], [maxB]
+    Staged<int> choice;                                            // [maxB][capLast]: scratch on the device, and match12 of the triangulation, with which its host side appears
+    DevBuf<int> minOwner;                                          // scratch [maxB][capCur]
+    struct Result { int* match; int n; int* nmatches; };
+    std::vector<Result> out;                                       // the caller's outputs of the call in progress, per frame
     DevBuf<float4> curPack;                                        // keypoint records of match_local.hip, on first use
     // map-point side of sind_match_local_map (capacity from sind_match_reserve_map_points) and of sind_match_by_projection_kf (cap_last, on first use)
     struct PointSide {
         int cap = 0;
-        DevBuf<sind::LocalPose> pose; DevBuf<int> nPts, level, choice, nToMatch; DevBuf<float> x3Dw, normal, maxDist, minDist, angle, projXYR, viewCos;
-        DevBuf<uint8_t> flags, inView; DevBuf<uint32_t> desc;
-        std::vector<sind::LocalPose> h_pose; std::vector<int> h_nPts, h_level, h_nToMatch; std::vector<float> h_x3Dw, h_normal, h_maxDist, h_minDist, h_angle, h_projXYR, h_viewCos;
-        std::vector<uint8_t> h_flags, h_inView, h_desc;
+        Staged<sind::LocalPose> pose; Staged<int> n, level, nToMatch; Staged<float> x3Dw, normal, maxDist, minDist, angle, projXYR, viewCos; Staged<uint8_t> flags, inView; Staged<uint32_t> desc;
+        DevBuf<int> choice;
         int reserve(size_t B, int c) {
-            const size_t n = B * (size_t)c; int r = SIND_OK;
-            if ((r = pose.alloc(B)) || (r = nPts.alloc(B)) || (r = nToMatch.alloc(B)) || (r = level.alloc(n)) || (r = choice.alloc(n)) || (r = x3Dw.alloc(n * 3)) || (r = normal.alloc(n * 3)) ||
-                (r = maxDist.alloc(n)) || (r = minDist.alloc(n)) || (r = angle.alloc(n)) || (r = projXYR.alloc(n * 3)) || (r = viewCos.alloc(n)) || (r = flags.alloc(n)) || (r = inView.alloc(n)) ||
-                (r = desc.alloc(n * 8))) return r;
-            h_pose.resize(B); h_nPts.resize(B); h_nToMatch.resize(B); h_level.resize(n); h_x3Dw.resize(n * 3); h_normal.resize(n * 3); h_maxDist.resize(n); h_minDist.resize(n); h_angle.resize(n);
-            h_projXYR.resize(n * 3); h_viewCos.resize(n); h_flags.resize(n); h_inView.resize(n); h_desc.resize(n * 32);
+            const size_t k = B * (size_t)c; int r = SIND_OK;
+            if ((r = pose.alloc(B)) || (r = n.alloc(B)) || (r = nToMatch.alloc(B)) || (r = level.alloc(k)) || (r = choice.alloc(k)) || (r = x3Dw.alloc(k * 3)) || (r = normal.alloc(k * 3)) ||
+                (r = maxDist.alloc(k)) || (r = minDist.alloc(k)) || (r = angle.alloc(k)) || (r = projXYR.alloc(k * 3)) || (r = viewCos.alloc(k)) || (r = flags.alloc(k)) || (r = inView.alloc(k)) ||
+                (r = desc.alloc(k * DESC_WORDS))) return r;
             cap = c; return SIND_OK;
         }
     } local, reloc;
-    // node ids, sort scratch and the extra key-frame arrays of sind_match_by_bow / sind_match_for_triangulation (match_bow.hip), on first use
+    // sort scratch and pair geometry of sind_match_by_bow / sind_match_for_triangulation (match_bow.hip); with them the two sides get their node ids and side A xy and uRight
     struct BowSide {
-        bool ready = false;
-        DevBuf<int> nodeA, nodeB, segStart, nSeg, nValid; DevBuf<int2> sortedA, sortedB; DevBuf<float> lastXY, lastUR; DevBuf<sind::TriPose> pose;
-        std::vector<int> h_nodeA, h_nodeB, h_match12; std::vector<float> h_lastXY, h_lastUR; std::vector<sind::TriPose> h_pose;
-        int reserve(size_t B, size_t cl, size_t cc) {
-            if (ready) return SIND_OK;
-            int r = SIND_OK;
-            if ((r = nodeA.alloc(B * cl)) || (r = nodeB.alloc(B * cc)) || (r = segStart.alloc(B * cl)) || (r = nSeg.alloc(B)) || (r = nValid.alloc(2 * B)) || (r = sortedA.alloc(B * cl)) ||
-                (r = sortedB.alloc(B * cc)) || (r = lastXY.alloc(B * cl * 2)) || (r = lastUR.alloc(B * cl)) || (r = pose.alloc(B))) return r;
-            h_nodeA.resize(B * cl); h_nodeB.resize(B * cc); h_match12.resize(B * cl); h_lastXY.resize(B * cl * 2); h_lastUR.resize(B * cl); h_pose.resize(B);
-            ready = true; return SIND_OK;
-        }
+        Staged<sind::TriPose> pose; DevBuf<int> segStart, nSeg, nValid; DevBuf<int2> sortedA, sortedB;
     } bow;
+    int reserve_bow() {
+        const size_t B = maxB, nl = B * prm.capLast, nc = B * prm.capCur; int r = SIND_OK;
+        (r = last.node.alloc(nl)) || (r = last.xy.alloc(nl * 2)) || (r = last.uRight.alloc(nl)) || (r = cur.node.alloc(nc)) || (r = choice.alloc(nl)) || (r = bow.pose.alloc(B)) ||
+            (r = bow.segStart.alloc(nl)) || (r = bow.nSeg.alloc(B)) || (r = bow.nValid.alloc(2 * B)) || (r = bow.sortedA.alloc(nl)) || (r = bow.sortedB.alloc(nc));
+        return r;
+    }
 };
+
+namespace {
+// The tail of every search: the matches ([B][stride]), nmatches and, for the projection searches, rounds come down; then every frame's results go where m->out[b] says
+int finish(sind_match* m, int B, Staged<int>& matches, size_t stride, bool rounds) {
+    hipStream_t s = m->stream;
+    SIND_TRY(matches.down(B * stride, s)); SIND_TRY(m->nmatches.down(B, s)); if (rounds) SIND_TRY(m->rounds.down(B, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (rounds) m->last_rounds = std::max(0, *std::max_element(m->rounds.h.begin(), m->rounds.h.begin() + B));
+    for (int b = 0; b < B; b++) { const sind_match::Result& r = m->out[b]; cpy(r.match, &matches.h[b * stride], (size_t)r.n * sizeof(int)); *r.nmatches = m->nmatches.h[b]; }
+    return SIND_OK;
+}
 
 // CurrentFrame / LastFrame pose algebra of ORBmatcher.cc:1338-1349 (cv::gemm semantics: A*b+c without transposition = FP32 row
 // product then FP64 alpha/beta; -A^T*b = FP64 accumulation)
-static void forward_backward(const float* Tc, const float* Tl, float mb, bool mono, int& fwd, int& bwd) {
+void forward_backward(const float* Tc, const float* Tl, float mb, bool mono, int& fwd, int& bwd) {
     float twc[3], tlc[3];
     for (int r = 0; r < 3; r++) { double s = 0; for (int k = 0; k < 3; k++) s += (double)Tc[4 * k + r] * (double)Tc[4 * k + 3]; twc[r] = (float)(s * -1.0); }
     for (int r = 0; r < 3; r++) { const float t = Tl[4 * r] * twc[0] + Tl[4 * r + 1] * twc[1] + Tl[4 * r + 2] * twc[2]; tlc[r] = (float)((double)t * 1.0 + (double)Tl[4 * r + 3] * 1.0); }
     fwd = tlc[2] > mb && !mono; bwd = -tlc[2] > mb && !mono;
 }
 
-template <class T> static int up(DevBuf<T>& d, const std::vector<T>& h, size_t n, hipStream_t s) { HIP_TRY(hipMemcpyAsync(d.p, h.data(), n * sizeof(T), hipMemcpyHostToDevice, s)); return SIND_OK; }
+// ---- local-map search and relocalisation search (match_local.hip) ----
+struct PointsFrame {                                               // one frame of either call, the public structs flattened to one shape
+    const float* Tcw; int n_points; const float* x3Dw; const float* normal; const float* max_dist; const float* min_dist; const uint8_t* flags; const float* angle; const uint8_t* desc;
+    Keys cur;
+    uint8_t* in_view; float* proj_xyr; int* level; float* view_cos; int* n_to_match; int* match_of_cur; int* nmatches;
+};
 
+int run_points(sind_match* m, sind_match::PointSide& ps, const std::vector<PointsFrame>& fr, sind::LocalParams p, int reloc, const char* who) {
+    const int B = (int)fr.size(), cp = ps.cap, use = K_XY | K_OCTAVE | K_FLAGS | K_GRID | (reloc ? K_ANGLE : K_URIGHT);
+    Side& c = m->cur;
+    p.capPts = cp;
+    p.logScaleFactor = (float)std::log((double)p.scale[1]);       // Frame.cc:71 with log as match_local.hip defines it
+    bool wantFrustum = false;
+    for (int b = 0; b < B; b++) {
+        const PointsFrame& q = fr[b];
+        const Keys pts{q.n_points, nullptr, nullptr, reloc ? q.angle : nullptr, nullptr, q.desc, nullptr, nullptr, nullptr, nullptr};      // as far as check() goes
+        SIND_TRY(check(who, b, !q.Tcw || !q.match_of_cur || !q.nmatches || (q.n_points && (!q.x3Dw || !q.max_dist || !q.min_dist || !q.flags || (!reloc && !q.normal))), pts, cp, reloc ? K_ANGLE : 0,
+                       q.cur, c.cap, use));
+        wantFrustum = wantFrustum || q.in_view || q.proj_xyr || q.level || q.view_cos;
+        sind::LocalPose& po = ps.pose.h[b]; cpy(po.Tcw, q.Tcw, sizeof(po.Tcw));
+        for (int r = 0; r < 3; r++) { double s = 0; for (int k = 0; k < 3; k++) s += (double)q.Tcw[4 * k + r] * (double)q.Tcw[4 * k + 3]; po.Ow[r] = (float)(s * -1.0); }   // -Rcw^T * tcw
+        const size_t o = (size_t)b * cp, n = (size_t)q.n_points;
+        ps.n.h[b] = q.n_points; put(ps.x3Dw, o * 3, q.x3Dw, n * 3); put(ps.maxDist, o, q.max_dist, n); put(ps.minDist, o, q.min_dist, n); put(ps.desc, o * DESC_WORDS, q.desc, n * DESC_WORDS);
+        if (reloc) { put(ps.angle, o, q.angle, n); for (size_t i = 0; i < n; i++) ps.flags.h[o + i] = q.flags[i] ? 3 : 0; }     // every assignment closes its keypoint (:1541)
+        else { put(ps.normal, o * 3, q.normal, n * 3); for (size_t i = 0; i < n; i++) ps.flags.h[o + i] = q.flags[i] & 3; }
+        c.stage(b, q.cur, use);
+        m->out[b] = {q.match_of_cur, q.cur.n, q.nmatches};
+    }
+    SIND_TRY(m->curPack.alloc((size_t)m->maxB * c.cap));
+    hipStream_t s = m->stream; const size_t np = (size_t)B * cp;
+    SIND_TRY(ps.pose.up(B, s)); SIND_TRY(ps.n.up(B, s)); SIND_TRY(ps.x3Dw.up(np * 3, s)); SIND_TRY(ps.maxDist.up(np, s)); SIND_TRY(ps.minDist.up(np, s)); SIND_TRY(ps.flags.up(np, s));
+    SIND_TRY(ps.desc.up(np * DESC_WORDS, s)); SIND_TRY(reloc ? ps.angle.up(np, s) : ps.normal.up(np * 3, s)); SIND_TRY(c.upload(B, use, s));
+    HIP_TRY(hipMemsetAsync(ps.nToMatch.d.p, 0, (size_t)B * 4, s));
+    sind::LocalArrays a{ps.pose.d.p, ps.n.d.p, c.n.d.p, ps.x3Dw.d.p, ps.normal.d.p, ps.maxDist.d.p, ps.minDist.d.p, ps.flags.d.p, ps.angle.d.p, ps.desc.d.p, c.xy.d.p, c.octave.d.p, c.angle.d.p,
+                        c.uRight.d.p, c.desc.d.p, c.gridStart.d.p, c.gridIdx.d.p, c.flags.d.p, ps.inView.d.p, ps.projXYR.d.p, ps.level.d.p, ps.viewCos.d.p, ps.nToMatch.d.p, ps.choice.p,
+                        m->minOwner.p, m->curPack.p, m->matchOfCur.d.p, m->nmatches.d.p, m->rounds.d.p};
+    SIND_TRY(sind::launch_project_points(p, a, B, reloc, s));
+    SIND_TRY(sind::launch_search_points(p, a, B, reloc, s));
+    if (wantFrustum) { SIND_TRY(ps.inView.down(np, s)); SIND_TRY(ps.projXYR.down(np * 3, s)); SIND_TRY(ps.level.down(np, s)); SIND_TRY(ps.viewCos.down(np, s)); }
+    SIND_TRY(ps.nToMatch.down(B, s));
+    SIND_TRY(finish(m, B, m->matchOfCur, c.cap, true));
+    for (int b = 0; b < B; b++) {
+        const PointsFrame& q = fr[b]; const size_t o = (size_t)b * cp, n = (size_t)q.n_points;
+        if (q.in_view) cpy(q.in_view, &ps.inView.h[o], n); if (q.proj_xyr) cpy(q.proj_xyr, &ps.projXYR.h[o * 3], n * 12);
+        if (q.level) cpy(q.level, &ps.level.h[o], n * 4); if (q.view_cos) cpy(q.view_cos, &ps.viewCos.h[o], n * 4);
+        if (q.n_to_match) *q.n_to_match = ps.nToMatch.h[b];
+    }
+    return SIND_OK;
+}
+
+sind::LocalParams local_params(const sind_match* m, float th) {
+    sind::LocalParams p{}; const sind::MatchParams& c = m->prm;
+    p.fx = c.fx; p.fy = c.fy; p.cx = c.cx; p.cy = c.cy; p.bf = c.bf; std::memcpy(p.bounds, c.bounds, sizeof(p.bounds)); std::memcpy(p.scale, c.scale, sizeof(p.scale));
+    p.nlevels = c.nlevels; p.capCur = c.capCur; p.th = th;
+    return p;
+}
+
+// ---- vocabulary-guided searches (match_bow.hip) ----
+Keys side_a(const sind_match_bow& q) { return Keys{q.n_kf, nullptr, nullptr, q.kf_angle, nullptr, q.kf_desc, q.kf_valid, nullptr, nullptr, q.kf_node}; }
+Keys side_b(const sind_match_bow& q) { return Keys{q.n_cur, nullptr, nullptr, q.cur_angle, nullptr, q.cur_desc, nullptr, nullptr, nullptr, q.cur_node}; }
+Keys side_a(const sind_match_tri& q) { return Keys{q.n1, q.un_xy1, nullptr, q.angle1, q.u_right1, q.desc1, q.has_mp1, nullptr, nullptr, q.node1}; }
+Keys side_b(const sind_match_tri& q) { return Keys{q.n2, q.un_xy2, q.octave2, q.angle2, q.u_right2, q.desc2, q.has_mp2, nullptr, nullptr, q.node2}; }
+
+sind::BowParams bow_params(const sind_match* m, int maxN) {
+    sind::BowParams p{}; const sind::MatchParams& c = m->prm;
+    p.fx = c.fx; p.fy = c.fy; p.cx = c.cx; p.cy = c.cy; std::memcpy(p.scale, c.scale, sizeof(p.scale)); p.capA = c.capLast; p.capB = c.capCur;
+    p.sortLen = 1; while (p.sortLen < maxN) p.sortLen <<= 1;
+    return p;
+}
+
+sind::BowArrays bow_arrays(sind_match* m) {
+    Side& l = m->last; Side& c = m->cur; sind_match::BowSide& w = m->bow;
+    return sind::BowArrays{l.n.d.p, c.n.d.p, l.node.d.p, c.node.d.p, l.flags.d.p, l.angle.d.p, l.desc.d.p, c.angle.d.p, c.desc.d.p, w.pose.d.p, l.xy.d.p, l.uRight.d.p, c.flags.d.p,
+                           c.xy.d.p, c.octave.d.p, c.uRight.d.p, w.sortedA.p, w.sortedB.p, w.segStart.p, w.nSeg.p, w.nValid.p, m->choice.d.p, m->matchOfCur.d.p, m->nmatches.d.p};
+}
+}  // namespace
+
+// ---- the C ABI ----
 extern "C" {
 
 int sind_match_create(const sind_match_config* c, sind_match** out) {
@@ -68,15 +207,14 @@ int sind_match_create(const sind_match_config* c, sind_match** out) {
     for (int i = 0; i < 16; i++) p.scale[i] = i < c->nlevels ? c->scale_factors[i] : 0.f;
     p.nlevels = c->nlevels; p.capLast = c->cap_last; p.capCur = c->cap_cur; m->mb = c->bf / c->fx;                 // Frame.cc:167 mb = mbf / fx
     const size_t B = c->max_batch, nl = B * c->cap_last, nc = B * c->cap_cur;
+    Side& l = m->last; Side& k = m->cur; l.cap = c->cap_last; k.cap = c->cap_cur;
     int r = SIND_OK;
-    if ((r = m->pose.alloc(B)) || (r = m->nLast.alloc(B)) || (r = m->nCur.alloc(B)) || (r = m->lastOct.alloc(nl)) || (r = m->curOct.alloc(nc)) || (r = m->gstart.alloc(B * 3073)) ||
-        (r = m->gidx.alloc(nc)) || (r = m->choice.alloc(nl)) || (r = m->minOwner.alloc(nc)) || (r = m->matchOfCur.alloc(nc)) || (r = m->nmatches.alloc(B)) || (r = m->rounds.alloc(B)) ||
-        (r = m->x3Dw.alloc(nl * 3)) || (r = m->lastAng.alloc(nl)) || (r = m->curXY.alloc(nc * 2)) || (r = m->curAng.alloc(nc)) || (r = m->curUR.alloc(nc)) || (r = m->lastFlags.alloc(nl)) ||
-        (r = m->curTaken.alloc(nc)) || (r = m->lastDesc.alloc(nl * 8)) || (r = m->curDesc.alloc(nc * 8))) { delete m; return r; }
+    if ((r = m->pose.alloc(B)) || (r = m->x3Dw.alloc(nl * 3)) || (r = l.n.alloc(B)) || (r = l.octave.alloc(nl)) || (r = l.angle.alloc(nl)) || (r = l.flags.alloc(nl)) || (r = l.desc.alloc(nl * DESC_WORDS)) ||
+        (r = k.n.alloc(B)) || (r = k.xy.alloc(nc * 2)) || (r = k.octave.alloc(nc)) || (r = k.angle.alloc(nc)) || (r = k.uRight.alloc(nc)) || (r = k.flags.alloc(nc)) || (r = k.desc.alloc(nc * DESC_WORDS)) ||
+        (r = k.gridStart.alloc(B * (GRID_CELLS + 1))) || (r = k.gridIdx.alloc(nc)) || (r = m->matchOfCur.alloc(nc)) || (r = m->nmatches.alloc(B)) || (r = m->rounds.alloc(B)) || (r = m->choice.d.alloc(nl)) ||
+        (r = m->minOwner.alloc(nc))) { delete m; return r; }
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { delete m; sind_set_error("sind_match_create: stream creation failed"); return SIND_E_HIP; }
-    m->h_pose.resize(B); m->h_nLast.resize(B); m->h_nCur.resize(B); m->h_lastOct.resize(nl); m->h_curOct.resize(nc); m->h_gstart.resize(B * 3073); m->h_gidx.resize(nc); m->h_match.resize(nc);
-    m->h_nm.resize(B); m->h_rounds.resize(B); m->h_x3Dw.resize(nl * 3); m->h_lastAng.resize(nl); m->h_curXY.resize(nc * 2); m->h_curAng.resize(nc); m->h_curUR.resize(nc);
-    m->h_lastFlags.resize(nl); m->h_curTaken.resize(nc); m->h_lastDesc.resize(nl * 32); m->h_curDesc.resize(nc * 32);
+    m->out.resize(B);
     *out = m; return SIND_OK;
 }
 int sind_match_destroy(sind_match* m) {
@@ -91,136 +229,32 @@ int sind_match_by_projection(sind_match* m, const sind_match_pair* pairs, int B,
     if (!m || !pairs || B < 1 || B > m->maxB || !(th > 0)) { sind_set_error("sind_match_by_projection: bad arguments (B=%d, max %d)", B, m ? m->maxB : 0); return SIND_E_ARG; }
     HIP_TRY(hipSetDevice(m->device));
     sind::MatchParams p = m->prm; p.th = th; p.checkOrientation = check_orientation ? 1 : 0;
-    const int cl = p.capLast, cc = p.capCur;
+    const int useLast = K_OCTAVE | K_ANGLE, useCur = K_XY | K_OCTAVE | K_ANGLE | K_URIGHT | K_FLAGS | K_GRID;      // last.flags is put together here
+    Side& l = m->last; Side& c = m->cur;
     for (int b = 0; b < B; b++) {
         const sind_match_pair& q = pairs[b];
-        if (q.n_last < 0 || q.n_last > cl || q.n_cur < 0 || q.n_cur > cc) { sind_set_error("sind_match_by_projection: pair %d has %d / %d points, capacity %d / %d", b, q.n_last, q.n_cur, cl, cc); return SIND_E_CAPACITY; }
-        if (!q.Tcw_cur || !q.Tcw_last || !q.match_of_cur || !q.nmatches || (q.n_last && (!q.x3Dw || !q.last_valid || !q.last_has_obs || !q.last_octave || !q.last_angle || !q.last_desc)) ||
-            (q.n_cur && (!q.cur_un_xy || !q.cur_octave || !q.cur_angle || !q.cur_u_right || !q.cur_desc || !q.grid_idx)) || !q.grid_start) { sind_set_error("sind_match_by_projection: null array in pair %d", b); return SIND_E_ARG; }
-        sind::MatchPose& ps = m->h_pose[b]; std::memcpy(ps.Tcw, q.Tcw_cur, sizeof(ps.Tcw));
-        forward_backward(q.Tcw_cur, q.Tcw_last, m->mb, mono != 0, ps.forward, ps.backward);
-        m->h_nLast[b] = q.n_last; m->h_nCur[b] = q.n_cur;
+        const Keys last{q.n_last, nullptr, q.last_octave, q.last_angle, nullptr, q.last_desc, nullptr, nullptr, nullptr, nullptr};
+        const Keys cur{q.n_cur, q.cur_un_xy, q.cur_octave, q.cur_angle, q.cur_u_right, q.cur_desc, q.cur_taken, q.grid_start, q.grid_idx, nullptr};
+        SIND_TRY(check("sind_match_by_projection: pair", b, !q.Tcw_cur || !q.Tcw_last || !q.match_of_cur || !q.nmatches || (q.n_last && (!q.x3Dw || !q.last_valid || !q.last_has_obs)), last, l.cap, useLast,
+                       cur, c.cap, useCur));
+        const size_t o = (size_t)b * l.cap;
         for (int i = 0; i < q.n_last; i++) {
             if (q.last_octave[i] < 0 || q.last_octave[i] >= p.nlevels) { sind_set_error("sind_match_by_projection: octave %d outside [0,%d)", q.last_octave[i], p.nlevels); return SIND_E_ARG; }
-            m->h_lastFlags[(size_t)b * cl + i] = (uint8_t)((q.last_valid[i] ? 1 : 0) | (q.last_has_obs[i] ? 2 : 0));
+            l.flags.h[o + i] = (uint8_t)((q.last_valid[i] ? 1 : 0) | (q.last_has_obs[i] ? 2 : 0));
         }
-        std::memcpy(&m->h_x3Dw[(size_t)b * cl * 3], q.x3Dw, (size_t)q.n_last * 12); std::memcpy(&m->h_lastOct[(size_t)b * cl], q.last_octave, (size_t)q.n_last * 4);
-        std::memcpy(&m->h_lastAng[(size_t)b * cl], q.last_angle, (size_t)q.n_last * 4); std::memcpy(&m->h_lastDesc[(size_t)b * cl * 32], q.last_desc, (size_t)q.n_last * 32);
-        std::memcpy(&m->h_curXY[(size_t)b * cc * 2], q.cur_un_xy, (size_t)q.n_cur * 8); std::memcpy(&m->h_curOct[(size_t)b * cc], q.cur_octave, (size_t)q.n_cur * 4);
-        std::memcpy(&m->h_curAng[(size_t)b * cc], q.cur_angle, (size_t)q.n_cur * 4); std::memcpy(&m->h_curUR[(size_t)b * cc], q.cur_u_right, (size_t)q.n_cur * 4);
-        std::memcpy(&m->h_curDesc[(size_t)b * cc * 32], q.cur_desc, (size_t)q.n_cur * 32);
-        if (q.grid_start[0] != 0 || q.grid_start[3072] < 0 || q.grid_start[3072] > q.n_cur) { sind_set_error("sind_match_by_projection: malformed grid of pair %d", b); return SIND_E_ARG; }
-        for (int c = 0; c < 3072; c++) if (q.grid_start[c + 1] < q.grid_start[c]) { sind_set_error("sind_match_by_projection: malformed grid of pair %d", b); return SIND_E_ARG; }
-        for (int j = 0; j < q.grid_start[3072]; j++) if (q.grid_idx[j] < 0 || q.grid_idx[j] >= q.n_cur) { sind_set_error("sind_match_by_projection: grid index outside the keypoints (pair %d)", b); return SIND_E_ARG; }
-        std::memcpy(&m->h_gstart[(size_t)b * 3073], q.grid_start, 3073 * 4); std::memcpy(&m->h_gidx[(size_t)b * cc], q.grid_idx, (size_t)q.grid_start[3072] * 4);
-        if (q.cur_taken) std::memcpy(&m->h_curTaken[(size_t)b * cc], q.cur_taken, q.n_cur); else std::memset(&m->h_curTaken[(size_t)b * cc], 0, q.n_cur);
+        sind::MatchPose& ps = m->pose.h[b]; std::memcpy(ps.Tcw, q.Tcw_cur, sizeof(ps.Tcw));
+        forward_backward(q.Tcw_cur, q.Tcw_last, m->mb, mono != 0, ps.forward, ps.backward);
+        put(m->x3Dw, o * 3, q.x3Dw, (size_t)q.n_last * 3); l.stage(b, last, useLast); c.stage(b, cur, useCur);
+        m->out[b] = {q.match_of_cur, q.n_cur, q.nmatches};
     }
-    hipStream_t s = m->stream; const size_t nl = (size_t)B * cl, nc = (size_t)B * cc;
-    SIND_TRY(up(m->pose, m->h_pose, B, s)); SIND_TRY(up(m->nLast, m->h_nLast, B, s)); SIND_TRY(up(m->nCur, m->h_nCur, B, s)); SIND_TRY(up(m->x3Dw, m->h_x3Dw, nl * 3, s));
-    SIND_TRY(up(m->lastFlags, m->h_lastFlags, nl, s)); SIND_TRY(up(m->lastOct, m->h_lastOct, nl, s)); SIND_TRY(up(m->lastAng, m->h_lastAng, nl, s));
-    HIP_TRY(hipMemcpyAsync(m->lastDesc.p, m->h_lastDesc.data(), nl * 32, hipMemcpyHostToDevice, s)); HIP_TRY(hipMemcpyAsync(m->curDesc.p, m->h_curDesc.data(), nc * 32, hipMemcpyHostToDevice, s));
-    SIND_TRY(up(m->curXY, m->h_curXY, nc * 2, s)); SIND_TRY(up(m->curOct, m->h_curOct, nc, s)); SIND_TRY(up(m->curAng, m->h_curAng, nc, s)); SIND_TRY(up(m->curUR, m->h_curUR, nc, s));
-    SIND_TRY(up(m->gstart, m->h_gstart, (size_t)B * 3073, s)); SIND_TRY(up(m->gidx, m->h_gidx, nc, s)); SIND_TRY(up(m->curTaken, m->h_curTaken, nc, s));
-    sind::MatchArrays a{m->pose.p, m->nLast.p, m->nCur.p, m->x3Dw.p, m->lastFlags.p, m->lastOct.p, m->lastAng.p, m->lastDesc.p, m->curXY.p, m->curOct.p, m->curAng.p, m->curUR.p,
-                        m->curDesc.p, m->gstart.p, m->gidx.p, m->curTaken.p, m->choice.p, m->minOwner.p, m->matchOfCur.p, m->nmatches.p, m->rounds.p};
+    hipStream_t s = m->stream; const size_t nl = (size_t)B * l.cap;
+    SIND_TRY(m->pose.up(B, s)); SIND_TRY(m->x3Dw.up(nl * 3, s)); SIND_TRY(l.flags.up(nl, s)); SIND_TRY(l.upload(B, useLast, s)); SIND_TRY(c.upload(B, useCur, s));
+    sind::MatchArrays a{m->pose.d.p, l.n.d.p, c.n.d.p, m->x3Dw.d.p, l.flags.d.p, l.octave.d.p, l.angle.d.p, l.desc.d.p, c.xy.d.p, c.octave.d.p, c.angle.d.p, c.uRight.d.p,
+                        c.desc.d.p, c.gridStart.d.p, c.gridIdx.d.p, c.flags.d.p, m->choice.d.p, m->minOwner.p, m->matchOfCur.d.p, m->nmatches.d.p, m->rounds.d.p};
     SIND_TRY(sind::launch_search_by_projection(p, a, B, s));
-    HIP_TRY(hipMemcpyAsync(m->h_match.data(), m->matchOfCur.p, nc * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(m->h_nm.data(), m->nmatches.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(m->h_rounds.data(), m->rounds.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    m->last_rounds = 0;
-    for (int b = 0; b < B; b++) {
-        std::memcpy(pairs[b].match_of_cur, &m->h_match[(size_t)b * cc], (size_t)pairs[b].n_cur * 4); *pairs[b].nmatches = m->h_nm[b];
-        m->last_rounds = std::max(m->last_rounds, m->h_rounds[b]);
-    }
-    return SIND_OK;
+    return finish(m, B, m->matchOfCur, m->cur.cap, true);
 }
 int sind_match_last_rounds(sind_match* m) { return m ? m->last_rounds : SIND_E_ARG; }
-
-}  // extern "C"
-
-// ---- local-map search and relocalisation search (match_local.hip) ----
-namespace {
-struct PointsFrame {                                               // one frame of either call, the public structs flattened to one shape
-    const float* Tcw; int n_points; const float* x3Dw; const float* normal; const float* max_dist; const float* min_dist; const uint8_t* flags; const float* angle; const uint8_t* desc;
-    int n_cur; const float* cur_un_xy; const int* cur_octave; const float* cur_angle; const float* cur_u_right; const uint8_t* cur_desc; const int* grid_start; const int* grid_idx;
-    const uint8_t* cur_taken;
-    uint8_t* in_view; float* proj_xyr; int* level; float* view_cos; int* n_to_match; int* match_of_cur; int* nmatches;
-};
-}
-
-static void cpy(void* d, const void* s, size_t n) { if (n) std::memcpy(d, s, n); }                  // empty frames may pass NULL arrays
-
-static int run_points(sind_match* m, sind_match::PointSide& ps, const std::vector<PointsFrame>& fr, sind::LocalParams p, int reloc, const char* who) {
-    const int B = (int)fr.size(), cp = ps.cap, cc = p.capCur;
-    p.capPts = cp;
-    p.logScaleFactor = (float)std::log((double)p.scale[1]);       // Frame.cc:71 with log as match_local.hip defines it
-    bool wantFrustum = false;
-    for (int b = 0; b < B; b++) {
-        const PointsFrame& q = fr[b];
-        if (q.n_points < 0 || q.n_points > cp || q.n_cur < 0 || q.n_cur > cc) { sind_set_error("%s: frame %d has %d points / %d keypoints, capacity %d / %d", who, b, q.n_points, q.n_cur, cp, cc); return SIND_E_CAPACITY; }
-        if (!q.Tcw || !q.match_of_cur || !q.nmatches || !q.grid_start || (q.n_points && (!q.x3Dw || !q.max_dist || !q.min_dist || !q.flags || !q.desc || (reloc ? !q.angle : !q.normal))) ||
-            (q.n_cur && (!q.cur_un_xy || !q.cur_octave || !q.cur_desc || !q.grid_idx || (reloc ? !q.cur_angle : !q.cur_u_right)))) { sind_set_error("%s: null array in frame %d", who, b); return SIND_E_ARG; }
-        if (q.grid_start[0] != 0 || q.grid_start[3072] < 0 || q.grid_start[3072] > q.n_cur) { sind_set_error("%s: malformed grid of frame %d", who, b); return SIND_E_ARG; }
-        for (int c = 0; c < 3072; c++) if (q.grid_start[c + 1] < q.grid_start[c]) { sind_set_error("%s: malformed grid of frame %d", who, b); return SIND_E_ARG; }
-        for (int j = 0; j < q.grid_start[3072]; j++) if (q.grid_idx[j] < 0 || q.grid_idx[j] >= q.n_cur) { sind_set_error("%s: grid index outside the keypoints (frame %d)", who, b); return SIND_E_ARG; }
-        wantFrustum = wantFrustum || q.in_view || q.proj_xyr || q.level || q.view_cos;
-        sind::LocalPose& po = ps.h_pose[b]; cpy(po.Tcw, q.Tcw, sizeof(po.Tcw));
-        for (int r = 0; r < 3; r++) { double s = 0; for (int k = 0; k < 3; k++) s += (double)q.Tcw[4 * k + r] * (double)q.Tcw[4 * k + 3]; po.Ow[r] = (float)(s * -1.0); }   // -Rcw^T * tcw
-        ps.h_nPts[b] = q.n_points; m->h_nCur[b] = q.n_cur;
-        const size_t o = (size_t)b * cp, c0 = (size_t)b * cc, np = (size_t)q.n_points, nc = (size_t)q.n_cur;
-        cpy(&ps.h_x3Dw[o * 3], q.x3Dw, np * 12); cpy(&ps.h_maxDist[o], q.max_dist, np * 4); cpy(&ps.h_minDist[o], q.min_dist, np * 4);
-        cpy(&ps.h_desc[o * 32], q.desc, np * 32);
-        if (reloc) { cpy(&ps.h_angle[o], q.angle, np * 4); for (size_t i = 0; i < np; i++) ps.h_flags[o + i] = q.flags[i] ? 3 : 0; }     // every assignment closes its keypoint (:1541)
-        else { cpy(&ps.h_normal[o * 3], q.normal, np * 12); for (size_t i = 0; i < np; i++) ps.h_flags[o + i] = q.flags[i] & 3; }
-        cpy(&m->h_curXY[c0 * 2], q.cur_un_xy, nc * 8); cpy(&m->h_curOct[c0], q.cur_octave, nc * 4); cpy(&m->h_curDesc[c0 * 32], q.cur_desc, nc * 32);
-        if (reloc) cpy(&m->h_curAng[c0], q.cur_angle, nc * 4); else cpy(&m->h_curUR[c0], q.cur_u_right, nc * 4);
-        cpy(&m->h_gstart[(size_t)b * 3073], q.grid_start, 3073 * 4); cpy(&m->h_gidx[c0], q.grid_idx, (size_t)q.grid_start[3072] * 4);
-        if (q.cur_taken) cpy(&m->h_curTaken[c0], q.cur_taken, nc); else std::memset(&m->h_curTaken[c0], 0, nc);
-    }
-    SIND_TRY(m->curPack.alloc((size_t)m->maxB * cc));
-    hipStream_t s = m->stream; const size_t np = (size_t)B * cp, nc = (size_t)B * cc;
-    SIND_TRY(up(ps.pose, ps.h_pose, B, s)); SIND_TRY(up(ps.nPts, ps.h_nPts, B, s)); SIND_TRY(up(m->nCur, m->h_nCur, B, s)); SIND_TRY(up(ps.x3Dw, ps.h_x3Dw, np * 3, s));
-    SIND_TRY(up(ps.maxDist, ps.h_maxDist, np, s)); SIND_TRY(up(ps.minDist, ps.h_minDist, np, s)); SIND_TRY(up(ps.flags, ps.h_flags, np, s));
-    HIP_TRY(hipMemcpyAsync(ps.desc.p, ps.h_desc.data(), np * 32, hipMemcpyHostToDevice, s)); HIP_TRY(hipMemcpyAsync(m->curDesc.p, m->h_curDesc.data(), nc * 32, hipMemcpyHostToDevice, s));
-    if (reloc) { SIND_TRY(up(ps.angle, ps.h_angle, np, s)); SIND_TRY(up(m->curAng, m->h_curAng, nc, s)); } else { SIND_TRY(up(ps.normal, ps.h_normal, np * 3, s)); SIND_TRY(up(m->curUR, m->h_curUR, nc, s)); }
-    SIND_TRY(up(m->curXY, m->h_curXY, nc * 2, s)); SIND_TRY(up(m->curOct, m->h_curOct, nc, s));
-    SIND_TRY(up(m->gstart, m->h_gstart, (size_t)B * 3073, s)); SIND_TRY(up(m->gidx, m->h_gidx, nc, s)); SIND_TRY(up(m->curTaken, m->h_curTaken, nc, s));
-    HIP_TRY(hipMemsetAsync(ps.nToMatch.p, 0, (size_t)B * 4, s));
-    sind::LocalArrays a{ps.pose.p, ps.nPts.p, m->nCur.p, ps.x3Dw.p, ps.normal.p, ps.maxDist.p, ps.minDist.p, ps.flags.p, ps.angle.p, ps.desc.p, m->curXY.p, m->curOct.p, m->curAng.p, m->curUR.p,
-                        m->curDesc.p, m->gstart.p, m->gidx.p, m->curTaken.p, ps.inView.p, ps.projXYR.p, ps.level.p, ps.viewCos.p, ps.nToMatch.p, ps.choice.p, m->minOwner.p, m->curPack.p, m->matchOfCur.p,
-                        m->nmatches.p, m->rounds.p};
-    SIND_TRY(sind::launch_project_points(p, a, B, reloc, s));
-    SIND_TRY(sind::launch_search_points(p, a, B, reloc, s));
-    if (wantFrustum) {
-        HIP_TRY(hipMemcpyAsync(ps.h_inView.data(), ps.inView.p, np, hipMemcpyDeviceToHost, s)); HIP_TRY(hipMemcpyAsync(ps.h_projXYR.data(), ps.projXYR.p, np * 12, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(ps.h_level.data(), ps.level.p, np * 4, hipMemcpyDeviceToHost, s)); HIP_TRY(hipMemcpyAsync(ps.h_viewCos.data(), ps.viewCos.p, np * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipMemcpyAsync(ps.h_nToMatch.data(), ps.nToMatch.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(m->h_match.data(), m->matchOfCur.p, nc * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(m->h_nm.data(), m->nmatches.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(m->h_rounds.data(), m->rounds.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    m->last_rounds = 0;
-    for (int b = 0; b < B; b++) {
-        const PointsFrame& q = fr[b]; const size_t o = (size_t)b * cp, n = (size_t)q.n_points;
-        if (q.in_view) cpy(q.in_view, &ps.h_inView[o], n); if (q.proj_xyr) cpy(q.proj_xyr, &ps.h_projXYR[o * 3], n * 12);
-        if (q.level) cpy(q.level, &ps.h_level[o], n * 4); if (q.view_cos) cpy(q.view_cos, &ps.h_viewCos[o], n * 4);
-        if (q.n_to_match) *q.n_to_match = ps.h_nToMatch[b];
-        cpy(q.match_of_cur, &m->h_match[(size_t)b * cc], (size_t)q.n_cur * 4); *q.nmatches = m->h_nm[b];
-        m->last_rounds = std::max(m->last_rounds, m->h_rounds[b]);
-    }
-    return SIND_OK;
-}
-
-static sind::LocalParams local_params(const sind_match* m, float th) {
-    sind::LocalParams p{}; const sind::MatchParams& c = m->prm;
-    p.fx = c.fx; p.fy = c.fy; p.cx = c.cx; p.cy = c.cy; p.bf = c.bf; std::memcpy(p.bounds, c.bounds, sizeof(p.bounds)); std::memcpy(p.scale, c.scale, sizeof(p.scale));
-    p.nlevels = c.nlevels; p.capCur = c.capCur; p.th = th;
-    return p;
-}
-
-extern "C" {
 
 int sind_match_reserve_map_points(sind_match* m, int cap_points) {
     if (!m || cap_points < 1) { sind_set_error("sind_match_reserve_map_points: bad arguments"); return SIND_E_ARG; }
@@ -237,10 +271,11 @@ int sind_match_local_map(sind_match* m, const sind_match_local* frames, int B, f
     std::vector<PointsFrame> fr(B);
     for (int b = 0; b < B; b++) {
         const sind_match_local& q = frames[b];
-        fr[b] = PointsFrame{q.Tcw, q.n_points, q.x3Dw, q.normal, q.max_dist, q.min_dist, q.flags, nullptr, q.desc, q.n_cur, q.cur_un_xy, q.cur_octave, nullptr, q.cur_u_right, q.cur_desc,
-                            q.grid_start, q.grid_idx, q.cur_taken, q.in_view, q.proj_xyr, q.level, q.view_cos, q.n_to_match, q.match_of_cur, q.nmatches};
+        fr[b] = PointsFrame{q.Tcw, q.n_points, q.x3Dw, q.normal, q.max_dist, q.min_dist, q.flags, nullptr, q.desc,
+                            Keys{q.n_cur, q.cur_un_xy, q.cur_octave, nullptr, q.cur_u_right, q.cur_desc, q.cur_taken, q.grid_start, q.grid_idx, nullptr},
+                            q.in_view, q.proj_xyr, q.level, q.view_cos, q.n_to_match, q.match_of_cur, q.nmatches};
     }
-    return run_points(m, m->local, fr, p, 0, "sind_match_local_map");
+    return run_points(m, m->local, fr, p, 0, "sind_match_local_map: frame");
 }
 
 int sind_match_by_projection_kf(sind_match* m, const sind_match_reloc* frames, int B, float th, int orb_dist, int check_orientation) {
@@ -251,112 +286,57 @@ int sind_match_by_projection_kf(sind_match* m, const sind_match_reloc* frames, i
     std::vector<PointsFrame> fr(B);
     for (int b = 0; b < B; b++) {
         const sind_match_reloc& q = frames[b];
-        fr[b] = PointsFrame{q.Tcw, q.n_points, q.x3Dw, nullptr, q.max_dist, q.min_dist, q.valid, q.kf_angle, q.desc, q.n_cur, q.cur_un_xy, q.cur_octave, q.cur_angle, nullptr, q.cur_desc,
-                            q.grid_start, q.grid_idx, q.cur_taken, nullptr, nullptr, nullptr, nullptr, nullptr, q.match_of_cur, q.nmatches};
+        fr[b] = PointsFrame{q.Tcw, q.n_points, q.x3Dw, nullptr, q.max_dist, q.min_dist, q.valid, q.kf_angle, q.desc,
+                            Keys{q.n_cur, q.cur_un_xy, q.cur_octave, q.cur_angle, nullptr, q.cur_desc, q.cur_taken, q.grid_start, q.grid_idx, nullptr},
+                            nullptr, nullptr, nullptr, nullptr, nullptr, q.match_of_cur, q.nmatches};
     }
-    return run_points(m, m->reloc, fr, p, 1, "sind_match_by_projection_kf");
+    return run_points(m, m->reloc, fr, p, 1, "sind_match_by_projection_kf: frame");
 }
-
-}  // extern "C"
-
-// ---- vocabulary-guided searches (match_bow.hip) ----
-static int sort_length(int n) { int p = 1; while (p < n) p <<= 1; return p; }
-
-static int check_nodes(const int* node, int n) { for (int i = 0; i < n; i++) if (node[i] < -1) return 0; return 1; }
-
-static sind::BowParams bow_params(const sind_match* m, int maxN) {
-    sind::BowParams p{}; const sind::MatchParams& c = m->prm;
-    p.fx = c.fx; p.fy = c.fy; p.cx = c.cx; p.cy = c.cy; std::memcpy(p.scale, c.scale, sizeof(p.scale)); p.capA = c.capLast; p.capB = c.capCur; p.sortLen = sort_length(maxN);
-    return p;
-}
-
-static sind::BowArrays bow_arrays(sind_match* m) {
-    sind_match::BowSide& w = m->bow;
-    return sind::BowArrays{m->nLast.p, m->nCur.p, w.nodeA.p, w.nodeB.p, m->lastFlags.p, m->lastAng.p, m->lastDesc.p, m->curAng.p, m->curDesc.p, w.pose.p, w.lastXY.p, w.lastUR.p, m->curTaken.p,
-                           m->curXY.p, m->curOct.p, m->curUR.p, w.sortedA.p, w.sortedB.p, w.segStart.p, w.nSeg.p, w.nValid.p, m->choice.p, m->matchOfCur.p, m->nmatches.p};
-}
-
-extern "C" {
 
 int sind_match_by_bow(sind_match* m, const sind_match_bow* pairs, int B, float nnratio, int check_orientation) {
-    const char* who = "sind_match_by_bow";
-    if (!m || !pairs || B < 1 || B > m->maxB) { sind_set_error("%s: bad arguments (B=%d, max %d)", who, B, m ? m->maxB : 0); return SIND_E_ARG; }
+    const char* who = "sind_match_by_bow: pair";
+    if (!m || !pairs || B < 1 || B > m->maxB) { sind_set_error("sind_match_by_bow: bad arguments (B=%d, max %d)", B, m ? m->maxB : 0); return SIND_E_ARG; }
     HIP_TRY(hipSetDevice(m->device));
-    const int cl = std::min(m->prm.capLast, BOW_MAX_KEYS), cc = std::min(m->prm.capCur, BOW_MAX_KEYS);
+    const int useA = K_NODE | K_FLAGS | K_ANGLE, useB = K_NODE | K_ANGLE, cl = std::min(m->last.cap, BOW_MAX_KEYS), cc = std::min(m->cur.cap, BOW_MAX_KEYS);
     int maxN = 1;
     for (int b = 0; b < B; b++) {
         const sind_match_bow& q = pairs[b];
-        if (q.n_kf < 0 || q.n_kf > cl || q.n_cur < 0 || q.n_cur > cc) { sind_set_error("%s: pair %d has %d / %d keypoints, capacity %d / %d", who, b, q.n_kf, q.n_cur, cl, cc); return SIND_E_CAPACITY; }
-        if (!q.nmatches || (q.n_kf && (!q.kf_node || !q.kf_valid || !q.kf_angle || !q.kf_desc)) || (q.n_cur && (!q.cur_node || !q.cur_angle || !q.cur_desc || !q.match_of_cur))) {
-            sind_set_error("%s: null array in pair %d", who, b); return SIND_E_ARG;
-        }
-        if (!check_nodes(q.kf_node, q.n_kf) || !check_nodes(q.cur_node, q.n_cur)) { sind_set_error("%s: node id below -1 in pair %d", who, b); return SIND_E_ARG; }
+        SIND_TRY(check(who, b, !q.nmatches || (q.n_cur && !q.match_of_cur) || (q.n_kf && !q.kf_valid), side_a(q), cl, useA, side_b(q), cc, useB));
         maxN = std::max(maxN, std::max(q.n_kf, q.n_cur));
     }
-    const size_t sl = m->prm.capLast, sc = m->prm.capCur;
-    SIND_TRY(m->bow.reserve((size_t)m->maxB, sl, sc));
-    sind_match::BowSide& w = m->bow;
-    for (int b = 0; b < B; b++) {
-        const sind_match_bow& q = pairs[b]; const size_t oa = b * sl, ob = b * sc, na = (size_t)q.n_kf, nb = (size_t)q.n_cur;
-        m->h_nLast[b] = q.n_kf; m->h_nCur[b] = q.n_cur;
-        cpy(&w.h_nodeA[oa], q.kf_node, na * 4); for (size_t i = 0; i < na; i++) m->h_lastFlags[oa + i] = q.kf_valid[i] ? 1 : 0;
-        cpy(&m->h_lastAng[oa], q.kf_angle, na * 4); cpy(&m->h_lastDesc[oa * 32], q.kf_desc, na * 32);
-        cpy(&w.h_nodeB[ob], q.cur_node, nb * 4); cpy(&m->h_curAng[ob], q.cur_angle, nb * 4); cpy(&m->h_curDesc[ob * 32], q.cur_desc, nb * 32);
-    }
-    hipStream_t s = m->stream; const size_t nl = (size_t)B * sl, nc = (size_t)B * sc;
-    SIND_TRY(up(m->nLast, m->h_nLast, B, s)); SIND_TRY(up(m->nCur, m->h_nCur, B, s)); SIND_TRY(up(w.nodeA, w.h_nodeA, nl, s)); SIND_TRY(up(w.nodeB, w.h_nodeB, nc, s));
-    SIND_TRY(up(m->lastFlags, m->h_lastFlags, nl, s)); SIND_TRY(up(m->lastAng, m->h_lastAng, nl, s)); SIND_TRY(up(m->curAng, m->h_curAng, nc, s));
-    HIP_TRY(hipMemcpyAsync(m->lastDesc.p, m->h_lastDesc.data(), nl * 32, hipMemcpyHostToDevice, s)); HIP_TRY(hipMemcpyAsync(m->curDesc.p, m->h_curDesc.data(), nc * 32, hipMemcpyHostToDevice, s));
+    SIND_TRY(m->reserve_bow());
+    for (int b = 0; b < B; b++) { const sind_match_bow& q = pairs[b]; m->last.stage(b, side_a(q), useA); m->cur.stage(b, side_b(q), useB); m->out[b] = {q.match_of_cur, q.n_cur, q.nmatches}; }
+    hipStream_t s = m->stream;
+    SIND_TRY(m->last.upload(B, useA, s)); SIND_TRY(m->cur.upload(B, useB, s));
     sind::BowParams p = bow_params(m, maxN); p.nnratio = nnratio; p.checkOrientation = check_orientation ? 1 : 0;
     SIND_TRY(sind::launch_match_by_bow(p, bow_arrays(m), B, s));
-    HIP_TRY(hipMemcpyAsync(m->h_match.data(), m->matchOfCur.p, nc * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(m->h_nm.data(), m->nmatches.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int b = 0; b < B; b++) { cpy(pairs[b].match_of_cur, &m->h_match[b * sc], (size_t)pairs[b].n_cur * 4); *pairs[b].nmatches = m->h_nm[b]; }
-    return SIND_OK;
+    return finish(m, B, m->matchOfCur, m->cur.cap, false);
 }
 
 int sind_match_for_triangulation(sind_match* m, const sind_match_tri* pairs, int B, int only_stereo, int check_orientation) {
-    const char* who = "sind_match_for_triangulation";
-    if (!m || !pairs || B < 1 || B > m->maxB) { sind_set_error("%s: bad arguments (B=%d, max %d)", who, B, m ? m->maxB : 0); return SIND_E_ARG; }
+    const char* who = "sind_match_for_triangulation: pair";
+    if (!m || !pairs || B < 1 || B > m->maxB) { sind_set_error("sind_match_for_triangulation: bad arguments (B=%d, max %d)", B, m ? m->maxB : 0); return SIND_E_ARG; }
     HIP_TRY(hipSetDevice(m->device));
-    const int cl = std::min(m->prm.capLast, BOW_MAX_KEYS), cc = std::min(m->prm.capCur, BOW_MAX_KEYS);
+    const int useA = K_NODE | K_FLAGS | K_XY | K_ANGLE | K_URIGHT, useB = useA | K_OCTAVE, cl = std::min(m->last.cap, BOW_MAX_KEYS), cc = std::min(m->cur.cap, BOW_MAX_KEYS);
     int maxN = 1;
     for (int b = 0; b < B; b++) {
         const sind_match_tri& q = pairs[b];
-        if (q.n1 < 0 || q.n1 > cl || q.n2 < 0 || q.n2 > cc) { sind_set_error("%s: pair %d has %d / %d keypoints, capacity %d / %d", who, b, q.n1, q.n2, cl, cc); return SIND_E_CAPACITY; }
-        if (!q.Tcw2 || !q.Cw1 || !q.F12 || !q.nmatches || (q.n1 && (!q.node1 || !q.has_mp1 || !q.un_xy1 || !q.angle1 || !q.u_right1 || !q.desc1 || !q.match12)) ||
-            (q.n2 && (!q.node2 || !q.has_mp2 || !q.un_xy2 || !q.octave2 || !q.angle2 || !q.u_right2 || !q.desc2))) { sind_set_error("%s: null array in pair %d", who, b); return SIND_E_ARG; }
-        if (!check_nodes(q.node1, q.n1) || !check_nodes(q.node2, q.n2)) { sind_set_error("%s: node id below -1 in pair %d", who, b); return SIND_E_ARG; }
-        for (int i = 0; i < q.n2; i++) if (q.octave2[i] < 0 || q.octave2[i] >= m->prm.nlevels) { sind_set_error("%s: octave %d outside [0,%d)", who, q.octave2[i], m->prm.nlevels); return SIND_E_ARG; }
+        SIND_TRY(check(who, b, !q.Tcw2 || !q.Cw1 || !q.F12 || !q.nmatches || (q.n1 && (!q.match12 || !q.has_mp1)) || (q.n2 && !q.has_mp2), side_a(q), cl, useA, side_b(q), cc, useB));
+        for (int i = 0; i < q.n2; i++) if (q.octave2[i] < 0 || q.octave2[i] >= m->prm.nlevels) { sind_set_error("%s %d: octave %d outside [0,%d)", who, b, q.octave2[i], m->prm.nlevels); return SIND_E_ARG; }
         maxN = std::max(maxN, std::max(q.n1, q.n2));
     }
-    const size_t sl = m->prm.capLast, sc = m->prm.capCur;
-    SIND_TRY(m->bow.reserve((size_t)m->maxB, sl, sc));
+    SIND_TRY(m->reserve_bow());
     sind_match::BowSide& w = m->bow;
     for (int b = 0; b < B; b++) {
-        const sind_match_tri& q = pairs[b]; const size_t oa = b * sl, ob = b * sc, na = (size_t)q.n1, nb = (size_t)q.n2;
-        sind::TriPose& ps = w.h_pose[b]; cpy(ps.Tcw2, q.Tcw2, sizeof(ps.Tcw2)); cpy(ps.Cw1, q.Cw1, sizeof(ps.Cw1)); cpy(ps.F12, q.F12, sizeof(ps.F12));
-        m->h_nLast[b] = q.n1; m->h_nCur[b] = q.n2;
-        cpy(&w.h_nodeA[oa], q.node1, na * 4); for (size_t i = 0; i < na; i++) m->h_lastFlags[oa + i] = q.has_mp1[i] ? 1 : 0;
-        cpy(&w.h_lastXY[oa * 2], q.un_xy1, na * 8); cpy(&m->h_lastAng[oa], q.angle1, na * 4); cpy(&w.h_lastUR[oa], q.u_right1, na * 4); cpy(&m->h_lastDesc[oa * 32], q.desc1, na * 32);
-        cpy(&w.h_nodeB[ob], q.node2, nb * 4); for (size_t i = 0; i < nb; i++) m->h_curTaken[ob + i] = q.has_mp2[i] ? 1 : 0;
-        cpy(&m->h_curXY[ob * 2], q.un_xy2, nb * 8); cpy(&m->h_curOct[ob], q.octave2, nb * 4); cpy(&m->h_curAng[ob], q.angle2, nb * 4); cpy(&m->h_curUR[ob], q.u_right2, nb * 4);
-        cpy(&m->h_curDesc[ob * 32], q.desc2, nb * 32);
+        const sind_match_tri& q = pairs[b];
+        sind::TriPose& ps = w.pose.h[b]; cpy(ps.Tcw2, q.Tcw2, sizeof(ps.Tcw2)); cpy(ps.Cw1, q.Cw1, sizeof(ps.Cw1)); cpy(ps.F12, q.F12, sizeof(ps.F12));
+        m->last.stage(b, side_a(q), useA); m->cur.stage(b, side_b(q), useB); m->out[b] = {q.match12, q.n1, q.nmatches};
     }
-    hipStream_t s = m->stream; const size_t nl = (size_t)B * sl, nc = (size_t)B * sc;
-    SIND_TRY(up(w.pose, w.h_pose, B, s)); SIND_TRY(up(m->nLast, m->h_nLast, B, s)); SIND_TRY(up(m->nCur, m->h_nCur, B, s)); SIND_TRY(up(w.nodeA, w.h_nodeA, nl, s)); SIND_TRY(up(w.nodeB, w.h_nodeB, nc, s));
-    SIND_TRY(up(m->lastFlags, m->h_lastFlags, nl, s)); SIND_TRY(up(w.lastXY, w.h_lastXY, nl * 2, s)); SIND_TRY(up(m->lastAng, m->h_lastAng, nl, s)); SIND_TRY(up(w.lastUR, w.h_lastUR, nl, s));
-    SIND_TRY(up(m->curTaken, m->h_curTaken, nc, s)); SIND_TRY(up(m->curXY, m->h_curXY, nc * 2, s)); SIND_TRY(up(m->curOct, m->h_curOct, nc, s)); SIND_TRY(up(m->curAng, m->h_curAng, nc, s));
-    SIND_TRY(up(m->curUR, m->h_curUR, nc, s));
-    HIP_TRY(hipMemcpyAsync(m->lastDesc.p, m->h_lastDesc.data(), nl * 32, hipMemcpyHostToDevice, s)); HIP_TRY(hipMemcpyAsync(m->curDesc.p, m->h_curDesc.data(), nc * 32, hipMemcpyHostToDevice, s));
+    hipStream_t s = m->stream;
+    SIND_TRY(w.pose.up(B, s)); SIND_TRY(m->last.upload(B, useA, s)); SIND_TRY(m->cur.upload(B, useB, s));
     sind::BowParams p = bow_params(m, maxN); p.onlyStereo = only_stereo ? 1 : 0; p.checkOrientation = check_orientation ? 1 : 0;
     SIND_TRY(sind::launch_match_for_triangulation(p, bow_arrays(m), B, s));
-    HIP_TRY(hipMemcpyAsync(w.h_match12.data(), m->choice.p, nl * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(m->h_nm.data(), m->nmatches.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int b = 0; b < B; b++) { cpy(pairs[b].match12, &w.h_match12[b * sl], (size_t)pairs[b].n1 * 4); *pairs[b].nmatches = m->h_nm[b]; }
-    return SIND_OK;
+    return finish(m, B, m->choice, m->last.cap, false);
 }
 
 }  // extern "C"

@@ -7,8 +7,8 @@
 
 struct sind_voc {
     int device = 0, cap = 0, maxB = 0, levels = 0, nNodes = 0; hipStream_t stream = nullptr;
-    DevBuf<int> childStart, child, wordId, n, outNode, outWord; DevBuf<uint32_t> nodeDesc, desc; DevBuf<uint8_t> stopped;
-    std::vector<int> h_n, h_node, h_word; std::vector<uint8_t> h_desc;
+    DevBuf<int> childStart, child, wordId; DevBuf<uint32_t> nodeDesc; DevBuf<uint8_t> stopped;                     // the tree
+    Staged<int> n, outNode, outWord; Staged<uint32_t> desc;                                                          // [maxB], [maxB][cap], descriptors as 8 words
 };
 
 // a tree rooted at node 0: CSR in range, every node but the root the child of exactly one node and reachable from the root, every leaf with a word
@@ -53,7 +53,6 @@ int sind_voc_create(const sind_voc_tree* tree, int cap, int max_batch, int devic
         hipMemcpy(v->stopped.p, stopped.data(), n, hipMemcpyHostToDevice) != hipSuccess || hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess) {
         delete v; sind_set_error("sind_voc_create: uploading the tree failed"); return SIND_E_HIP;
     }
-    v->h_n.resize(max_batch); v->h_node.resize(nd); v->h_word.resize(nd); v->h_desc.resize(nd * 32);
     *out = v; return SIND_OK;
 }
 
@@ -77,19 +76,17 @@ int sind_voc_transform(sind_voc* v, const uint8_t* const* desc, const int* n, in
     if (!maxN) return SIND_OK;
     HIP_TRY(hipSetDevice(v->device));
     const size_t cap = v->cap, nd = (size_t)B * cap;
-    for (int b = 0; b < B; b++) { v->h_n[b] = n[b]; if (n[b]) std::memcpy(&v->h_desc[b * cap * 32], desc[b], (size_t)n[b] * 32); }
+    for (int b = 0; b < B; b++) { v->n.h[b] = n[b]; if (n[b]) std::memcpy(&v->desc.h[b * cap * 8], desc[b], (size_t)n[b] * 32); }
     hipStream_t s = v->stream;
-    HIP_TRY(hipMemcpyAsync(v->n.p, v->h_n.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(v->desc.p, v->h_desc.data(), nd * 32, hipMemcpyHostToDevice, s));
+    SIND_TRY(v->n.up(B, s)); SIND_TRY(v->desc.up(nd * 8, s));
     const sind::VocTree tr{v->nNodes, v->childStart.p, v->child.p, v->nodeDesc.p, v->wordId.p, v->stopped.p};
-    SIND_TRY(sind::launch_voc_transform(tr, v->desc.p, v->n.p, v->cap, maxN, B, v->levels - levelsup, v->outNode.p, v->outWord.p, s));
-    HIP_TRY(hipMemcpyAsync(v->h_node.data(), v->outNode.p, nd * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(v->h_word.data(), v->outWord.p, nd * 4, hipMemcpyDeviceToHost, s));
+    SIND_TRY(sind::launch_voc_transform(tr, v->desc.d.p, v->n.d.p, v->cap, maxN, B, v->levels - levelsup, v->outNode.d.p, v->outWord.d.p, s));
+    SIND_TRY(v->outNode.down(nd, s)); SIND_TRY(v->outWord.down(nd, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (int b = 0; b < B; b++) {
         if (!n[b]) continue;
-        if (node_id && node_id[b]) std::memcpy(node_id[b], &v->h_node[b * cap], (size_t)n[b] * 4);
-        if (word_id && word_id[b]) std::memcpy(word_id[b], &v->h_word[b * cap], (size_t)n[b] * 4);
+        if (node_id && node_id[b]) std::memcpy(node_id[b], &v->outNode.h[b * cap], (size_t)n[b] * 4);
+        if (word_id && word_id[b]) std::memcpy(word_id[b], &v->outWord.h[b * cap], (size_t)n[b] * 4);
     }
     return SIND_OK;
 }

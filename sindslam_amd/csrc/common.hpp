@@ -148,6 +148,15 @@ struct PinnedBuf {
     PinnedBuf() = default; PinnedBuf(const PinnedBuf&) = delete; PinnedBuf& operator=(const PinnedBuf&) = delete;
 };
 
+// device array with its host staging copy (pageable): one alloc sizes both sides, up / down move the first count elements on a stream
+template <class T>
+struct Staged {
+    DevBuf<T> d; std::vector<T> h;
+    int alloc(size_t count) { SIND_TRY(d.alloc(count)); if (h.size() < count) h.resize(count); return SIND_OK; }
+    int up(size_t count, hipStream_t s) { HIP_TRY(hipMemcpyAsync(d.p, h.data(), count * sizeof(T), hipMemcpyHostToDevice, s)); return SIND_OK; }
+    int down(size_t count, hipStream_t s) { HIP_TRY(hipMemcpyAsync(h.data(), d.p, count * sizeof(T), hipMemcpyDeviceToHost, s)); return SIND_OK; }
+};
+
 #ifdef __HIPCC__
 // OpenCV-compatible scalar helpers (device)
 __device__ __forceinline__ int d_cvRound(float v) { return __float2int_rn(v); }          // round half to even

@@ -57,6 +57,25 @@ _u8 = lambda a: np.ascontiguousarray(a, np.uint8)
 _i32 = lambda a: np.ascontiguousarray(a, np.int32)
 
 
+def _cur(cur, *floats):
+    """the searched frame's fields of sind_match_pair / _local / _reloc, with the float arrays that the call reads besides un_xy"""
+    a = dict(n_cur=len(cur["octave"]), cur_un_xy=_f32(cur["un_xy"]), cur_octave=_i32(cur["octave"]), cur_desc=_u8(cur["desc"]), grid_start=_i32(cur["grid_start"]), grid_idx=_i32(cur["grid_idx"]))
+    a.update({"cur_" + k: _f32(cur[k]) for k in floats})
+    if cur.get("taken") is not None:
+        a["cur_taken"] = _u8(cur["taken"])
+    return a
+
+
+def _outputs(a, count, key="match_of_cur"):
+    """adds the two outputs that every search has to the fields of a frame: a[count] matches and their number"""
+    a[key] = np.full(max(a[count], 1), -1, np.int32); a["nmatches"] = np.zeros(1, np.int32)
+    return a
+
+
+def _matches(a, count, key="match_of_cur"):
+    return a[key][:a[count]].copy(), int(a["nmatches"][0])
+
+
 class ORBmatcher:
     """ORBmatcher(nnratio, checkOri) of the reference.  Provided: SearchByProjection(CurrentFrame, LastFrame, th, bMono) (TrackWithMotionModel),
     SearchLocalPoints = Frame::isInFrustum over the local map + SearchByProjection(F, vpMapPoints, th) (TrackLocalMap), and SearchByProjectionKF =
@@ -82,103 +101,71 @@ class ORBmatcher:
 
     __del__ = close
 
-    def SearchByProjection(self, pairs, th, bMono=False):
-        """pairs: list of (Tcw_cur, Tcw_last, last, cur) -> list of (match_of_cur i32 [n_cur], nmatches)"""
-        keep, arr = [], (_Pair * len(pairs))()
-        f32 = lambda a: np.ascontiguousarray(a, np.float32); u8 = lambda a: np.ascontiguousarray(a, np.uint8); i32 = lambda a: np.ascontiguousarray(a, np.int32)
-        outs = []
-        for b, (tc, tl, last, cur) in enumerate(pairs):
-            a = dict(Tcw_cur=f32(tc), Tcw_last=f32(tl), x3Dw=f32(last["x3Dw"]), last_valid=u8(last["valid"]), last_has_obs=u8(last["has_obs"]),
-                     last_octave=i32(last["octave"]), last_angle=f32(last["angle"]), last_desc=u8(last["desc"]), cur_un_xy=f32(cur["un_xy"]),
-                     cur_octave=i32(cur["octave"]), cur_angle=f32(cur["angle"]), cur_u_right=f32(cur["u_right"]), cur_desc=u8(cur["desc"]),
-                     grid_start=i32(cur["grid_start"]), grid_idx=i32(cur["grid_idx"]))
-            if cur.get("taken") is not None:
-                a["cur_taken"] = u8(cur["taken"])
-            nl, nc = len(a["last_valid"]), len(a["cur_octave"])
-            a["match_of_cur"] = np.full(max(nc, 1), -1, np.int32); a["nmatches"] = np.zeros(1, np.int32)
-            keep.append(a); arr[b].n_last = nl; arr[b].n_cur = nc
-            for k, v in a.items():
-                setattr(arr[b], k, v.ctypes.data if v.size else None)
-            outs.append((a["match_of_cur"], a["nmatches"], nc))
-        check(lib().sind_match_by_projection(self._h, arr, len(pairs), C.c_float(th), int(bMono), int(self.checkOri)), "sind_match_by_projection")
-        return [(m[:nc].copy(), int(n[0])) for m, n, nc in outs]
-
     def reserve_map_points(self, cap_points):
         """capacity for local map points per frame; needed once before SearchLocalPoints (or pass cap_points to the constructor)"""
         check(lib().sind_match_reserve_map_points(self._h, int(cap_points)), "sind_match_reserve_map_points")
 
-    def _call(self, fn, name, arr, keep, *args):
-        for b, a in enumerate(keep):
+    def _call(self, name, ctype, items, *args):
+        """One call of the C ABI on a batch.  items: per frame, the fields of its struct by name: counts as int, arrays as numpy (an empty one goes as NULL)"""
+        arr = (ctype * len(items))()
+        for q, a in zip(arr, items):
             for k, v in a.items():
-                setattr(arr[b], k, v.ctypes.data if v.size else None)
-        check(fn(self._h, arr, len(keep), *args), name)
+                setattr(q, k, v if isinstance(v, int) else v.ctypes.data if v.size else None)
+        check(getattr(lib(), name)(self._h, arr, len(items), *args), name)
+
+    def SearchByProjection(self, pairs, th, bMono=False):
+        """pairs: list of (Tcw_cur, Tcw_last, last, cur) -> list of (match_of_cur i32 [n_cur], nmatches)"""
+        items = [_outputs(dict(Tcw_cur=_f32(tc), Tcw_last=_f32(tl), n_last=len(last["valid"]), x3Dw=_f32(last["x3Dw"]), last_valid=_u8(last["valid"]), last_has_obs=_u8(last["has_obs"]),
+                               last_octave=_i32(last["octave"]), last_angle=_f32(last["angle"]), last_desc=_u8(last["desc"]), **_cur(cur, "angle", "u_right")), "n_cur")
+                 for tc, tl, last, cur in pairs]
+        self._call("sind_match_by_projection", _Pair, items, C.c_float(th), int(bMono), int(self.checkOri))
+        return [_matches(a, "n_cur") for a in items]
 
     def SearchLocalPoints(self, frames, th, viewingCosLimit=0.5):
         """frames: list of (Tcw, mp, cur); mp: x3Dw, normal, max_dist, min_dist, flags (bit0 candidate, bit1 observed), desc; cur as for SearchByProjection
         (angle unused).  Uses the constructor's nnratio.  -> list of dicts: match_of_cur i32 [n_cur] (index of the map point, -1: none), nmatches,
         in_view u8 [n], proj_xyr f32 [n, 3], level i32 [n], view_cos f32 [n], n_to_match."""
-        keep, arr, outs = [], (_Local * len(frames))(), []
-        for b, (T, mp, cur) in enumerate(frames):
-            a = dict(Tcw=_f32(T), x3Dw=_f32(mp["x3Dw"]), normal=_f32(mp["normal"]), max_dist=_f32(mp["max_dist"]), min_dist=_f32(mp["min_dist"]), flags=_u8(mp["flags"]),
-                     desc=_u8(mp["desc"]), cur_un_xy=_f32(cur["un_xy"]), cur_octave=_i32(cur["octave"]), cur_u_right=_f32(cur["u_right"]), cur_desc=_u8(cur["desc"]),
-                     grid_start=_i32(cur["grid_start"]), grid_idx=_i32(cur["grid_idx"]))
-            if cur.get("taken") is not None:
-                a["cur_taken"] = _u8(cur["taken"])
-            n, nc = len(a["flags"]), len(a["cur_octave"])
-            a.update(in_view=np.zeros(max(n, 1), np.uint8), proj_xyr=np.zeros((max(n, 1), 3), np.float32), level=np.zeros(max(n, 1), np.int32), view_cos=np.zeros(max(n, 1), np.float32),
-                     n_to_match=np.zeros(1, np.int32), match_of_cur=np.full(max(nc, 1), -1, np.int32), nmatches=np.zeros(1, np.int32))
-            keep.append(a); arr[b].n_points = n; arr[b].n_cur = nc; outs.append((a, n, nc))
-        self._call(lib().sind_match_local_map, "sind_match_local_map", arr, keep, C.c_float(th), C.c_float(self.nnratio), C.c_float(viewingCosLimit))
-        return [dict(match_of_cur=a["match_of_cur"][:nc].copy(), nmatches=int(a["nmatches"][0]), in_view=a["in_view"][:n].copy(), proj_xyr=a["proj_xyr"][:n].copy(),
-                     level=a["level"][:n].copy(), view_cos=a["view_cos"][:n].copy(), n_to_match=int(a["n_to_match"][0])) for a, n, nc in outs]
+        items = []
+        for T, mp, cur in frames:
+            n = len(mp["flags"])
+            items.append(_outputs(dict(Tcw=_f32(T), n_points=n, x3Dw=_f32(mp["x3Dw"]), normal=_f32(mp["normal"]), max_dist=_f32(mp["max_dist"]), min_dist=_f32(mp["min_dist"]), flags=_u8(mp["flags"]),
+                                       desc=_u8(mp["desc"]), in_view=np.zeros(max(n, 1), np.uint8), proj_xyr=np.zeros((max(n, 1), 3), np.float32), level=np.zeros(max(n, 1), np.int32),
+                                       view_cos=np.zeros(max(n, 1), np.float32), n_to_match=np.zeros(1, np.int32), **_cur(cur, "u_right")), "n_cur"))
+        self._call("sind_match_local_map", _Local, items, C.c_float(th), C.c_float(self.nnratio), C.c_float(viewingCosLimit))
+        return [dict(zip(("match_of_cur", "nmatches"), _matches(a, "n_cur")), n_to_match=int(a["n_to_match"][0]),
+                     **{k: a[k][:a["n_points"]].copy() for k in ("in_view", "proj_xyr", "level", "view_cos")}) for a in items]
 
     def SearchByProjectionKF(self, pairs, th, ORBdist):
         """pairs: list of (Tcw_cur, kf, cur); kf, per slot of the key frame: x3Dw, max_dist, min_dist, valid (pMP && !isBad && not already found), angle, desc;
         cur as for SearchByProjection, taken = the keypoint holds any map point.  At most `cap` slots.  -> list of (match_of_cur i32 [n_cur], nmatches)"""
-        keep, arr, outs = [], (_Reloc * len(pairs))(), []
-        for b, (T, kf, cur) in enumerate(pairs):
-            a = dict(Tcw=_f32(T), x3Dw=_f32(kf["x3Dw"]), max_dist=_f32(kf["max_dist"]), min_dist=_f32(kf["min_dist"]), valid=_u8(kf["valid"]), kf_angle=_f32(kf["angle"]),
-                     desc=_u8(kf["desc"]), cur_un_xy=_f32(cur["un_xy"]), cur_octave=_i32(cur["octave"]), cur_angle=_f32(cur["angle"]), cur_desc=_u8(cur["desc"]),
-                     grid_start=_i32(cur["grid_start"]), grid_idx=_i32(cur["grid_idx"]))
-            if cur.get("taken") is not None:
-                a["cur_taken"] = _u8(cur["taken"])
-            n, nc = len(a["valid"]), len(a["cur_octave"])
-            a.update(match_of_cur=np.full(max(nc, 1), -1, np.int32), nmatches=np.zeros(1, np.int32))
-            keep.append(a); arr[b].n_points = n; arr[b].n_cur = nc; outs.append((a, nc))
-        self._call(lib().sind_match_by_projection_kf, "sind_match_by_projection_kf", arr, keep, C.c_float(th), int(ORBdist), int(self.checkOri))
-        return [(a["match_of_cur"][:nc].copy(), int(a["nmatches"][0])) for a, nc in outs]
+        items = [_outputs(dict(Tcw=_f32(T), n_points=len(kf["valid"]), x3Dw=_f32(kf["x3Dw"]), max_dist=_f32(kf["max_dist"]), min_dist=_f32(kf["min_dist"]), valid=_u8(kf["valid"]),
+                               kf_angle=_f32(kf["angle"]), desc=_u8(kf["desc"]), **_cur(cur, "angle")), "n_cur") for T, kf, cur in pairs]
+        self._call("sind_match_by_projection_kf", _Reloc, items, C.c_float(th), int(ORBdist), int(self.checkOri))
+        return [_matches(a, "n_cur") for a in items]
 
     def SearchByBoW(self, pairs, nnratio=None):
         """pairs: list of (kf, cur); kf, per keypoint of the key frame: node (as ORBVocabulary.transform returns it), valid (pMP && !isBad), angle, desc (the key
         frame's own descriptors); cur: node, angle, desc.  nnratio None = the constructor's.  -> list of (match_of_cur i32 [n_cur], nmatches)"""
-        keep, arr, outs = [], (_Bow * len(pairs))(), []
-        for b, (kf, cur) in enumerate(pairs):
-            a = dict(kf_node=_i32(kf["node"]), kf_valid=_u8(kf["valid"]), kf_angle=_f32(kf["angle"]), kf_desc=_u8(kf["desc"]),
-                     cur_node=_i32(cur["node"]), cur_angle=_f32(cur["angle"]), cur_desc=_u8(cur["desc"]))
-            n, nc = len(a["kf_node"]), len(a["cur_node"])
-            a.update(match_of_cur=np.full(max(nc, 1), -1, np.int32), nmatches=np.zeros(1, np.int32))
-            keep.append(a); arr[b].n_kf = n; arr[b].n_cur = nc; outs.append((a, nc))
-        self._call(lib().sind_match_by_bow, "sind_match_by_bow", arr, keep, C.c_float(self.nnratio if nnratio is None else nnratio), int(self.checkOri))
-        return [(a["match_of_cur"][:nc].copy(), int(a["nmatches"][0])) for a, nc in outs]
+        items = [_outputs(dict(n_kf=len(kf["node"]), kf_node=_i32(kf["node"]), kf_valid=_u8(kf["valid"]), kf_angle=_f32(kf["angle"]), kf_desc=_u8(kf["desc"]),
+                               n_cur=len(cur["node"]), cur_node=_i32(cur["node"]), cur_angle=_f32(cur["angle"]), cur_desc=_u8(cur["desc"])), "n_cur") for kf, cur in pairs]
+        self._call("sind_match_by_bow", _Bow, items, C.c_float(self.nnratio if nnratio is None else nnratio), int(self.checkOri))
+        return [_matches(a, "n_cur") for a in items]
 
     def SearchForTriangulation(self, pairs, bOnlyStereo=False):
         """pairs: list of (Tcw2, Cw1, F12, kf1, kf2); kf1, per keypoint: node, has_mp, un_xy, angle, u_right, desc; kf2: the same and octave.
         -> list of (match12 i32 [n1], nmatches, matched_pairs i64 [nmatches, 2] = vMatchedPairs, ascending idx1)"""
-        keep, arr, outs = [], (_Tri * len(pairs))(), []
-        for b, (T2, Cw1, F12, k1, k2) in enumerate(pairs):
-            a = dict(Tcw2=_f32(T2), Cw1=_f32(Cw1), F12=_f32(F12))
+        items = []
+        for T2, Cw1, F12, k1, k2 in pairs:
+            a = dict(Tcw2=_f32(T2), Cw1=_f32(Cw1), F12=_f32(F12), octave2=_i32(k2["octave"]))
             for s, k in (("1", k1), ("2", k2)):
-                a.update({"node" + s: _i32(k["node"]), "has_mp" + s: _u8(k["has_mp"]), "un_xy" + s: _f32(k["un_xy"]), "angle" + s: _f32(k["angle"]), "u_right" + s: _f32(k["u_right"]),
-                          "desc" + s: _u8(k["desc"])})
-            a["octave2"] = _i32(k2["octave"])
-            n1, n2 = len(a["node1"]), len(a["node2"])
-            a.update(match12=np.full(max(n1, 1), -1, np.int32), nmatches=np.zeros(1, np.int32))
-            keep.append(a); arr[b].n1 = n1; arr[b].n2 = n2; outs.append((a, n1))
-        self._call(lib().sind_match_for_triangulation, "sind_match_for_triangulation", arr, keep, int(bOnlyStereo), int(self.checkOri))
+                a.update({"n" + s: len(k["node"]), "node" + s: _i32(k["node"]), "has_mp" + s: _u8(k["has_mp"]), "un_xy" + s: _f32(k["un_xy"]), "angle" + s: _f32(k["angle"]),
+                          "u_right" + s: _f32(k["u_right"]), "desc" + s: _u8(k["desc"])})
+            items.append(_outputs(a, "n1", "match12"))
+        self._call("sind_match_for_triangulation", _Tri, items, int(bOnlyStereo), int(self.checkOri))
         res = []
-        for a, n1 in outs:
-            m = a["match12"][:n1].copy(); i1 = np.nonzero(m >= 0)[0]
-            res.append((m, int(a["nmatches"][0]), np.stack([i1, m[i1]], 1).astype(np.int64)))
+        for m, n in (_matches(a, "n1", "match12") for a in items):
+            i1 = np.nonzero(m >= 0)[0]
+            res.append((m, n, np.stack([i1, m[i1]], 1).astype(np.int64)))
         return res
 
     def last_rounds(self):
