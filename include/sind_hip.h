@@ -484,6 +484,88 @@ typedef struct sind_match_tri {
 } sind_match_tri;
 int sind_match_for_triangulation(sind_match* m, const sind_match_tri* pairs, int B, int only_stereo, int check_orientation);
 
+/* Projections of map points into a key frame: the local mapper's Fuse and the three searches of the loop closer.  All run on the sind_match handle; intrinsics,
+ * bounds, scale factors and nlevels are the handle's, map points per item are limited by sind_match_reserve_map_points (SIND_E_STATE before it) and key-frame
+ * keypoints by cap_cur.  A key frame keeps mnMinX .. mnMaxY as int (include/KeyFrame.h:185-188): the handle's bounds are truncated toward zero for
+ * KeyFrame::IsInImage and the window, and mfGridElementWidthInv / HeightInv stay those of the float bounds, as the KeyFrame constructor copies them.
+ * Common to the three calls:
+ *   KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:569-608), KeyFrame::IsInImage (:610-613: the upper bounds are strict),
+ *   MapPoint::PredictScale(dist, KeyFrame*) (src/MapPoint.cc:385-400; std::log as for sind_match_local_map), ORBmatcher::DescriptorDistance.
+ *   map points, per entry i of the list:  x3Dw = pMP->GetWorldPos(), normal = pMP->GetNormal(), max_dist / min_dist = the members mfMaxDistance / mfMinDistance
+ *       (the 1.2f / 0.8f of Get...DistanceInvariance() are applied inside), desc = pMP->GetDescriptor() (32 B), valid: see each call
+ *   key frame, per keypoint:  kf_un_xy / kf_octave = mvKeysUn, kf_desc = mDescriptors rows, grid_start / grid_idx = mGrid in the sind_frame_post_orb layout
+ * Errors: an item over capacity -> SIND_E_CAPACITY; a NULL array with a non-zero count, a malformed grid or a kf_octave outside [0, nlevels) -> SIND_E_ARG;
+ * nothing is launched and the outputs are untouched.  A count of 0 is valid.  The small-matrix algebra (Scw decomposition, sR12, sR21, t21) is done on the host
+ * once per item, rounded as csrc/match_local.hip (5)-(7) defines it.
+ *
+ * sind_match_fuse.  Replaces, for B (key frame, point list) items at once, the search of
+ *   int ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th)               src/ORBmatcher.cc:825-949   (sim3 = 0)
+ *   int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th, vector<MapPoint*>& vpReplacePoint)   :977-1079   (sim3 = 1)
+ * (LocalMapping::SearchInNeighbors, th 3; LoopClosing::SearchAndFuse, th 4).
+ *   Tcw: sim3 = 0: pKF->GetPose(); sim3 = 1: Scw, decomposed as :986-990 (4x4 row-major, rows 0..2 are read)
+ *   valid: sim3 = 0: pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF); sim3 = 1: !pMP->isBad() && !spAlreadyFound.count(pMP)
+ *   kf_u_right = mvuRight: read for sim3 = 0 only (the chi-square test :914-938, mvInvLevelSigma2[l] = 1.0f / (scale[l] * scale[l])); may be NULL for sim3 = 1
+ * Outputs, per point: best_idx[i] = bestIdx if bestDist <= TH_LOW (50), else -1; best_dist[i] = bestDist where best_idx[i] >= 0, else -1;
+ * *nfused = number of best_idx[i] >= 0 = the function's return value for the inputs as given.
+ * The tail on the object graph (:952-971, :1082-1096: GetMapPoint(bestIdx), Replace, AddObservation, AddMapPoint, vpReplacePoint[iMP]) stays with the caller,
+ * who replays it in point order over the entries with best_idx[i] >= 0.  For sim3 = 0 the caller re-tests isBad() || IsInKeyFrame(pKF) before applying entry i
+ * and skips it, uncounted, if true.  This replay reproduces the reference: the search of point i reads only point i's own position, normal, distances and
+ * descriptor and the key frame's immutable arrays (mvKeysUn, mvuRight, mDescriptors, mGrid), and within one call an earlier iteration changes a point's own data
+ * only (a) for a point that was already in pKF (Replace on pMPinKF: such a point is filtered by `valid`, and by the re-test if it got into pKF during the call),
+ * or (b) for a point that has itself been processed (Replace makes it bad after its own iteration; AddObservation does not touch what the search reads).  The
+ * survivor of a Replace gets a new descriptor only through ComputeDistinctiveDescriptors, and the survivor is either pMPinKF (case a) or pMP, already
+ * processed (case b).  A repeated list entry was either added to pKF (IsInKeyFrame) or replaced (isBad) by its first occurrence: the re-test catches both.
+ * For sim3 = 1 nothing in the loop changes what `valid` is made of: spAlreadyFound is a snapshot in the reference (:993) and the loop sets no bad flag.
+ * NOT exact: batching one point list over several target key frames (LocalMapping.cc:485-490) searches every key frame against the list as it was on entry,
+ * whereas the reference lets key frame k's Replace calls change the list for key frame k+1 (a bad flag, a recomputed descriptor).  Exactness needs one item
+ * per call with refreshed inputs.
+ */
+typedef struct sind_match_fuse_item {
+    const float* Tcw;                                                                     /* pose (sim3 = 0) or Scw (sim3 = 1) */
+    int n_points; const float* x3Dw; const float* normal; const float* max_dist; const float* min_dist; const uint8_t* valid; const uint8_t* desc;
+    int n_kf; const float* kf_un_xy; const int* kf_octave; const float* kf_u_right; const uint8_t* kf_desc; const int* grid_start; const int* grid_idx;
+    int* best_idx; int* best_dist; int* nfused;                                           /* outputs (host): [n_points], [n_points], [1] */
+} sind_match_fuse_item;
+int sind_match_fuse(sind_match* m, const sind_match_fuse_item* items, int B, float th, int sim3);
+
+/* sind_match_by_projection_sim3.  Replaces, for B items at once,
+ *   int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched, int th)   src/ORBmatcher.cc:290-403
+ * (LoopClosing::ComputeSim3, th 10).  Points as above with valid = !pMP->isBad() && !spAlreadyFound.count(pMP); the key frame as above without kf_u_right, and
+ * kf_taken[idx] = vpMatched[idx] != NULL on entry (NULL = none).  th is the reference's int: the radius is (float)th * mvScaleFactors[level].
+ * Output: match_of_kf[idx] = index i of the point the reference writes to vpMatched[idx] (-1: untouched); *nmatches = the function's return value.
+ * The reference's order is kept: a keypoint matched by point j is skipped by every later point, before its distance is computed (:375).
+ * sind_match_last_rounds reports the resolution rounds this took.
+ */
+typedef struct sind_match_proj_sim3 {
+    const float* Scw;
+    int n_points; const float* x3Dw; const float* normal; const float* max_dist; const float* min_dist; const uint8_t* valid; const uint8_t* desc;
+    int n_kf; const float* kf_un_xy; const int* kf_octave; const uint8_t* kf_desc; const int* grid_start; const int* grid_idx; const uint8_t* kf_taken;
+    int* match_of_kf; int* nmatches;                                                      /* outputs (host): [n_kf], [1] */
+} sind_match_proj_sim3;
+int sind_match_by_projection_sim3(sind_match* m, const sind_match_proj_sim3* items, int B, int th);
+
+/* sind_match_by_sim3.  Replaces, for B (pKF1, pKF2) pairs at once,
+ *   int ORBmatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12, const float& s12, const cv::Mat& R12, const cv::Mat& t12, const float th)
+ *                                                                                                      src/ORBmatcher.cc:1102-1326
+ * (LoopClosing::ComputeSim3, th 7.5).  Each side holds at most min(cap_last, cap_cur) slots; sind_match_reserve_map_points is not needed.
+ *   T1w, T2w = poses of pKF1 / pKF2 (4x4 row-major, rows 0..2 are read), s12, R12 (3x3 row-major), t12 (3); sR12, sR21 and t21 are formed as :1119-1121
+ *   per side s (1, 2) and slot i of pKFs->GetMapPointMatches():  valid = pMP && !pMP->isBad() && !vbAlreadyMatcheds[i] (the caller builds vbAlreadyMatched1/2 as
+ *       :1132-1142), x3Dw / max_dist / min_dist / mp_desc = pMP->GetWorldPos(), mfMaxDistance, mfMinDistance, pMP->GetDescriptor() of the map point in that slot;
+ *       the slot's own keypoint: un_xy / octave = mvKeysUn[i], kf_desc = row i of mDescriptors; grid_start / grid_idx = the side's mGrid
+ * Output: match12[i1] = idx2 where vnMatch1[i1] == idx2 && vnMatch2[idx2] == i1, else -1: the slots whose vpMatches12[i1] the reference sets to
+ * vpMapPoints2[idx2]; *nfound = the function's return value.  TH_HIGH = 100; no viewing-angle test; the distance is the norm of the camera-frame vector.
+ */
+typedef struct sind_match_sim3_side {
+    int n; const uint8_t* valid; const float* x3Dw; const float* max_dist; const float* min_dist; const uint8_t* mp_desc;
+    const float* un_xy; const int* octave; const uint8_t* kf_desc; const int* grid_start; const int* grid_idx;
+} sind_match_sim3_side;
+typedef struct sind_match_sim3_pair {
+    const float* T1w; const float* T2w; float s12; const float* R12; const float* t12;
+    sind_match_sim3_side side1, side2;
+    int* match12; int* nfound;                                                            /* outputs (host): [side1.n], [1] */
+} sind_match_sim3_pair;
+int sind_match_by_sim3(sind_match* m, const sind_match_sim3_pair* pairs, int B, float th);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of
  *   generatePointCloud(imgRGB, imgDepth, imgDepthLast, imgDynaMask, imgDynaMaskLast, imgLabel, poseRelative, Twc)

@@ -91,6 +91,20 @@ struct sind_match {
     struct BowSide {
         Staged<sind::TriPose> pose; DevBuf<int> segStart, nSeg, nValid; DevBuf<int2> sortedA, sortedB;
     } bow;
+    // projections into a key frame (match_fuse.hip), on first use.  fuse: sind_match_fuse, [maxB] items of local.cap points and cap_cur keypoints; sim3: sind_match_by_sim3,
+    // [2 maxB] items (pair b, side s -> item 2b + s) of min(cap_last, cap_cur) slots, which are points and keypoints at once
+    struct KfSide {
+        int capP = 0, capK = 0;
+        Staged<sind::KfPose> pose; Staged<int> nP, gridStart, gridIdx, bestIdx, bestDist, count, match12; Staged<float> x3Dw, normal, maxDist, minDist; Staged<uint8_t> valid;
+        Staged<uint32_t> ptDesc, keyDesc; Staged<float4> pack;
+        int reserve(size_t items, int cp, int ck) {
+            const size_t np = items * (size_t)cp, nk = items * (size_t)ck; int r = SIND_OK;
+            if ((r = pose.alloc(items)) || (r = nP.alloc(items)) || (r = count.alloc(items)) || (r = gridStart.alloc(items * (GRID_CELLS + 1))) || (r = gridIdx.alloc(nk)) ||
+                (r = bestIdx.alloc(np)) || (r = bestDist.alloc(np)) || (r = match12.alloc(np)) || (r = x3Dw.alloc(np * 3)) || (r = normal.alloc(np * 3)) || (r = maxDist.alloc(np)) ||
+                (r = minDist.alloc(np)) || (r = valid.alloc(np)) || (r = ptDesc.alloc(np * DESC_WORDS)) || (r = keyDesc.alloc(nk * DESC_WORDS)) || (r = pack.alloc(nk))) return r;
+            capP = cp; capK = ck; return SIND_OK;
+        }
+    } fuse, sim3;
     int reserve_bow() {
         const size_t B = maxB, nl = B * prm.capLast, nc = B * prm.capCur; int r = SIND_OK;
         (r = last.node.alloc(nl)) || (r = last.xy.alloc(nl * 2)) || (r = last.uRight.alloc(nl)) || (r = cur.node.alloc(nc)) || (r = choice.alloc(nl)) || (r = bow.pose.alloc(B)) ||
@@ -119,15 +133,39 @@ void forward_backward(const float* Tc, const float* Tl, float mb, bool mono, int
     fwd = tlc[2] > mb && !mono; bwd = -tlc[2] > mb && !mono;
 }
 
-// ---- local-map search and relocalisation search (match_local.hip) ----
+// mOw = -Rcw^T * tcw of rows 0..2 of a pose (match_local.hip (2))
+void camera_centre(const float* T, float* Ow) {
+    for (int r = 0; r < 3; r++) { double s = 0; for (int k = 0; k < 3; k++) s += (double)T[4 * k + r] * (double)T[4 * k + 3]; Ow[r] = (float)(s * -1.0); }
+}
+
+// Scw -> rows 0..2 of [Rcw | tcw] (ORBmatcher.cc:298-302, :986-989; match_local.hip (5), (6))
+void decompose_scw(const float* S, float* T) {
+    double d = 0; for (int k = 0; k < 3; k++) d += (double)S[k] * (double)S[k];
+    const float scw = (float)std::sqrt(d), inv = (float)(1.0 / (double)scw);
+    for (int k = 0; k < 12; k++) T[k] = S[k] * inv;
+}
+
+// a key frame's int bounds and the grid cell sizes it copies from its frame (include/KeyFrame.h:185-188; Frame constructors, src/Frame.cc:155-156)
+void kf_bounds(const float* b, float* kb, float* gridInv) {
+    for (int k = 0; k < 4; k++) kb[k] = std::trunc(b[k]);
+    gridInv[0] = 64.f / (float)(b[1] - b[0]); gridInv[1] = 48.f / (float)(b[3] - b[2]);
+}
+
+int check_octaves(const char* who, int b, const Keys& q, int nlevels) {
+    for (int i = 0; i < q.n; i++) if (q.octave[i] < 0 || q.octave[i] >= nlevels) { sind_set_error("%s %d: octave %d outside [0,%d)", who, b, q.octave[i], nlevels); return SIND_E_ARG; }
+    return SIND_OK;
+}
+
+// ---- local-map search, relocalisation search (match_local.hip) and SearchByProjection(pKF, Scw) (mode 2: projection of match_fuse.hip) ----
 struct PointsFrame {                                               // one frame of either call, the public structs flattened to one shape
     const float* Tcw; int n_points; const float* x3Dw; const float* normal; const float* max_dist; const float* min_dist; const uint8_t* flags; const float* angle; const uint8_t* desc;
     Keys cur;
     uint8_t* in_view; float* proj_xyr; int* level; float* view_cos; int* n_to_match; int* match_of_cur; int* nmatches;
 };
 
-int run_points(sind_match* m, sind_match::PointSide& ps, const std::vector<PointsFrame>& fr, sind::LocalParams p, int reloc, const char* who) {
-    const int B = (int)fr.size(), cp = ps.cap, use = K_XY | K_OCTAVE | K_FLAGS | K_GRID | (reloc ? K_ANGLE : K_URIGHT);
+int run_points(sind_match* m, sind_match::PointSide& ps, const std::vector<PointsFrame>& fr, sind::LocalParams p, int mode, const char* who) {
+    const bool reloc = mode == 1, closing = mode != 0, normals = mode != 1;                  // modes 1 and 2: every assignment closes its keypoint (:1541, :396)
+    const int B = (int)fr.size(), cp = ps.cap, use = K_XY | K_OCTAVE | K_FLAGS | K_GRID | (mode == 1 ? K_ANGLE : mode == 0 ? K_URIGHT : 0);
     Side& c = m->cur;
     p.capPts = cp;
     p.logScaleFactor = (float)std::log((double)p.scale[1]);       // Frame.cc:71 with log as match_local.hip defines it
@@ -135,28 +173,30 @@ int run_points(sind_match* m, sind_match::PointSide& ps, const std::vector<Point
     for (int b = 0; b < B; b++) {
         const PointsFrame& q = fr[b];
         const Keys pts{q.n_points, nullptr, nullptr, reloc ? q.angle : nullptr, nullptr, q.desc, nullptr, nullptr, nullptr, nullptr};      // as far as check() goes
-        SIND_TRY(check(who, b, !q.Tcw || !q.match_of_cur || !q.nmatches || (q.n_points && (!q.x3Dw || !q.max_dist || !q.min_dist || !q.flags || (!reloc && !q.normal))), pts, cp, reloc ? K_ANGLE : 0,
+        SIND_TRY(check(who, b, !q.Tcw || !q.match_of_cur || !q.nmatches || (q.n_points && (!q.x3Dw || !q.max_dist || !q.min_dist || !q.flags || (normals && !q.normal))), pts, cp, reloc ? K_ANGLE : 0,
                        q.cur, c.cap, use));
+        if (mode == 2) SIND_TRY(check_octaves(who, b, q.cur, p.nlevels));
         wantFrustum = wantFrustum || q.in_view || q.proj_xyr || q.level || q.view_cos;
         sind::LocalPose& po = ps.pose.h[b]; cpy(po.Tcw, q.Tcw, sizeof(po.Tcw));
-        for (int r = 0; r < 3; r++) { double s = 0; for (int k = 0; k < 3; k++) s += (double)q.Tcw[4 * k + r] * (double)q.Tcw[4 * k + 3]; po.Ow[r] = (float)(s * -1.0); }   // -Rcw^T * tcw
+        camera_centre(q.Tcw, po.Ow);
         const size_t o = (size_t)b * cp, n = (size_t)q.n_points;
         ps.n.h[b] = q.n_points; put(ps.x3Dw, o * 3, q.x3Dw, n * 3); put(ps.maxDist, o, q.max_dist, n); put(ps.minDist, o, q.min_dist, n); put(ps.desc, o * DESC_WORDS, q.desc, n * DESC_WORDS);
-        if (reloc) { put(ps.angle, o, q.angle, n); for (size_t i = 0; i < n; i++) ps.flags.h[o + i] = q.flags[i] ? 3 : 0; }     // every assignment closes its keypoint (:1541)
-        else { put(ps.normal, o * 3, q.normal, n * 3); for (size_t i = 0; i < n; i++) ps.flags.h[o + i] = q.flags[i] & 3; }
+        if (reloc) put(ps.angle, o, q.angle, n);
+        if (normals) put(ps.normal, o * 3, q.normal, n * 3);
+        for (size_t i = 0; i < n; i++) ps.flags.h[o + i] = closing ? (q.flags[i] ? 3 : 0) : q.flags[i] & 3;
         c.stage(b, q.cur, use);
         m->out[b] = {q.match_of_cur, q.cur.n, q.nmatches};
     }
     SIND_TRY(m->curPack.alloc((size_t)m->maxB * c.cap));
     hipStream_t s = m->stream; const size_t np = (size_t)B * cp;
     SIND_TRY(ps.pose.up(B, s)); SIND_TRY(ps.n.up(B, s)); SIND_TRY(ps.x3Dw.up(np * 3, s)); SIND_TRY(ps.maxDist.up(np, s)); SIND_TRY(ps.minDist.up(np, s)); SIND_TRY(ps.flags.up(np, s));
-    SIND_TRY(ps.desc.up(np * DESC_WORDS, s)); SIND_TRY(reloc ? ps.angle.up(np, s) : ps.normal.up(np * 3, s)); SIND_TRY(c.upload(B, use, s));
+    SIND_TRY(ps.desc.up(np * DESC_WORDS, s)); if (reloc) SIND_TRY(ps.angle.up(np, s)); if (normals) SIND_TRY(ps.normal.up(np * 3, s)); SIND_TRY(c.upload(B, use, s));
     HIP_TRY(hipMemsetAsync(ps.nToMatch.d.p, 0, (size_t)B * 4, s));
     sind::LocalArrays a{ps.pose.d.p, ps.n.d.p, c.n.d.p, ps.x3Dw.d.p, ps.normal.d.p, ps.maxDist.d.p, ps.minDist.d.p, ps.flags.d.p, ps.angle.d.p, ps.desc.d.p, c.xy.d.p, c.octave.d.p, c.angle.d.p,
                         c.uRight.d.p, c.desc.d.p, c.gridStart.d.p, c.gridIdx.d.p, c.flags.d.p, ps.inView.d.p, ps.projXYR.d.p, ps.level.d.p, ps.viewCos.d.p, ps.nToMatch.d.p, ps.choice.p,
                         m->minOwner.p, m->curPack.p, m->matchOfCur.d.p, m->nmatches.d.p, m->rounds.d.p};
-    SIND_TRY(sind::launch_project_points(p, a, B, reloc, s));
-    SIND_TRY(sind::launch_search_points(p, a, B, reloc, s));
+    SIND_TRY(mode == 2 ? sind::launch_project_kf(p, a, B, s) : sind::launch_project_points(p, a, B, mode, s));
+    SIND_TRY(sind::launch_search_points(p, a, B, mode, s));
     if (wantFrustum) { SIND_TRY(ps.inView.down(np, s)); SIND_TRY(ps.projXYR.down(np * 3, s)); SIND_TRY(ps.level.down(np, s)); SIND_TRY(ps.viewCos.down(np, s)); }
     SIND_TRY(ps.nToMatch.down(B, s));
     SIND_TRY(finish(m, B, m->matchOfCur, c.cap, true));
@@ -175,6 +215,51 @@ sind::LocalParams local_params(const sind_match* m, float th) {
     p.nlevels = c.nlevels; p.capCur = c.capCur; p.th = th;
     return p;
 }
+
+// ---- independent projections into a key frame (match_fuse.hip) ----
+sind::KfParams kf_params(const sind_match* m, float th, int thDist, int capP, int capK) {
+    sind::KfParams p{}; const sind::MatchParams& c = m->prm;
+    p.fx = c.fx; p.fy = c.fy; p.cx = c.cx; p.cy = c.cy; p.bf = c.bf; kf_bounds(c.bounds, p.bounds, p.gridInv); std::memcpy(p.scale, c.scale, sizeof(p.scale));
+    for (int l = 0; l < c.nlevels; l++) p.invSigma2[l] = 1.0f / (c.scale[l] * c.scale[l]);       // mvLevelSigma2, mvInvLevelSigma2 (src/ORBextractor.cc:425-431)
+    p.nlevels = c.nlevels; p.th = th; p.thDist = thDist; p.capPts = capP; p.capKeys = capK;
+    p.logScaleFactor = (float)std::log((double)p.scale[1]);
+    return p;
+}
+
+struct KfPoints { int n; const float* x3Dw; const float* normal; const float* maxDist; const float* minDist; const uint8_t* valid; const uint8_t* desc; };
+
+int check_kf(const char* who, int b, bool otherNull, const KfPoints& pt, int capP, bool normals, const Keys& k, int capK, int useK, int nlevels) {
+    const Keys pts{pt.n, nullptr, nullptr, nullptr, nullptr, pt.desc, nullptr, nullptr, nullptr, nullptr};
+    SIND_TRY(check(who, b, otherNull || (pt.n && (!pt.x3Dw || !pt.maxDist || !pt.minDist || !pt.valid || (normals && !pt.normal))), pts, capP, 0, k, capK, useK));
+    return check_octaves(who, b, k, nlevels);
+}
+
+// item q of a KfSide: its points and the keypoints an item searches (its own, or for sind_match_by_sim3 those the other side of the pair searches)
+void stage_kf(sind_match::KfSide& w, int q, const KfPoints& pt, const Keys& k) {
+    const size_t o = (size_t)q * w.capP, n = (size_t)pt.n, co = (size_t)q * w.capK;
+    w.nP.h[q] = pt.n; put(w.x3Dw, o * 3, pt.x3Dw, n * 3); if (pt.normal) put(w.normal, o * 3, pt.normal, n * 3); put(w.maxDist, o, pt.maxDist, n); put(w.minDist, o, pt.minDist, n);
+    put(w.valid, o, pt.valid, n); put(w.ptDesc, o * DESC_WORDS, pt.desc, n * DESC_WORDS);
+    put(w.keyDesc, co * DESC_WORDS, k.desc, (size_t)k.n * DESC_WORDS);
+    put(w.gridStart, (size_t)q * (GRID_CELLS + 1), k.gridStart, GRID_CELLS + 1); put(w.gridIdx, co, k.gridIdx, (size_t)k.gridStart[GRID_CELLS]);
+    for (int c = 0; c < k.n; c++) { float4 r; r.x = k.xy[2 * c]; r.y = k.xy[2 * c + 1]; r.z = k.uRight ? k.uRight[c] : 0.f; int oc = k.octave[c]; std::memcpy(&r.w, &oc, 4); w.pack.h[co + c] = r; }
+}
+
+int upload_kf(sind_match::KfSide& w, int items, bool normals, hipStream_t s) {
+    const size_t np = (size_t)items * w.capP, nk = (size_t)items * w.capK;
+    SIND_TRY(w.pose.up(items, s)); SIND_TRY(w.nP.up(items, s)); SIND_TRY(w.x3Dw.up(np * 3, s)); if (normals) SIND_TRY(w.normal.up(np * 3, s));
+    SIND_TRY(w.maxDist.up(np, s)); SIND_TRY(w.minDist.up(np, s)); SIND_TRY(w.valid.up(np, s)); SIND_TRY(w.ptDesc.up(np * DESC_WORDS, s)); SIND_TRY(w.keyDesc.up(nk * DESC_WORDS, s));
+    SIND_TRY(w.gridStart.up((size_t)items * (GRID_CELLS + 1), s)); SIND_TRY(w.gridIdx.up(nk, s)); SIND_TRY(w.pack.up(nk, s));
+    HIP_TRY(hipMemsetAsync(w.count.d.p, 0, (size_t)items * sizeof(int), s));
+    return SIND_OK;
+}
+
+sind::KfArrays kf_arrays(sind_match::KfSide& w) {
+    return sind::KfArrays{w.pose.d.p, w.nP.d.p, w.x3Dw.d.p, w.normal.d.p, w.maxDist.d.p, w.minDist.d.p, w.valid.d.p, w.ptDesc.d.p, w.pack.d.p, w.keyDesc.d.p, w.gridStart.d.p, w.gridIdx.d.p,
+                          w.bestIdx.d.p, w.bestDist.d.p, w.count.d.p, w.match12.d.p};
+}
+
+KfPoints points_of(const sind_match_sim3_side& q) { return KfPoints{q.n, q.x3Dw, nullptr, q.max_dist, q.min_dist, q.valid, q.mp_desc}; }
+Keys keys_of(const sind_match_sim3_side& q) { return Keys{q.n, q.un_xy, q.octave, nullptr, nullptr, q.kf_desc, nullptr, q.grid_start, q.grid_idx, nullptr}; }
 
 // ---- vocabulary-guided searches (match_bow.hip) ----
 Keys side_a(const sind_match_bow& q) { return Keys{q.n_kf, nullptr, nullptr, q.kf_angle, nullptr, q.kf_desc, q.kf_valid, nullptr, nullptr, q.kf_node}; }
@@ -291,6 +376,94 @@ int sind_match_by_projection_kf(sind_match* m, const sind_match_reloc* frames, i
                             nullptr, nullptr, nullptr, nullptr, nullptr, q.match_of_cur, q.nmatches};
     }
     return run_points(m, m->reloc, fr, p, 1, "sind_match_by_projection_kf: frame");
+}
+
+int sind_match_fuse(sind_match* m, const sind_match_fuse_item* items, int B, float th, int sim3) {
+    const char* who = "sind_match_fuse: item";
+    if (!m || !items || B < 1 || B > m->maxB || !(th > 0)) { sind_set_error("sind_match_fuse: bad arguments (B=%d, max %d)", B, m ? m->maxB : 0); return SIND_E_ARG; }
+    if (!m->local.cap) { sind_set_error("sind_match_fuse: call sind_match_reserve_map_points first"); return SIND_E_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    const int cp = m->local.cap, ck = m->cur.cap, useK = K_XY | K_OCTAVE | K_GRID | (sim3 ? 0 : K_URIGHT);
+    auto points = [](const sind_match_fuse_item& q) { return KfPoints{q.n_points, q.x3Dw, q.normal, q.max_dist, q.min_dist, q.valid, q.desc}; };
+    auto keys = [sim3](const sind_match_fuse_item& q) { return Keys{q.n_kf, q.kf_un_xy, q.kf_octave, nullptr, sim3 ? nullptr : q.kf_u_right, q.kf_desc, nullptr, q.grid_start, q.grid_idx, nullptr}; };
+    for (int b = 0; b < B; b++) {
+        const sind_match_fuse_item& q = items[b];
+        SIND_TRY(check_kf(who, b, !q.Tcw || !q.nfused || (q.n_points && (!q.best_idx || !q.best_dist)), points(q), cp, true, keys(q), ck, useK, m->prm.nlevels));
+    }
+    sind_match::KfSide& w = m->fuse;
+    SIND_TRY(w.reserve((size_t)m->maxB, cp, ck));
+    for (int b = 0; b < B; b++) {
+        const sind_match_fuse_item& q = items[b];
+        sind::KfPose& ps = w.pose.h[b];
+        if (sim3) decompose_scw(q.Tcw, ps.T); else cpy(ps.T, q.Tcw, sizeof(ps.T));
+        camera_centre(ps.T, ps.Ow);
+        stage_kf(w, b, points(q), keys(q));
+    }
+    hipStream_t s = m->stream; const size_t np = (size_t)B * cp;
+    SIND_TRY(upload_kf(w, B, true, s));
+    SIND_TRY(sind::launch_search_kf(kf_params(m, th, 50, cp, ck), kf_arrays(w), B, sim3 ? sind::KF_FUSE_SIM3 : sind::KF_FUSE, s));
+    SIND_TRY(w.bestIdx.down(np, s)); SIND_TRY(w.bestDist.down(np, s)); SIND_TRY(w.count.down(B, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) {
+        const sind_match_fuse_item& q = items[b]; const size_t o = (size_t)b * cp, n = (size_t)q.n_points;
+        cpy(q.best_idx, &w.bestIdx.h[o], n * sizeof(int)); cpy(q.best_dist, &w.bestDist.h[o], n * sizeof(int)); *q.nfused = w.count.h[b];
+    }
+    return SIND_OK;
+}
+
+int sind_match_by_projection_sim3(sind_match* m, const sind_match_proj_sim3* items, int B, int th) {
+    if (!m || !items || B < 1 || B > m->maxB || th < 1) { sind_set_error("sind_match_by_projection_sim3: bad arguments (B=%d, max %d)", B, m ? m->maxB : 0); return SIND_E_ARG; }
+    if (!m->local.cap) { sind_set_error("sind_match_by_projection_sim3: call sind_match_reserve_map_points first"); return SIND_E_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    sind::LocalParams p = local_params(m, (float)th); p.orbDist = 50; p.checkOrientation = 0;              // TH_LOW
+    kf_bounds(m->prm.bounds, p.bounds, p.gridInv);
+    std::vector<PointsFrame> fr(B); std::vector<float> T((size_t)B * 12);
+    for (int b = 0; b < B; b++) {
+        const sind_match_proj_sim3& q = items[b];
+        if (q.Scw) decompose_scw(q.Scw, &T[(size_t)b * 12]);
+        fr[b] = PointsFrame{q.Scw ? &T[(size_t)b * 12] : nullptr, q.n_points, q.x3Dw, q.normal, q.max_dist, q.min_dist, q.valid, nullptr, q.desc,
+                            Keys{q.n_kf, q.kf_un_xy, q.kf_octave, nullptr, nullptr, q.kf_desc, q.kf_taken, q.grid_start, q.grid_idx, nullptr},
+                            nullptr, nullptr, nullptr, nullptr, nullptr, q.match_of_kf, q.nmatches};
+    }
+    return run_points(m, m->local, fr, p, 2, "sind_match_by_projection_sim3: item");
+}
+
+int sind_match_by_sim3(sind_match* m, const sind_match_sim3_pair* pairs, int B, float th) {
+    const char* who = "sind_match_by_sim3: pair";
+    if (!m || !pairs || B < 1 || B > m->maxB || !(th > 0)) { sind_set_error("sind_match_by_sim3: bad arguments (B=%d, max %d)", B, m ? m->maxB : 0); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(m->device));
+    const int cs = std::min(m->last.cap, m->cur.cap), useK = K_XY | K_OCTAVE | K_GRID;
+    for (int b = 0; b < B; b++) {
+        const sind_match_sim3_pair& q = pairs[b];
+        const bool otherNull = !q.T1w || !q.T2w || !q.R12 || !q.t12 || !q.nfound || (q.side1.n && !q.match12);
+        if (q.side1.n < 0 || q.side1.n > cs || q.side2.n < 0 || q.side2.n > cs) { sind_set_error("%s %d has %d / %d slots, capacity %d", who, b, q.side1.n, q.side2.n, cs); return SIND_E_CAPACITY; }
+        SIND_TRY(check_kf(who, b, otherNull, points_of(q.side1), cs, false, keys_of(q.side1), cs, useK, m->prm.nlevels));
+        SIND_TRY(check_kf(who, b, otherNull, points_of(q.side2), cs, false, keys_of(q.side2), cs, useK, m->prm.nlevels));
+    }
+    sind_match::KfSide& w = m->sim3;
+    SIND_TRY(w.reserve(2 * (size_t)m->maxB, cs, cs));
+    for (int b = 0; b < B; b++) {
+        const sind_match_sim3_pair& q = pairs[b];
+        sind::KfPose& p1 = w.pose.h[2 * b]; sind::KfPose& p2 = w.pose.h[2 * b + 1];
+        cpy(p1.T, q.T1w, sizeof(p1.T)); cpy(p2.T, q.T2w, sizeof(p2.T));
+        const float ia = (float)(1.0 / (double)q.s12);                                                   // :1119-1121; match_local.hip (5), (7)
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) { p2.T2[4 * r + c] = q.s12 * q.R12[3 * r + c]; p1.T2[4 * r + c] = ia * q.R12[3 * c + r]; }
+            p2.T2[4 * r + 3] = q.t12[r];
+        }
+        for (int r = 0; r < 3; r++) { const float t = p1.T2[4 * r] * q.t12[0] + p1.T2[4 * r + 1] * q.t12[1] + p1.T2[4 * r + 2] * q.t12[2]; p1.T2[4 * r + 3] = (float)((double)t * -1.0); }
+        for (int k = 0; k < 3; k++) p1.Ow[k] = p2.Ow[k] = 0.f;                                           // not read: the distance is |p3Dc|
+        stage_kf(w, 2 * b, points_of(q.side1), keys_of(q.side1)); stage_kf(w, 2 * b + 1, points_of(q.side2), keys_of(q.side2));
+    }
+    hipStream_t s = m->stream;
+    SIND_TRY(upload_kf(w, 2 * B, false, s));
+    const sind::KfParams p = kf_params(m, th, 100, cs, cs); const sind::KfArrays a = kf_arrays(w);
+    SIND_TRY(sind::launch_search_kf(p, a, 2 * B, sind::KF_BY_SIM3, s));
+    SIND_TRY(sind::launch_sim3_agree(p, a, B, s));
+    SIND_TRY(w.match12.down((size_t)B * cs, s)); SIND_TRY(w.count.down(B, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) { const sind_match_sim3_pair& q = pairs[b]; cpy(q.match12, &w.match12.h[(size_t)b * cs], (size_t)q.side1.n * sizeof(int)); *q.nfound = w.count.h[b]; }
+    return SIND_OK;
 }
 
 int sind_match_by_bow(sind_match* m, const sind_match_bow* pairs, int B, float nnratio, int check_orientation) {

@@ -1,5 +1,5 @@
-// Matcher interface: projection searches (reference src/ORBmatcher.cc:45-129, :1328-1470, :1472-1599; kernels in match_kernels.hip, match_local.hip) and
-// vocabulary-guided searches (:159-288, :657-823; match_bow.hip, bow_kernels.hip).
+// Matcher interface: projection searches (reference src/ORBmatcher.cc:45-129, :1328-1470, :1472-1599; kernels in match_kernels.hip, match_local.hip),
+// vocabulary-guided searches (:159-288, :657-823; match_bow.hip, bow_kernels.hip) and projections into a key frame (:290-403, :825-1326; match_fuse.hip).
 #pragma once
 #include "common.hpp"
 
@@ -26,6 +26,7 @@ int launch_search_by_projection(const MatchParams& p, const MatchArrays& a, int 
 struct LocalParams {
     float fx, fy, cx, cy, bf, bounds[4], th, nnratio, viewCosLimit, logScaleFactor; float scale[16]; int nlevels;
     int capPts, capCur, orbDist, checkOrientation;
+    float gridInv[2];                                             // mode 2 only: a key frame's mfGridElementWidthInv / HeightInv, which are not those of its (int) bounds
 };
 struct LocalPose { float Tcw[12]; float Ow[3]; };                // per frame: rows 0..2 of CurrentFrame.mTcw, camera centre mOw
 
@@ -40,9 +41,30 @@ struct LocalArrays {                                              // device poin
     int* matchOfCur; int* nmatches; int* rounds;                  // outputs [B][capCur], [B], [B]
 };
 
-// reloc = 0: Frame::isInFrustum + SearchByProjection(F, vpMapPoints, th); reloc = 1: SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)
+// mode 0: Frame::isInFrustum + SearchByProjection(F, vpMapPoints, th); mode 1: SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist);
+// mode 2 (search only, after launch_project_kf): SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)
 int launch_project_points(const LocalParams& p, const LocalArrays& a, int B, int reloc, hipStream_t s);
-int launch_search_points(const LocalParams& p, const LocalArrays& a, int B, int reloc, hipStream_t s);
+int launch_search_points(const LocalParams& p, const LocalArrays& a, int B, int mode, hipStream_t s);
+
+// Projections of map points into a key frame (match_fuse.hip).  KF_FUSE, KF_FUSE_SIM3 and KF_BY_SIM3 have no dependence between points: one launch over
+// (blocks of points) x items; KF_BY_SIM3 runs 2B items (item 2b + s = the slots of side s of pair b, searched against the keys of item 2b + 1 - s) and then the
+// agreement pass.  KF_PROJ_SIM3 projects into LocalArrays (launch_project_kf) and resolves its closed keypoints in launch_search_points(mode 2).
+enum { KF_FUSE = 0, KF_FUSE_SIM3 = 1, KF_PROJ_SIM3 = 2, KF_BY_SIM3 = 3 };
+struct KfParams {
+    float fx, fy, cx, cy, bf, bounds[4] /* the key frame's: int */, gridInv[2], th, logScaleFactor; float scale[16], invSigma2[16]; int nlevels;
+    int capPts, capKeys, thDist /* TH_LOW or TH_HIGH */;
+};
+struct KfPose { float T[12]; float Ow[3]; float T2[12]; };         // per item: rows 0..2 of [Rcw | tcw], camera centre; KF_BY_SIM3: T = the side's own pose, T2 = [sR21 | t21] or [sR12 | t12]
+struct KfArrays {                                                 // device pointers, dense [items][cap...]
+    const KfPose* pose; const int* nPts;
+    const float* x3Dw; const float* normal; const float* maxDist; const float* minDist; const uint8_t* valid; const uint32_t* ptDesc;
+    const float4* keyPack /* x, y, uRight, octave */; const uint32_t* keyDesc; const int* gridStart; const int* gridIdx;
+    int* bestIdx; int* bestDist; int* count;                      // outputs [items][capPts] x2, [items] (zeroed by the caller; KF_BY_SIM3: [B], written by the agreement pass)
+    int* match12;                                                 // KF_BY_SIM3: output [B][capPts]
+};
+int launch_search_kf(const KfParams& p, const KfArrays& a, int items, int mode, hipStream_t s);
+int launch_sim3_agree(const KfParams& p, const KfArrays& a, int B, hipStream_t s);
+int launch_project_kf(const LocalParams& p, const LocalArrays& a, int B, hipStream_t s);
 
 // Vocabulary-guided searches (match_bow.hip): SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation.  Side A is the one whose entries act
 // (the key frame / pKF1, capacity capLast), side B the one searched (the frame / pKF2, capacity capCur).

@@ -20,8 +20,13 @@
 //                            of probability ~2^-29), here for ratio and on the host for mfLogScaleFactor = log(mvScaleFactors[1]).
 //                            The reference calls the FP32 std::log, whose last bit differs between C libraries, and that bit
 //                            decides the level of a point seen again at the distance it was created at (ratio == scale[octave]).
-// (1)-(4) are recollections of OpenCV 4.2.0 (cv::gemm small-matrix path, cv::gemm with GEMM_1_T, cv::norm of a CV_32F matrix,
-// Mat::dot returning double) that nothing in this repository can pin.
+//   A / s, s * A             (Scw decomposition, sR12, sR21 of match_fuse.hip, on the host) every element times (float)(1.0 / (double)s), resp. (float)s,
+//                            in FP32: a MatExpr with a scale factor, evaluated by convertTo                  parity UNPINNED (5)
+//   scw                      (float)sqrt(row0 . row0), the dot product as in (4): FP64 accumulation          parity UNPINNED (6)
+//   t21 = -sR21 * t12        FP32 row product, then (float)((double)t * -1.0): the alpha of (1)              parity UNPINNED (7)
+//   Ow of an Scw             -Rcw^T * tcw as (2), on Rcw and tcw of (5)
+// (1)-(7) are recollections of OpenCV 4.2.0 (cv::gemm small-matrix path, cv::gemm with GEMM_1_T, cv::norm of a CV_32F matrix,
+// Mat::dot returning double, MatExpr scaling through convertTo) that nothing in this repository can pin.
 #include "match.hpp"
 #include "match_device.hpp"
 
@@ -66,8 +71,11 @@ __global__ __launch_bounds__(PP_NT) void k_project_points(LocalParams p, LocalAr
     if (!RELOC) atomicAdd(&a.nToMatch[b], 1);
 }
 
-template <bool RELOC>
+// MODE 0: local map, 1: relocalisation, 2: SearchByProjection(pKF, Scw, ...) after k_project_kf (match_fuse.hip): the relocalisation search with levels [lv-1, lv],
+// TH_LOW in orbDist, the key frame's int bounds in p.bounds and its grid cell size in p.gridInv
+template <int MODE>
 __global__ __launch_bounds__(MT_NT) void k_search_points(LocalParams p, LocalArrays a) {
+    constexpr bool RELOC = MODE != 0;
     __shared__ int changed; __shared__ MatchTailShared tail;
     const int b = blockIdx.x, t = threadIdx.x, nP = min(a.nPts[b], p.capPts), nC = min(a.nCur[b], p.capCur);
     const size_t po = (size_t)b * p.capPts, co = (size_t)b * p.capCur;
@@ -77,7 +85,7 @@ __global__ __launch_bounds__(MT_NT) void k_search_points(LocalParams p, LocalArr
     const int* gs = a.gridStart + (size_t)b * 3073; const int* gi = a.gridIdx + co; const uint8_t* taken0 = a.curTaken + co;
     int* choice = a.choice + po; int* minOwner = a.minOwner + co; int* matchOfCur = a.matchOfCur + co; float4* pack = a.curPack + co;
     const float minX = p.bounds[0], minY = p.bounds[2];
-    const float wInv = 64.f / (float)(p.bounds[1] - p.bounds[0]), hInv = 48.f / (float)(p.bounds[3] - p.bounds[2]);
+    const float wInv = MODE == 2 ? p.gridInv[0] : 64.f / (float)(p.bounds[1] - p.bounds[0]), hInv = MODE == 2 ? p.gridInv[1] : 48.f / (float)(p.bounds[3] - p.bounds[2]);
     const int thHigh = RELOC ? p.orbDist : 100;
 
     for (int i = t; i < nP; i += MT_NT) choice[i] = -1;
@@ -101,7 +109,7 @@ __global__ __launch_bounds__(MT_NT) void k_search_points(LocalParams p, LocalArr
                     if (p.th != 1.0f) r *= p.th;
                     r = r * p.scale[lv];
                 }
-                const int minL = lv - 1, maxL = RELOC ? lv + 1 : lv;                               // maxL >= 0: levels are always checked
+                const int minL = lv - 1, maxL = MODE == 1 ? lv + 1 : lv;                              // maxL >= 0: levels are always checked
                 const float x = proj[3 * i], y = proj[3 * i + 1], xr = proj[3 * i + 2];
                 const int x0 = max(0, (int)floorf((x - minX - r) * wInv)), x1 = min(63, (int)ceilf((x - minX + r) * wInv));
                 const int y0 = max(0, (int)floorf((y - minY - r) * hInv)), y1 = min(47, (int)ceilf((y - minY + r) * hInv));
@@ -156,9 +164,10 @@ int launch_project_points(const LocalParams& p, const LocalArrays& a, int B, int
     return SIND_OK;
 }
 
-int launch_search_points(const LocalParams& p, const LocalArrays& a, int B, int reloc, hipStream_t s) {
-    if (reloc) hipLaunchKernelGGL(k_search_points<true>, dim3(B), dim3(MT_NT), 0, s, p, a);
-    else hipLaunchKernelGGL(k_search_points<false>, dim3(B), dim3(MT_NT), 0, s, p, a);
+int launch_search_points(const LocalParams& p, const LocalArrays& a, int B, int mode, hipStream_t s) {
+    if (mode == 2) hipLaunchKernelGGL(k_search_points<2>, dim3(B), dim3(MT_NT), 0, s, p, a);
+    else if (mode) hipLaunchKernelGGL(k_search_points<1>, dim3(B), dim3(MT_NT), 0, s, p, a);
+    else hipLaunchKernelGGL(k_search_points<0>, dim3(B), dim3(MT_NT), 0, s, p, a);
     HIP_TRY(hipGetLastError());
     return SIND_OK;
 }

@@ -1,4 +1,5 @@
-"""ORBmatcher — Python mirror of the reference's projection matchers of the RGB-D tracker (src/ORBmatcher.cc:45-129, :1328-1470, :1472-1599) over the C ABI."""
+"""ORBmatcher — Python mirror of the reference's projection matchers of the RGB-D tracker (src/ORBmatcher.cc:45-129, :1328-1470, :1472-1599), its vocabulary-guided
+searches and its projections into a key frame (Fuse, SearchByProjection(pKF, Scw), SearchBySim3; :290-403, :825-1326) over the C ABI."""
 from __future__ import annotations
 
 import ctypes as C
@@ -52,6 +53,29 @@ class _Tri(C.Structure):
                 ("desc2", C.c_void_p), ("match12", C.c_void_p), ("nmatches", C.c_void_p)]
 
 
+_POINTS = [("n_points", C.c_int), ("x3Dw", C.c_void_p), ("normal", C.c_void_p), ("max_dist", C.c_void_p), ("min_dist", C.c_void_p), ("valid", C.c_void_p), ("desc", C.c_void_p)]
+
+
+class _Fuse(C.Structure):
+    _fields_ = [("Tcw", C.c_void_p)] + _POINTS + [("n_kf", C.c_int), ("kf_un_xy", C.c_void_p), ("kf_octave", C.c_void_p), ("kf_u_right", C.c_void_p), ("kf_desc", C.c_void_p),
+                                                  ("grid_start", C.c_void_p), ("grid_idx", C.c_void_p), ("best_idx", C.c_void_p), ("best_dist", C.c_void_p), ("nfused", C.c_void_p)]
+
+
+class _ProjSim3(C.Structure):
+    _fields_ = [("Scw", C.c_void_p)] + _POINTS + [("n_kf", C.c_int), ("kf_un_xy", C.c_void_p), ("kf_octave", C.c_void_p), ("kf_desc", C.c_void_p), ("grid_start", C.c_void_p),
+                                                  ("grid_idx", C.c_void_p), ("kf_taken", C.c_void_p), ("match_of_kf", C.c_void_p), ("nmatches", C.c_void_p)]
+
+
+class _Sim3Side(C.Structure):
+    _fields_ = [("n", C.c_int), ("valid", C.c_void_p), ("x3Dw", C.c_void_p), ("max_dist", C.c_void_p), ("min_dist", C.c_void_p), ("mp_desc", C.c_void_p),
+                ("un_xy", C.c_void_p), ("octave", C.c_void_p), ("kf_desc", C.c_void_p), ("grid_start", C.c_void_p), ("grid_idx", C.c_void_p)]
+
+
+class _Sim3Pair(C.Structure):
+    _fields_ = [("T1w", C.c_void_p), ("T2w", C.c_void_p), ("s12", C.c_float), ("R12", C.c_void_p), ("t12", C.c_void_p), ("side1", _Sim3Side), ("side2", _Sim3Side),
+                ("match12", C.c_void_p), ("nfound", C.c_void_p)]
+
+
 _f32 = lambda a: np.ascontiguousarray(a, np.float32)
 _u8 = lambda a: np.ascontiguousarray(a, np.uint8)
 _i32 = lambda a: np.ascontiguousarray(a, np.int32)
@@ -63,6 +87,15 @@ def _cur(cur, *floats):
     a.update({"cur_" + k: _f32(cur[k]) for k in floats})
     if cur.get("taken") is not None:
         a["cur_taken"] = _u8(cur["taken"])
+    return a
+
+
+def _points_kf(mp, kf, u_right=False):
+    """the map-point list and the key frame of sind_match_fuse_item / sind_match_proj_sim3"""
+    a = dict(n_points=len(mp["valid"]), x3Dw=_f32(mp["x3Dw"]), normal=_f32(mp["normal"]), max_dist=_f32(mp["max_dist"]), min_dist=_f32(mp["min_dist"]), valid=_u8(mp["valid"]), desc=_u8(mp["desc"]),
+             n_kf=len(kf["octave"]), kf_un_xy=_f32(kf["un_xy"]), kf_octave=_i32(kf["octave"]), kf_desc=_u8(kf["desc"]), grid_start=_i32(kf["grid_start"]), grid_idx=_i32(kf["grid_idx"]))
+    if u_right:
+        a["kf_u_right"] = _f32(kf["u_right"])
     return a
 
 
@@ -167,6 +200,59 @@ class ORBmatcher:
             i1 = np.nonzero(m >= 0)[0]
             res.append((m, n, np.stack([i1, m[i1]], 1).astype(np.int64)))
         return res
+
+    def _fuse(self, items, th, sim3):
+        its = []
+        for T, mp, kf in items:
+            a = _points_kf(mp, kf, u_right=not sim3); n = max(a["n_points"], 1)
+            a.update(Tcw=_f32(T), best_idx=np.full(n, -1, np.int32), best_dist=np.full(n, -1, np.int32), nfused=np.zeros(1, np.int32))
+            its.append(a)
+        self._call("sind_match_fuse", _Fuse, its, C.c_float(th), int(sim3))
+        return [dict(best_idx=a["best_idx"][:a["n_points"]].copy(), best_dist=a["best_dist"][:a["n_points"]].copy(), nfused=int(a["nfused"][0])) for a in its]
+
+    def Fuse(self, items, th=3.0):
+        """Fuse(pKF, vpMapPoints, th) up to its graph tail (:825-949).  items: list of (Tcw, mp, kf); mp, per entry of the list: x3Dw, normal, max_dist, min_dist,
+        valid (pMP && !isBad && !IsInKeyFrame(pKF)), desc; kf, per keypoint: un_xy, octave, u_right, desc, grid_start, grid_idx.  Needs cap_points.
+        -> list of dicts: best_idx i32 [n] (bestIdx if bestDist <= TH_LOW, else -1), best_dist i32 [n], nfused.  The caller replays the tail."""
+        return self._fuse(items, th, 0)
+
+    def FuseSim3(self, items, th):
+        """Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) up to its graph tail (:977-1079).  items: list of (Scw, mp, kf) as for Fuse with
+        valid = !isBad && !spAlreadyFound.count(pMP); kf["u_right"] is not read.  -> as Fuse"""
+        return self._fuse(items, th, 1)
+
+    def SearchByProjectionSim3(self, items, th):
+        """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (:290-403).  items: list of (Scw, mp, kf) as for FuseSim3; kf["taken"] = vpMatched[idx] != NULL on entry
+        (None = none).  th: int.  -> list of (match_of_kf i32 [n_kf] = index of the point written to vpMatched[idx] or -1, nmatches)"""
+        its = []
+        for S, mp, kf in items:
+            a = _points_kf(mp, kf); a["Scw"] = _f32(S)
+            if kf.get("taken") is not None:
+                a["kf_taken"] = _u8(kf["taken"])
+            its.append(_outputs(a, "n_kf", "match_of_kf"))
+        self._call("sind_match_by_projection_sim3", _ProjSim3, its, int(th))
+        return [_matches(a, "n_kf", "match_of_kf") for a in its]
+
+    def SearchBySim3(self, pairs, th):
+        """SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (:1102-1326).  pairs: list of (T1w, T2w, s12, R12, t12, side1, side2); a side, per slot of the key
+        frame: valid (pMP && !isBad && !vbAlreadyMatched), x3Dw, max_dist, min_dist, mp_desc (of the slot's map point), un_xy, octave, kf_desc (of the slot's keypoint),
+        and grid_start, grid_idx.  -> list of (match12 i32 [n1] = idx2 where both directions agree or -1, nfound)"""
+        arr = (_Sim3Pair * len(pairs))(); keep = []
+        for q, (T1, T2, s12, R12, t12, s1, s2) in zip(arr, pairs):
+            a = dict(T1w=_f32(T1), T2w=_f32(T2), R12=_f32(R12), t12=_f32(t12), match12=np.full(max(len(s1["valid"]), 1), -1, np.int32), nfound=np.zeros(1, np.int32))
+            for k, v in a.items():
+                setattr(q, k, v.ctypes.data)
+            q.s12 = float(s12)
+            for name, side, d in (("side1", q.side1, s1), ("side2", q.side2, s2)):
+                b = dict(valid=_u8(d["valid"]), x3Dw=_f32(d["x3Dw"]), max_dist=_f32(d["max_dist"]), min_dist=_f32(d["min_dist"]), mp_desc=_u8(d["mp_desc"]), un_xy=_f32(d["un_xy"]),
+                         octave=_i32(d["octave"]), kf_desc=_u8(d["kf_desc"]), grid_start=_i32(d["grid_start"]), grid_idx=_i32(d["grid_idx"]))
+                side.n = len(d["valid"])
+                for k, v in b.items():
+                    setattr(side, k, v.ctypes.data if v.size else None)
+                a[name] = b                                           # the arrays live as long as the call
+            a["n1"] = len(s1["valid"]); keep.append(a)
+        check(lib().sind_match_by_sim3(self._h, arr, len(pairs), C.c_float(th)), "sind_match_by_sim3")
+        return [(a["match12"][:a["n1"]].copy(), int(a["nfound"][0])) for a in keep]
 
     def last_rounds(self):
         return lib().sind_match_last_rounds(self._h)
