@@ -422,7 +422,7 @@ int sind_match_by_projection_kf(sind_match* m, const sind_match_reloc* frames, i
  * (ORB-SLAM2 passes levelsup = 4); 0 if levels - levelsup <= 0; the leaf's own id if the path ends above that level (the reference leaves nid uninitialised
  * there); -1 if the word is stopped, !(weight > 0): such a feature is not in mFeatVec (:1157-1161).  DBoW2 fills mFeatVec in feature order
  * (FeatureVector.cpp:31-45), so node_id per keypoint determines it: nodes ascend, indices ascend inside a node.  The BowVector (word weights, normalisation) is
- * left to the caller, who gets word_id for it.
+ * left to the caller, who gets word_id for it, or comes from sind_voc_transform_bow below.
  *   desc[b] = n[b] x 32 bytes (host); node_id[b], word_id[b] = n[b] ints (host); node_id, word_id and their entries may be NULL.
  * Errors: n[b] > cap or B > max_batch -> SIND_E_CAPACITY, a NULL desc[b] with n[b] > 0 -> SIND_E_ARG; nothing is launched, the outputs are untouched.
  */
@@ -438,6 +438,66 @@ typedef struct sind_voc_tree {
 int sind_voc_create(const sind_voc_tree* tree, int cap, int max_batch, int device, sind_voc** out);
 int sind_voc_destroy(sind_voc* v);
 int sind_voc_transform(sind_voc* v, const uint8_t* const* desc, const int* n, int B, int levelsup, int* const* node_id, int* const* word_id);
+
+/* The whole of ComputeBoW: sind_voc_transform and the BowVector, for B frames at once, without a host step between the descent and the vector.  Adds
+ *   the BowVector half of TemplatedVocabulary::transform(features, v, fv, levelsup)                      Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1194
+ *   void BowVector::addWeight(WordId id, WordValue v)                                                    Thirdparty/DBoW2/DBoW2/BowVector.cpp:34-46
+ *   void BowVector::normalize(LNorm norm_type)                                                           :62-84
+ * for TF_IDF weighting and L1_NORM scoring, the ORB vocabulary's; no other mode is implemented (TF would be the same with weights of 1; IDF / BINARY use
+ * addIfNotExist, and the L2 norm and the "divide by size" of a scoring that does not normalise are absent).
+ * node_id / word_id are sind_voc_transform's, bit for bit.  bow_word[b] / bow_value[b] = the std::map<WordId, WordValue> of frame b in its iteration order:
+ * n_words[b] <= n[b] entries, word ids strictly ascending; the caller gives room for n[b] of each, the entries past n_words[b] are left alone.
+ * The values are the reference's FP64 operations in the reference's order:
+ *   value of a word = the weight of the leaf, added once per feature that fell on the word, in feature order, starting from the first weight:
+ *       w, w + w, (w + w) + w, ...  -- not count * w; a stopped word, !(w > 0), is absent (:1157);
+ *   norm = the sum of fabs(value) over ascending word id, left to right;  if norm > 0 every value becomes value / norm (IEEE division);
+ *   a frame without a word that counts has n_words[b] = 0.
+ * The weights stay on the device as the FP64 given to sind_voc_create.  A frame holds at most min(cap, 4096) descriptors here (one workgroup sorts a frame's
+ * words in LDS, as for the two searches by vocabulary node).
+ * Errors as for sind_voc_transform (n[b] over that limit or B > max_batch -> SIND_E_CAPACITY; a NULL desc[b], bow_word[b] or bow_value[b] with n[b] > 0, or a
+ * NULL bow_word, bow_value or n_words -> SIND_E_ARG): nothing is launched, the outputs are untouched.
+ */
+int sind_voc_transform_bow(sind_voc* v, const uint8_t* const* desc, const int* n, int B, int levelsup, int* const* node_id, int* const* word_id,
+                           int* const* bow_word, double* const* bow_value, int* n_words /* [B] */);
+
+/* Key-frame database: the scoring of KeyFrameDatabase on the device.  Replaces the inverted file and the scores of
+ *   void KeyFrameDatabase::add(KeyFrame*), ::erase(KeyFrame*), ::clear()                                 src/KeyFrameDatabase.cc:40-73
+ *   vector<KeyFrame*> KeyFrameDatabase::DetectLoopCandidates(KeyFrame* pKF, float minScore)              :76-197
+ *   vector<KeyFrame*> KeyFrameDatabase::DetectRelocalizationCandidates(Frame* F)                         :199-309
+ *   double L1Scoring::score(const BowVector& v1, const BowVector& v2)                                    Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68
+ * and serves mpORBVocabulary->score against the connected key frames in LoopClosing::DetectLoop (src/LoopClosing.cc:124-141): minScore is the smallest
+ * `score` among the connected key frames' slots.
+ * A slot is the caller's index for a key frame (0 .. cap_slots - 1).  The BowVectors live on the device, cap_words per slot.
+ *   add     stores a BowVector (word ids >= 0, strictly ascending, as sind_voc_transform_bow returns them) in a dead slot and gives the slot the next value of a
+ *           sequence counter (sind_bowdb_sequence; -1 for a dead slot).  The reference keeps one list<KeyFrame*> per word in push_back order and erase
+ *           keeps the order of the others, so every list is ordered by that counter.
+ *   erase   makes the slot dead; erasing a dead slot does nothing, as in the reference.  clear makes every slot dead; the counter runs on.
+ *   query   Q query vectors at once.  For every live slot:  common = the number of words both vectors hold = mnLoopWords / mnRelocWords;
+ *           first_word = the smallest common word, -1 if none;  score = (float)(-sum / 2.0), sum = the FP64 sum over the common words in ascending order of
+ *           fabs(vi - wi) - fabs(vi) - fabs(wi) (vi the query's value, wi the slot's), evaluated left to right without contraction, added one term after
+ *           another: the float the reference stores in mLoopScore / mRelocScore.  Dead slots get 0, -1 and 0.0f.
+ * The reference scores only key frames with more than minCommonWords common words; here every live slot is scored and the caller filters: the values of
+ * the ones the reference scores are the reference's.  The list and graph logic that follows is order-dependent and stays with the caller (INTEGRATION.md
+ * gives it in C++, sindslam_amd/keyframe_db.py in Python): lKFsSharingWords is the live slots with common > 0 (without the connected key frames for the
+ * loop version) ordered by (first_word, sequence).
+ * One point is a definition, not a reproduction: DetectRelocalizationCandidates adds pKF2->mRelocScore for any neighbour that shares a word with the frame,
+ * also one that was not scored in this query (:273-276), and the reference never initialises that member (src/KeyFrame.cc:35).  The tails given with this
+ * library keep a per-slot reloc_score that is 0.0f at add and overwritten only when the slot is scored.
+ * Errors: a slot outside [0, cap_slots), a NULL array with a non-zero count, a NULL output, words that do not ascend strictly -> SIND_E_ARG; more than
+ * cap_words words or Q > max_queries -> SIND_E_CAPACITY; add on a live slot -> SIND_E_STATE.  Nothing is launched, the database and the outputs are untouched.
+ */
+typedef struct sind_bowdb sind_bowdb;
+int sind_bowdb_create(int cap_slots, int cap_words, int max_queries, int device, sind_bowdb** out);
+int sind_bowdb_destroy(sind_bowdb* db);
+int sind_bowdb_add(sind_bowdb* db, int slot, const int* word, const double* value, int n);
+int sind_bowdb_erase(sind_bowdb* db, int slot);
+int sind_bowdb_clear(sind_bowdb* db);
+long long sind_bowdb_sequence(const sind_bowdb* db, int slot);
+typedef struct sind_bowdb_query_item {
+    int n; const int* word; const double* value;                                          /* the query's BowVector */
+    int* common; int* first_word; float* score;                                           /* outputs (host), [cap_slots] each */
+} sind_bowdb_query_item;
+int sind_bowdb_query(sind_bowdb* db, const sind_bowdb_query_item* q, int Q);
 
 /* Search by vocabulary node.  Replaces, for B (KeyFrame, Frame) pairs at once,
  *   int ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches)          src/ORBmatcher.cc:159-288
@@ -460,6 +520,24 @@ typedef struct sind_match_bow {
     int* match_of_cur; int* nmatches;                                                     /* outputs (host) */
 } sind_match_bow;
 int sind_match_by_bow(sind_match* m, const sind_match_bow* pairs, int B, float nnratio, int check_orientation);
+
+/* Search by vocabulary node between two key frames.  Replaces, for B (pKF1, pKF2) pairs at once,
+ *   int ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12)         src/ORBmatcher.cc:522-655
+ * (LoopClosing::ComputeSim3, src/LoopClosing.cc:265, once per loop candidate with ORBmatcher(0.75, true): the current key frame against all candidates is one
+ * call, and the pairs may share side 1's arrays).  Capacities as for sind_match_by_bow: side 1 at most min(cap_last, 4096), side 2 at most min(cap_cur, 4096).
+ *   per side s (1, 2) and keypoint i:  nodes = node id of pKFs->mFeatVec (-1: not in it), valids = pMP && !pMP->isBad() for pMP = pKFs->GetMapPointMatches()[i],
+ *       angles = pKFs->mvKeysUn[i].angle, descs = row i of pKFs->mDescriptors
+ * Output: match12[idx1] = idx2 of the map point the reference leaves in vpMatches12[idx1] (-1: none, or removed by the orientation check); *nmatches = the
+ * function's return value.  What differs from sind_match_by_bow: both sides carry validity, a keypoint of side 2 is closed once matched (vbMatched2), the
+ * result and the rotation histogram are indexed by idx1, both angles are the undistorted keypoints', and the bound is bestDist1 < TH_LOW (50), strict.
+ * Errors as for sind_match_by_bow.
+ */
+typedef struct sind_match_bow_kf {
+    int n1; const int* node1; const uint8_t* valid1; const float* angle1; const uint8_t* desc1;
+    int n2; const int* node2; const uint8_t* valid2; const float* angle2; const uint8_t* desc2;
+    int* match12; int* nmatches;                                                          /* outputs (host): match12[idx1] = idx2 or -1 */
+} sind_match_bow_kf;
+int sind_match_by_bow_kf(sind_match* m, const sind_match_bow_kf* pairs, int B, float nnratio, int check_orientation);
 
 /* Search for triangulation.  Replaces, for B (pKF1, pKF2) pairs at once (LocalMapping::CreateNewMapPoints, one key frame against its neighbours),
  *   int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t, size_t>>& vMatchedPairs, bool bOnlyStereo)

@@ -264,6 +264,8 @@ Keys keys_of(const sind_match_sim3_side& q) { return Keys{q.n, q.un_xy, q.octave
 // ---- vocabulary-guided searches (match_bow.hip) ----
 Keys side_a(const sind_match_bow& q) { return Keys{q.n_kf, nullptr, nullptr, q.kf_angle, nullptr, q.kf_desc, q.kf_valid, nullptr, nullptr, q.kf_node}; }
 Keys side_b(const sind_match_bow& q) { return Keys{q.n_cur, nullptr, nullptr, q.cur_angle, nullptr, q.cur_desc, nullptr, nullptr, nullptr, q.cur_node}; }
+Keys side_a(const sind_match_bow_kf& q) { return Keys{q.n1, nullptr, nullptr, q.angle1, nullptr, q.desc1, q.valid1, nullptr, nullptr, q.node1}; }
+Keys side_b(const sind_match_bow_kf& q) { return Keys{q.n2, nullptr, nullptr, q.angle2, nullptr, q.desc2, q.valid2, nullptr, nullptr, q.node2}; }
 Keys side_a(const sind_match_tri& q) { return Keys{q.n1, q.un_xy1, nullptr, q.angle1, q.u_right1, q.desc1, q.has_mp1, nullptr, nullptr, q.node1}; }
 Keys side_b(const sind_match_tri& q) { return Keys{q.n2, q.un_xy2, q.octave2, q.angle2, q.u_right2, q.desc2, q.has_mp2, nullptr, nullptr, q.node2}; }
 
@@ -484,6 +486,26 @@ int sind_match_by_bow(sind_match* m, const sind_match_bow* pairs, int B, float n
     sind::BowParams p = bow_params(m, maxN); p.nnratio = nnratio; p.checkOrientation = check_orientation ? 1 : 0;
     SIND_TRY(sind::launch_match_by_bow(p, bow_arrays(m), B, s));
     return finish(m, B, m->matchOfCur, m->cur.cap, false);
+}
+
+int sind_match_by_bow_kf(sind_match* m, const sind_match_bow_kf* pairs, int B, float nnratio, int check_orientation) {
+    const char* who = "sind_match_by_bow_kf: pair";
+    if (!m || !pairs || B < 1 || B > m->maxB) { sind_set_error("sind_match_by_bow_kf: bad arguments (B=%d, max %d)", B, m ? m->maxB : 0); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(m->device));
+    const int use = K_NODE | K_FLAGS | K_ANGLE, cl = std::min(m->last.cap, BOW_MAX_KEYS), cc = std::min(m->cur.cap, BOW_MAX_KEYS);
+    int maxN = 1;
+    for (int b = 0; b < B; b++) {
+        const sind_match_bow_kf& q = pairs[b];
+        SIND_TRY(check(who, b, !q.nmatches || (q.n1 && (!q.match12 || !q.valid1)) || (q.n2 && !q.valid2), side_a(q), cl, use, side_b(q), cc, use));
+        maxN = std::max(maxN, std::max(q.n1, q.n2));
+    }
+    SIND_TRY(m->reserve_bow());
+    for (int b = 0; b < B; b++) { const sind_match_bow_kf& q = pairs[b]; m->last.stage(b, side_a(q), use); m->cur.stage(b, side_b(q), use); m->out[b] = {q.match12, q.n1, q.nmatches}; }
+    hipStream_t s = m->stream;
+    SIND_TRY(m->last.upload(B, use, s)); SIND_TRY(m->cur.upload(B, use, s));
+    sind::BowParams p = bow_params(m, maxN); p.nnratio = nnratio; p.checkOrientation = check_orientation ? 1 : 0;
+    SIND_TRY(sind::launch_match_by_bow_kf(p, bow_arrays(m), B, s));
+    return finish(m, B, m->choice, m->last.cap, false);
 }
 
 int sind_match_for_triangulation(sind_match* m, const sind_match_tri* pairs, int B, int only_stereo, int check_orientation) {

@@ -84,10 +84,22 @@ struct BowArrays {                                                // device poin
     int* matchOfCur; int* nmatches;                               // outputs [B][capB] (by_bow), [B]
 };
 int launch_match_by_bow(const BowParams& p, const BowArrays& a, int B, hipStream_t s);
+int launch_match_by_bow_kf(const BowParams& p, const BowArrays& a, int B, hipStream_t s);      // SearchByBoW(pKF1, pKF2): flagsA = valid1, flagsB = valid2, choice = match12 (output)
 int launch_match_for_triangulation(const BowParams& p, const BowArrays& a, int B, hipStream_t s);
 
 // Vocabulary transform (bow_kernels.hip): descriptor -> word and node at a level, TemplatedVocabulary::transform
 struct VocTree { int nNodes; const int* childStart; const int* child; const uint32_t* desc; const int* wordId; const uint8_t* stopped; };   // device pointers
 int launch_voc_transform(const VocTree& tree, const uint32_t* desc /* [B][cap][8] */, const int* n, int cap, int maxN /* >= 1 */, int B, int nidLevel, int* nodeId, int* wordId, hipStream_t s);
+// the same and the BowVector: weight = the nodes' weights (FP64, read for leaves), leafId = scratch [B][cap]; maxN <= BOW_MAX_KEYS; bowWord / bowValue [B][cap], nWords [B]
+int launch_voc_transform_bow(const VocTree& tree, const double* weight, const uint32_t* desc, const int* n, int cap, int maxN, int B, int nidLevel, int* nodeId, int* wordId, int* leafId,
+                             int* bowWord, double* bowValue, int* nWords, hipStream_t s);
+
+// Key-frame database (bowdb_kernels.hip): one query BowVector against every slot's, L1Scoring::score in the reference's order of additions
+struct BowDbArrays {                                              // device pointers
+    const int* slotN /* [capSlots], -1: dead */; const int* slotWord; const double* slotValue;      // [capSlots][capWords]
+    const int* qN; const int* qWord; const double* qValue;        // [Q], [Q][capWords]
+    int* common; int* firstWord; float* score;                    // outputs [Q][capSlots]
+};
+int launch_bowdb_query(const BowDbArrays& a, int capSlots, int capWords, int Q, hipStream_t s);
 
 }  // namespace sind

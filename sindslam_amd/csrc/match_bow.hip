@@ -1,7 +1,8 @@
 // The two vocabulary-guided searches on the GPU:
 //   ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches)   reference src/ORBmatcher.cc:159-288   (TrackReferenceKeyFrame, Relocalization)
 //   ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo)   :657-823, CheckDistEpipolarLine :140-157   (LocalMapping::CreateNewMapPoints)
-// Both walk two DBoW2 feature vectors node by node and compare only keypoints that share a node.  A keypoint has one node, and DBoW2 fills a node's index list in
+//   ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12)   :522-655   (LoopClosing::ComputeSim3, once per loop candidate)
+// All walk two DBoW2 feature vectors node by node and compare only keypoints that share a node.  A keypoint has one node, and DBoW2 fills a node's index list in
 // keypoint order (FeatureVector.cpp:31-45), so the per-keypoint node id the vocabulary transform returns (bow_kernels.hip) carries the whole map: nodes are
 // independent of one another, and inside a node the entries act in ascending keypoint index.  Side A is the side whose entries act (pKF / pKF1), side B the side
 // searched (F / pKF2).  Three launches per call, B pairs each:
@@ -15,6 +16,9 @@
 //       are one bit per chunk in a lane's register.  best = min over (distance, position) = the first of the smallest, as the strict '<' scan finds it;
 //       bestDist2 = the minimum again without that position = the second element of the sorted distances, equal ones included.  TH_LOW 50 with '<=', then the
 //       ratio test in FP32.
+//     SearchByBoW(pKF1, pKF2) is k_bow_match<true>: side A is pKF1, side B pKF2; side B carries validity too (!pMP2 || isBad() is skipped like a claimed
+//       keypoint, :576-580, so it starts as a claim), the claims are vbMatched2, and the bound is 'bestDist1 < TH_LOW', strict (:598).  The result is
+//       vpMatches12 by idx1 and so is the rotation histogram (both angles mvKeysUn): the tail is k_tri_tail.
 //     SearchForTriangulation: vbMatched2 is never set in the reference, so the entries are independent: among the node's idx2 that pass the tests (no map
 //       point, the stereo flags, dist <= 50, the epipole distance for mono-mono pairs, the epipolar line) the smallest distance, the later one on equal distance
 //       ('dist > bestDist' is the skip test) = min over (distance, -position).
@@ -96,6 +100,7 @@ __device__ __forceinline__ Seg d_segment(const int2* sA, int nvA, const int2* sB
     return g;
 }
 
+template <bool KF>
 __global__ __launch_bounds__(BW_NT) void k_bow_match(BowParams p, BowArrays a, int B) {
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (BW_NT / 64) + (threadIdx.x >> 6)), nWaves = gridDim.x * (BW_NT / 64);
     const size_t oa = (size_t)b * p.capA, ob = (size_t)b * p.capB;
@@ -107,6 +112,7 @@ __global__ __launch_bounds__(BW_NT) void k_bow_match(BowParams p, BowArrays a, i
         int i0 = 0; uint4 c0 = make_uint4(0, 0, 0, 0), c1 = c0;       // the lane's frame keypoint of chunk 0
         if (lane < g.nF) { i0 = sB[g.f0 + lane].y; c0 = *(const uint4*)(dB + 8 * (size_t)i0); c1 = *(const uint4*)(dB + 8 * (size_t)i0 + 4); }
         unsigned long long claimed = 0;                            // bit c: this lane's keypoint of chunk c holds a map point
+        if (KF) for (int c = 0, pos = lane; pos < g.nF; c++, pos += 64) if (!a.flagsB[ob + sB[g.f0 + pos].y]) claimed |= 1ull << c;      // pKF2's keypoints without a good map point
         for (int e0 = g.k0; e0 < g.k1; e0 += 64) {                    // 64 entries are loaded by the lanes at once and then taken one after another
             int ikv = 0, okv = 0; uint4 qa = make_uint4(0, 0, 0, 0), qb = qa;
             if (e0 + lane < g.k1) { ikv = sA[e0 + lane].y; okv = valid[ikv]; qa = *(const uint4*)(dA + 8 * (size_t)ikv); qb = *(const uint4*)(dA + 8 * (size_t)ikv + 4); }
@@ -122,7 +128,7 @@ __global__ __launch_bounds__(BW_NT) void k_bow_match(BowParams p, BowArrays a, i
                     if (dist < bestD) { secondD = bestD; bestD = dist; bestPos = pos; bestIdx = idx; } else if (dist < secondD) secondD = dist;
                 }
                 const int key = d_wave_min((bestD << 12) | bestPos), best1 = key >> 12, pos1 = key & (BOW_MAX_KEYS - 1);
-                if (best1 > TH_LOW) continue;
+                if (KF ? best1 >= TH_LOW : best1 > TH_LOW) continue;
                 const bool mine = bestD == best1 && bestPos == pos1;
                 const int best2 = d_wave_min(mine ? secondD : bestD);
                 if (mine && (float)best1 < p.nnratio * (float)best2) { claimed |= 1ull << (pos1 >> 6); choice[ik] = bestIdx; }
@@ -236,9 +242,18 @@ static int launch_group(const BowParams& p, const BowArrays& a, int B, hipStream
 
 int launch_match_by_bow(const BowParams& p, const BowArrays& a, int B, hipStream_t s) {
     SIND_TRY(launch_group(p, a, B, s));
-    hipLaunchKernelGGL(k_bow_match, dim3(BW_GROUPS, B), dim3(BW_NT), 0, s, p, a, B);
+    hipLaunchKernelGGL(k_bow_match<false>, dim3(BW_GROUPS, B), dim3(BW_NT), 0, s, p, a, B);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_bow_tail, dim3(B), dim3(MT_NT), 0, s, p, a);
+    HIP_TRY(hipGetLastError());
+    return SIND_OK;
+}
+
+int launch_match_by_bow_kf(const BowParams& p, const BowArrays& a, int B, hipStream_t s) {
+    SIND_TRY(launch_group(p, a, B, s));
+    hipLaunchKernelGGL(k_bow_match<true>, dim3(BW_GROUPS, B), dim3(BW_NT), 0, s, p, a, B);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tri_tail, dim3(B), dim3(MT_NT), 0, s, p, a);
     HIP_TRY(hipGetLastError());
     return SIND_OK;
 }

@@ -46,6 +46,12 @@ class _Bow(C.Structure):
                 ("match_of_cur", C.c_void_p), ("nmatches", C.c_void_p)]
 
 
+class _BowKF(C.Structure):
+    _fields_ = [("n1", C.c_int), ("node1", C.c_void_p), ("valid1", C.c_void_p), ("angle1", C.c_void_p), ("desc1", C.c_void_p),
+                ("n2", C.c_int), ("node2", C.c_void_p), ("valid2", C.c_void_p), ("angle2", C.c_void_p), ("desc2", C.c_void_p),
+                ("match12", C.c_void_p), ("nmatches", C.c_void_p)]
+
+
 class _Tri(C.Structure):
     _fields_ = [("Tcw2", C.c_void_p), ("Cw1", C.c_void_p), ("F12", C.c_void_p),
                 ("n1", C.c_int), ("node1", C.c_void_p), ("has_mp1", C.c_void_p), ("un_xy1", C.c_void_p), ("angle1", C.c_void_p), ("u_right1", C.c_void_p), ("desc1", C.c_void_p),
@@ -114,7 +120,8 @@ class ORBmatcher:
     SearchLocalPoints = Frame::isInFrustum over the local map + SearchByProjection(F, vpMapPoints, th) (TrackLocalMap), and SearchByProjectionKF =
     SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (Relocalization).  A frame / a set of map points is a dict of arrays
     (see include/sind_hip.h: sind_match_pair, sind_match_local, sind_match_reloc).  By vocabulary node: SearchByBoW(pKF, F) (TrackReferenceKeyFrame, Relocalization;
-    :159-288) and SearchForTriangulation (LocalMapping::CreateNewMapPoints; :657-823), on node ids from vocabulary.ORBVocabulary (sind_match_bow, sind_match_tri)."""
+    :159-288) and SearchForTriangulation (LocalMapping::CreateNewMapPoints; :657-823), on node ids from vocabulary.ORBVocabulary (sind_match_bow, sind_match_tri), and SearchByBoWKF =
+    SearchByBoW(pKF1, pKF2) (LoopClosing::ComputeSim3; :522-655; sind_match_bow_kf).  Of ORBmatcher.cc only the monocular SearchForInitialization is not provided."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
 
     def __init__(self, fx, fy, cx, cy, bf, bounds, scale_factors, nnratio=0.6, checkOri=True, cap=4096, max_batch=1, device=0, cap_points=0):
@@ -183,6 +190,18 @@ class ORBmatcher:
                                n_cur=len(cur["node"]), cur_node=_i32(cur["node"]), cur_angle=_f32(cur["angle"]), cur_desc=_u8(cur["desc"])), "n_cur") for kf, cur in pairs]
         self._call("sind_match_by_bow", _Bow, items, C.c_float(self.nnratio if nnratio is None else nnratio), int(self.checkOri))
         return [_matches(a, "n_cur") for a in items]
+
+    def SearchByBoWKF(self, pairs, nnratio=None):
+        """SearchByBoW(pKF1, pKF2, vpMatches12) (:522-655; LoopClosing::ComputeSim3, one call for all candidates).  pairs: list of (kf1, kf2); either, per keypoint:
+        node, valid (pMP && !isBad), angle (mvKeysUn), desc.  nnratio None = the constructor's.  -> list of (match12 i32 [n1] = idx2 or -1, nmatches)"""
+        items = []
+        for k1, k2 in pairs:
+            a = {}
+            for s, k in (("1", k1), ("2", k2)):
+                a.update({"n" + s: len(k["node"]), "node" + s: _i32(k["node"]), "valid" + s: _u8(k["valid"]), "angle" + s: _f32(k["angle"]), "desc" + s: _u8(k["desc"])})
+            items.append(_outputs(a, "n1", "match12"))
+        self._call("sind_match_by_bow_kf", _BowKF, items, C.c_float(self.nnratio if nnratio is None else nnratio), int(self.checkOri))
+        return [_matches(a, "n1", "match12") for a in items]
 
     def SearchForTriangulation(self, pairs, bOnlyStereo=False):
         """pairs: list of (Tcw2, Cw1, F12, kf1, kf2); kf1, per keypoint: node, has_mp, un_xy, angle, u_right, desc; kf2: the same and octave.

@@ -1,4 +1,5 @@
-"""ORBVocabulary — the feature-vector half of the reference's ComputeBoW (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1259) over the C ABI."""
+"""ORBVocabulary — the reference's ComputeBoW (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1259, BowVector.cpp:34-84) over the C ABI: transform gives the
+feature vector, transform_bow the feature vector and the BowVector."""
 from __future__ import annotations
 
 import ctypes as C
@@ -45,3 +46,15 @@ class ORBVocabulary:
         n = (C.c_int * B)(*[len(d) for d in desc])
         check(lib().sind_voc_transform(self._h, ptrs(desc), n, B, int(levelsup), ptrs(node), ptrs(word)), "sind_voc_transform")
         return list(zip(node, word))
+
+    def transform_bow(self, list_of_desc, levelsup=4):
+        """list_of_desc: per frame u8 [n, 32] -> list of (node_id i32 [n], word_id i32 [n], bow_word i32 [n_words], bow_value f64 [n_words]): transform's two arrays
+        and the frame's BowVector as std::map iterates it (TF_IDF, L1 norm; word ids ascending, values in the reference's order of FP64 operations)"""
+        B = len(list_of_desc)
+        desc = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in list_of_desc]
+        node = [np.full(len(d), -1, np.int32) for d in desc]; word = [np.full(len(d), -1, np.int32) for d in desc]
+        bw = [np.zeros(len(d), np.int32) for d in desc]; bv = [np.zeros(len(d), np.float64) for d in desc]
+        ptrs = lambda arrs: (C.c_void_p * B)(*[x.ctypes.data if x.size else None for x in arrs])
+        n = (C.c_int * B)(*[len(d) for d in desc]); nw = (C.c_int * B)()
+        check(lib().sind_voc_transform_bow(self._h, ptrs(desc), n, B, int(levelsup), ptrs(node), ptrs(word), ptrs(bw), ptrs(bv), nw), "sind_voc_transform_bow")
+        return [(node[b], word[b], bw[b][:nw[b]].copy(), bv[b][:nw[b]].copy()) for b in range(B)]
