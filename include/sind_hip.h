@@ -644,6 +644,42 @@ typedef struct sind_match_sim3_pair {
 } sind_match_sim3_pair;
 int sind_match_by_sim3(sind_match* m, const sind_match_sim3_pair* pairs, int B, float th);
 
+/* sind_match_sim3_ransac.  Replaces, for B loop candidates at once and for all of their RANSAC iterations, the arithmetic of
+ *   Sim3Solver::Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale)            src/Sim3Solver.cc:37-112  (from :84 on: the per-correspondence values)
+ *   void Sim3Solver::ComputeSim3(cv::Mat& P1, cv::Mat& P2)                :226-337, ComputeCentroid :215-224
+ *   void Sim3Solver::CheckInliers()                                       :340-364, Project :382-403, FromCameraToImage :405-423
+ * (LoopClosing::ComputeSim3, src/LoopClosing.cc:274-301: the solver that turns the matches of sind_match_by_bow_kf into the s12, R12, t12 that
+ * sind_match_by_sim3 takes).  In Sim3Solver::iterate (:140-207) the sample of an iteration depends only on the random stream and on N, so the caller draws
+ * every triple beforehand, this call evaluates all of them, and iterate's bookkeeping (mnBestInliers, the early return, bNoMore, five iterations per candidate
+ * in turn) is a replay over `count` (INTEGRATION.md gives it in C++, sindslam_amd/sim3.py in Python).  Runs on the sind_match handle; fx fy cx cy are the
+ * handle's (the reference's mK1 and mK2 are the same matrix in an RGB-D run).
+ *   T1w, T2w = pKF1->GetPose(), pKF2->GetPose() (GetRotation / GetTranslation are their blocks)
+ *   per correspondence, i.e. per i1 that passes the tests of :64-79, in ascending i1 (the caller keeps mvnIndices1):
+ *       x3Dw1 = pMP1->GetWorldPos(), x3Dw2 = pMP2->GetWorldPos(), sigma2_1 = pKF1->mvLevelSigma2[kp1.octave], sigma2_2 = pKF2->mvLevelSigma2[kp2.octave]
+ *       (finite, >= 0).  The bound is (size_t)(9.210 * sigma2) as include/Sim3Solver.h:78-79 declares mvnMaxError1/2: an integer.
+ *   triple[3 h + k] = the index idx of :170 for draw k of iteration h (into the correspondences, not into pKF1's slots)
+ *   n_its <= sind_sim3_iterations(n, ...): the caller may pass fewer
+ * Outputs, per iteration h: count[h] = mnInliersi, inlier_bits[h * ceil(n / 64) + (i >> 6)] bit (i & 63) = mvbInliersi[i], s12[h] = ms12i, R12 = mR12i
+ * (row-major), t12 = mt12i; mT12i is [s12 * R12 | t12] in FP32.  A degenerate sample (NaN hypothesis) has count 0, as every comparison in the reference fails.
+ * ComputeSim3 runs on the host (csrc/host/sim3.cpp: FP64 libm calls, restated from OpenCV 4.2.0, parity unpinned), CheckInliers on the device in one launch
+ * (csrc/match_sim3.hip).
+ * Limits: n <= min(cap_last, cap_cur), n_its <= 300, B <= max_batch: beyond them SIND_E_CAPACITY.  A NULL array with a non-zero count, a triple index outside
+ * [0, n) or a sigma2 that is negative or not finite -> SIND_E_ARG.  On an error nothing is launched and the outputs are untouched.  n_its = 0 and B = 0 are valid.
+ *
+ * sind_sim3_iterations = mRansacMaxIts after Sim3Solver::SetRansacParameters(probability, min_inliers, max_its) (:114-138; LoopClosing: 0.99, 20, 300) for n
+ * correspondences; 0 if n < min_inliers, where iterate reports bNoMore at once (:146-150).  No handle, no device.
+ */
+typedef struct sind_sim3_item {
+    const float* T1w; const float* T2w;                 /* poses of pKF1 / pKF2, 4x4 row-major, rows 0..2 read */
+    int n; const float* x3Dw1; const float* x3Dw2;      /* the correspondences that survive :64-79, in i1 order: [n][3] each */
+    const float* sigma2_1; const float* sigma2_2;       /* mvLevelSigma2[kp.octave] per correspondence */
+    int n_its; const int* triple;                       /* [n_its][3] indices into 0..n-1 */
+    int* count; uint64_t* inlier_bits;                  /* outputs (host): [n_its], [n_its][ceil(n / 64)] */
+    float* s12; float* R12; float* t12;                 /* [n_its], [n_its][9], [n_its][3] */
+} sind_sim3_item;
+int sind_match_sim3_ransac(sind_match* m, const sind_sim3_item* items, int B, int fix_scale);
+int sind_sim3_iterations(int n, double probability, int min_inliers, int max_its);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of
  *   generatePointCloud(imgRGB, imgDepth, imgDepthLast, imgDynaMask, imgDynaMaskLast, imgLabel, poseRelative, Twc)

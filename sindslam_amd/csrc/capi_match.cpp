@@ -5,6 +5,7 @@
 #include <vector>
 #include "../../include/sind_hip.h"
 #include "match.hpp"
+#include "host/sim3.hpp"
 
 namespace {
 const int GRID_CELLS = 3072;                                       // Frame's 64 x 48 grid; grid_start has one entry more
@@ -105,6 +106,16 @@ struct sind_match {
             capP = cp; capK = ck; return SIND_OK;
         }
     } fuse, sim3;
+    // sind_match_sim3_ransac (match_sim3.hip), on first use: [maxB] candidates of min(cap_last, cap_cur) correspondences and SIM3_MAX_ITS hypotheses
+    struct RansacSide {
+        int cap = 0;
+        Staged<int> n, nIts, count; Staged<float4> corr; Staged<sind::Sim3Pose> hyp; Staged<unsigned long long> bits; std::vector<sind::Sim3Hyp> solved;
+        int reserve(size_t B, int c) {
+            const size_t nh = B * SIM3_MAX_ITS; int r = SIND_OK;
+            if ((r = n.alloc(B)) || (r = nIts.alloc(B)) || (r = count.alloc(nh)) || (r = corr.alloc(B * 3 * (size_t)c)) || (r = hyp.alloc(nh)) || (r = bits.alloc(nh * (size_t)divup(c, 64)))) return r;
+            solved.resize(nh); cap = c; return SIND_OK;
+        }
+    } ransac;
     int reserve_bow() {
         const size_t B = maxB, nl = B * prm.capLast, nc = B * prm.capCur; int r = SIND_OK;
         (r = last.node.alloc(nl)) || (r = last.xy.alloc(nl * 2)) || (r = last.uRight.alloc(nl)) || (r = cur.node.alloc(nc)) || (r = choice.alloc(nl)) || (r = bow.pose.alloc(B)) ||
@@ -465,6 +476,64 @@ int sind_match_by_sim3(sind_match* m, const sind_match_sim3_pair* pairs, int B, 
     SIND_TRY(w.match12.down((size_t)B * cs, s)); SIND_TRY(w.count.down(B, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (int b = 0; b < B; b++) { const sind_match_sim3_pair& q = pairs[b]; cpy(q.match12, &w.match12.h[(size_t)b * cs], (size_t)q.side1.n * sizeof(int)); *q.nfound = w.count.h[b]; }
+    return SIND_OK;
+}
+
+int sind_match_sim3_ransac(sind_match* m, const sind_sim3_item* items, int B, int fix_scale) {
+    const char* who = "sind_match_sim3_ransac: item";
+    if (!m || B < 0 || (B && !items)) { sind_set_error("sind_match_sim3_ransac: bad arguments"); return SIND_E_ARG; }
+    if (B > m->maxB) { sind_set_error("sind_match_sim3_ransac: B=%d over max_batch %d", B, m->maxB); return SIND_E_CAPACITY; }
+    const int cs = std::min(m->last.cap, m->cur.cap);
+    int its = 0, maxN = 0;
+    for (int b = 0; b < B; b++) {
+        const sind_sim3_item& q = items[b];
+        if (q.n < 0 || q.n_its < 0) { sind_set_error("%s %d: negative count", who, b); return SIND_E_ARG; }
+        if (q.n > cs || q.n_its > SIM3_MAX_ITS) { sind_set_error("%s %d has %d correspondences / %d iterations, capacity %d / %d", who, b, q.n, q.n_its, cs, SIM3_MAX_ITS); return SIND_E_CAPACITY; }
+        if ((q.n && (!q.T1w || !q.T2w || !q.x3Dw1 || !q.x3Dw2 || !q.sigma2_1 || !q.sigma2_2)) || (q.n_its && (!q.triple || !q.count || !q.s12 || !q.R12 || !q.t12 || (q.n && !q.inlier_bits)))) {
+            sind_set_error("%s %d: null array", who, b); return SIND_E_ARG;
+        }
+        for (int i = 0; i < q.n; i++) if (!(q.sigma2_1[i] >= 0 && q.sigma2_2[i] >= 0 && std::isfinite(q.sigma2_1[i]) && std::isfinite(q.sigma2_2[i]))) { sind_set_error("%s %d: sigma2 %d is not a finite non-negative number", who, b, i); return SIND_E_ARG; }
+        for (int k = 0; k < 3 * q.n_its; k++) if (q.triple[k] < 0 || q.triple[k] >= q.n) { sind_set_error("%s %d: triple index %d outside [0,%d)", who, b, q.triple[k], q.n); return SIND_E_ARG; }
+        its = std::max(its, q.n_its); maxN = std::max(maxN, q.n);
+    }
+    if (!its) return SIND_OK;                                                                          // nothing to evaluate, nothing to write
+    HIP_TRY(hipSetDevice(m->device));
+    sind_match::RansacSide& w = m->ransac;
+    if (!w.cap) SIND_TRY(w.reserve((size_t)m->maxB, cs));
+    const sind::MatchParams& c = m->prm;
+    const sind::Sim3Params p{c.fx, c.fy, c.cx, c.cy, cs, its, std::max(1, divup(maxN, 64))};
+    for (int b = 0; b < B; b++) {
+        const sind_sim3_item& q = items[b];
+        float4* c1 = &w.corr.h[(size_t)b * 3 * cs]; float4* c2 = c1 + cs; float4* im = c2 + cs;
+        for (int i = 0; i < q.n; i++) {                                                                // the constructor (:84-109)
+            float x1[3], x2[3], p1[2], p2[2];
+            sind::sim3_to_camera(q.T1w, q.x3Dw1 + 3 * i, x1); sind::sim3_to_camera(q.T2w, q.x3Dw2 + 3 * i, x2);
+            sind::sim3_to_image(c.fx, c.fy, c.cx, c.cy, x1, p1); sind::sim3_to_image(c.fx, c.fy, c.cx, c.cy, x2, p2);
+            c1[i] = make_float4(x1[0], x1[1], x1[2], sind::sim3_max_error(q.sigma2_1[i])); c2[i] = make_float4(x2[0], x2[1], x2[2], sind::sim3_max_error(q.sigma2_2[i]));
+            im[i] = make_float4(p1[0], p1[1], p2[0], p2[1]);
+        }
+        w.n.h[b] = q.n; w.nIts.h[b] = q.n_its;
+        for (int h = 0; h < q.n_its; h++) {                                                            // the sample (:166-177) and ComputeSim3
+            float P1[9], P2[9];
+            for (int k = 0; k < 3; k++) { const float4 a1 = c1[q.triple[3 * h + k]], a2 = c2[q.triple[3 * h + k]]; P1[k] = a1.x; P1[3 + k] = a1.y; P1[6 + k] = a1.z; P2[k] = a2.x; P2[3 + k] = a2.y; P2[6 + k] = a2.z; }
+            sind::Sim3Hyp& s = w.solved[(size_t)b * its + h];
+            sind::sim3_horn(P1, P2, fix_scale != 0, s);
+            sind::Sim3Pose& d = w.hyp.h[(size_t)b * its + h]; cpy(d.T12, s.T12, sizeof(d.T12)); cpy(d.T21, s.T21, sizeof(d.T21));
+        }
+    }
+    hipStream_t s = m->stream; const size_t nh = (size_t)B * its;
+    SIND_TRY(w.n.up(B, s)); SIND_TRY(w.nIts.up(B, s)); SIND_TRY(w.corr.up((size_t)B * 3 * cs, s)); SIND_TRY(w.hyp.up(nh, s));
+    SIND_TRY(sind::launch_sim3_check(p, sind::Sim3Arrays{w.n.d.p, w.nIts.d.p, w.corr.d.p, w.hyp.d.p, w.count.d.p, w.bits.d.p}, B, s));
+    SIND_TRY(w.count.down(nh, s)); SIND_TRY(w.bits.down(nh * p.words, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) {
+        const sind_sim3_item& q = items[b]; const int nw = divup(q.n, 64);
+        for (int h = 0; h < q.n_its; h++) {
+            const size_t o = (size_t)b * its + h; const sind::Sim3Hyp& r = w.solved[o];
+            q.count[h] = w.count.h[o]; cpy(q.inlier_bits + (size_t)h * nw, &w.bits.h[o * p.words], (size_t)nw * sizeof(uint64_t));
+            q.s12[h] = r.s12; cpy(q.R12 + 9 * h, r.R12, sizeof(r.R12)); cpy(q.t12 + 3 * h, r.t12, sizeof(r.t12));
+        }
+    }
     return SIND_OK;
 }
 

@@ -66,6 +66,18 @@ int launch_search_kf(const KfParams& p, const KfArrays& a, int items, int mode, 
 int launch_sim3_agree(const KfParams& p, const KfArrays& a, int B, hipStream_t s);
 int launch_project_kf(const LocalParams& p, const LocalArrays& a, int B, hipStream_t s);
 
+// Sim3Solver::CheckInliers for every (candidate, hypothesis) of a call (match_sim3.hip).  The hypotheses come from the host (host/sim3.cpp).
+#define SIM3_MAX_ITS 300                                          // mRansacMaxIts of LoopClosing::ComputeSim3
+struct Sim3Params { float fx, fy, cx, cy; int cap /* correspondences per candidate */, its /* hypotheses per candidate, this call */, words /* >= ceil(n / 64) of every candidate */; };
+struct Sim3Pose { float T12[12], T21[12]; };                       // rows 0..2 of mT12i, mT21i
+struct Sim3Arrays {                                               // device pointers
+    const int* n; const int* nIts;                                // [B]
+    const float4* corr;                                           // [B][3][cap]: (mvX3Dc1, mvnMaxError1), (mvX3Dc2, mvnMaxError2), (mvP1im1, mvP2im2)
+    const Sim3Pose* hyp;                                          // [B][its]
+    int* count; unsigned long long* bits;                         // outputs [B][its], [B][its][words]: mnInliersi, mvbInliersi (bit i & 63 of word i >> 6)
+};
+int launch_sim3_check(const Sim3Params& p, const Sim3Arrays& a, int B, hipStream_t s);
+
 // Vocabulary-guided searches (match_bow.hip): SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation.  Side A is the one whose entries act
 // (the key frame / pKF1, capacity capLast), side B the one searched (the frame / pKF2, capacity capCur).
 #define BOW_MAX_KEYS 4096                                         // keypoints per side one workgroup sorts in LDS

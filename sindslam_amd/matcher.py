@@ -82,6 +82,11 @@ class _Sim3Pair(C.Structure):
                 ("match12", C.c_void_p), ("nfound", C.c_void_p)]
 
 
+class _Sim3Item(C.Structure):
+    _fields_ = [("T1w", C.c_void_p), ("T2w", C.c_void_p), ("n", C.c_int), ("x3Dw1", C.c_void_p), ("x3Dw2", C.c_void_p), ("sigma2_1", C.c_void_p), ("sigma2_2", C.c_void_p),
+                ("n_its", C.c_int), ("triple", C.c_void_p), ("count", C.c_void_p), ("inlier_bits", C.c_void_p), ("s12", C.c_void_p), ("R12", C.c_void_p), ("t12", C.c_void_p)]
+
+
 _f32 = lambda a: np.ascontiguousarray(a, np.float32)
 _u8 = lambda a: np.ascontiguousarray(a, np.uint8)
 _i32 = lambda a: np.ascontiguousarray(a, np.int32)
@@ -121,7 +126,8 @@ class ORBmatcher:
     SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (Relocalization).  A frame / a set of map points is a dict of arrays
     (see include/sind_hip.h: sind_match_pair, sind_match_local, sind_match_reloc).  By vocabulary node: SearchByBoW(pKF, F) (TrackReferenceKeyFrame, Relocalization;
     :159-288) and SearchForTriangulation (LocalMapping::CreateNewMapPoints; :657-823), on node ids from vocabulary.ORBVocabulary (sind_match_bow, sind_match_tri), and SearchByBoWKF =
-    SearchByBoW(pKF1, pKF2) (LoopClosing::ComputeSim3; :522-655; sind_match_bow_kf).  Of ORBmatcher.cc only the monocular SearchForInitialization is not provided."""
+    SearchByBoW(pKF1, pKF2) (LoopClosing::ComputeSim3; :522-655; sind_match_bow_kf).  Of ORBmatcher.cc only the monocular SearchForInitialization is not provided.
+    On the same handle, between SearchByBoWKF and SearchBySim3 in LoopClosing::ComputeSim3: the Sim3Solver (src/Sim3Solver.cc; Sim3Ransac, sim3_solvers, sindslam_amd/sim3.py)."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
 
     def __init__(self, fx, fy, cx, cy, bf, bounds, scale_factors, nnratio=0.6, checkOri=True, cap=4096, max_batch=1, device=0, cap_points=0):
@@ -272,6 +278,28 @@ class ORBmatcher:
             a["n1"] = len(s1["valid"]); keep.append(a)
         check(lib().sind_match_by_sim3(self._h, arr, len(pairs), C.c_float(th)), "sind_match_by_sim3")
         return [(a["match12"][:a["n1"]].copy(), int(a["nfound"][0])) for a in keep]
+
+    def Sim3Ransac(self, items, bFixScale):
+        """sind_match_sim3_ransac: ComputeSim3 + CheckInliers (src/Sim3Solver.cc:226-364) of every given sample of every candidate, one call.  items: list of (inp, triples);
+        inp: T1w, T2w and, per correspondence, x3Dw1, x3Dw2, sigma2_1, sigma2_2; triples i32 [k, 3] into the correspondences.
+        -> list of dicts: count i32 [k], bits u64 [k, ceil(n / 64)], s12 f32 [k], R12 f32 [k, 3, 3], t12 f32 [k, 3]"""
+        its = []
+        for inp, tri in items:
+            n, k = len(inp["sigma2_1"]), len(tri)
+            its.append(dict(T1w=_f32(inp["T1w"]), T2w=_f32(inp["T2w"]), n=n, x3Dw1=_f32(inp["x3Dw1"]), x3Dw2=_f32(inp["x3Dw2"]), sigma2_1=_f32(inp["sigma2_1"]), sigma2_2=_f32(inp["sigma2_2"]),
+                            n_its=k, triple=_i32(tri), count=np.zeros(k, np.int32), inlier_bits=np.zeros((k, (n + 63) // 64), np.uint64), s12=np.zeros(k, np.float32),
+                            R12=np.zeros((k, 3, 3), np.float32), t12=np.zeros((k, 3), np.float32)))
+        self._call("sind_match_sim3_ransac", _Sim3Item, its, int(bool(bFixScale)))
+        return [dict(count=a["count"], bits=a["inlier_bits"], s12=a["s12"], R12=a["R12"], t12=a["t12"]) for a in its]
+
+    def sim3_solvers(self, candidates, bFixScale, rand, rand_max=2147483647):
+        """The Sim3Solvers of LoopClosing::ComputeSim3 (src/LoopClosing.cc:252-280), on one tape of `rand`'s raw values and on this handle.  candidates: per initial candidate
+        None (vbDiscarded: a bad key frame, fewer than 20 matches) or the flattened constructor (src/Sim3Solver.cc:37-112): T1w, T2w, and per correspondence that passes :64-79, in i1
+        order: x3Dw1, x3Dw2, sigma2_1, sigma2_2, indices1 (= i1, mvnIndices1); N1 = vpMatched12.size().  -> list of sim3.Sim3Solver or None, for sim3.compute_sim3"""
+        from .sim3 import Sim3Solver, Tape
+        tape = Tape(rand, rand_max)
+        evaluate = lambda requests, fix: self.Sim3Ransac([(s.inp, tri) for s, tri in requests], fix)
+        return [None if c is None else Sim3Solver(evaluate, tape, c, bFixScale) for c in candidates]
 
     def last_rounds(self):
         return lib().sind_match_last_rounds(self._h)
