@@ -680,6 +680,48 @@ typedef struct sind_sim3_item {
 int sind_match_sim3_ransac(sind_match* m, const sind_sim3_item* items, int B, int fix_scale);
 int sind_sim3_iterations(int n, double probability, int min_inliers, int max_its);
 
+/* sind_match_pnp_ransac.  Replaces, for B relocalisation candidates at once and for all of their RANSAC iterations, the arithmetic of
+ *   double PnPsolver::compute_pose(double R[3][3], double t[3])           src/PnPsolver.cc:477-525 and everything it calls (:375-950): EPnP
+ *   void PnPsolver::CheckInliers()                                        :308-339
+ *   bool PnPsolver::Refine()                                              :260-305
+ * (Tracking::Relocalization, src/Tracking.cc:1347-1540: the solver between sind_match_by_bow and sind_match_by_projection_kf).  In PnPsolver::iterate
+ * (:165-258) the sample of an iteration depends only on the random stream and on N, so the caller draws every sample beforehand; this call evaluates all of
+ * them ON THE DEVICE (csrc/match_pnp.hip; csrc/host/epnp.hpp is one source for host and device, FP64, restated from OpenCV 4.2.0, parity unpinned: see that
+ * header), finds on the host which Refine problems the reference would solve, and evaluates those as well.  iterate's bookkeeping is a replay over `count`
+ * and `refine` (INTEGRATION.md gives it in C++, sindslam_amd/pnp.py in Python).  Runs on the sind_match handle.
+ * Calibration: fu fv uc vc are the handle's fx fy cx cy, read as the FP64 of the FP32 the handle holds (PnPsolver: `fu = F.fx`, a double member from a float).
+ * The constructor (:67-110) stays with the caller, flattened: per correspondence, i.e. per keypoint i with pMP && !pMP->isBad(), in ascending i (the caller
+ * keeps mvKeyPointIndices):  p2d = F.mvKeysUn[i].pt, sigma2 = F.mvLevelSigma2[kp.octave] (finite, >= 0), x3Dw = pMP->GetWorldPos().
+ *   th2, min_inliers: mvMaxError[i] = sigma2[i] * th2 (a float product) and mRansacMinInliers AFTER SetRansacParameters (sind_pnp_ransac_params); min_inliers >= 1
+ *   samples[4 h + k] = the index idx of :195 for draw k of iteration h (into the correspondences); the four of an iteration are distinct
+ *   best_count, best_bits = mnBestInliers and mvbBestInliers the solver holds from earlier calls (0 and NULL: none); best_bits has best_count bits set
+ * Outputs, per iteration h: count[h] = mnInliersi, inlier_bits[h * ceil(n / 64) + (i >> 6)] bit (i & 63) = mvbInliersi[i], R (row-major) = mRi, t = mti,
+ * refine[h] = the row of the refine outputs that holds what Refine() computes in iteration h, -1 if count[h] < min_inliers (no Refine).
+ * Per refine r < *n_refines (at most n_its + 1 rows): refine_hyp[r] = the iteration whose inlier set it refines, -1 for best_bits; refine_count, refine_bits,
+ * refine_R, refine_t = mnRefinedInliers, mvbRefinedInliers, mRi, mti after Refine()'s compute_pose and CheckInliers.  Refine() returns true iff
+ * refine_count > min_inliers; mBestTcw / mRefinedTcw are R, t converted to FP32.  A NaN pose has count 0, as every comparison in the reference fails.
+ * The refine problems are solved PNP_REFINE_SLOTS at a time; more of them means further rounds inside the call, not an error.
+ * Limits: n <= min(cap_last, cap_cur), n_its <= 300, B <= max_batch: beyond them SIND_E_CAPACITY.  A NULL array with a non-zero count, a sample index outside
+ * [0, n), a repeated index inside a sample, a sigma2 that is negative or not finite, min_inliers < 1, or a best_count that is not the number of bits set in
+ * best_bits -> SIND_E_ARG.  On an error nothing is launched and the outputs are untouched.  n_its = 0 and B = 0 are valid: a call in which no item has an iteration writes nothing;
+ * in a call in which some item has, an item with n_its = 0 gets *n_refines = 0 (if n_refines is not NULL) and nothing else.
+ *
+ * sind_pnp_ransac_params = mRansacMinInliers and mRansacMaxIts after PnPsolver::SetRansacParameters(probability, min_inliers, max_its, min_set, epsilon, th2)
+ * (:121-157; the header's defaults 0.99, 8, 300, 4, 0.4, 5.991; Relocalization: 0.99, 10, 300, 4, 0.5, 5.991) for n > 0 correspondences.  No handle, no device.
+ */
+typedef struct sind_pnp_item {
+    int n; const float* x3Dw; const float* p2d; const float* sigma2;   /* the correspondences: [n][3], [n][2], [n] */
+    float th2; int min_inliers;
+    int n_its; const int* samples;                      /* [n_its][4] indices into 0..n-1 */
+    int best_count; const uint64_t* best_bits;          /* [ceil(n / 64)] or NULL */
+    int* count; uint64_t* inlier_bits;                  /* outputs (host): [n_its], [n_its][ceil(n / 64)] */
+    double* R; double* t; int* refine;                  /* [n_its][9], [n_its][3], [n_its] */
+    int* n_refines; int* refine_hyp; int* refine_count; /* [1], [n_its + 1], [n_its + 1] */
+    uint64_t* refine_bits; double* refine_R; double* refine_t;   /* [n_its + 1][ceil(n / 64)], [n_its + 1][9], [n_its + 1][3] */
+} sind_pnp_item;
+int sind_match_pnp_ransac(sind_match* m, const sind_pnp_item* items, int B);
+void sind_pnp_ransac_params(int n, double probability, int min_inliers, int max_its, int min_set, float epsilon, int* min_inliers_out, int* max_its_out);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of
  *   generatePointCloud(imgRGB, imgDepth, imgDepthLast, imgDynaMask, imgDynaMaskLast, imgLabel, poseRelative, Twc)

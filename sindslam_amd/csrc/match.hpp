@@ -78,6 +78,25 @@ struct Sim3Arrays {                                               // device poin
 };
 int launch_sim3_check(const Sim3Params& p, const Sim3Arrays& a, int B, hipStream_t s);
 
+// PnPsolver: EPnP and CheckInliers for every (candidate, sample) of a call, and for the Refine problems that follow from their counts (match_pnp.hip, host/epnp.hpp)
+#define PNP_MAX_ITS 300                                           // mRansacMaxIts of Tracking::Relocalization
+#define PNP_REFINE_SLOTS 32                                       // Refine problems per round: each holds 12 cap doubles of workspace
+struct PnpParams { double fu, fv, uc, vc; int cap /* correspondences per candidate */, its /* samples per candidate, this call */, words /* >= ceil(n / 64) of every candidate */; };
+struct PnpPose { double R[9], t[3]; };                            // mRi (row-major), mti
+struct PnpRefine { int b, hyp; };                                 // candidate; the iteration whose inlier bits are the set, -1: the candidate's bestBits
+struct PnpArrays {                                                // device pointers
+    const int* n; const int* nIts;                                // [B]
+    const float4* pts; const float2* uv;                          // [B][cap]: (mvP3Dw, mvMaxError), mvP2D
+    const int4* samples;                                          // [B][its]
+    const unsigned long long* bestBits;                           // [B][words]
+    PnpPose* pose; int* count; unsigned long long* bits;          // outputs [B][its], [B][its], [B][its][words]
+    const PnpRefine* refine;                                      // [PNP_REFINE_SLOTS], this round's
+    double* work;                                                 // [12 cap][PNP_REFINE_SLOTS]: pws, us, alphas, pcs of every slot, slots interleaved
+    PnpPose* refPose; int* refCount; unsigned long long* refBits; // outputs [PNP_REFINE_SLOTS], .., [PNP_REFINE_SLOTS][words]
+};
+int launch_pnp_samples(const PnpParams& p, const PnpArrays& a, int B, hipStream_t s);        // compute_pose + CheckInliers of every sample
+int launch_pnp_refines(const PnpParams& p, const PnpArrays& a, int nRefines, hipStream_t s); // Refine(): compute_pose on an inlier set + CheckInliers
+
 // Vocabulary-guided searches (match_bow.hip): SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation.  Side A is the one whose entries act
 // (the key frame / pKF1, capacity capLast), side B the one searched (the frame / pKF2, capacity capCur).
 #define BOW_MAX_KEYS 4096                                         // keypoints per side one workgroup sorts in LDS

@@ -87,6 +87,12 @@ class _Sim3Item(C.Structure):
                 ("n_its", C.c_int), ("triple", C.c_void_p), ("count", C.c_void_p), ("inlier_bits", C.c_void_p), ("s12", C.c_void_p), ("R12", C.c_void_p), ("t12", C.c_void_p)]
 
 
+class _PnpItem(C.Structure):
+    _fields_ = [("n", C.c_int), ("x3Dw", C.c_void_p), ("p2d", C.c_void_p), ("sigma2", C.c_void_p), ("th2", C.c_float), ("min_inliers", C.c_int), ("n_its", C.c_int), ("samples", C.c_void_p),
+                ("best_count", C.c_int), ("best_bits", C.c_void_p), ("count", C.c_void_p), ("inlier_bits", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p), ("refine", C.c_void_p),
+                ("n_refines", C.c_void_p), ("refine_hyp", C.c_void_p), ("refine_count", C.c_void_p), ("refine_bits", C.c_void_p), ("refine_R", C.c_void_p), ("refine_t", C.c_void_p)]
+
+
 _f32 = lambda a: np.ascontiguousarray(a, np.float32)
 _u8 = lambda a: np.ascontiguousarray(a, np.uint8)
 _i32 = lambda a: np.ascontiguousarray(a, np.int32)
@@ -127,14 +133,15 @@ class ORBmatcher:
     (see include/sind_hip.h: sind_match_pair, sind_match_local, sind_match_reloc).  By vocabulary node: SearchByBoW(pKF, F) (TrackReferenceKeyFrame, Relocalization;
     :159-288) and SearchForTriangulation (LocalMapping::CreateNewMapPoints; :657-823), on node ids from vocabulary.ORBVocabulary (sind_match_bow, sind_match_tri), and SearchByBoWKF =
     SearchByBoW(pKF1, pKF2) (LoopClosing::ComputeSim3; :522-655; sind_match_bow_kf).  Of ORBmatcher.cc only the monocular SearchForInitialization is not provided.
-    On the same handle, between SearchByBoWKF and SearchBySim3 in LoopClosing::ComputeSim3: the Sim3Solver (src/Sim3Solver.cc; Sim3Ransac, sim3_solvers, sindslam_amd/sim3.py)."""
+    On the same handle, between SearchByBoWKF and SearchBySim3 in LoopClosing::ComputeSim3: the Sim3Solver (src/Sim3Solver.cc; Sim3Ransac, sim3_solvers, sindslam_amd/sim3.py).
+    Between SearchByBoW and SearchByProjectionKF in Tracking::Relocalization: the PnPsolver (src/PnPsolver.cc; PnPRansac, pnp_solvers, sindslam_amd/pnp.py)."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
 
     def __init__(self, fx, fy, cx, cy, bf, bounds, scale_factors, nnratio=0.6, checkOri=True, cap=4096, max_batch=1, device=0, cap_points=0):
         cfg = _Config(fx, fy, cx, cy, bf, (C.c_float * 4)(*[float(b) for b in bounds]),
                       (C.c_float * 16)(*([float(s) for s in scale_factors] + [0.0] * (16 - len(scale_factors)))),
                       len(scale_factors), cap, cap, max_batch, device)
-        self.checkOri, self.nnratio = checkOri, nnratio
+        self.checkOri, self.nnratio, self.max_batch = checkOri, nnratio, int(max_batch)
         h = C.c_void_p()
         check(lib().sind_match_create(C.byref(cfg), C.byref(h)), "sind_match_create")
         self._h = h
@@ -300,6 +307,45 @@ class ORBmatcher:
         tape = Tape(rand, rand_max)
         evaluate = lambda requests, fix: self.Sim3Ransac([(s.inp, tri) for s, tri in requests], fix)
         return [None if c is None else Sim3Solver(evaluate, tape, c, bFixScale) for c in candidates]
+
+    def PnPRansac(self, items):
+        """sind_match_pnp_ransac: EPnP + CheckInliers (src/PnPsolver.cc:308-339, :375-950) of every given sample of every candidate and of the Refine problems (:260-305)
+        that follow from the counts, one call, all on the device.  items: list of (inp, samples, min_inliers, best_count, best_bits); inp, per correspondence: x3Dw, p2d,
+        sigma2, and th2; samples i32 [k, 4] into the correspondences; min_inliers = mRansacMinInliers; best_count, best_bits (u64 words or None) = mnBestInliers,
+        mvbBestInliers held from earlier calls.  -> list of dicts: count i32 [k], bits u64 [k, ceil(n / 64)], R f64 [k, 3, 3], t f64 [k, 3], refine i32 [k] (row of the
+        refine_* arrays or -1), refine_hyp i32 [r], refine_count i32 [r], refine_bits u64 [r, words], refine_R f64 [r, 3, 3], refine_t f64 [r, 3]"""
+        arr = (_PnpItem * len(items))(); keep = []
+        for q, (inp, samples, min_inliers, best_count, best_bits) in zip(arr, items):
+            n, k = len(inp["sigma2"]), len(samples); w = (n + 63) // 64
+            a = dict(x3Dw=_f32(inp["x3Dw"]), p2d=_f32(inp["p2d"]), sigma2=_f32(inp["sigma2"]), samples=_i32(samples), count=np.zeros(k, np.int32), inlier_bits=np.zeros((k, w), np.uint64),
+                     R=np.zeros((k, 3, 3), np.float64), t=np.zeros((k, 3), np.float64), refine=np.full(k, -1, np.int32), n_refines=np.zeros(1, np.int32), refine_hyp=np.full(k + 1, -1, np.int32),
+                     refine_count=np.zeros(k + 1, np.int32), refine_bits=np.zeros((k + 1, w), np.uint64), refine_R=np.zeros((k + 1, 3, 3), np.float64), refine_t=np.zeros((k + 1, 3), np.float64))
+            if best_bits is not None:
+                a["best_bits"] = np.ascontiguousarray(best_bits, np.uint64)
+            for key, v in a.items():
+                setattr(q, key, v.ctypes.data if v.size else None)
+            q.n, q.n_its, q.th2, q.min_inliers, q.best_count = n, k, float(inp["th2"]), int(min_inliers), int(best_count)
+            keep.append(a)
+        check(lib().sind_match_pnp_ransac(self._h, arr, len(items)), "sind_match_pnp_ransac")
+        out = []
+        for a in keep:
+            r = int(a["n_refines"][0])
+            out.append(dict(count=a["count"], bits=a["inlier_bits"], R=a["R"], t=a["t"], refine=a["refine"], **{key: a[key][:r] for key in ("refine_hyp", "refine_count", "refine_bits", "refine_R", "refine_t")}))
+        return out
+
+    def pnp_solvers(self, candidates, rand, rand_max=2147483647):
+        """The PnPsolvers of Tracking::Relocalization (src/Tracking.cc:1407-1428), on one tape of `rand`'s raw values and on this handle.  candidates: per candidate None
+        (vbDiscarded: a bad key frame, fewer than 15 matches) or the flattened constructor (src/PnPsolver.cc:67-110): per keypoint i with pMP && !pMP->isBad(), in ascending i:
+        x3Dw, p2d, sigma2, indices (= i, mvKeyPointIndices); n_keypoints = vpMapPointMatches.size().  -> list of pnp.PnPsolver or None, for pnp.relocalization_pnp.
+        Every solver has the header's default parameters; Relocalization calls SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991) on each."""
+        from .pnp import PnPsolver
+        from .sim3 import Tape
+        tape = Tape(rand, rand_max)
+        solvers = [None if c is None else PnPsolver(self.PnPRansac, tape, c) for c in candidates]
+        for s in solvers:
+            if s is not None:
+                s.max_batch = self.max_batch                            # relocalization_pnp evaluates that many candidates per call
+        return solvers
 
     def last_rounds(self):
         return lib().sind_match_last_rounds(self._h)

@@ -53,6 +53,16 @@ class Tape:
             moved[randi] = moved.get(size - 1, size - 1)                  # vAvailableIndices[randi] = vAvailableIndices.back(); pop_back()
         return out
 
+    def sample(self, pos, n, k):
+        """the k distinct idx that k draws at tape positions pos .. pos + k - 1 take from vAvailableIndices = 0 .. n - 1 (PnPsolver::iterate :188-201, k = mRansacMinSet)"""
+        moved, out = {}, []
+        for i in range(k):
+            size = n - i
+            randi = random_int(self.at(pos + i), 0, size - 1, self.rand_max)
+            out.append(moved.get(randi, randi))
+            moved[randi] = moved.get(size - 1, size - 1)
+        return out
+
 
 class Sim3Solver:
     """Sim3Solver of the reference, its state and semantics; made by ORBmatcher.sim3_solvers.  iterate / find / GetEstimated* as there; SetRansacParameters as there."""
