@@ -722,6 +722,34 @@ typedef struct sind_pnp_item {
 int sind_match_pnp_ransac(sind_match* m, const sind_pnp_item* items, int B);
 void sind_pnp_ransac_params(int n, double probability, int min_inliers, int max_its, int min_set, float epsilon, int* min_inliers_out, int* max_its_out);
 
+/* sind_match_pose_optimize.  Replaces, for B frames (or relocalisation candidates) at once, the whole of
+ *   int Optimizer::PoseOptimization(Frame *pFrame)                        src/Optimizer.cc:239-451
+ * (Tracking::TrackReferenceKeyFrame, TrackWithMotionModel, TrackLocalMap: src/Tracking.cc:812, 935, 977; Relocalization: :1477, 1493, 1508): the g2o graph of one
+ * VertexSE3Expmap and N EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose with Huber kernels, OptimizationAlgorithmLevenberg over LinearSolverDense, the
+ * four rounds of ten iterations from the input pose and the outlier classification between them, ONE launch for all items (csrc/match_pose.hip, one workgroup
+ * per item; csrc/host/pose_opt.hpp is one FP64 source for host and device).  H, b and the robust chi2 are g2o's sums: every entry added in ascending edge order.
+ * Calibration: fx fy cx cy bf are the handle's, read as the FP64 of the FP32 it holds (`e->fx = pFrame->fx`).  Runs on the sind_match handle.
+ * What stays with the caller is the flattening (:280-360): per keypoint i with pFrame->mvpMapPoints[i] != NULL, in ascending i (PoseOptimization does not test
+ * isBad; the caller keeps the index list and scatters `outlier` back into mvbOutlier):  x3Dw = pMP->GetWorldPos(), obs_xy = mvKeysUn[i].pt, u_right = mvuRight[i]
+ * (< 0: the monocular edge), inv_sigma2 = mvInvLevelSigma2[kpUn.octave] (finite, >= 0); Tcw = pFrame->mTcw (finite).  And pFrame->SetPose(Tcw_out) afterwards.
+ * Outputs: Tcw_out = the matrix SetPose gets; outlier[i] = mvbOutlier of the correspondence; *n_good = nInitialCorrespondences - nBad.  n < 3: *n_good = 0,
+ * *n_rounds = 0 and NOTHING else is written (the reference returns before SetPose).  n < 10: one round only (:440).  The round arrays may be NULL; rounds that
+ * did not run keep zeros: round_iters = optimize()'s return, round_nbad = nBad after the round, round_pose = [R row-major | t] of the vertex, round_chi2 =
+ * activeRobustChi2 after the round's last accepted step, round_lambda = _currentLambda at its end.
+ * Unpinned: parity with a real g2o / Eigen build (Eigen's evaluation order in the small products, its LDLT, the reference's -march=native contraction, and sin / cos /
+ * pow, which pose_opt.hpp defines instead of calling a maths library); see the head of that file, also for the two places where the reference reads state it never set.
+ * Limits: n <= min(cap_last, cap_cur), B <= max_batch: beyond them SIND_E_CAPACITY.  A NULL array with n > 0 (Tcw, Tcw_out, n_good, n_rounds always), an inv_sigma2 that
+ * is negative or not finite, a pose that is not finite -> SIND_E_ARG.  On an error nothing is launched and the outputs are untouched.  B = 0 and n = 0 are valid.
+ */
+typedef struct sind_poseopt_item {
+    int n; const float* x3Dw; const float* obs_xy; const float* u_right; const float* inv_sigma2;  /* [n][3], [n][2], [n] (< 0: monocular edge), [n] */
+    const float* Tcw;                                   /* [16] row-major: pFrame->mTcw on entry */
+    float* Tcw_out; uint8_t* outlier; int* n_good;      /* [16] = the pose SetPose gets; [n] = mvbOutlier; nInitialCorrespondences - nBad */
+    int* n_rounds; int* round_iters; int* round_nbad;   /* [1]; [4] optimize()'s return per round; [4] */
+    double* round_pose; double* round_chi2; double* round_lambda;  /* [4][12] R row-major | t after the round; [4] activeRobustChi2 after its last accepted step; [4] _currentLambda at its end */
+} sind_poseopt_item;
+int sind_match_pose_optimize(sind_match* m, const sind_poseopt_item* items, int B);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of
  *   generatePointCloud(imgRGB, imgDepth, imgDepthLast, imgDynaMask, imgDynaMaskLast, imgLabel, poseRelative, Twc)

@@ -7,6 +7,7 @@
 #include "match.hpp"
 #include "host/sim3.hpp"
 #include "host/pnp.hpp"
+#include "host/pose_opt.hpp"
 
 namespace {
 const int GRID_CELLS = 3072;                                       // Frame's 64 x 48 grid; grid_start has one entry more
@@ -131,6 +132,16 @@ struct sind_match {
             refineOfHyp.resize(PNP_MAX_ITS); hypOfRefine.resize(PNP_MAX_ITS + 1); cap = c; return SIND_OK;
         }
     } pnp;
+    // sind_match_pose_optimize (match_pose.hip), on first use: [maxB] items of min(cap_last, cap_cur) correspondences
+    struct PoseSide {
+        int cap = 0;
+        Staged<int> n; Staged<float> Tcw; Staged<float4> pts, obs; Staged<uint8_t> outlier; Staged<sind::PoseOptResult> res;
+        int reserve(size_t B, int c) {
+            int r = SIND_OK;
+            if ((r = n.alloc(B)) || (r = Tcw.alloc(B * 16)) || (r = pts.alloc(B * (size_t)c)) || (r = obs.alloc(B * (size_t)c)) || (r = outlier.alloc(B * (size_t)c)) || (r = res.alloc(B))) return r;
+            cap = c; return SIND_OK;
+        }
+    } poseopt;
     int reserve_bow() {
         const size_t B = maxB, nl = B * prm.capLast, nc = B * prm.capCur; int r = SIND_OK;
         (r = last.node.alloc(nl)) || (r = last.xy.alloc(nl * 2)) || (r = last.uRight.alloc(nl)) || (r = cur.node.alloc(nc)) || (r = choice.alloc(nl)) || (r = bow.pose.alloc(B)) ||
@@ -630,6 +641,49 @@ int sind_match_pnp_ransac(sind_match* m, const sind_pnp_item* items, int B) {
             q.refine_count[r] = w.refCount.h[j]; cpy(q.refine_bits + (size_t)r * nw, &w.refBits.h[(size_t)j * p.words], (size_t)nw * sizeof(uint64_t));
             cpy(q.refine_R + 9 * r, o.R, sizeof(o.R)); cpy(q.refine_t + 3 * r, o.t, sizeof(o.t));
         }
+    }
+    return SIND_OK;
+}
+
+int sind_match_pose_optimize(sind_match* m, const sind_poseopt_item* items, int B) {
+    const char* who = "sind_match_pose_optimize: item";
+    if (!m || B < 0 || (B && !items)) { sind_set_error("sind_match_pose_optimize: bad arguments"); return SIND_E_ARG; }
+    if (B > m->maxB) { sind_set_error("sind_match_pose_optimize: B=%d over max_batch %d", B, m->maxB); return SIND_E_CAPACITY; }
+    const int cs = std::min(m->last.cap, m->cur.cap);
+    int maxN = 0;
+    for (int b = 0; b < B; b++) {
+        const sind_poseopt_item& q = items[b];
+        if (q.n > cs) { sind_set_error("%s %d has %d correspondences, capacity %d", who, b, q.n, cs); return SIND_E_CAPACITY; }
+        static const char* const what[] = {"", "negative count", "null array", "an inv_sigma2 is not a finite non-negative number", "the pose is not finite"};
+        if (const int bad = sind::poseopt_check(q)) { sind_set_error("%s %d: %s", who, b, what[bad]); return SIND_E_ARG; }
+        maxN = std::max(maxN, q.n);
+    }
+    if (!B) return SIND_OK;
+    static_assert(sizeof(sind::PoseOptResult) == sizeof(sind::PoseOptOut), "PoseOptResult is PoseOptOut");
+    if (maxN < 3) {                                                                                     // the reference's `return 0` for every item: nothing to launch
+        for (int b = 0; b < B; b++) { *items[b].n_good = 0; *items[b].n_rounds = 0; }
+        return SIND_OK;
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    sind_match::PoseSide& w = m->poseopt;
+    if (!w.cap) SIND_TRY(w.reserve((size_t)m->maxB, cs));
+    const sind::MatchParams& c = m->prm;
+    const sind::PoseOptParams p{(double)c.fx, (double)c.fy, (double)c.cx, (double)c.cy, (double)c.bf, cs};
+    for (int b = 0; b < B; b++) {
+        const sind_poseopt_item& q = items[b];
+        float4* pt = &w.pts.h[(size_t)b * cs]; float4* ob = &w.obs.h[(size_t)b * cs];
+        for (int i = 0; i < q.n; i++) { pt[i] = make_float4(q.x3Dw[3 * i], q.x3Dw[3 * i + 1], q.x3Dw[3 * i + 2], q.inv_sigma2[i]); ob[i] = make_float4(q.obs_xy[2 * i], q.obs_xy[2 * i + 1], q.u_right[i], 0.f); }
+        w.n.h[b] = q.n; cpy(&w.Tcw.h[(size_t)b * 16], q.Tcw, 16 * sizeof(float));
+    }
+    hipStream_t s = m->stream; const size_t k = (size_t)B * cs;
+    sind::PoseOptArrays a{w.n.d.p, w.Tcw.d.p, w.pts.d.p, w.obs.d.p, w.outlier.d.p, w.res.d.p};
+    SIND_TRY(w.n.up(B, s)); SIND_TRY(w.Tcw.up((size_t)B * 16, s)); SIND_TRY(w.pts.up(k, s)); SIND_TRY(w.obs.up(k, s));
+    SIND_TRY(sind::launch_pose_optimize(p, a, B, s));
+    SIND_TRY(w.outlier.down(k, s)); SIND_TRY(w.res.down(B, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) {
+        sind::PoseOptOut o; std::memcpy(&o, &w.res.h[b], sizeof(o));
+        sind::poseopt_store(items[b], o, &w.outlier.h[(size_t)b * cs]);
     }
     return SIND_OK;
 }

@@ -97,6 +97,16 @@ struct PnpArrays {                                                // device poin
 int launch_pnp_samples(const PnpParams& p, const PnpArrays& a, int B, hipStream_t s);        // compute_pose + CheckInliers of every sample
 int launch_pnp_refines(const PnpParams& p, const PnpArrays& a, int nRefines, hipStream_t s); // Refine(): compute_pose on an inlier set + CheckInliers
 
+// Optimizer::PoseOptimization, whole, one workgroup per item (match_pose.hip, host/pose_opt.hpp)
+struct PoseOptParams { double fx, fy, cx, cy, bf; int cap /* correspondences per item */; };
+struct PoseOptResult { float Tcw[16]; int nGood, nRounds, iters[4], nbad[4]; double pose[4][12], chi2[4], lambda[4]; };    // = sind::PoseOptOut of pose_opt.hpp
+struct PoseOptArrays {                                            // device pointers
+    const int* n; const float* Tcw;                               // [B], [B][16]
+    const float4* pts; const float4* obs;                         // [B][cap]: (Xw, invSigma2), (kpUn.pt, mvuRight, unused)
+    uint8_t* outlier; PoseOptResult* res;                         // outputs [B][cap] (mvbOutlier = the edge's level, the kernel's working state too), [B]
+};
+int launch_pose_optimize(const PoseOptParams& p, const PoseOptArrays& a, int B, hipStream_t s);
+
 // Vocabulary-guided searches (match_bow.hip): SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation.  Side A is the one whose entries act
 // (the key frame / pKF1, capacity capLast), side B the one searched (the frame / pKF2, capacity capCur).
 #define BOW_MAX_KEYS 4096                                         // keypoints per side one workgroup sorts in LDS

@@ -93,6 +93,12 @@ class _PnpItem(C.Structure):
                 ("n_refines", C.c_void_p), ("refine_hyp", C.c_void_p), ("refine_count", C.c_void_p), ("refine_bits", C.c_void_p), ("refine_R", C.c_void_p), ("refine_t", C.c_void_p)]
 
 
+class _PoseOptItem(C.Structure):
+    _fields_ = [("n", C.c_int), ("x3Dw", C.c_void_p), ("obs_xy", C.c_void_p), ("u_right", C.c_void_p), ("inv_sigma2", C.c_void_p), ("Tcw", C.c_void_p), ("Tcw_out", C.c_void_p),
+                ("outlier", C.c_void_p), ("n_good", C.c_void_p), ("n_rounds", C.c_void_p), ("round_iters", C.c_void_p), ("round_nbad", C.c_void_p), ("round_pose", C.c_void_p),
+                ("round_chi2", C.c_void_p), ("round_lambda", C.c_void_p)]
+
+
 _f32 = lambda a: np.ascontiguousarray(a, np.float32)
 _u8 = lambda a: np.ascontiguousarray(a, np.uint8)
 _i32 = lambda a: np.ascontiguousarray(a, np.int32)
@@ -126,6 +132,26 @@ def _matches(a, count, key="match_of_cur"):
     return a[key][:a[count]].copy(), int(a["nmatches"][0])
 
 
+def poseopt_items(items):
+    """the sind_poseopt_item array of ORBmatcher.PoseOptimization's items, and the arrays it points to (which live as long as the caller keeps them)"""
+    arr = (_PoseOptItem * len(items))(); keep = []
+    for q, it in zip(arr, items):
+        n = len(it["u_right"])
+        a = dict(x3Dw=_f32(it["x3Dw"]), obs_xy=_f32(it["obs_xy"]), u_right=_f32(it["u_right"]), inv_sigma2=_f32(it["inv_sigma2"]), Tcw=_f32(it["Tcw"]).reshape(4, 4).copy())
+        a.update(Tcw_out=a["Tcw"].copy(), outlier=np.zeros(n, np.uint8), n_good=np.zeros(1, np.int32), n_rounds=np.zeros(1, np.int32), round_iters=np.zeros(4, np.int32),
+                 round_nbad=np.zeros(4, np.int32), round_pose=np.zeros((4, 12), np.float64), round_chi2=np.zeros(4, np.float64), round_lambda=np.zeros(4, np.float64))
+        for key, v in a.items():
+            setattr(q, key, v.ctypes.data if v.size else None)
+        q.n = n
+        keep.append(a)
+    return arr, keep
+
+
+def poseopt_result(a):
+    return dict(Tcw=a["Tcw_out"], outlier=a["outlier"], n_good=int(a["n_good"][0]), n_rounds=int(a["n_rounds"][0]),
+                **{k: a[k] for k in ("round_iters", "round_nbad", "round_pose", "round_chi2", "round_lambda")})
+
+
 class ORBmatcher:
     """ORBmatcher(nnratio, checkOri) of the reference.  Provided: SearchByProjection(CurrentFrame, LastFrame, th, bMono) (TrackWithMotionModel),
     SearchLocalPoints = Frame::isInFrustum over the local map + SearchByProjection(F, vpMapPoints, th) (TrackLocalMap), and SearchByProjectionKF =
@@ -134,7 +160,8 @@ class ORBmatcher:
     :159-288) and SearchForTriangulation (LocalMapping::CreateNewMapPoints; :657-823), on node ids from vocabulary.ORBVocabulary (sind_match_bow, sind_match_tri), and SearchByBoWKF =
     SearchByBoW(pKF1, pKF2) (LoopClosing::ComputeSim3; :522-655; sind_match_bow_kf).  Of ORBmatcher.cc only the monocular SearchForInitialization is not provided.
     On the same handle, between SearchByBoWKF and SearchBySim3 in LoopClosing::ComputeSim3: the Sim3Solver (src/Sim3Solver.cc; Sim3Ransac, sim3_solvers, sindslam_amd/sim3.py).
-    Between SearchByBoW and SearchByProjectionKF in Tracking::Relocalization: the PnPsolver (src/PnPsolver.cc; PnPRansac, pnp_solvers, sindslam_amd/pnp.py)."""
+    Between SearchByBoW and SearchByProjectionKF in Tracking::Relocalization: the PnPsolver (src/PnPsolver.cc; PnPRansac, pnp_solvers, sindslam_amd/pnp.py).
+    After every search of the tracking thread: Optimizer::PoseOptimization (src/Optimizer.cc:239-451; PoseOptimization, sindslam_amd/optimizer.py)."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
 
     def __init__(self, fx, fy, cx, cy, bf, bounds, scale_factors, nnratio=0.6, checkOri=True, cap=4096, max_batch=1, device=0, cap_points=0):
@@ -346,6 +373,15 @@ class ORBmatcher:
             if s is not None:
                 s.max_batch = self.max_batch                            # relocalization_pnp evaluates that many candidates per call
         return solvers
+
+    def PoseOptimization(self, items):
+        """sind_match_pose_optimize: Optimizer::PoseOptimization (src/Optimizer.cc:239-451) of every item, one launch.  items: list of dicts, per correspondence (keypoint i
+        with mvpMapPoints[i] != NULL, ascending i): x3Dw [n, 3], obs_xy [n, 2], u_right [n] (< 0: monocular edge), inv_sigma2 [n]; and Tcw [4, 4] = mTcw on entry.
+        -> list of dicts: Tcw f32 [4, 4] (the pose SetPose gets; the input pose where n < 3, which the reference leaves untouched), outlier u8 [n], n_good, n_rounds,
+        round_iters i32 [4], round_nbad i32 [4], round_pose f64 [4, 12], round_chi2 f64 [4], round_lambda f64 [4]"""
+        arr, keep = poseopt_items(items)
+        check(lib().sind_match_pose_optimize(self._h, arr, len(items)), "sind_match_pose_optimize")
+        return [poseopt_result(a) for a in keep]
 
     def last_rounds(self):
         return lib().sind_match_last_rounds(self._h)
