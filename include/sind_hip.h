@@ -750,6 +750,43 @@ typedef struct sind_poseopt_item {
 } sind_poseopt_item;
 int sind_match_pose_optimize(sind_match* m, const sind_poseopt_item* items, int B);
 
+/* sind_match_sim3_optimize.  Replaces, for B loop candidates at once, the whole of
+ *   int Optimizer::OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint *> &vpMatches1, g2o::Sim3 &g2oS12, const float th2, const bool bFixScale)
+ * (src/Optimizer.cc:1046-1241; LoopClosing::ComputeSim3, src/LoopClosing.cc:300): the g2o graph of one VertexSim3Expmap and, per correspondence, two fixed points and
+ * the edges EdgeSim3ProjectXYZ and EdgeInverseSim3ProjectXYZ with Huber kernels (delta = the float sqrt(th2)), their NUMERIC Jacobians (the reference has no analytic
+ * ones: central differences with 1e-9), OptimizationAlgorithmLevenberg over LinearSolverDense, optimize(5), the bad pairs removed, optimize(5 or 10) from where the
+ * first stage stopped, the final classification.  ONE launch for all items (csrc/match_sim3opt.hip, one workgroup per item; csrc/host/sim3_opt.hpp is one FP64
+ * source for host and device).  H, b and the robust chi2 are g2o's sums: every entry added in edge order (e12 of pair 0, e21 of pair 0, e12 of pair 1, ...).
+ * What stays with the caller is the flattening (:1099-1178): per index i with vpMatches1[i] != NULL, pKF1's map point i and the match both non-NULL and not bad and
+ * the match seen in pKF2 (i2 >= 0), in ascending i: x3Dc1 = R1w * P3D1w + t1w and x3Dc2 = R2w * P3D2w + t2w in FP32 (as for sind_match_sim3_ransac), obs1_xy =
+ * pKF1->mvKeysUn[i].pt, obs2_xy = pKF2->mvKeysUn[i2].pt, inv_sigma2_1 / _2 = mvInvLevelSigma2[octave] of the two (finite, >= 0), K1 / K2 = fx fy cx cy of the two key
+ * frames, s12 R12 t12 = what g2o::Sim3(Converter::toMatrix3d(R), Converter::toVector3d(t), s) gets (finite).  The caller keeps the index list and nulls
+ * vpMatches1[idx] where removed is 1.
+ * Outputs: q_out (x y z w, NOT normalised: g2o::Sim3 never normalises), t_out, s_out = g2oS12 afterwards in FP64, equal to the input (Quaterniond(R12), t12, s12) when 0
+ * is returned early; removed[i] = 1 where either classification nulled the match; *n_inliers = the return value.  n = 0: the empty graph, 0 returned, nothing else
+ * happens.  1 <= n and fewer than 10 pairs left after the first stage: the first stage has run and removed is set, 0 returned, the Sim3 stays the input.
+ * The diagnostics may be NULL: n_bad = nBad of the first stage, n_stages = stages run (0, 1, 2), stage_iters = optimize()'s return, stage_chi2 = activeRobustChi2 after
+ * the stage's last accepted step, stage_lambda = _currentLambda at its end; a stage that did not run keeps zeros.
+ * fix_scale: VertexSim3Expmap::_fix_scale (mbFixScale: true for stereo / RGB-D).  th2: 10 in LoopClosing.
+ * Unpinned: parity with a real g2o / Eigen build (Eigen's evaluation order in Sim3's exponential and the small products, its LDLT, -march=native contraction, and
+ * sin / cos / exp, which pose_opt.hpp and sim3_opt.hpp define instead of calling a maths library); see the head of sim3_opt.hpp.
+ * Limits: n <= min(cap_last, cap_cur), B <= max_batch: beyond them SIND_E_CAPACITY.  A NULL array (with n = 0 the per-pair arrays may be NULL), an inv_sigma2 that is
+ * negative or not finite, an input Sim3, intrinsic or th2 that is not finite -> SIND_E_ARG.  On an error nothing is launched and the outputs are untouched.  B = 0 is valid.
+ */
+typedef struct sind_sim3opt_item {
+    int n; float s12;                                    /* pairs; the input scale */
+    const float* x3Dc1; const float* x3Dc2;              /* [n][3] the points in their own cameras */
+    const float* obs1_xy; const float* obs2_xy;          /* [n][2] */
+    const float* inv_sigma2_1; const float* inv_sigma2_2;/* [n] */
+    const float* K1; const float* K2;                    /* [4] fx fy cx cy */
+    const float* R12; const float* t12;                  /* [9] row-major, [3] */
+    double* q_out; double* t_out; double* s_out;         /* [4] x y z w, [3], [1] */
+    uint8_t* removed; int* n_inliers;                    /* [n]; [1] */
+    int* n_bad; int* n_stages; int* stage_iters;         /* [1]; [1]; [2] */
+    double* stage_chi2; double* stage_lambda;            /* [2]; [2] */
+} sind_sim3opt_item;
+int sind_match_sim3_optimize(sind_match* m, const sind_sim3opt_item* items, int B, float th2, int fix_scale);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of
  *   generatePointCloud(imgRGB, imgDepth, imgDepthLast, imgDynaMask, imgDynaMaskLast, imgLabel, poseRelative, Twc)

@@ -8,6 +8,7 @@
 #include "host/sim3.hpp"
 #include "host/pnp.hpp"
 #include "host/pose_opt.hpp"
+#include "host/sim3_opt.hpp"
 
 namespace {
 const int GRID_CELLS = 3072;                                       // Frame's 64 x 48 grid; grid_start has one entry more
@@ -142,6 +143,16 @@ struct sind_match {
             cap = c; return SIND_OK;
         }
     } poseopt;
+    // sind_match_sim3_optimize (match_sim3opt.hip), on first use: [maxB] items of min(cap_last, cap_cur) pairs
+    struct Sim3OptSide {
+        int cap = 0;
+        Staged<sind::Sim3OptHead> head; Staged<float4> p1, p2, ob; Staged<uint8_t> removed; Staged<sind::Sim3OptResult> res;
+        int reserve(size_t B, int c) {
+            int r = SIND_OK;
+            if ((r = head.alloc(B)) || (r = p1.alloc(B * (size_t)c)) || (r = p2.alloc(B * (size_t)c)) || (r = ob.alloc(B * (size_t)c)) || (r = removed.alloc(B * (size_t)c)) || (r = res.alloc(B))) return r;
+            cap = c; return SIND_OK;
+        }
+    } sim3opt;
     int reserve_bow() {
         const size_t B = maxB, nl = B * prm.capLast, nc = B * prm.capCur; int r = SIND_OK;
         (r = last.node.alloc(nl)) || (r = last.xy.alloc(nl * 2)) || (r = last.uRight.alloc(nl)) || (r = cur.node.alloc(nc)) || (r = choice.alloc(nl)) || (r = bow.pose.alloc(B)) ||
@@ -684,6 +695,57 @@ int sind_match_pose_optimize(sind_match* m, const sind_poseopt_item* items, int 
     for (int b = 0; b < B; b++) {
         sind::PoseOptOut o; std::memcpy(&o, &w.res.h[b], sizeof(o));
         sind::poseopt_store(items[b], o, &w.outlier.h[(size_t)b * cs]);
+    }
+    return SIND_OK;
+}
+
+int sind_match_sim3_optimize(sind_match* m, const sind_sim3opt_item* items, int B, float th2, int fix_scale) {
+    const char* who = "sind_match_sim3_optimize: item";
+    if (!m || B < 0 || (B && !items) || !std::isfinite(th2) || th2 < 0) { sind_set_error("sind_match_sim3_optimize: bad arguments"); return SIND_E_ARG; }
+    if (B > m->maxB) { sind_set_error("sind_match_sim3_optimize: B=%d over max_batch %d", B, m->maxB); return SIND_E_CAPACITY; }
+    const int cs = std::min(m->last.cap, m->cur.cap);
+    int maxN = 0;
+    for (int b = 0; b < B; b++) {
+        const sind_sim3opt_item& q = items[b];
+        if (q.n > cs) { sind_set_error("%s %d has %d pairs, capacity %d", who, b, q.n, cs); return SIND_E_CAPACITY; }
+        static const char* const what[] = {"", "negative count", "null array", "an inv_sigma2 is not a finite non-negative number", "the input Sim3 or an intrinsic is not finite"};
+        if (const int bad = sind::sim3opt_check(q)) { sind_set_error("%s %d: %s", who, b, what[bad]); return SIND_E_ARG; }
+        maxN = std::max(maxN, q.n);
+    }
+    if (!B) return SIND_OK;
+    static_assert(sizeof(sind::Sim3OptResult) == sizeof(sind::Sim3OptOut), "Sim3OptResult is Sim3OptOut");
+    if (maxN < 1) {                                                                                     // every graph is empty: the reference's `return 0`, nothing to launch
+        for (int b = 0; b < B; b++) {
+            sind::Sim3Q S0; sind::s3_from_input(items[b].s12, items[b].R12, items[b].t12, S0);
+            sind::Sim3OptOut o{}; std::memcpy(o.q, S0.q, sizeof(o.q)); std::memcpy(o.t, S0.t, sizeof(o.t)); o.s = S0.s;
+            sind::sim3opt_store(items[b], o, nullptr);
+        }
+        return SIND_OK;
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    sind_match::Sim3OptSide& w = m->sim3opt;
+    if (!w.cap) SIND_TRY(w.reserve((size_t)m->maxB, cs));
+    const sind::Sim3OptParams p{th2, fix_scale != 0, cs};
+    for (int b = 0; b < B; b++) {
+        const sind_sim3opt_item& q = items[b];
+        float4* p1 = &w.p1.h[(size_t)b * cs]; float4* p2 = &w.p2.h[(size_t)b * cs]; float4* ob = &w.ob.h[(size_t)b * cs];
+        for (int i = 0; i < q.n; i++) {
+            p1[i] = make_float4(q.x3Dc1[3 * i], q.x3Dc1[3 * i + 1], q.x3Dc1[3 * i + 2], q.inv_sigma2_1[i]);
+            p2[i] = make_float4(q.x3Dc2[3 * i], q.x3Dc2[3 * i + 1], q.x3Dc2[3 * i + 2], q.inv_sigma2_2[i]);
+            ob[i] = make_float4(q.obs1_xy[2 * i], q.obs1_xy[2 * i + 1], q.obs2_xy[2 * i], q.obs2_xy[2 * i + 1]);
+        }
+        sind::Sim3OptHead& h = w.head.h[b];
+        cpy(h.K1, q.K1, 4 * sizeof(float)); cpy(h.K2, q.K2, 4 * sizeof(float)); h.s12 = q.s12; cpy(h.R12, q.R12, 9 * sizeof(float)); cpy(h.t12, q.t12, 3 * sizeof(float)); h.n = q.n;
+    }
+    hipStream_t s = m->stream; const size_t k = (size_t)B * cs;
+    sind::Sim3OptArrays a{w.head.d.p, w.p1.d.p, w.p2.d.p, w.ob.d.p, w.removed.d.p, w.res.d.p};
+    SIND_TRY(w.head.up(B, s)); SIND_TRY(w.p1.up(k, s)); SIND_TRY(w.p2.up(k, s)); SIND_TRY(w.ob.up(k, s));
+    SIND_TRY(sind::launch_sim3_optimize(p, a, B, s));
+    SIND_TRY(w.removed.down(k, s)); SIND_TRY(w.res.down(B, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) {
+        sind::Sim3OptOut o; std::memcpy(&o, &w.res.h[b], sizeof(o));
+        sind::sim3opt_store(items[b], o, &w.removed.h[(size_t)b * cs]);
     }
     return SIND_OK;
 }

@@ -107,6 +107,17 @@ struct PoseOptArrays {                                            // device poin
 };
 int launch_pose_optimize(const PoseOptParams& p, const PoseOptArrays& a, int B, hipStream_t s);
 
+// Optimizer::OptimizeSim3, whole, one workgroup per item (match_sim3opt.hip, host/sim3_opt.hpp)
+struct Sim3OptParams { float th2; int fixScale; int cap /* pairs per item */; };
+struct Sim3OptHead { float K1[4], K2[4], s12, R12[9], t12[3]; int n; };               // per item: fx fy cx cy of both key frames, the input Sim3, the pair count
+struct Sim3OptResult { double q[4], t[3], s; int nIn, nBad, stages, iters[2]; double chi2[2], lambda[2]; };              // = sind::Sim3OptOut of sim3_opt.hpp
+struct Sim3OptArrays {                                            // device pointers
+    const Sim3OptHead* head;                                      // [B]
+    const float4* p1; const float4* p2; const float4* ob;         // [B][cap]: (X1c, invSigma2_1), (X2c, invSigma2_2), (obs1, obs2)
+    uint8_t* removed; Sim3OptResult* res;                         // outputs [B][cap] (the kernel's working state too), [B]
+};
+int launch_sim3_optimize(const Sim3OptParams& p, const Sim3OptArrays& a, int B, hipStream_t s);
+
 // Vocabulary-guided searches (match_bow.hip): SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation.  Side A is the one whose entries act
 // (the key frame / pKF1, capacity capLast), side B the one searched (the frame / pKF2, capacity capCur).
 #define BOW_MAX_KEYS 4096                                         // keypoints per side one workgroup sorts in LDS

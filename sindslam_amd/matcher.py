@@ -99,6 +99,13 @@ class _PoseOptItem(C.Structure):
                 ("round_chi2", C.c_void_p), ("round_lambda", C.c_void_p)]
 
 
+class _Sim3OptItem(C.Structure):
+    _fields_ = [("n", C.c_int), ("s12", C.c_float), ("x3Dc1", C.c_void_p), ("x3Dc2", C.c_void_p), ("obs1_xy", C.c_void_p), ("obs2_xy", C.c_void_p), ("inv_sigma2_1", C.c_void_p),
+                ("inv_sigma2_2", C.c_void_p), ("K1", C.c_void_p), ("K2", C.c_void_p), ("R12", C.c_void_p), ("t12", C.c_void_p), ("q_out", C.c_void_p), ("t_out", C.c_void_p),
+                ("s_out", C.c_void_p), ("removed", C.c_void_p), ("n_inliers", C.c_void_p), ("n_bad", C.c_void_p), ("n_stages", C.c_void_p), ("stage_iters", C.c_void_p),
+                ("stage_chi2", C.c_void_p), ("stage_lambda", C.c_void_p)]
+
+
 _f32 = lambda a: np.ascontiguousarray(a, np.float32)
 _u8 = lambda a: np.ascontiguousarray(a, np.uint8)
 _i32 = lambda a: np.ascontiguousarray(a, np.int32)
@@ -152,6 +159,28 @@ def poseopt_result(a):
                 **{k: a[k] for k in ("round_iters", "round_nbad", "round_pose", "round_chi2", "round_lambda")})
 
 
+def sim3opt_items(items):
+    """the sind_sim3opt_item array of ORBmatcher.OptimizeSim3's items, and the arrays it points to (which live as long as the caller keeps them)"""
+    arr = (_Sim3OptItem * len(items))(); keep = []
+    for q, it in zip(arr, items):
+        n = len(it["inv_sigma2_1"])
+        a = dict(x3Dc1=_f32(it["x3Dc1"]), x3Dc2=_f32(it["x3Dc2"]), obs1_xy=_f32(it["obs1_xy"]), obs2_xy=_f32(it["obs2_xy"]), inv_sigma2_1=_f32(it["inv_sigma2_1"]),
+                 inv_sigma2_2=_f32(it["inv_sigma2_2"]), K1=_f32(it["K1"]).reshape(4).copy(), K2=_f32(it["K2"]).reshape(4).copy(), R12=_f32(it["R12"]).reshape(3, 3).copy(),
+                 t12=_f32(it["t12"]).reshape(3).copy())
+        a.update(q_out=np.zeros(4, np.float64), t_out=np.zeros(3, np.float64), s_out=np.zeros(1, np.float64), removed=np.zeros(n, np.uint8), n_inliers=np.zeros(1, np.int32),
+                 n_bad=np.zeros(1, np.int32), n_stages=np.zeros(1, np.int32), stage_iters=np.zeros(2, np.int32), stage_chi2=np.zeros(2, np.float64), stage_lambda=np.zeros(2, np.float64))
+        for key, v in a.items():
+            setattr(q, key, v.ctypes.data if v.size else None)
+        q.n = n; q.s12 = float(np.float32(it["s12"]))
+        keep.append(a)
+    return arr, keep
+
+
+def sim3opt_result(a):
+    return dict(q=a["q_out"], t=a["t_out"], s=np.float64(a["s_out"][0]), removed=a["removed"], n_inliers=int(a["n_inliers"][0]), n_bad=int(a["n_bad"][0]), n_stages=int(a["n_stages"][0]),
+                **{k: a[k] for k in ("stage_iters", "stage_chi2", "stage_lambda")})
+
+
 class ORBmatcher:
     """ORBmatcher(nnratio, checkOri) of the reference.  Provided: SearchByProjection(CurrentFrame, LastFrame, th, bMono) (TrackWithMotionModel),
     SearchLocalPoints = Frame::isInFrustum over the local map + SearchByProjection(F, vpMapPoints, th) (TrackLocalMap), and SearchByProjectionKF =
@@ -161,7 +190,8 @@ class ORBmatcher:
     SearchByBoW(pKF1, pKF2) (LoopClosing::ComputeSim3; :522-655; sind_match_bow_kf).  Of ORBmatcher.cc only the monocular SearchForInitialization is not provided.
     On the same handle, between SearchByBoWKF and SearchBySim3 in LoopClosing::ComputeSim3: the Sim3Solver (src/Sim3Solver.cc; Sim3Ransac, sim3_solvers, sindslam_amd/sim3.py).
     Between SearchByBoW and SearchByProjectionKF in Tracking::Relocalization: the PnPsolver (src/PnPsolver.cc; PnPRansac, pnp_solvers, sindslam_amd/pnp.py).
-    After every search of the tracking thread: Optimizer::PoseOptimization (src/Optimizer.cc:239-451; PoseOptimization, sindslam_amd/optimizer.py)."""
+    After every search of the tracking thread: Optimizer::PoseOptimization (src/Optimizer.cc:239-451; PoseOptimization, sindslam_amd/optimizer.py).
+    After SearchBySim3 in LoopClosing::ComputeSim3: Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241; OptimizeSim3, sindslam_amd/optimizer.py)."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
 
     def __init__(self, fx, fy, cx, cy, bf, bounds, scale_factors, nnratio=0.6, checkOri=True, cap=4096, max_batch=1, device=0, cap_points=0):
@@ -382,6 +412,16 @@ class ORBmatcher:
         arr, keep = poseopt_items(items)
         check(lib().sind_match_pose_optimize(self._h, arr, len(items)), "sind_match_pose_optimize")
         return [poseopt_result(a) for a in keep]
+
+    def OptimizeSim3(self, items, th2=10, fix_scale=True):
+        """sind_match_sim3_optimize: Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241) of every item, one launch.  items: list of dicts, per correspondence (the pairs that
+        pass :1099-1136, ascending i): x3Dc1, x3Dc2 [n, 3] (the map points in their own cameras), obs1_xy, obs2_xy [n, 2], inv_sigma2_1, inv_sigma2_2 [n]; and K1, K2 [4]
+        (fx fy cx cy), s12, R12 [3, 3], t12 [3] = g2oS12 on entry.  th2 and fix_scale as in the reference (10 and mbFixScale in LoopClosing).
+        -> list of dicts: q f64 [4] (x y z w, not normalised), t f64 [3], s f64 = g2oS12 afterwards (the input where 0 is returned early), removed u8 [n] (1 where
+        vpMatches1[idx] was nulled), n_inliers (the return value), n_bad, n_stages, stage_iters i32 [2], stage_chi2 f64 [2], stage_lambda f64 [2]"""
+        arr, keep = sim3opt_items(items)
+        check(lib().sind_match_sim3_optimize(self._h, arr, len(items), C.c_float(float(th2)), int(bool(fix_scale))), "sind_match_sim3_optimize")
+        return [sim3opt_result(a) for a in keep]
 
     def last_rounds(self):
         return lib().sind_match_last_rounds(self._h)

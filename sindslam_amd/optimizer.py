@@ -1,8 +1,12 @@
-"""Optimizer — Python mirror of the one Optimizer entry point of the reference's tracking thread, Optimizer::PoseOptimization (src/Optimizer.cc:239-451), over
-sind_match_pose_optimize, and the chain of Tracking::Relocalization that is built on it (src/Tracking.cc:1460-1524) as the `accept` callback of pnp.relocalization_pnp.
+"""Optimizer — Python mirror of the Optimizer entry points of the reference that run on the matcher handle.  Optimizer::PoseOptimization (src/Optimizer.cc:239-451), the
+one call of the tracking thread, over sind_match_pose_optimize, and the chain of Tracking::Relocalization that is built on it (src/Tracking.cc:1460-1524) as the `accept`
+callback of pnp.relocalization_pnp.  Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241), the one call of LoopClosing::ComputeSim3, over sind_match_sim3_optimize, and the
+rest of ComputeSim3 built on it (src/LoopClosing.cc:310-398): compute_sim3_accept, the `accept` callback of sim3.compute_sim3, loop_scw and loop_accept.
 
 A frame is a dict of per-keypoint arrays: un_xy [N, 2] (mvKeysUn[i].pt), u_right [N] (mvuRight), inv_sigma2 [N] (mvInvLevelSigma2[mvKeysUn[i].octave]), mp i64 [N] (the id of
-mvpMapPoints[i], -1 for NULL), x3Dw [N, 3] (GetWorldPos() of that map point; rows without one are not read), Tcw [4, 4] (mTcw), and optionally outlier [N] (mvbOutlier)."""
+mvpMapPoints[i], -1 for NULL), x3Dw [N, 3] (GetWorldPos() of that map point; rows without one are not read), Tcw [4, 4] (mTcw), and optionally outlier [N] (mvbOutlier).
+A key frame (for the Sim3 functions) is such a dict with K [4] (fx fy cx cy) and optionally bad u8 [N] (isBad() of the slot's map point), plus, where SearchBySim3 or
+SearchByProjection read it: octave, max_dist, min_dist, normal, mp_desc (the map point's descriptor), kf_desc (the keypoint's), grid_start, grid_idx."""
 from __future__ import annotations
 
 import numpy as np
@@ -83,3 +87,161 @@ def relocalization_accept(matcher, frame, candidates, search=None, optimize=None
         note("verdict", nGood >= 50)
         return nGood >= 50                                              # :1520
     return accept
+
+
+# ---------------------------------------------------------------- Optimizer::OptimizeSim3 and the rest of LoopClosing::ComputeSim3
+def _to_camera(T, X):
+    """R * P + t as cv::Mat forms it in FP32 (Optimizer.cc:1118, :1126), per row: ((r0 x + r1 y) + r2 z) + t"""
+    T = np.asarray(T, np.float32).reshape(4, 4); X = np.asarray(X, np.float32).reshape(-1, 3)
+    return np.stack([((T[r, 0] * X[:, 0] + T[r, 1] * X[:, 1]) + T[r, 2] * X[:, 2]) + T[r, 3] for r in range(3)], 1).astype(np.float32)
+
+
+def sim3_item(kf1, kf2, vpMatches1, s12, R12, t12):
+    """The flattening of Optimizer::OptimizeSim3 (:1099-1178).  vpMatches1 i32 [N1]: the slot of pKF2 whose map point is vpMatches1[i] (GetIndexInKeyFrame(pKF2)), -1 for
+    NULL.  Skipped, as there: a pair whose map point in pKF1 is NULL, or with either map point bad.  -> (item of ORBmatcher.OptimizeSim3, idx = vnIndexEdge: the index i of every row)"""
+    m = np.asarray(vpMatches1, np.int64)
+    mp1, mp2 = np.asarray(kf1["mp"]), np.asarray(kf2["mp"])
+    bad1 = np.zeros(len(mp1), bool) if kf1.get("bad") is None else np.asarray(kf1["bad"]).astype(bool)
+    bad2 = np.zeros(len(mp2), bool) if kf2.get("bad") is None else np.asarray(kf2["bad"]).astype(bool)
+    i2 = np.maximum(m, 0)
+    ok = (m >= 0) & (mp1 >= 0) & (mp2[i2] >= 0) & ~bad1 & ~bad2[i2]
+    idx = np.nonzero(ok)[0]; i2 = i2[idx]
+    f = lambda a: np.asarray(a, np.float32)
+    item = dict(x3Dc1=_to_camera(kf1["Tcw"], f(kf1["x3Dw"]).reshape(-1, 3)[idx]), x3Dc2=_to_camera(kf2["Tcw"], f(kf2["x3Dw"]).reshape(-1, 3)[i2]),
+                obs1_xy=f(kf1["un_xy"])[idx], obs2_xy=f(kf2["un_xy"])[i2], inv_sigma2_1=f(kf1["inv_sigma2"])[idx], inv_sigma2_2=f(kf2["inv_sigma2"])[i2],
+                K1=f(kf1["K"]), K2=f(kf2["K"]), s12=np.float32(s12), R12=f(R12).reshape(3, 3), t12=f(t12).reshape(3))
+    return item, idx
+
+
+def OptimizeSim3(matcher, kf1, kf2, vpMatches1, s12, R12, t12, th2=10, fix_scale=True):
+    """Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) with g2oS12 = Sim3(R12, t12, s12).  `matcher` is an ORBmatcher or anything with its
+    OptimizeSim3(items, th2, fix_scale).  -> (nInliers, vpMatches1 with the removed pairs nulled, g2oS12 afterwards as a dict q f64 [4] (x y z w), t f64 [3], s f64).
+    The inputs are not modified."""
+    item, idx = sim3_item(kf1, kf2, vpMatches1, s12, R12, t12)
+    r = matcher.OptimizeSim3([item], th2, fix_scale)[0]
+    m = np.array(vpMatches1, np.int32)
+    m[idx[r["removed"].astype(bool)]] = -1
+    return int(r["n_inliers"]), m, dict(q=np.array(r["q"], np.float64), t=np.array(r["t"], np.float64), s=np.float64(r["s"]))
+
+
+def _quat_from_matrix(m):
+    """Eigen's Quaterniond(Matrix3d), not normalised: what g2o::Sim3(R, t, s) holds"""
+    D = np.float64
+    t = m[0][0] + m[1][1] + m[2][2]
+    q = [D(0)] * 4
+    if t > 0:
+        t = np.sqrt(t + D(1)); q[3] = D(0.5) * t; t = D(0.5) / t
+        q[0] = (m[2][1] - m[1][2]) * t; q[1] = (m[0][2] - m[2][0]) * t; q[2] = (m[1][0] - m[0][1]) * t
+    else:
+        i = 0
+        if m[1][1] > m[0][0]:
+            i = 1
+        if m[2][2] > m[i][i]:
+            i = 2
+        j = (i + 1) % 3; k = (j + 1) % 3
+        t = np.sqrt(m[i][i] - m[j][j] - m[k][k] + D(1))
+        q[i] = D(0.5) * t; t = D(0.5) / t
+        q[3] = (m[k][j] - m[j][k]) * t; q[j] = (m[j][i] + m[i][j]) * t; q[k] = (m[k][i] + m[i][k]) * t
+    return q
+
+
+def _quat_rotate(q, v):
+    uv = [q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]]
+    uv = [u + u for u in uv]
+    return [v[0] + q[3] * uv[0] + (q[1] * uv[2] - q[2] * uv[1]), v[1] + q[3] * uv[1] + (q[2] * uv[0] - q[0] * uv[2]), v[2] + q[3] * uv[2] + (q[0] * uv[1] - q[1] * uv[0])]
+
+
+def loop_scw(S12, T2w):
+    """mg2oScw = gScm * gSmw and mScw = Converter::toCvMat(mg2oScw) (src/LoopClosing.cc:333-335): S12 = g2oS12 after OptimizeSim3 (dict q, t, s), T2w = the matched key
+    frame's pose, gSmw = Sim3(Rmw, tmw, 1.0).  FP64 in the order of csrc/host/sim3_opt.hpp (Sim3's operator*, no normalisation).
+    -> (mScw f32 [4, 4] = [s R | t], mg2oScw as a dict q, t, s)"""
+    D = np.float64
+    T = np.asarray(T2w, np.float32).reshape(4, 4)
+    a = [D(v) for v in S12["q"]]; ta = [D(v) for v in S12["t"]]; sa = D(S12["s"])
+    b = _quat_from_matrix([[D(T[i, j]) for j in range(3)] for i in range(3)]); tb = [D(T[i, 3]) for i in range(3)]
+    with np.errstate(all="ignore"):
+        q = [a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1], a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2], a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0],
+             a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2]]
+        rt = _quat_rotate(a, tb)
+        t = [sa * rt[i] + ta[i] for i in range(3)]
+        s = sa * D(1.0)
+        tx, ty, tz = D(2) * q[0], D(2) * q[1], D(2) * q[2]                 # toRotationMatrix
+        twx, twy, twz = tx * q[3], ty * q[3], tz * q[3]
+        txx, txy, txz, tyy, tyz, tzz = tx * q[0], ty * q[0], tz * q[0], ty * q[1], tz * q[1], tz * q[2]
+        R = [[D(1) - (tyy + tzz), txy - twz, txz + twy], [txy + twz, D(1) - (txx + tzz), tyz - twx], [txz - twy, tyz + twx, D(1) - (txx + tyy)]]
+        Scw = np.eye(4, dtype=np.float32)
+        for i in range(3):
+            for j in range(3):
+                Scw[i, j] = np.float32(s * R[i][j])
+            Scw[i, 3] = np.float32(t[i])
+    return Scw, dict(q=np.array(q, np.float64), t=np.array(t, np.float64), s=s)
+
+
+def _sim3_side(kf, already):
+    valid = np.asarray(kf["mp"]) >= 0
+    if kf.get("bad") is not None:
+        valid &= ~np.asarray(kf["bad"]).astype(bool)
+    return dict(valid=(valid & ~already).astype(np.uint8), x3Dw=kf["x3Dw"], max_dist=kf["max_dist"], min_dist=kf["min_dist"], mp_desc=kf["mp_desc"], un_xy=kf["un_xy"], octave=kf["octave"],
+                kf_desc=kf["kf_desc"], grid_start=kf["grid_start"], grid_idx=kf["grid_idx"])
+
+
+def search_by_sim3(matcher, kf1, kf2, vpMatches12, s12, R12, t12, th=7.5):
+    """matcher.SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) on key-frame dicts: vbAlreadyMatched1 / 2 from vpMatches12 (slots of pKF2, -1 for NULL), the new
+    matches written into it.  -> (vpMatches12 i32 [N1], nFound)"""
+    m = np.array(vpMatches12, np.int32)
+    already1 = m >= 0
+    already2 = np.zeros(len(np.asarray(kf2["mp"])), bool); already2[m[already1]] = True
+    (new, nfound), = matcher.SearchBySim3([(kf1["Tcw"], kf2["Tcw"], s12, R12, t12, _sim3_side(kf1, already1), _sim3_side(kf2, already2))], th)
+    j = np.nonzero(new[:len(m)] >= 0)[0]
+    m[j] = new[j]
+    return m, int(nfound)
+
+
+def compute_sim3_accept(matcher, kf1, candidates, solvers, fix_scale, optimizer=None, state=None, trace=None):
+    """The `accept` callback of sim3.compute_sim3: what LoopClosing::ComputeSim3 does with an Scm an iterate returned (src/LoopClosing.cc:311-339), with real calls:
+    SearchBySim3 (th 7.5), OptimizeSim3 (th2 10), nInliers >= 20.  kf1 = mpCurrentKF; candidates[i]: kf = the candidate key frame, match12 i32 [N1] =
+    vvpMapPointMatches[i] as slots of that key frame (what SearchByBoWKF returned); solvers = the list given to compute_sim3 (GetEstimatedRotation / Translation / Scale).
+    optimizer: whose OptimizeSim3(items, th2, fix_scale) is called, default the matcher.  state: a dict that gets, on acceptance, matched (the index i), vpMatches (mvpCurrentMatchedPoints
+    as slots of the matched key frame), S12 (the optimised g2oScm), Scw and g2oScw (loop_scw).  trace: a list that gets the steps taken.  -> accept(i, Scm, vbInliers)"""
+    optimizer = optimizer or matcher
+    state = {} if state is None else state
+    note = (lambda *a: trace.append(a)) if trace is not None else (lambda *a: None)
+
+    def accept(i, Scm, vbInliers):
+        kf2 = candidates[i]["kf"]
+        m = np.where(np.asarray(vbInliers, bool), np.asarray(candidates[i]["match12"], np.int32), -1).astype(np.int32)        # :313-318
+        R, t, s = solvers[i].GetEstimatedRotation(), solvers[i].GetEstimatedTranslation(), solvers[i].GetEstimatedScale()
+        m, nfound = search_by_sim3(matcher, kf1, kf2, m, s, R, t, 7.5); note("search_by_sim3", i, nfound, int((m >= 0).sum()))     # :323
+        nInliers, m, S12 = OptimizeSim3(optimizer, kf1, kf2, m, s, R, t, 10, fix_scale); note("optimize_sim3", i, nInliers)        # :325-326
+        if nInliers < 20:
+            return False
+        Scw, g2oScw = loop_scw(S12, kf2["Tcw"])
+        state.update(matched=i, vpMatches=m, S12=S12, Scw=Scw, g2oScw=g2oScw)
+        return True
+    accept.state = state
+    return accept
+
+
+def loop_accept(matcher, kf1, Scw, loop_kfs, matched_ids, th=10, min_matches=40):
+    """The tail of LoopClosing::ComputeSim3 (src/LoopClosing.cc:352-398).  kf1 = mpCurrentKF as SearchByProjectionSim3's key frame (un_xy, octave, u_right, desc = kf_desc,
+    grid_start, grid_idx); Scw = mScw; loop_kfs = vpLoopConnectedKFs in order (the covisibles of the matched key frame, then it), each with mp, bad, x3Dw, normal,
+    max_dist, min_dist, mp_desc; matched_ids i64 [N1] = mvpCurrentMatchedPoints as map-point ids, -1 for NULL.
+    -> (nTotalMatches >= 40, nTotalMatches, mvpCurrentMatchedPoints i64 [N1], mvpLoopMapPoints as ids)"""
+    ids, rows = [], []
+    seen = set()
+    for k, kf in enumerate(loop_kfs):                                   # :356-372: each good map point once, in this order
+        mp = np.asarray(kf["mp"]); bad = np.zeros(len(mp), bool) if kf.get("bad") is None else np.asarray(kf["bad"]).astype(bool)
+        for i in np.nonzero((mp >= 0) & ~bad)[0]:
+            if int(mp[i]) not in seen:
+                seen.add(int(mp[i])); ids.append(int(mp[i])); rows.append((k, int(i)))
+    ids = np.array(ids, np.int64)
+    matched = np.array(matched_ids, np.int64)
+    take = lambda key, dt: np.array([np.asarray(loop_kfs[k][key])[i] for k, i in rows], dt).reshape((len(rows),) + np.asarray(loop_kfs[0][key]).shape[1:]) if rows else np.zeros((0,) + np.asarray(loop_kfs[0][key]).shape[1:], dt)
+    mp = dict(x3Dw=take("x3Dw", np.float32), normal=take("normal", np.float32), max_dist=take("max_dist", np.float32), min_dist=take("min_dist", np.float32), desc=take("mp_desc", np.uint8),
+              valid=(~np.isin(ids, matched[matched >= 0])).astype(np.uint8))   # spAlreadyFound; the bad ones are not in the list
+    kf = dict(un_xy=kf1["un_xy"], octave=kf1["octave"], desc=kf1["kf_desc"], grid_start=kf1["grid_start"], grid_idx=kf1["grid_idx"], taken=(matched >= 0).astype(np.uint8))
+    (match_of_kf, _), = matcher.SearchByProjectionSim3([(Scw, mp, kf)], th)                                    # :375
+    j = np.nonzero(match_of_kf[:len(matched)] >= 0)[0]
+    matched[j] = ids[match_of_kf[j]]
+    nTotalMatches = int((matched >= 0).sum())                           # :378-383
+    return nTotalMatches >= min_matches, nTotalMatches, matched, ids
