@@ -787,6 +787,50 @@ typedef struct sind_sim3opt_item {
 } sind_sim3opt_item;
 int sind_match_sim3_optimize(sind_match* m, const sind_sim3opt_item* items, int B, float th2, int fix_scale);
 
+/* sind_match_local_ba.  Replaces, for B local windows at once, the whole of
+ *   void Optimizer::LocalBundleAdjustment(KeyFrame *pKF, bool* pbStopFlag, Map* pMap)
+ * from the optimizer's set-up on (src/Optimizer.cc:506-743; LocalMapping::Run, src/LocalMapping.cc:100): the g2o graph of the local key frames (free, the one with
+ * mnId 0 fixed), the fixed cameras and the local map points (marginalised), one EdgeSE3ProjectXYZ or EdgeStereoSE3ProjectXYZ with a Huber kernel per observation,
+ * BlockSolver_6_3's Schur complement under OptimizationAlgorithmLevenberg, optimize(5), the outliers moved to level 1 and the kernels removed, optimize(10), the final
+ * classification.  ONE launch for all items (csrc/match_localba.hip, one workgroup per item; csrc/host/local_ba.hpp is one FP64 source for host and device and states
+ * the order of every sum).  Calibration is the handle's fx fy cx cy bf, as for sind_match_pose_optimize.
+ * What stays with the caller: the graph collection (:455-504: lLocalKeyFrames, lLocalMapPoints, lFixedCameras; sindslam_amd/optimizer.py mirrors it), and after the
+ * call, under the map mutex, EraseMapPointMatch and EraseObservation for every erased observation (:748-757), SetPose (:762-768), SetWorldPos and
+ * UpdateNormalAndDepth (:771-777).
+ * Inputs: kf_kind 0 = a local key frame, 1 = a local key frame that is fixed (mnId == 0), 2 = a fixed camera; Tcw = GetPose(); the points in lLocalMapPoints order
+ * with x3Dw = GetWorldPos(); the observations of point j are obs_start[j] .. obs_start[j + 1] - 1 in the order the edges are added (key frames that are bad left out):
+ * obs_kf the index of the key frame in 0 .. n_kf - 1, obs_xy = mvKeysUn[slot].pt, u_right = mvuRight[slot] (< 0: the monocular edge), inv_sigma2 =
+ * mvInvLevelSigma2[octave].  In the reference the order of a point's observations is that of a std::map keyed by pointers, which no caller can reproduce; the
+ * Python mirror uses ascending mnId.  do_more = 0 is bDoMore = false (the stop flag seen after the first optimize): no level changes and no second stage.
+ * Outputs: Tcw_out = toCvMat(estimate) for kinds 0 and 1 (a round trip through the quaternion, for the fixed one too), the input for kind 2; x3Dw_out = the float of
+ * the estimate; erase[k] = 1 where observation k is in vToErase.  The diagnostics may be NULL: n_stages = the optimize calls that had something to optimise (0..2),
+ * stage_iters = their return values, n_level1 = the edges at level 1 after the first classification, stage_chi2 = activeRobustChi2 after the stage's last accepted
+ * step, stage_lambda = _currentLambda at its end; a stage that did not run keeps zeros.
+ * Valid: B = 0; n_obs = 0 (initializeOptimization refuses an empty graph and nothing is optimised: the outputs are the conversions alone).
+ * Unpinned: parity with a real g2o / Eigen build, above all the reduced system (a dense LDL^T in natural order here, SimplicialLDLT under AMD ordering there); see the
+ * head of local_ba.hpp.  Not offered: a stop flag that flips in the middle of an optimize.
+ * Limits: 256 key frames of kind 0, 4096 key frames, 65536 points, 2^20 observations, 2^24 entries of the co-observation lists (sum over the points of k (k + 1) / 2,
+ * k = its observations in key frames of kind 0), B <= max_batch: beyond them SIND_E_CAPACITY.  The workspace lives on the handle, grows between calls to the largest
+ * call seen and is freed with the handle.
+ * SIND_E_ARG: a NULL array with a non-zero count, ids that repeat, a kind outside 0..2, an obs_kf out of range, the same key frame twice in one point's observations, an
+ * obs_start that does not start at 0 or decreases, an inv_sigma2 that is negative or not finite, a pose or point that is not finite, no key frame of kind 0.  On an
+ * error nothing is launched and the outputs are untouched.
+ */
+typedef struct sind_localba_item {
+    int n_kf; const int64_t* kf_id; const uint8_t* kf_kind;   /* [n_kf]; 0 local, 1 local and fixed (mnId == 0), 2 fixed camera */
+    const float* Tcw;                                         /* [n_kf][16] GetPose() */
+    int n_mp; const int64_t* mp_id; const float* x3Dw;        /* [n_mp], [n_mp][3]; in lLocalMapPoints order */
+    const int* obs_start;                                     /* [n_mp + 1]: the observations of point j, in the order the edges are added */
+    const int* obs_kf;                                        /* [n_obs] index into 0..n_kf-1 */
+    const float* obs_xy; const float* u_right; const float* inv_sigma2;   /* [n_obs][2], [n_obs] (< 0: mono), [n_obs] */
+    int do_more;
+    float* Tcw_out; float* x3Dw_out; uint8_t* erase;          /* [n_kf][16] (kind 2 rows: the input), [n_mp][3], [n_obs] = vToErase */
+    int* n_stages; int* stage_iters; int* n_level1;           /* diagnostics, may be NULL: [1], [2], [1] */
+    double* stage_chi2; double* stage_lambda;                 /* [2], [2] */
+} sind_localba_item;
+int sind_match_local_ba(sind_match* m, const sind_localba_item* items, int B);
+int sindh_local_ba(const sind_localba_item* items, int B, const float* K5);   /* host twin (libsind_host.so too): K5 = fx fy cx cy bf */
+
 /* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of
  *   generatePointCloud(imgRGB, imgDepth, imgDepthLast, imgDynaMask, imgDynaMaskLast, imgLabel, poseRelative, Twc)

@@ -9,6 +9,7 @@
 #include "host/pnp.hpp"
 #include "host/pose_opt.hpp"
 #include "host/sim3_opt.hpp"
+#include "host/local_ba.hpp"
 
 namespace {
 const int GRID_CELLS = 3072;                                       // Frame's 64 x 48 grid; grid_start has one entry more
@@ -153,6 +154,10 @@ struct sind_match {
             cap = c; return SIND_OK;
         }
     } sim3opt;
+    // sind_match_local_ba (match_localba.hip): the items of a call one after the other in four buffers, grown between calls to the largest call seen
+    struct LocalBaSide {
+        Staged<int> I; Staged<float> Fin, Fout; DevBuf<double> D; Staged<sind::LbaView> views; Staged<sind::LbaDiag> diag; std::vector<sind::LbaPlan> plan;
+    } localba;
     int reserve_bow() {
         const size_t B = maxB, nl = B * prm.capLast, nc = B * prm.capCur; int r = SIND_OK;
         (r = last.node.alloc(nl)) || (r = last.xy.alloc(nl * 2)) || (r = last.uRight.alloc(nl)) || (r = cur.node.alloc(nc)) || (r = choice.alloc(nl)) || (r = bow.pose.alloc(B)) ||
@@ -747,6 +752,48 @@ int sind_match_sim3_optimize(sind_match* m, const sind_sim3opt_item* items, int 
         sind::Sim3OptOut o; std::memcpy(&o, &w.res.h[b], sizeof(o));
         sind::sim3opt_store(items[b], o, &w.removed.h[(size_t)b * cs]);
     }
+    return SIND_OK;
+}
+
+int sind_match_local_ba(sind_match* m, const sind_localba_item* items, int B) {
+    const char* who = "sind_match_local_ba: item";
+    if (!m || B < 0 || (B && !items)) { sind_set_error("sind_match_local_ba: bad arguments"); return SIND_E_ARG; }
+    if (B > m->maxB) { sind_set_error("sind_match_local_ba: B=%d over max_batch %d", B, m->maxB); return SIND_E_CAPACITY; }
+    for (int b = 0; b < B; b++) if (const int bad = sind::lba_check(items[b])) { sind_set_error("%s %d: %s", who, b, sind::lba_check_text[bad]); return SIND_E_ARG; }
+    if (!B) return SIND_OK;
+    sind_match::LocalBaSide& w = m->localba;
+    w.plan.resize((size_t)m->maxB);
+    std::vector<size_t> oI((size_t)B + 1, 0), oFi((size_t)B + 1, 0), oFo((size_t)B + 1, 0), oD((size_t)B + 1, 0);
+    for (int b = 0; b < B; b++) {
+        sind::LbaPlan& pl = w.plan[b];
+        if (sind::lba_plan(items[b], pl)) {
+            sind_set_error("%s %d is beyond a limit: %d key frames of kind 0, %d key frames, %d points, %d observations, %d co-observation entries", who, b, LBA_MAX_POSES, LBA_MAX_KF, LBA_MAX_MP, LBA_MAX_OBS, LBA_MAX_PAIRS);
+            return SIND_E_CAPACITY;
+        }
+        oI[b + 1] = oI[b] + pl.nI; oFi[b + 1] = oFi[b] + sind::lba_floats_in(pl); oFo[b + 1] = oFo[b] + sind::lba_floats_out(pl); oD[b + 1] = oD[b] + pl.nD;
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    SIND_TRY(w.I.alloc(oI[B] + 1)); SIND_TRY(w.Fin.alloc(oFi[B] + 1)); SIND_TRY(w.Fout.alloc(oFo[B] + 1)); SIND_TRY(w.D.alloc(oD[B] + 1));       // grown here, between launches
+    SIND_TRY(w.views.alloc((size_t)m->maxB)); SIND_TRY(w.diag.alloc((size_t)m->maxB));
+    const sind::MatchParams& c = m->prm;
+    const sind::PoseOptCam K{(double)c.fx, (double)c.fy, (double)c.cx, (double)c.cy, (double)c.bf};
+    for (int b = 0; b < B; b++) {
+        const sind::LbaPlan& pl = w.plan[b];
+        cpy(&w.I.h[oI[b]], pl.I.data(), pl.nI * sizeof(int));
+        sind::lba_fill_floats(items[b], &w.Fin.h[oFi[b]]);
+        sind::lba_bind(pl, items[b].do_more, K, w.I.d.p + oI[b], w.Fin.d.p + oFi[b], w.Fout.d.p + oFo[b], w.D.p + oD[b], w.views.h[b]);
+        w.views.h[b].diag = w.diag.d.p + b;
+    }
+    hipStream_t s = m->stream;
+    SIND_TRY(w.I.up(oI[B], s)); SIND_TRY(w.Fin.up(oFi[B], s)); SIND_TRY(w.views.up(B, s));
+    SIND_TRY(sind::launch_local_ba(w.views.d.p, B, s));
+    for (int b = 0; b < B; b++) {                                                                       // the erase flags are the tail of an item's ints
+        const sind::LbaPlan& pl = w.plan[b];
+        if (pl.nObs) HIP_TRY(hipMemcpyAsync(&w.I.h[oI[b] + pl.oErase], w.I.d.p + oI[b] + pl.oErase, (size_t)pl.nObs * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    SIND_TRY(w.Fout.down(oFo[B], s)); SIND_TRY(w.diag.down(B, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) sind::lba_store(items[b], w.plan[b], &w.I.h[oI[b] + w.plan[b].oErase], &w.Fout.h[oFo[b]], w.diag.h[b]);
     return SIND_OK;
 }
 

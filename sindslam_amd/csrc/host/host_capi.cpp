@@ -1,7 +1,7 @@
 // CPU-only test shim over the product's HOST stages (bit-image morphology, border following, homography, PEAC graph,
 // octree).  Built with plain g++ into libsind_host.so so that `pytest -m "not gpu"` can exercise the host logic against
 // the oracle without a GPU.  Not part of libsind_hip.so's ABI and never used by the product path.
-// The entry points of the solvers live with their sources: sindh_sim3_* in sim3.cpp, sindh_pnp_* in pnp.cpp, sindh_pose_optimize in pose_opt.cpp, sindh_sim3_optimize in sim3_opt.cpp.
+// The entry points of the solvers live with their sources: sindh_sim3_* in sim3.cpp, sindh_pnp_* in pnp.cpp, sindh_pose_optimize in pose_opt.cpp, sindh_sim3_optimize in sim3_opt.cpp, sindh_local_ba in local_ba.cpp.
 #include <cstring>
 #include "host.hpp"
 #include "peac_fit4.hpp"

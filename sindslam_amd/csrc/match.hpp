@@ -2,6 +2,7 @@
 // vocabulary-guided searches (:159-288, :657-823; match_bow.hip, bow_kernels.hip) and projections into a key frame (:290-403, :825-1326; match_fuse.hip).
 #pragma once
 #include "common.hpp"
+#include "host/local_ba.hpp"
 
 namespace sind {
 
@@ -117,6 +118,10 @@ struct Sim3OptArrays {                                            // device poin
     uint8_t* removed; Sim3OptResult* res;                         // outputs [B][cap] (the kernel's working state too), [B]
 };
 int launch_sim3_optimize(const Sim3OptParams& p, const Sim3OptArrays& a, int B, hipStream_t s);
+
+// Optimizer::LocalBundleAdjustment, whole, one workgroup per item (match_localba.hip, host/local_ba.hpp).  views [B]: device pointers throughout
+#define LBA_THREADS 512                                              // profiles/match_local_ba.txt: the compiler's resource report and the choice
+int launch_local_ba(const LbaView* views, int B, hipStream_t s);
 
 // Vocabulary-guided searches (match_bow.hip): SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation.  Side A is the one whose entries act
 // (the key frame / pKF1, capacity capLast), side B the one searched (the frame / pKF2, capacity capCur).

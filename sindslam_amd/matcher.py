@@ -106,6 +106,13 @@ class _Sim3OptItem(C.Structure):
                 ("stage_chi2", C.c_void_p), ("stage_lambda", C.c_void_p)]
 
 
+class _LocalBaItem(C.Structure):
+    _fields_ = [("n_kf", C.c_int), ("kf_id", C.c_void_p), ("kf_kind", C.c_void_p), ("Tcw", C.c_void_p), ("n_mp", C.c_int), ("mp_id", C.c_void_p), ("x3Dw", C.c_void_p),
+                ("obs_start", C.c_void_p), ("obs_kf", C.c_void_p), ("obs_xy", C.c_void_p), ("u_right", C.c_void_p), ("inv_sigma2", C.c_void_p), ("do_more", C.c_int),
+                ("Tcw_out", C.c_void_p), ("x3Dw_out", C.c_void_p), ("erase", C.c_void_p), ("n_stages", C.c_void_p), ("stage_iters", C.c_void_p), ("n_level1", C.c_void_p),
+                ("stage_chi2", C.c_void_p), ("stage_lambda", C.c_void_p)]
+
+
 _f32 = lambda a: np.ascontiguousarray(a, np.float32)
 _u8 = lambda a: np.ascontiguousarray(a, np.uint8)
 _i32 = lambda a: np.ascontiguousarray(a, np.int32)
@@ -181,6 +188,29 @@ def sim3opt_result(a):
                 **{k: a[k] for k in ("stage_iters", "stage_chi2", "stage_lambda")})
 
 
+def localba_items(items):
+    """the sind_localba_item array of ORBmatcher.LocalBundleAdjustment's items, and the arrays it points to (which live as long as the caller keeps them)"""
+    arr = (_LocalBaItem * len(items))(); keep = []
+    for q, it in zip(arr, items):
+        n_kf, n_mp = len(it["kf_id"]), len(it["mp_id"])
+        a = dict(kf_id=np.ascontiguousarray(it["kf_id"], np.int64), kf_kind=_u8(it["kf_kind"]), Tcw=_f32(it["Tcw"]).reshape(n_kf, 16).copy(), mp_id=np.ascontiguousarray(it["mp_id"], np.int64),
+                 x3Dw=_f32(it["x3Dw"]).reshape(n_mp, 3).copy(), obs_start=_i32(it["obs_start"]), obs_kf=_i32(it["obs_kf"]), obs_xy=_f32(it["obs_xy"]), u_right=_f32(it["u_right"]),
+                 inv_sigma2=_f32(it["inv_sigma2"]))
+        n_obs = len(a["obs_kf"])
+        a.update(Tcw_out=a["Tcw"].copy(), x3Dw_out=a["x3Dw"].copy(), erase=np.zeros(n_obs, np.uint8), n_stages=np.zeros(1, np.int32), stage_iters=np.zeros(2, np.int32),
+                 n_level1=np.zeros(1, np.int32), stage_chi2=np.zeros(2, np.float64), stage_lambda=np.zeros(2, np.float64))
+        for key, v in a.items():
+            setattr(q, key, v.ctypes.data if v.size else None)
+        q.n_kf = n_kf; q.n_mp = n_mp; q.do_more = int(bool(it.get("do_more", True)))
+        keep.append(a)
+    return arr, keep
+
+
+def localba_result(a):
+    return dict(Tcw=a["Tcw_out"].reshape(-1, 4, 4), x3Dw=a["x3Dw_out"], erase=a["erase"], n_stages=int(a["n_stages"][0]), n_level1=int(a["n_level1"][0]),
+                **{k: a[k] for k in ("stage_iters", "stage_chi2", "stage_lambda")})
+
+
 class ORBmatcher:
     """ORBmatcher(nnratio, checkOri) of the reference.  Provided: SearchByProjection(CurrentFrame, LastFrame, th, bMono) (TrackWithMotionModel),
     SearchLocalPoints = Frame::isInFrustum over the local map + SearchByProjection(F, vpMapPoints, th) (TrackLocalMap), and SearchByProjectionKF =
@@ -191,7 +221,8 @@ class ORBmatcher:
     On the same handle, between SearchByBoWKF and SearchBySim3 in LoopClosing::ComputeSim3: the Sim3Solver (src/Sim3Solver.cc; Sim3Ransac, sim3_solvers, sindslam_amd/sim3.py).
     Between SearchByBoW and SearchByProjectionKF in Tracking::Relocalization: the PnPsolver (src/PnPsolver.cc; PnPRansac, pnp_solvers, sindslam_amd/pnp.py).
     After every search of the tracking thread: Optimizer::PoseOptimization (src/Optimizer.cc:239-451; PoseOptimization, sindslam_amd/optimizer.py).
-    After SearchBySim3 in LoopClosing::ComputeSim3: Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241; OptimizeSim3, sindslam_amd/optimizer.py)."""
+    After SearchBySim3 in LoopClosing::ComputeSim3: Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241; OptimizeSim3, sindslam_amd/optimizer.py).
+    After SearchInNeighbors in LocalMapping::Run: Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778; LocalBundleAdjustment, sindslam_amd/optimizer.py)."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
 
     def __init__(self, fx, fy, cx, cy, bf, bounds, scale_factors, nnratio=0.6, checkOri=True, cap=4096, max_batch=1, device=0, cap_points=0):
@@ -422,6 +453,16 @@ class ORBmatcher:
         arr, keep = sim3opt_items(items)
         check(lib().sind_match_sim3_optimize(self._h, arr, len(items), C.c_float(float(th2)), int(bool(fix_scale))), "sind_match_sim3_optimize")
         return [sim3opt_result(a) for a in keep]
+
+    def LocalBundleAdjustment(self, items):
+        """sind_match_local_ba: Optimizer::LocalBundleAdjustment (src/Optimizer.cc:506-743) of every item, one launch.  items: list of dicts: kf_id i64 [n_kf], kf_kind u8 [n_kf]
+        (0 local, 1 local and fixed, 2 fixed camera), Tcw [n_kf, 4, 4]; mp_id i64 [n_mp], x3Dw [n_mp, 3]; obs_start i32 [n_mp + 1], and per observation in the order the edges
+        are added obs_kf i32 (index into the key frames), obs_xy [n_obs, 2], u_right [n_obs] (< 0: monocular edge), inv_sigma2 [n_obs]; do_more (default True).
+        -> list of dicts: Tcw f32 [n_kf, 4, 4] (what SetPose gets; a fixed camera's row is its input), x3Dw f32 [n_mp, 3], erase u8 [n_obs] (vToErase), n_stages, n_level1,
+        stage_iters i32 [2], stage_chi2 f64 [2], stage_lambda f64 [2].  The lists the kernel walks are built inside the call."""
+        arr, keep = localba_items(items)
+        check(lib().sind_match_local_ba(self._h, arr, len(items)), "sind_match_local_ba")
+        return [localba_result(a) for a in keep]
 
     def last_rounds(self):
         return lib().sind_match_last_rounds(self._h)

@@ -2,6 +2,8 @@
 one call of the tracking thread, over sind_match_pose_optimize, and the chain of Tracking::Relocalization that is built on it (src/Tracking.cc:1460-1524) as the `accept`
 callback of pnp.relocalization_pnp.  Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241), the one call of LoopClosing::ComputeSim3, over sind_match_sim3_optimize, and the
 rest of ComputeSim3 built on it (src/LoopClosing.cc:310-398): compute_sim3_accept, the `accept` callback of sim3.compute_sim3, loop_scw and loop_accept.
+Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778), the one call of LocalMapping::Run, over sind_match_local_ba: LocalBundleAdjustment collects the graph
+(:455-504) from a map of plain dicts, apply_local_ba writes the result back (:746-777).
 
 A frame is a dict of per-keypoint arrays: un_xy [N, 2] (mvKeysUn[i].pt), u_right [N] (mvuRight), inv_sigma2 [N] (mvInvLevelSigma2[mvKeysUn[i].octave]), mp i64 [N] (the id of
 mvpMapPoints[i], -1 for NULL), x3Dw [N, 3] (GetWorldPos() of that map point; rows without one are not read), Tcw [4, 4] (mTcw), and optionally outlier [N] (mvbOutlier).
@@ -245,3 +247,74 @@ def loop_accept(matcher, kf1, Scw, loop_kfs, matched_ids, th=10, min_matches=40)
     matched[j] = ids[match_of_kf[j]]
     nTotalMatches = int((matched >= 0).sum())                           # :378-383
     return nTotalMatches >= min_matches, nTotalMatches, matched, ids
+
+
+def local_ba_graph(kf_id, keyframes, mappoints):
+    """The graph collection of Optimizer::LocalBundleAdjustment (:455-504) and the edges of :572-653, over plain dicts.
+    keyframes {id: dict(Tcw [4, 4], un_xy [N, 2], u_right [N], inv_sigma2 [N] (mvInvLevelSigma2[octave] per slot), mp i64 [N] (the id of mvpMapPoints[slot], -1 for NULL), bad,
+    covisible (the ids of GetVectorCovisibleKeyFrames(), in its order))}; mappoints {id: dict(x3Dw [3], obs {kf id: slot}, bad)}.
+    -> (local key frames, local map points, fixed cameras: lists of ids in the reference's list orders; item: the dict ORBmatcher.LocalBundleAdjustment takes, with pairs =
+    the (kf id, mp id) of every observation).  A point's observations are walked in ascending key-frame id (the reference walks a std::map keyed by pointers)."""
+    local = [kf_id] + [k for k in keyframes[kf_id]["covisible"] if not keyframes[k].get("bad")]     # pKF itself is not asked isBad()
+    marked = set([kf_id]) | set(keyframes[kf_id]["covisible"])          # mnBALocalForKF is set on the bad neighbours too
+    points, seen = [], set()
+    for k in local:
+        for m in np.asarray(keyframes[k]["mp"]).tolist():
+            if m >= 0 and not mappoints[m].get("bad") and m not in seen:
+                points.append(m); seen.add(m)
+    fixed, fmark = [], set()
+    for m in points:
+        for k in sorted(mappoints[m]["obs"]):
+            if k not in marked and k not in fmark:
+                fmark.add(k)
+                if not keyframes[k].get("bad"):
+                    fixed.append(k)
+    kfs = local + fixed
+    row = {k: i for i, k in enumerate(kfs)}
+    obs_start, obs_kf, xy, ur, s2, pairs = [0], [], [], [], [], []
+    for m in points:
+        for k in sorted(mappoints[m]["obs"]):
+            if keyframes[k].get("bad"):
+                continue
+            slot = mappoints[m]["obs"][k]; f = keyframes[k]
+            obs_kf.append(row[k]); xy.append(np.asarray(f["un_xy"], np.float32)[slot]); ur.append(np.float32(f["u_right"][slot])); s2.append(np.float32(f["inv_sigma2"][slot])); pairs.append((k, m))
+        obs_start.append(len(obs_kf))
+    item = dict(kf_id=np.array(kfs, np.int64), kf_kind=np.array([(1 if k == 0 else 0) for k in local] + [2] * len(fixed), np.uint8),
+                Tcw=np.array([np.asarray(keyframes[k]["Tcw"], np.float32).reshape(4, 4) for k in kfs], np.float32).reshape(len(kfs), 4, 4), mp_id=np.array(points, np.int64),
+                x3Dw=np.array([np.asarray(mappoints[m]["x3Dw"], np.float32) for m in points], np.float32).reshape(len(points), 3), obs_start=np.array(obs_start, np.int32),
+                obs_kf=np.array(obs_kf, np.int32), obs_xy=np.array(xy, np.float32).reshape(len(obs_kf), 2), u_right=np.array(ur, np.float32), inv_sigma2=np.array(s2, np.float32), pairs=pairs)
+    return local, points, fixed, item
+
+
+def LocalBundleAdjustment(matcher, kf_id, keyframes, mappoints, do_more=True):
+    """Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) up to the map mutex (:453-743): local_ba_graph, then matcher.LocalBundleAdjustment (an ORBmatcher or anything
+    with that method).  do_more = False is the stop flag seen after the first optimize.  The map is not modified: apply_local_ba does that.
+    -> dict(poses {kf id: Tcw f32 [4, 4]} of the local key frames, points {mp id: x3Dw f32 [3]}, erase = vToErase as (kf id, mp id), the monocular edges first and then
+    the stereo ones as there, local / map_points / fixed = the three lists, result = the call's raw result)"""
+    local, points, fixed, item = local_ba_graph(kf_id, keyframes, mappoints)
+    item["do_more"] = do_more
+    r = matcher.LocalBundleAdjustment([item])[0]
+    mono = np.asarray(item["u_right"]) < 0
+    erase = [item["pairs"][e] for e in np.nonzero(r["erase"] & mono)[0]] + [item["pairs"][e] for e in np.nonzero(r["erase"] & ~mono)[0]]
+    return dict(poses={k: np.array(r["Tcw"][i], np.float32) for i, k in enumerate(local)}, points={m: np.array(r["x3Dw"][j], np.float32) for j, m in enumerate(points)}, erase=erase,
+                local=local, map_points=points, fixed=fixed, result=r)
+
+
+def apply_local_ba(keyframes, mappoints, result):
+    """:746-777 on the dicts: for every pair of vToErase EraseMapPointMatch (the slot's map point becomes -1) and EraseObservation (the observation goes; with two or
+    fewer observations left, a stereo one counting twice, the point gets its bad flag and loses the rest, src/MapPoint.cc:118-146), then SetPose and SetWorldPos.
+    UpdateNormalAndDepth is not in the library: it stays the caller's step after this one."""
+    for k, m in result["erase"]:
+        mp = mappoints[m]
+        if k not in mp["obs"]:
+            continue
+        keyframes[k]["mp"][mp["obs"][k]] = -1
+        del mp["obs"][k]
+        if sum(2 if keyframes[q]["u_right"][sl] >= 0 else 1 for q, sl in mp["obs"].items()) <= 2:      # SetBadFlag
+            for q, sl in mp["obs"].items():
+                keyframes[q]["mp"][sl] = -1
+            mp["obs"] = {}; mp["bad"] = True
+    for k, T in result["poses"].items():
+        keyframes[k]["Tcw"] = np.array(T, np.float32).reshape(4, 4)
+    for m, X in result["points"].items():
+        mappoints[m]["x3Dw"] = np.array(X, np.float32)
