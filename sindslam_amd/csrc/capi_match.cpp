@@ -521,10 +521,16 @@ int sind_match_by_sim3(sind_match* m, const sind_match_sim3_pair* pairs, int B, 
     return SIND_OK;
 }
 
+// the opening of the five solver entry points below: the handle, the batch and whether the call's own scalars are in order.  -> SIND_OK, or the error, its text set
+static int solver_prologue(const char* fn, const sind_match* m, const void* items, int B, bool scalars_ok = true) {
+    if (!m || B < 0 || (B && !items) || !scalars_ok) { sind_set_error("%s: bad arguments", fn); return SIND_E_ARG; }
+    if (B > m->maxB) { sind_set_error("%s: B=%d over max_batch %d", fn, B, m->maxB); return SIND_E_CAPACITY; }
+    return SIND_OK;
+}
+
 int sind_match_sim3_ransac(sind_match* m, const sind_sim3_item* items, int B, int fix_scale) {
     const char* who = "sind_match_sim3_ransac: item";
-    if (!m || B < 0 || (B && !items)) { sind_set_error("sind_match_sim3_ransac: bad arguments"); return SIND_E_ARG; }
-    if (B > m->maxB) { sind_set_error("sind_match_sim3_ransac: B=%d over max_batch %d", B, m->maxB); return SIND_E_CAPACITY; }
+    SIND_TRY(solver_prologue("sind_match_sim3_ransac", m, items, B));
     const int cs = std::min(m->last.cap, m->cur.cap);
     int its = 0, maxN = 0;
     for (int b = 0; b < B; b++) {
@@ -581,8 +587,7 @@ int sind_match_sim3_ransac(sind_match* m, const sind_sim3_item* items, int B, in
 
 int sind_match_pnp_ransac(sind_match* m, const sind_pnp_item* items, int B) {
     const char* who = "sind_match_pnp_ransac: item";
-    if (!m || B < 0 || (B && !items)) { sind_set_error("sind_match_pnp_ransac: bad arguments"); return SIND_E_ARG; }
-    if (B > m->maxB) { sind_set_error("sind_match_pnp_ransac: B=%d over max_batch %d", B, m->maxB); return SIND_E_CAPACITY; }
+    SIND_TRY(solver_prologue("sind_match_pnp_ransac", m, items, B));
     const int cs = std::min(m->last.cap, m->cur.cap);
     int its = 0, maxN = 0;
     for (int b = 0; b < B; b++) {
@@ -663,8 +668,7 @@ int sind_match_pnp_ransac(sind_match* m, const sind_pnp_item* items, int B) {
 
 int sind_match_pose_optimize(sind_match* m, const sind_poseopt_item* items, int B) {
     const char* who = "sind_match_pose_optimize: item";
-    if (!m || B < 0 || (B && !items)) { sind_set_error("sind_match_pose_optimize: bad arguments"); return SIND_E_ARG; }
-    if (B > m->maxB) { sind_set_error("sind_match_pose_optimize: B=%d over max_batch %d", B, m->maxB); return SIND_E_CAPACITY; }
+    SIND_TRY(solver_prologue("sind_match_pose_optimize", m, items, B));
     const int cs = std::min(m->last.cap, m->cur.cap);
     int maxN = 0;
     for (int b = 0; b < B; b++) {
@@ -706,8 +710,7 @@ int sind_match_pose_optimize(sind_match* m, const sind_poseopt_item* items, int 
 
 int sind_match_sim3_optimize(sind_match* m, const sind_sim3opt_item* items, int B, float th2, int fix_scale) {
     const char* who = "sind_match_sim3_optimize: item";
-    if (!m || B < 0 || (B && !items) || !std::isfinite(th2) || th2 < 0) { sind_set_error("sind_match_sim3_optimize: bad arguments"); return SIND_E_ARG; }
-    if (B > m->maxB) { sind_set_error("sind_match_sim3_optimize: B=%d over max_batch %d", B, m->maxB); return SIND_E_CAPACITY; }
+    SIND_TRY(solver_prologue("sind_match_sim3_optimize", m, items, B, std::isfinite(th2) && th2 >= 0));
     const int cs = std::min(m->last.cap, m->cur.cap);
     int maxN = 0;
     for (int b = 0; b < B; b++) {
@@ -757,8 +760,7 @@ int sind_match_sim3_optimize(sind_match* m, const sind_sim3opt_item* items, int 
 
 int sind_match_local_ba(sind_match* m, const sind_localba_item* items, int B) {
     const char* who = "sind_match_local_ba: item";
-    if (!m || B < 0 || (B && !items)) { sind_set_error("sind_match_local_ba: bad arguments"); return SIND_E_ARG; }
-    if (B > m->maxB) { sind_set_error("sind_match_local_ba: B=%d over max_batch %d", B, m->maxB); return SIND_E_CAPACITY; }
+    SIND_TRY(solver_prologue("sind_match_local_ba", m, items, B));
     for (int b = 0; b < B; b++) if (const int bad = sind::lba_check(items[b])) { sind_set_error("%s %d: %s", who, b, sind::lba_check_text[bad]); return SIND_E_ARG; }
     if (!B) return SIND_OK;
     sind_match::LocalBaSide& w = m->localba;

@@ -10,8 +10,10 @@
 // The Levenberg-Marquardt scalars are computed by every lane from the same workspace values, so the control flow is uniform over the workgroup.
 //
 // RECALLED from pose_opt.hpp (not defined again): PoseQ, po_from_tcw, po_to_tcw, po_quat_to_matrix, po_map, po_exp, po_mul, po_oplus, po_edge_error (the error and chi2
-// of both edge types; the stereo cam_project keeps `const float invz`), po_huber, po_delta, and the control flow of OptimizationAlgorithmLevenberg::solve.
-// DEFINED here: lba_inv3, lba_edge (the two binary edges' linearizeOplus and constructQuadraticForm), the phases lba_* and local_ba.
+// of both edge types; the stereo cam_project keeps `const float invz`), po_huber, po_delta; from g2o_lm.hpp jtwj_upper and levenberg_optimize, the control flow of
+// OptimizationAlgorithmLevenberg::solve with the literal points all three optimizers share.
+// DEFINED here: lba_inv3, lba_edge (the two binary edges' linearizeOplus and constructQuadraticForm), the phases lba_*, their grouping into the driver's operations
+// (LbaLm) and local_ba.
 //
 // THE CONTRACT that makes host and device equal, and what it restates of g2o.
 // Vertex order (sparse_optimizer.cpp buildIndexMapping :166-190 over the sorted active vertices).  Poses first, then points, each in ascending id, over the vertices
@@ -146,24 +148,14 @@ SIND_HD inline void lba_edge(const PoseQ& P, const PoseOptCam& K, const double X
     const double W = robust ? rho1 * s : s;                          // weightedOmega = rho[1] * information
     double wr[3];                                                    // omega_r = - omega * _error; omega_r *= rho[1]
     for (int d = 0; d < 3; d++) { wr[d] = -(s * e[d]); if (robust) wr[d] = wr[d] * rho1; }
-    int k = 27;
-    for (int i = 0; i < 3; i++) for (int j = i; j < 3; j++) {
-        double h = (A[0][i] * W) * A[0][j] + (A[1][i] * W) * A[1][j];
-        if (stereo) h = h + (A[2][i] * W) * A[2][j];
-        c[k++] = h;
-    }
+    jtwj_upper(A, W, stereo, c + 27);
     for (int j = 0; j < 3; j++) {
         double t = A[0][j] * wr[0] + A[1][j] * wr[1];
         if (stereo) t = t + A[2][j] * wr[2];
         c[33 + j] = t;
     }
     if (!poseFree) return;
-    k = 0;
-    for (int i = 0; i < 6; i++) for (int j = i; j < 6; j++) {
-        double h = (B[0][i] * W) * B[0][j] + (B[1][i] * W) * B[1][j];
-        if (stereo) h = h + (B[2][i] * W) * B[2][j];
-        c[k++] = h;
-    }
+    jtwj_upper(B, W, stereo, c);
     for (int j = 0; j < 6; j++) {
         double t = B[0][j] * wr[0] + B[1][j] * wr[1];
         if (stereo) t = t + B[2][j] * wr[2];
@@ -359,50 +351,25 @@ template <class Ex> SIND_HD inline void lba_classify(Ex& ex, const LbaView& w, b
     if (toLevel) ex.par(1, [&](int) { int c = 0; for (int e = 0; e < w.nObs; e++) c += w.level[e]; w.isc[LBA_IS_NL1] = c; });
 }
 
-// SparseOptimizer::optimize(iterations) (sparse_optimizer.cpp:357-414) over OptimizationAlgorithmLevenberg::solve (:61-164), as pose_optimize has them.  -> iterations run
+// One optimize call as levenberg_optimize's problem (g2o_lm.hpp): each operation is the phases above and then the read of the scalar they left, which on the device is
+// a barrier of its own (ex.rd, ex.rdi).  The estimate the stored errors belong to is the workspace's: lba_eval leaves them in C, and nothing rewrites them on a pop.
+// computeScale's phases run after the trial's chi2 has been read, as g2o orders the two; they touch neither C nor sc[LBA_SC_CHI]
+template <class Ex> struct LbaLm {
+    Ex& ex; const LbaView& w; bool robust; int nAct;
+    SIND_HD double linearize() { lba_eval(ex, w, robust, true); lba_sums(ex, w, true); return ex.rd(&w.sc[LBA_SC_CHI]); }
+    SIND_HD double max_diagonal() { lba_maxdiag(ex, w); return ex.rd(&w.sc[LBA_SC_MAXD]); }
+    SIND_HD void push() { lba_push(ex, w); }
+    SIND_HD bool solve(double lambda) { lba_solve(ex, w, lambda, nAct); return ex.rdi(&w.isc[LBA_IS_FAIL]) == 0; }
+    SIND_HD void update() { lba_update(ex, w); }
+    SIND_HD double chi2() { lba_eval(ex, w, robust, false); lba_sums(ex, w, false); return ex.rd(&w.sc[LBA_SC_CHI]); }
+    SIND_HD double scale(double lambda) { lba_scale(ex, w, lambda); return ex.rd(&w.sc[LBA_SC_SCALE]); }
+    SIND_HD void pop() { lba_pop(ex, w); }
+};
+// SparseOptimizer::optimize(iterations): x is zeroed here, at buildStructure.  -> iterations run
 template <class Ex> SIND_HD inline int lba_optimize(Ex& ex, const LbaView& w, bool robust, int iterations, int nAct, double& chiOut, double& lambdaOut) {
     ex.par(6 * w.P + 3 * w.nMp, [&](int i) { w.x[i] = 0.0; });      // buildStructure
-    double lambda = -1.0, ni = 2.0, currentChi = 0.0;
-    int cj = 0, nBadLM = 0; bool ok = true;
-    for (int i = 0; i < iterations && ok; i++) {
-        lba_eval(ex, w, robust, true); lba_sums(ex, w, true);
-        currentChi = ex.rd(&w.sc[LBA_SC_CHI]);
-        double tempChi = currentChi; const double iniChi = currentChi;
-        if (i == 0) { lba_maxdiag(ex, w); lambda = 1e-5 * ex.rd(&w.sc[LBA_SC_MAXD]); ni = 2.0; nBadLM = 0; }
-        double rho = 0.0; int qmax = 0;
-        do {
-            lba_push(ex, w);
-            lba_solve(ex, w, lambda, nAct);
-            const bool ok2 = ex.rdi(&w.isc[LBA_IS_FAIL]) == 0;
-            lba_update(ex, w);
-            lba_eval(ex, w, robust, false); lba_sums(ex, w, false); lba_scale(ex, w, lambda);
-            tempChi = ex.rd(&w.sc[LBA_SC_CHI]);
-            if (!ok2) tempChi = DBL_MAX;
-            rho = currentChi - tempChi;
-            double scale = ex.rd(&w.sc[LBA_SC_SCALE]);
-            scale += 1e-3;
-            rho /= scale;
-            if (rho > 0 && fabs(tempChi) <= DBL_MAX) {               // g2o_isfinite
-                const double t = 2 * rho - 1;
-                double alpha = 1. - t * t * t;
-                alpha = (2. / 3. < alpha) ? 2. / 3. : alpha;
-                const double scaleFactor = (1. / 3. < alpha) ? alpha : 1. / 3.;
-                lambda *= scaleFactor; ni = 2; currentChi = tempChi;
-            } else {
-                lambda *= ni; ni *= 2; lba_pop(ex, w);
-            }
-            qmax++;
-        } while (rho < 0 && qmax < 10);
-        bool terminate = false;
-        if (qmax == 10 || rho == 0) terminate = true;
-        else {
-            if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++; else nBadLM = 0;       // Stop criterium (Raul)
-            if (nBadLM >= 3) terminate = true;
-        }
-        ok = !terminate; cj++;
-    }
-    chiOut = currentChi; lambdaOut = lambda;
-    return cj;
+    LbaLm<Ex> lm{ex, w, robust, nAct};
+    return levenberg_optimize(lm, iterations, chiOut, lambdaOut);
 }
 
 template <class Ex> SIND_HD inline void local_ba(Ex& ex, const LbaView& w) {

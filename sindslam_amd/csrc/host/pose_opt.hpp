@@ -8,22 +8,17 @@
 //   1. Eigen's evaluation order inside the small products (A^T Omega A, A^T Omega e, e^T Omega e, Omega * Omega, V * upsilon, the quaternion product and rotation, the
 //      norm of a quaternion).  DEFINED here: every sum in ascending index order, Omega = invSigma2 * I applied as one multiplication per row (no products with the
 //      zeros off its diagonal: with an infinite error Eigen's 0 * inf would give NaN where this gives inf).
-//   2. Eigen's LDLT (ldlt_inplace<Lower>::unblocked with its pivoting and sign tracking, isPositive(), solve with the pseudo-inverse of D at tolerance 1 / highest).
-//   3. The reference builds with -march=native, so its compiler may contract a * b + c; here nothing is contracted.
-//   4. Three definitions that replace maths-library calls: po_sincos for sin(theta) and cos(theta) of SE3Quat::exp (Cody-Waite reduction by pi/2 in fdlibm's
+//   2. The reference builds with -march=native, so its compiler may contract a * b + c; here nothing is contracted.
+//   3. Two definitions that replace maths-library calls: po_sincos for sin(theta) and cos(theta) of SE3Quat::exp (Cody-Waite reduction by pi/2 in fdlibm's
 //      second-iteration form, fdlibm / FreeBSD msun kernel polynomials; only add, mul, div, rint, compares; NaN gives NaN, 0 gives exactly 0 and 1; accurate below
-//      |theta| of about 2^20 pi/2, beyond it still total and the same on both sides), and pow(theta, 3), pow(2 rho - 1, 3) as x * x * x.
-// Two places where the reference reads state it never set are DEFINED: the solver's x starts as zeros (Solver::resizeVector leaves it uninitialised in a release
-// build; it is read by update() after a failed first solve), and it is kept across iterations and rounds as the BlockSolver keeps it.
-// One literal consequence kept: after a rejected trial the edges still hold the errors of the REJECTED pose (pop() restores the vertex, nobody recomputes
-// the errors), so after a round whose last trial was rejected the level-0 edges are classified with that pose and only the former outliers (computeError, :388-391)
-// with the restored one.
+//      |theta| of about 2^20 pi/2, beyond it still total and the same on both sides), and pow(theta, 3) as x * x * x.
+//   4. What g2o_lm.hpp lists: Eigen's LDLT and the Levenberg-Marquardt control flow, shared with sim3_opt.hpp and local_ba.hpp.
+// Of g2o_lm.hpp's literal points, here: the solver's x is kept across iterations AND rounds, as the BlockSolver keeps it; and after a round whose last trial was
+// rejected the level-0 edges are classified with the REJECTED pose (their stored errors) and only the former outliers (computeError, :388-391) with the restored one.
 #pragma once
-#include <cmath>
-#include <cfloat>
 #include <cstddef>
 #include <cstdint>
-#include "peac_fit.hpp"                                              // SIND_HD
+#include "g2o_lm.hpp"                                                // SIND_HD; the LDLT and the Levenberg-Marquardt driver
 
 struct sind_poseopt_item;
 
@@ -146,13 +141,9 @@ SIND_HD inline void po_exp(const double u[6], PoseQ& P) {
 // SE3Quat::operator* (se3quat.h:104-110): t = a.t + a.r * b.t, r = a.r * b.r (Eigen's quaternion product), normalizeRotation
 SIND_HD inline void po_mul(const PoseQ& A, const PoseQ& B, PoseQ& out) {
     double rt[3]; po_quat_rotate(A.q, B.t, rt);
-    const double* a = A.q; const double* b = B.q;
     PoseQ r;
     r.t[0] = A.t[0] + rt[0]; r.t[1] = A.t[1] + rt[1]; r.t[2] = A.t[2] + rt[2];
-    r.q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    r.q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    r.q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    r.q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    po_quat_mul(A.q, B.q, r.q);
     po_normalize_rotation(r.q);
     out = r;
 }
@@ -201,12 +192,7 @@ SIND_HD inline void po_edge_contrib(const PoseQ& P, const PoseOptCam& K, float X
     // constructQuadraticForm (base_unary_edge.hpp:55-67): weightedOmega = rho[1] * information; b -= rho[1] * A^T * omega * error
     const double W = robust ? rho1 * s : s;
     const double se[3] = {s * e[0], s * e[1], s * e[2]};
-    int k = 0;
-    for (int i = 0; i < 6; i++) for (int j = i; j < 6; j++) {
-        double h = (A[0][i] * W) * A[0][j] + (A[1][i] * W) * A[1][j];
-        if (stereo) h = h + (A[2][i] * W) * A[2][j];
-        c[k++] = h;
-    }
+    jtwj_upper(A, W, stereo, c);
     for (int j = 0; j < 6; j++) {
         double t = A[0][j] * se[0] + A[1][j] * se[1];
         if (stereo) t = t + A[2][j] * se[2];
@@ -222,57 +208,22 @@ SIND_HD inline bool po_edge_is_outlier(const PoseQ& P, const PoseOptCam& K, floa
     return chi2 > (stereo ? 7.815f : 5.991f);
 }
 
-// ---------------------------------------------------------------- LinearSolverDense::solve (linear_solver_dense.h:104-112): Eigen::LDLT, isPositive(), solve
-// H: the full symmetric 6 x 6 (only its lower triangle is read).  -> false if !isPositive(); x is then untouched
-SIND_HD inline bool po_ldlt_solve(const double Hin[6][6], const double b[6], double x[6]) {
-    double m[6][6]; int tr[6]; double temp[6];
-    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) m[i][j] = Hin[i][j];
-    int sign = 0;                                                    // ZeroSign 0, PositiveSemiDef 1, NegativeSemiDef -1, Indefinite 2
-    for (int k = 0; k < 6; k++) {
-        int big = k; double best = fabs(m[k][k]);                    // mat.diagonal().tail(size-k).cwiseAbs().maxCoeff(&index): the first maximum
-        for (int i = k + 1; i < 6; i++) if (fabs(m[i][i]) > best) { best = fabs(m[i][i]); big = i; }
-        tr[k] = big;
-        if (k != big) {
-            for (int j = 0; j < k; j++) { const double t = m[k][j]; m[k][j] = m[big][j]; m[big][j] = t; }
-            for (int i = big + 1; i < 6; i++) { const double t = m[i][k]; m[i][k] = m[i][big]; m[i][big] = t; }
-            { const double t = m[k][k]; m[k][k] = m[big][big]; m[big][big] = t; }
-            for (int i = k + 1; i < big; i++) { const double t = m[i][k]; m[i][k] = m[big][i]; m[big][i] = t; }
-        }
-        const int rs = 6 - k - 1;
-        if (k > 0) {
-            for (int j = 0; j < k; j++) temp[j] = m[j][j] * m[k][j];
-            double a = 0.0;
-            for (int j = 0; j < k; j++) a = a + m[k][j] * temp[j];
-            m[k][k] -= a;
-            for (int i = k + 1; i < 6; i++) { double v = 0.0; for (int j = 0; j < k; j++) v = v + m[i][j] * temp[j]; m[i][k] -= v; }
-        }
-        const double realAkk = m[k][k];
-        const bool valid = fabs(realAkk) > 0.0;
-        if (k == 0 && !valid) { sign = 0; for (int j = 0; j < 6; j++) tr[j] = j; break; }       // the entire matrix is zero
-        if (rs > 0 && valid) for (int i = k + 1; i < 6; i++) m[i][k] /= realAkk;
-        if (sign == 1) { if (realAkk < 0.0) sign = 2; }
-        else if (sign == -1) { if (realAkk > 0.0) sign = 2; }
-        else if (sign == 0) { if (realAkk > 0.0) sign = 1; else if (realAkk < 0.0) sign = -1; }
-    }
-    if (!(sign == 1 || sign == 0)) return false;                     // isPositive()
-    double d[6];
-    for (int i = 0; i < 6; i++) d[i] = b[i];
-    for (int k = 0; k < 6; k++) { const double t = d[k]; d[k] = d[tr[k]]; d[tr[k]] = t; }     // dst = P b
-    for (int j = 0; j < 6; j++) for (int i = j + 1; i < 6; i++) d[i] -= d[j] * m[i][j];        // L^-1
-    const double tol = 1.0 / DBL_MAX;                                // D^+ : RealScalar(1) / NumTraits<RealScalar>::highest()
-    for (int i = 0; i < 6; i++) { if (fabs(m[i][i]) > tol) d[i] /= m[i][i]; else d[i] = 0.0; }
-    for (int j = 5; j >= 0; j--) for (int i = j - 1; i >= 0; i--) d[i] -= d[j] * m[j][i];      // L^-T
-    for (int k = 5; k >= 0; k--) { const double t = d[k]; d[k] = d[tr[k]]; d[tr[k]] = t; }     // P^T
-    for (int i = 0; i < 6; i++) x[i] = d[i];
-    return true;
-}
-
-// ---------------------------------------------------------------- the outer function and OptimizationAlgorithmLevenberg::solve
+// ---------------------------------------------------------------- the outer function over levenberg_optimize (g2o_lm.hpp)
 // Ev: the edges of one frame.
 //   void sums(const PoseQ& P, bool robust, bool full, double* S)   over the level-0 edges in ascending order, each S[k] a sequential FP64 sum from 0: S[27] += rho[0]
 //                                                                  (computeActiveErrors + activeRobustChi2); full: S[0..20] += H entries, S[21..26] -= b terms (buildSystem)
 //   int classify(const PoseQ& Perr, const PoseQ& Pest)             :382-438: level-0 edges judged at Perr (their stored error), former outliers at Pest; sets
 //                                                                  mvbOutlier = level; -> nBad
+// One round as levenberg_optimize's problem: the frame's vertex est over Ev's edges; errPose is the pose the edges' stored errors belong to
+template <class Ev> struct PoseLm : DenseSystem<6> {
+    Ev& ev; PoseQ& est; PoseQ& errPose; bool robust; PoseQ backup;
+    SIND_HD PoseLm(Ev& ev_, PoseQ& est_, PoseQ& errPose_, bool robust_, double (&x_)[6]) : DenseSystem<6>(x_), ev(ev_), est(est_), errPose(errPose_), robust(robust_) {}
+    SIND_HD double linearize() { double S[POSEOPT_ENTRIES]; ev.sums(est, robust, true, S); errPose = est; load(S); return S[27]; }
+    SIND_HD void push() { backup = est; }
+    SIND_HD void update() { po_oplus(x, est); }
+    SIND_HD double chi2() { double T[POSEOPT_ENTRIES]; ev.sums(est, robust, false, T); errPose = est; return T[27]; }
+    SIND_HD void pop() { est = backup; }
+};
 template <class Ev> SIND_HD inline void pose_optimize(Ev& ev, int n, const float* Tcw, PoseOptOut& o) {
     o.nGood = 0; o.nRounds = 0;
     for (int r = 0; r < 4; r++) { o.iters[r] = 0; o.nbad[r] = 0; o.chi2[r] = 0.0; o.lambda[r] = 0.0; for (int k = 0; k < 12; k++) o.pose[r][k] = 0.0; }
@@ -281,61 +232,12 @@ template <class Ev> SIND_HD inline void pose_optimize(Ev& ev, int n, const float
     PoseQ P0; po_from_tcw(Tcw, P0);
     PoseQ est = P0;
     double x[6] = {0, 0, 0, 0, 0, 0};
-    double lambda = -1.0, ni = 2.0;                                  // _currentLambda, _ni
     int nBad = 0;
     for (int it = 0; it < 4; it++) {                                 // :374
         est = P0;                                                    // vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw)): the INPUT pose, every round
         PoseQ errPose = est;
-        const bool robust = it < 3;                                  // e->setRobustKernel(0) after round index 2 (:407, :436)
-        int cj = 0, nBadLM = 0; bool ok = true; double currentChi = 0.0;
-        for (int i = 0; i < 10 && ok; i++) {                         // SparseOptimizer::optimize (sparse_optimizer.cpp:376-414)
-            double S[POSEOPT_ENTRIES], H[6][6], b[6];
-            ev.sums(est, robust, true, S); errPose = est;
-            currentChi = S[27];
-            double tempChi = currentChi; const double iniChi = currentChi;
-            { int k = 0; for (int a = 0; a < 6; a++) for (int c = a; c < 6; c++) { H[a][c] = S[k]; H[c][a] = S[k]; k++; } }
-            for (int j = 0; j < 6; j++) b[j] = S[21 + j];
-            if (i == 0) {                                            // computeLambdaInit (:166-180), _tau = 1e-5
-                double maxDiagonal = 0.0;
-                for (int j = 0; j < 6; j++) { const double a = fabs(H[j][j]); maxDiagonal = (a < maxDiagonal) ? maxDiagonal : a; }
-                lambda = 1e-5 * maxDiagonal; ni = 2.0; nBadLM = 0;
-            }
-            double rho = 0.0; int qmax = 0;
-            do {
-                const PoseQ backup = est;                            // push
-                double Hl[6][6];
-                for (int a = 0; a < 6; a++) for (int c = 0; c < 6; c++) Hl[a][c] = (a == c) ? H[a][c] + lambda : H[a][c];    // setLambda(_currentLambda, true)
-                const bool ok2 = po_ldlt_solve(Hl, b, x);
-                po_oplus(x, est);                                    // update(_solver->x()); restoreDiagonal: H itself was never changed
-                double T[POSEOPT_ENTRIES];
-                ev.sums(est, robust, false, T); errPose = est;
-                tempChi = T[27];
-                if (!ok2) tempChi = DBL_MAX;
-                rho = currentChi - tempChi;
-                double scale = 0.0;                                  // computeScale (:182-189)
-                for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + b[j]);
-                scale += 1e-3;
-                rho /= scale;
-                if (rho > 0 && fabs(tempChi) <= DBL_MAX) {           // g2o_isfinite
-                    const double w = 2 * rho - 1;
-                    double alpha = 1. - w * w * w;
-                    alpha = (2. / 3. < alpha) ? 2. / 3. : alpha;     // (std::min)(alpha, _goodStepUpperScale)
-                    const double scaleFactor = (1. / 3. < alpha) ? alpha : 1. / 3.;   // (std::max)(_goodStepLowerScale, alpha)
-                    lambda *= scaleFactor; ni = 2; currentChi = tempChi;           // discardTop
-                } else {
-                    lambda *= ni; ni *= 2; est = backup;             // pop
-                }
-                qmax++;
-            } while (rho < 0 && qmax < 10);
-            bool terminate = false;
-            if (qmax == 10 || rho == 0) terminate = true;
-            else {
-                if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++; else nBadLM = 0;       // Stop criterium (Raul)
-                if (nBadLM >= 3) terminate = true;
-            }
-            ok = !terminate; cj++;
-        }
-        o.iters[it] = cj; o.chi2[it] = currentChi; o.lambda[it] = lambda;
+        PoseLm<Ev> lm(ev, est, errPose, it < 3, x);                  // e->setRobustKernel(0) after round index 2 (:407, :436)
+        o.iters[it] = levenberg_optimize(lm, 10, o.chi2[it], o.lambda[it]);
         { double R[3][3]; po_quat_to_matrix(est.q, R); for (int a = 0; a < 3; a++) { for (int c = 0; c < 3; c++) o.pose[it][3 * a + c] = R[a][c]; o.pose[it][9 + a] = est.t[a]; } }
         nBad = ev.classify(errPose, est);
         o.nbad[it] = nBad; o.nRounds = it + 1;

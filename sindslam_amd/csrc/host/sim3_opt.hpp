@@ -16,14 +16,13 @@
 //      right, entry by entry, (I + a O) + b O2 and (A O + B O2) + C I with I's entries 1.0 and 0.0 multiplied as written.
 //   2. Eigen's evaluation order inside the small products (Omega * Omega, W * upsilon, J^T Omega J, J^T omega_r, e^T Omega e, the quaternion product and rotation, the
 //      norm of omega).  DEFINED as in pose_opt.hpp: every sum in ascending index order, Omega = invSigma2 * I applied as one multiplication per row.
-//   3. Eigen's LDLT (ldlt_inplace<Lower>::unblocked, isPositive(), solve with the pseudo-inverse of D): s3_ldlt_solve is po_ldlt_solve with 7 for 6.
+//   3. What g2o_lm.hpp lists: Eigen's LDLT (here ldlt_solve<7>) and the Levenberg-Marquardt control flow, shared with pose_opt.hpp and local_ba.hpp.
 //   4. The reference builds with -march=native, so its compiler may contract a * b + c; here nothing is contracted.
 //   5. Maths-library calls: sin and cos are po_sincos; std::exp is s3_exp, DEFINED here: reduction x = k ln2 + r with k = rint(x / ln2) (ln2 split in two as in fdlibm's
 //      e_exp.c), fdlibm's polynomial c = r - r^2 (P1 + ...), y = 1 - ((lo - r c / (2 - c)) - hi) for every k (fdlibm's separate k = 0 form is not used), then an exact
 //      scaling by 2^k (ldexp).  Only add, mul, div, rint, compares and that scaling.  exp(0) = 1 exactly, NaN gives NaN, above 709.78 +inf, below -745.2 zero.
-// As in pose_opt.hpp: the solver's x starts as zeros and is kept across iterations and across the two stages (Solver::resizeVector reallocates on growth only), and
-// the classification reads the edges' STORED errors: those of the last evaluated estimate, which after a rejected trial is the rejected one (pop() restores the
-// vertex, nobody recomputes the errors).
+// Of g2o_lm.hpp's literal points, here: the solver's x is kept across iterations and across the two stages (Solver::resizeVector reallocates on growth only), and
+// the classification reads the edges' STORED errors: those of the last evaluated estimate, which after a rejected trial is the rejected one.
 // Kept literally: no quaternion is ever normalised (Sim3's constructors, operator* and inverse() do not), so its norm drifts; the second stage starts from the first
 // stage's estimate with lambda re-initialised; with fewer than 10 pairs left after the first stage the function returns 0 and the Sim3 stays the input, the matches
 // already nulled.  An empty graph (n = 0): initializeOptimization reports "Attempt to initialize an empty graph" and returns false, _ivMap stays empty, optimize
@@ -109,12 +108,8 @@ SIND_HD inline void s3_exp7(const double u[7], Sim3Q& S) {
 // operator* (sim3.h:266-272): r = r * other.r, t = s * (r * other.t) + t, s = s * other.s
 SIND_HD inline void s3_mul(const Sim3Q& A, const Sim3Q& B, Sim3Q& out) {
     double rt[3]; po_quat_rotate(A.q, B.t, rt);
-    const double* a = A.q; const double* b = B.q;
     Sim3Q r;
-    r.q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    r.q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    r.q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    r.q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    po_quat_mul(A.q, B.q, r.q);
     for (int i = 0; i < 3; i++) r.t[i] = A.s * rt[i] + A.t[i];
     r.s = A.s * B.s;
     out = r;
@@ -181,8 +176,7 @@ SIND_HD inline void s3_edge_contrib(const Sim3Q* T, const Sim3Cam& K, float Xx, 
     const double W = rho1 * s;
     double omr[2] = {-(s * e[0]), -(s * e[1])};
     omr[0] *= rho1; omr[1] *= rho1;
-    int k = 0;
-    for (int i = 0; i < 7; i++) for (int j = i; j < 7; j++) c[k++] = (J[0][i] * W) * J[0][j] + (J[1][i] * W) * J[1][j];
+    jtwj_upper(J, W, false, c);
     for (int j = 0; j < 7; j++) c[28 + j] = J[0][j] * omr[0] + J[1][j] * omr[1];
 }
 // `e12->chi2()>th2 || e21->chi2()>th2` (:1193, :1227) for one pair at the estimate S the edges' errors were last computed with; th2 is the float promoted
@@ -194,58 +188,23 @@ SIND_HD inline bool s3_pair_is_bad(const Sim3Q& S, const Sim3Q& Sinv, const Sim3
     return c12 > (double)th2 || c21 > (double)th2;
 }
 
-// ---------------------------------------------------------------- LinearSolverDense::solve for the 7 x 7 system: po_ldlt_solve of pose_opt.hpp with 7 for 6
-SIND_HD inline bool s3_ldlt_solve(const double Hin[7][7], const double b[7], double x[7]) {
-    const int N = 7;
-    double m[N][N]; int tr[N]; double temp[N];
-    for (int i = 0; i < N; i++) for (int j = 0; j < N; j++) m[i][j] = Hin[i][j];
-    int sign = 0;                                                    // ZeroSign 0, PositiveSemiDef 1, NegativeSemiDef -1, Indefinite 2
-    for (int k = 0; k < N; k++) {
-        int big = k; double best = fabs(m[k][k]);
-        for (int i = k + 1; i < N; i++) if (fabs(m[i][i]) > best) { best = fabs(m[i][i]); big = i; }
-        tr[k] = big;
-        if (k != big) {
-            for (int j = 0; j < k; j++) { const double t = m[k][j]; m[k][j] = m[big][j]; m[big][j] = t; }
-            for (int i = big + 1; i < N; i++) { const double t = m[i][k]; m[i][k] = m[i][big]; m[i][big] = t; }
-            { const double t = m[k][k]; m[k][k] = m[big][big]; m[big][big] = t; }
-            for (int i = k + 1; i < big; i++) { const double t = m[i][k]; m[i][k] = m[big][i]; m[big][i] = t; }
-        }
-        const int rs = N - k - 1;
-        if (k > 0) {
-            for (int j = 0; j < k; j++) temp[j] = m[j][j] * m[k][j];
-            double a = 0.0;
-            for (int j = 0; j < k; j++) a = a + m[k][j] * temp[j];
-            m[k][k] -= a;
-            for (int i = k + 1; i < N; i++) { double v = 0.0; for (int j = 0; j < k; j++) v = v + m[i][j] * temp[j]; m[i][k] -= v; }
-        }
-        const double realAkk = m[k][k];
-        const bool valid = fabs(realAkk) > 0.0;
-        if (k == 0 && !valid) { sign = 0; for (int j = 0; j < N; j++) tr[j] = j; break; }
-        if (rs > 0 && valid) for (int i = k + 1; i < N; i++) m[i][k] /= realAkk;
-        if (sign == 1) { if (realAkk < 0.0) sign = 2; }
-        else if (sign == -1) { if (realAkk > 0.0) sign = 2; }
-        else if (sign == 0) { if (realAkk > 0.0) sign = 1; else if (realAkk < 0.0) sign = -1; }
-    }
-    if (!(sign == 1 || sign == 0)) return false;                     // isPositive()
-    double d[N];
-    for (int i = 0; i < N; i++) d[i] = b[i];
-    for (int k = 0; k < N; k++) { const double t = d[k]; d[k] = d[tr[k]]; d[tr[k]] = t; }
-    for (int j = 0; j < N; j++) for (int i = j + 1; i < N; i++) d[i] -= d[j] * m[i][j];
-    const double tol = 1.0 / DBL_MAX;
-    for (int i = 0; i < N; i++) { if (fabs(m[i][i]) > tol) d[i] /= m[i][i]; else d[i] = 0.0; }
-    for (int j = N - 1; j >= 0; j--) for (int i = j - 1; i >= 0; i--) d[i] -= d[j] * m[j][i];
-    for (int k = N - 1; k >= 0; k--) { const double t = d[k]; d[k] = d[tr[k]]; d[tr[k]] = t; }
-    for (int i = 0; i < N; i++) x[i] = d[i];
-    return true;
-}
-
-// ---------------------------------------------------------------- the outer function (:1180-1240) and OptimizationAlgorithmLevenberg::solve
+// ---------------------------------------------------------------- the outer function (:1180-1240) over levenberg_optimize (g2o_lm.hpp)
 // Ev: the pairs of one item.
 //   void sums(const Sim3Q& est, bool full, double* S)   over the edges of the pairs not removed, in insertion order (e12 of pair 0, e21 of pair 0, e12 of pair 1, ...:
 //                                                       the active edges are sorted by internal id), each S[k] a sequential FP64 sum from 0: S[35] += rho[0];
 //                                                       full: S[0..27] += H entries, S[28..34] += b terms, linearised at est
 //   int classify(const Sim3Q& Serr, int* nIn)           :1186-1203 / :1220-1234 at the estimate of the stored errors: marks the pairs over th2 removed; -> how many it
 //                                                       marked, *nIn = how many of the pairs it looked at stay
+// Both stages as levenberg_optimize's problem: the Sim3 vertex est over Ev's edges; errS is the estimate the edges' stored errors belong to
+template <class Ev> struct Sim3Lm : DenseSystem<7> {
+    Ev& ev; Sim3Q& est; Sim3Q& errS; bool fixScale; Sim3Q backup;
+    SIND_HD Sim3Lm(Ev& ev_, Sim3Q& est_, Sim3Q& errS_, bool fixScale_, double (&x_)[7]) : DenseSystem<7>(x_), ev(ev_), est(est_), errS(errS_), fixScale(fixScale_) {}
+    SIND_HD double linearize() { double S[SIM3OPT_ENTRIES]; ev.sums(est, true, S); errS = est; load(S); return S[35]; }
+    SIND_HD void push() { backup = est; }
+    SIND_HD void update() { s3_oplus(x, fixScale, est); }            // x[6] = 0 stays in the solver's vector, where computeScale reads it
+    SIND_HD double chi2() { double T[SIM3OPT_ENTRIES]; ev.sums(est, false, T); errS = est; return T[35]; }
+    SIND_HD void pop() { est = backup; }
+};
 template <class Ev> SIND_HD inline void sim3_optimize(Ev& ev, int n, const Sim3Q& S0, bool fixScale, Sim3OptOut& o) {
     for (int k = 0; k < 4; k++) o.q[k] = S0.q[k];
     for (int k = 0; k < 3; k++) o.t[k] = S0.t[k];
@@ -254,59 +213,11 @@ template <class Ev> SIND_HD inline void sim3_optimize(Ev& ev, int n, const Sim3Q
     if (n < 1) return;                                               // the empty graph: see the head of this file
     Sim3Q est = S0, errS = S0;
     double x[7] = {0, 0, 0, 0, 0, 0, 0};
-    double lambda = -1.0, ni = 2.0;
+    Sim3Lm<Ev> lm(ev, est, errS, fixScale, x);
     int nBad = 0, nIn = 0;
     for (int stage = 0; stage < 2; stage++) {
-        const int iterations = stage == 0 ? 5 : (nBad > 0 ? 10 : 5);
-        int cj = 0, nBadLM = 0; bool ok = true; double currentChi = 0.0;
-        for (int i = 0; i < iterations && ok; i++) {                 // SparseOptimizer::optimize (sparse_optimizer.cpp:376-414)
-            double S[SIM3OPT_ENTRIES], H[7][7], b[7];
-            ev.sums(est, true, S); errS = est;
-            currentChi = S[35];
-            double tempChi = currentChi; const double iniChi = currentChi;
-            { int k = 0; for (int a = 0; a < 7; a++) for (int c = a; c < 7; c++) { H[a][c] = S[k]; H[c][a] = S[k]; k++; } }
-            for (int j = 0; j < 7; j++) b[j] = S[28 + j];
-            if (i == 0) {                                            // computeLambdaInit, _tau = 1e-5
-                double maxDiagonal = 0.0;
-                for (int j = 0; j < 7; j++) { const double a = fabs(H[j][j]); maxDiagonal = (a < maxDiagonal) ? maxDiagonal : a; }
-                lambda = 1e-5 * maxDiagonal; ni = 2.0; nBadLM = 0;
-            }
-            double rho = 0.0; int qmax = 0;
-            do {
-                const Sim3Q backup = est;                            // push
-                double Hl[7][7];
-                for (int a = 0; a < 7; a++) for (int c = 0; c < 7; c++) Hl[a][c] = (a == c) ? H[a][c] + lambda : H[a][c];
-                const bool ok2 = s3_ldlt_solve(Hl, b, x);
-                s3_oplus(x, fixScale, est);                          // update(_solver->x()): x[6] = 0 stays in the solver's vector
-                double T[SIM3OPT_ENTRIES];
-                ev.sums(est, false, T); errS = est;
-                tempChi = T[35];
-                if (!ok2) tempChi = DBL_MAX;
-                rho = currentChi - tempChi;
-                double scale = 0.0;                                  // computeScale
-                for (int j = 0; j < 7; j++) scale += x[j] * (lambda * x[j] + b[j]);
-                scale += 1e-3;
-                rho /= scale;
-                if (rho > 0 && fabs(tempChi) <= DBL_MAX) {           // g2o_isfinite
-                    const double w = 2 * rho - 1;
-                    double alpha = 1. - w * w * w;
-                    alpha = (2. / 3. < alpha) ? 2. / 3. : alpha;
-                    const double scaleFactor = (1. / 3. < alpha) ? alpha : 1. / 3.;
-                    lambda *= scaleFactor; ni = 2; currentChi = tempChi;
-                } else {
-                    lambda *= ni; ni *= 2; est = backup;             // pop
-                }
-                qmax++;
-            } while (rho < 0 && qmax < 10);
-            bool terminate = false;
-            if (qmax == 10 || rho == 0) terminate = true;
-            else {
-                if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++; else nBadLM = 0;       // Stop criterium (Raul)
-                if (nBadLM >= 3) terminate = true;
-            }
-            ok = !terminate; cj++;
-        }
-        o.iters[stage] = cj; o.chi2[stage] = currentChi; o.lambda[stage] = lambda; o.stages = stage + 1;
+        o.iters[stage] = levenberg_optimize(lm, stage == 0 ? 5 : (nBad > 0 ? 10 : 5), o.chi2[stage], o.lambda[stage]);
+        o.stages = stage + 1;
         if (stage == 0) {
             nBad = ev.classify(errS, &nIn);
             o.nBad = nBad;

@@ -3,10 +3,9 @@
 // source of the arithmetic and of the control flow for this file and for the host twin (host/pose_opt.cpp); this file supplies the evaluator: how a workgroup
 // forms g2o's sums over the edges.  The device result is compared with the host's bit for bit (tests/test_poseopt_gpu.py).
 //
-// Shape.  One workgroup of 192 threads per item.  Waves 1 and 2 are the 128 EDGE lanes: in a chunk of 128 consecutive edges each computes one edge (map, error,
-// robustify, the Jacobian, the 21 + 6 + 1 contributions of pose_opt.hpp's po_edge_contrib) and writes them as [entry][edge] into one of two LDS buffers.  Wave 0 is
-// the SUM wave: lane k < 28 carries the running sum of entry k and adds the chunk's values in ascending edge order, while the edge lanes fill the other buffer with
-// the next chunk; one barrier per chunk.  That is g2o's sum: H, b and the robust chi2 are cleared and every level-0 edge adds to them in edge order, each a sequential
+// Shape.  One workgroup of 192 threads per item, in the ordered sum of ordered_sum.hpp.  Waves 1 and 2 are the 128 EDGE lanes: in a chunk of 128 consecutive edges
+// each computes one edge (map, error, robustify, the Jacobian, the 21 + 6 + 1 contributions of pose_opt.hpp's po_edge_contrib).  Wave 0 is the SUM wave: lane k < 28
+// carries the running sum of entry k.  That is g2o's sum: H, b and the robust chi2 are cleared and every level-0 edge adds to them in edge order, each a sequential
 // FP64 sum (an edge of level 1 is skipped there and skipped here).  Rows are padded to 129 doubles so the 28 sum lanes read 28 different bank pairs.
 // The 6 x 6 part (LDLT, exp, the lambda logic) is not broadcast: every lane computes it from the same 28 sums, which keeps the control flow of pose_optimize
 // uniform over the workgroup (all barriers are reached by all threads) and costs nothing but the lanes' idle slots.  Its small matrices are indexed dynamically
@@ -18,6 +17,7 @@
 // them.  No atomics, no inline assembly.  mvbOutlier (= the edge's level) is the item's row of the outlier output; it is read and written by different lanes in
 // different phases, always with a barrier in between.
 #include "match.hpp"
+#include "ordered_sum.hpp"
 #include "host/pose_opt.hpp"
 
 namespace sind {
@@ -33,32 +33,14 @@ struct PoseOptWg {                                                   // the eval
     double (*buf)[POSEOPT_ENTRIES][PO_ROW]; double* total; int* cnt;                  // LDS: [2], [28], [PO_THREADS]
 
     __device__ void sums(const PoseQ& P, bool robust, bool full, double* S) {
-        const int nChunks = (n + PO_CHUNK - 1) / PO_CHUNK;
-        const int first = full ? 0 : 27;                             // not full: the chi2 row alone
-        double run = 0.0;
-        for (int c = 0; c <= nChunks; c++) {
-            if (tid >= 64 && c < nChunks) {                          // edge lanes: chunk c into buffer c & 1
-                const int e = tid - 64, i = c * PO_CHUNK + e;
-                if (i < n) {
-                    double v[POSEOPT_ENTRIES];
-                    const bool active = outlier[i] == 0;             // initializeOptimization(0): level-0 edges only
-                    if (active) { const float4 X = pts[i], U = obs[i]; po_edge_contrib(P, K, X.x, X.y, X.z, U.x, U.y, U.z, X.w, robust, full, v); }
-                    double (*B)[PO_ROW] = buf[c & 1];
-                    for (int k = first; k < POSEOPT_ENTRIES; k++) B[k][e] = active ? v[k] : 0.0;      // x + 0 = x - 0 = x for every x these sums can hold (never -0)
-                }
-            }
-            if (tid >= first && tid < POSEOPT_ENTRIES && c > 0) {    // sum lanes: chunk c - 1 from the other buffer
-                const int m = min(PO_CHUNK, n - (c - 1) * PO_CHUNK);
-                const double* row = buf[(c - 1) & 1][tid];
-                if (tid >= 21 && tid < 27) { for (int j = 0; j < m; j++) run = run - row[j]; }        // b -= ...
-                else { for (int j = 0; j < m; j++) run = run + row[j]; }
-            }
-            __syncthreads();
-        }
-        if (tid >= first && tid < POSEOPT_ENTRIES) total[tid] = run;
-        __syncthreads();
-        for (int k = 0; k < POSEOPT_ENTRIES; k++) S[k] = k >= first ? total[k] : 0.0;
-        // the next write to total[] or buf[] comes after the first barrier of the next call, which every lane reaches only after these reads
+        ordered_sums<POSEOPT_ENTRIES, PO_CHUNK, PO_ROW, PO_THREADS - PO_CHUNK>(tid, n, full ? 0 : 27 /* not full: the chi2 row alone */, buf, total,
+            [&](int i, double* v) {
+                if (outlier[i]) return false;                        // initializeOptimization(0): level-0 edges only
+                const float4 X = pts[i], U = obs[i];
+                po_edge_contrib(P, K, X.x, X.y, X.z, U.x, U.y, U.z, X.w, robust, full, v);
+                return true;
+            },
+            [](int k) { return k >= 21 && k < 27; }, S);             // b -= ...
     }
 
     __device__ int classify(const PoseQ& Perr, const PoseQ& Pest) {

@@ -4,11 +4,10 @@
 // bit for bit (tests/test_sim3opt_gpu.py).
 //
 // Shape.  One workgroup of 128 threads per item.  A pair has two edges, edge 2 i the EdgeSim3ProjectXYZ of pair i and edge 2 i + 1 its EdgeInverseSim3ProjectXYZ: the
-// order of g2o's active edges.  Wave 1 is the 64 EDGE lanes: in a chunk of 64 consecutive edges each computes one edge (its error, the Huber weight, the numeric
-// Jacobian from 14 more error evaluations, the 28 + 7 + 1 contributions of sim3_opt.hpp's s3_edge_contrib) and writes them as [entry][edge] into one of two LDS
-// buffers.  Wave 0 is the SUM wave: lane k < 36 carries the running sum of entry k and adds the chunk's values in ascending edge order while the edge lanes fill the
-// other buffer with the next chunk; one barrier per chunk.  Rows are padded to 65 doubles so the 36 sum lanes read different bank pairs; two buffers of 36 x 65
-// doubles are 37440 B, inside the 64 KB a kernel gets without asking.
+// order of g2o's active edges.  The sums are the ordered sum of ordered_sum.hpp: wave 1 is the 64 EDGE lanes, in a chunk of 64 consecutive edges each computes one
+// edge (its error, the Huber weight, the numeric Jacobian from 14 more error evaluations, the 28 + 7 + 1 contributions of sim3_opt.hpp's s3_edge_contrib); wave 0 is
+// the SUM wave: lane k < 36 carries the running sum of entry k.  Rows are padded to 65 doubles; two buffers of 36 x 65 doubles are 37440 B, inside the 64 KB a
+// kernel gets without asking.
 // The 15 transforms of a linearisation (the estimate and its 14 perturbations, each with its inverse) are the same for every edge: lanes 0..14 form one each into
 // LDS before the chunks start, and the edge lanes read them from there (a broadcast read).  A trial needs the estimate and its inverse only: lane 0.
 // The 7 x 7 part (LDLT, the Sim3 exponential, the lambda logic) is not broadcast: every lane computes it from the same 36 sums, which keeps the control flow of
@@ -19,6 +18,7 @@
 // them.  No atomics, no inline assembly.  removed[] is the item's row of the output and the kernel's working state; it is read and written by different lanes in
 // different phases, always with a barrier in between.
 #include "match.hpp"
+#include "ordered_sum.hpp"
 #include "host/sim3_opt.hpp"
 
 namespace sind {
@@ -34,35 +34,17 @@ struct Sim3OptWg {                                                   // the eval
     double (*buf)[SIM3OPT_ENTRIES][SO_ROW]; Sim3Q (*T)[SIM3OPT_TRANSFORMS]; double* total; int* cnt;   // LDS: [2], [2] (forward, inverse), [36], [2][SO_THREADS]
 
     __device__ void sums(const Sim3Q& est, bool full, double* S) {
-        const int nEdges = 2 * n, nChunks = (nEdges + SO_CHUNK - 1) / SO_CHUNK;
-        const int first = full ? 0 : 35;                             // not full: the chi2 row alone
         if (tid < (full ? SIM3OPT_TRANSFORMS : 1)) { Sim3Q a, b; s3_perturbed(est, tid, fixScale, a, b); T[0][tid] = a; T[1][tid] = b; }
         __syncthreads();
-        double run = 0.0;
-        for (int c = 0; c <= nChunks; c++) {
-            if (tid >= 64 && c < nChunks) {                          // edge lanes: chunk c into buffer c & 1
-                const int e = tid - 64, k = c * SO_CHUNK + e, i = k >> 1, side = k & 1;
-                if (k < nEdges) {
-                    double v[SIM3OPT_ENTRIES];
-                    const bool active = removed[i] == 0;             // optimizer.removeEdge(e12), removeEdge(e21)
-                    if (active) {
-                        const float4 X = side ? p1[i] : p2[i], P = side ? p2[i] : p1[i], U = ob[i];       // e12: the point of camera 2, obs1 and sigma of camera 1
-                        s3_edge_contrib(T[side], side ? K2 : K1, X.x, X.y, X.z, side ? U.z : U.x, side ? U.w : U.y, P.w, delta, full, v);
-                    }
-                    double (*B)[SO_ROW] = buf[c & 1];
-                    for (int r = first; r < SIM3OPT_ENTRIES; r++) B[r][e] = active ? v[r] : 0.0;          // x + 0 = x for every x these sums can hold (never -0)
-                }
-            }
-            if (tid >= first && tid < SIM3OPT_ENTRIES && c > 0) {    // sum lanes: chunk c - 1 from the other buffer
-                const int m = min(SO_CHUNK, nEdges - (c - 1) * SO_CHUNK);
-                const double* row = buf[(c - 1) & 1][tid];
-                for (int j = 0; j < m; j++) run = run + row[j];
-            }
-            __syncthreads();
-        }
-        if (tid >= first && tid < SIM3OPT_ENTRIES) total[tid] = run;
-        __syncthreads();
-        for (int k = 0; k < SIM3OPT_ENTRIES; k++) S[k] = k >= first ? total[k] : 0.0;
+        ordered_sums<SIM3OPT_ENTRIES, SO_CHUNK, SO_ROW, SO_THREADS - SO_CHUNK>(tid, 2 * n, full ? 0 : 35 /* not full: the chi2 row alone */, buf, total,
+            [&](int k, double* v) {
+                const int i = k >> 1, side = k & 1;
+                if (removed[i]) return false;                        // optimizer.removeEdge(e12), removeEdge(e21)
+                const float4 X = side ? p1[i] : p2[i], P = side ? p2[i] : p1[i], U = ob[i];               // e12: the point of camera 2, obs1 and sigma of camera 1
+                s3_edge_contrib(T[side], side ? K2 : K1, X.x, X.y, X.z, side ? U.z : U.x, side ? U.w : U.y, P.w, delta, full, v);
+                return true;
+            },
+            [](int) { return false; }, S);                           // every row is added: b += ...
         __syncthreads();                                             // the next call writes T[] before its first barrier: only after every lane has read total[] and T[]
     }
 
