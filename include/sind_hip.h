@@ -831,6 +831,49 @@ typedef struct sind_localba_item {
 int sind_match_local_ba(sind_match* m, const sind_localba_item* items, int B);
 int sindh_local_ba(const sind_localba_item* items, int B, const float* K5);   /* host twin (libsind_host.so too): K5 = fx fy cx cy bf */
 
+/* sind_match_essential_graph.  Replaces, for B pose graphs at once, the whole of
+ *   void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose &NonCorrectedSim3, const KeyFrameAndPose &CorrectedSim3,
+ *                                          const map<KeyFrame *, set<KeyFrame *> > &LoopConnections, const bool &bFixScale)
+ * from the optimizer's set-up on (src/Optimizer.cc:787-1043; LoopClosing::CorrectLoop, src/LoopClosing.cc:567): one VertexSim3Expmap per key frame (pLoopKF fixed), one
+ * EdgeSim3 with the identity as information per edge, OptimizationAlgorithmLevenberg with setUserLambdaInit(1e-16), optimize(20), the recovery of every key frame's
+ * SE3 pose (:999-1009) and the correction of every map point through its reference key frame (:1020-1040).  TWO launches on one stream with one host wait
+ * (csrc/match_essgraph.hip: k_ess_graph, one workgroup per item, then k_ess_points over the points of all items; csrc/host/essential_graph.hpp is one FP64 source for
+ * host and device and states the order of every sum).
+ * What stays with the caller: which edges exist (:853-983: the minFeat = 100 weights and the (cur, loop) exception, sInsertedEdges, parent, hasChild, sLoopEdges and
+ * the mnId comparisons; sindslam_amd/optimizer.py mirrors the collection) and, under the map mutex, SetPose, SetWorldPos and UpdateNormalAndDepth with the outputs.
+ * Inputs: the key frames in ascending mnId (kf_id), Tcw = GetPose(); has_corrected / corrected = the CorrectedSim3 entry of the key frame (qx qy qz qw tx ty tz s),
+ * has_noncorrected / noncorrected = its NonCorrectedSim3 entry; fixed_kf = the index of pLoopKF.  vScw[i] is the corrected entry if present, else Sim3(Rcw, tcw, 1.0).
+ * The edges in the order the reference adds them: edge_i is vertex 0 and edge_j vertex 1; edge_kind 0 = a LoopConnections edge, its measurement Sjw * Swi from vScw of
+ * both ends (:857-872); edge_kind 1 = a spanning-tree, loop or covisibility edge, both ends from the non-corrected Sim3 where one exists, else vScw (:889-979).  Several
+ * edges may join the same two key frames (LoopConnections holds both directions): their blocks add in edge order.  The map points that are not bad: x3Dw =
+ * GetWorldPos(), mp_ref = the index of the key frame of nIDr (mnCorrectedReference if mnCorrectedByKF == pCurKF->mnId, else the reference key frame).
+ * Outputs: Siw_out = the vertex estimates after optimize(20) (the input estimate of the fixed vertex and of a vertex without edges); Tiw_out =
+ * toCvSE3(q.toRotationMatrix(), t * (1. / s)); x3Dw_out = the float of Siw_out[ref].inverse().map(vScw[ref].map(P)).  The diagnostics may be NULL: n_iters =
+ * optimize's return (-1 where nothing was optimised), chi2 = activeChi2 after the last accepted step, lambda = _currentLambda at the end (-1 where nothing was
+ * optimised), n_active = the vertices with a Hessian index, solver_fail = the factorisations that failed.
+ * Valid: B = 0; n_edges = 0 (the empty graph: nothing is optimised, the outputs are the conversions alone); n_mp = 0; free vertices without edges.
+ * Unpinned: parity with a real g2o / Eigen build: the linear system (a natural-order envelope LDL^T here, SimplicialLDLT under AMD ordering there), W.lu().solve(t) of
+ * Sim3::log, std::log and acos (restated from fdlibm), the reference's iteration by pointer value; see the head of essential_graph.hpp.  Not offered: a stop flag,
+ * global bundle adjustment.
+ * Limits: 4096 key frames, 65536 edges, 2^20 points, 2^24 stored entries of the factor's envelope (sum over the free key frames with an edge, in ascending mnId with
+ * rank I, of 49 (I - first(I) + 1), first(I) the smallest rank among I and its neighbours), B <= max_batch: beyond them SIND_E_CAPACITY.  The workspace lives on the
+ * handle, grows between calls to the largest call seen and is freed with the handle.
+ * SIND_E_ARG: a NULL array with a non-zero count, a negative count, kf_id not strictly ascending, fixed_kf or an edge end or an mp_ref out of range, edge_i == edge_j,
+ * a kind outside 0..1, a pose, Sim3 or point that is not finite, a scale <= 0.  On an error nothing is launched and the outputs are untouched.
+ */
+typedef struct sind_essgraph_item {
+    int n_kf; const int64_t* kf_id; const float* Tcw;                  /* [n_kf] strictly ascending; [n_kf][16] GetPose() */
+    const uint8_t* has_corrected; const double* corrected;            /* [n_kf]; [n_kf][8] qx qy qz qw tx ty tz s (read where the flag is set) */
+    const uint8_t* has_noncorrected; const double* noncorrected;      /* [n_kf]; [n_kf][8] */
+    int fixed_kf;                                                      /* index of pLoopKF */
+    int n_edges; const int* edge_i; const int* edge_j; const uint8_t* edge_kind;   /* [n_edges] vertex 0, vertex 1, 0 LoopConnections / 1 normal */
+    int n_mp; const float* x3Dw; const int* mp_ref;                    /* [n_mp][3], [n_mp] index into 0..n_kf-1 */
+    double* Siw_out; float* Tiw_out; float* x3Dw_out;                  /* [n_kf][8], [n_kf][16], [n_mp][3] */
+    int* n_iters; double* chi2; double* lambda; int* n_active; int* solver_fail;   /* diagnostics, may be NULL: [1] each */
+} sind_essgraph_item;
+int sind_match_essential_graph(sind_match* m, const sind_essgraph_item* items, int B, int fix_scale);
+int sindh_essential_graph(const sind_essgraph_item* items, int B, int fix_scale);   /* host twin (libsind_host.so too) */
+
 /* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of
  *   generatePointCloud(imgRGB, imgDepth, imgDepthLast, imgDynaMask, imgDynaMaskLast, imgLabel, poseRelative, Twc)

@@ -10,6 +10,7 @@
 #include "host/pose_opt.hpp"
 #include "host/sim3_opt.hpp"
 #include "host/local_ba.hpp"
+#include "host/essential_graph.hpp"
 
 namespace {
 const int GRID_CELLS = 3072;                                       // Frame's 64 x 48 grid; grid_start has one entry more
@@ -158,6 +159,10 @@ struct sind_match {
     struct LocalBaSide {
         Staged<int> I; Staged<float> Fin, Fout; DevBuf<double> D; Staged<sind::LbaView> views; Staged<sind::LbaDiag> diag; std::vector<sind::LbaPlan> plan;
     } localba;
+    // sind_match_essential_graph (match_essgraph.hip): the same scheme, with the doubles that go up (the Sim3 maps) and those that come down (head)
+    struct EssSide {
+        Staged<int> I; Staged<float> Fin, Fout; Staged<double> Din, head; DevBuf<double> D; Staged<sind::EssView> views; std::vector<sind::EssPlan> plan;     // head: EssDiag and Siw_out of every item, one after the other
+    } ess;
     int reserve_bow() {
         const size_t B = maxB, nl = B * prm.capLast, nc = B * prm.capCur; int r = SIND_OK;
         (r = last.node.alloc(nl)) || (r = last.xy.alloc(nl * 2)) || (r = last.uRight.alloc(nl)) || (r = cur.node.alloc(nc)) || (r = choice.alloc(nl)) || (r = bow.pose.alloc(B)) ||
@@ -796,6 +801,46 @@ int sind_match_local_ba(sind_match* m, const sind_localba_item* items, int B) {
     SIND_TRY(w.Fout.down(oFo[B], s)); SIND_TRY(w.diag.down(B, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (int b = 0; b < B; b++) sind::lba_store(items[b], w.plan[b], &w.I.h[oI[b] + w.plan[b].oErase], &w.Fout.h[oFo[b]], w.diag.h[b]);
+    return SIND_OK;
+}
+
+int sind_match_essential_graph(sind_match* m, const sind_essgraph_item* items, int B, int fix_scale) {
+    const char* who = "sind_match_essential_graph: item";
+    SIND_TRY(solver_prologue("sind_match_essential_graph", m, items, B));
+    for (int b = 0; b < B; b++) if (const int bad = sind::ess_check(items[b])) { sind_set_error("%s %d: %s", who, b, sind::ess_check_text[bad]); return SIND_E_ARG; }
+    if (!B) return SIND_OK;
+    sind_match::EssSide& w = m->ess;
+    w.plan.resize((size_t)m->maxB);
+    std::vector<size_t> oI((size_t)B + 1, 0), oFi((size_t)B + 1, 0), oFo((size_t)B + 1, 0), oDi((size_t)B + 1, 0), oDo((size_t)B + 1, 0), oD((size_t)B + 1, 0);
+    int maxMp = 0;
+    for (int b = 0; b < B; b++) {
+        sind::EssPlan& pl = w.plan[b];
+        if (sind::ess_plan(items[b], pl)) {
+            sind_set_error("%s %d is beyond a limit: %d key frames, %d edges, %d points, %d entries of the factor's envelope", who, b, ESS_MAX_KF, ESS_MAX_EDGES, ESS_MAX_MP, ESS_MAX_ENV);
+            return SIND_E_CAPACITY;
+        }
+        oI[b + 1] = oI[b] + pl.nI; oFi[b + 1] = oFi[b] + sind::ess_floats_in(pl); oFo[b + 1] = oFo[b] + sind::ess_floats_out(pl); oDi[b + 1] = oDi[b] + sind::ess_doubles_in(pl);
+        oDo[b + 1] = oDo[b] + sind::ess_doubles_out(pl); oD[b + 1] = oD[b] + pl.nD;
+        maxMp = std::max(maxMp, pl.nMp);
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    SIND_TRY(w.I.alloc(oI[B] + 1)); SIND_TRY(w.Fin.alloc(oFi[B] + 1)); SIND_TRY(w.Fout.alloc(oFo[B] + 1)); SIND_TRY(w.Din.alloc(oDi[B] + 1)); SIND_TRY(w.D.alloc(oD[B] + 1));   // grown here, between launches
+    SIND_TRY(w.views.alloc((size_t)m->maxB));
+    SIND_TRY(w.head.alloc(oDo[B] + 1));
+    for (int b = 0; b < B; b++) {
+        const sind::EssPlan& pl = w.plan[b];
+        cpy(&w.I.h[oI[b]], pl.I.data(), pl.nI * sizeof(int));
+        sind::ess_fill(items[b], &w.Fin.h[oFi[b]], &w.Din.h[oDi[b]]);
+        sind::ess_bind(pl, fix_scale, w.I.d.p + oI[b], w.Fin.d.p + oFi[b], w.Din.d.p + oDi[b], w.Fout.d.p + oFo[b], w.D.p + oD[b], w.views.h[b]);
+        w.views.h[b].diag = (sind::EssDiag*)(w.head.d.p + oDo[b]); w.views.h[b].SiwOut = w.head.d.p + oDo[b] + 8;                           // what comes down lies together
+    }
+    hipStream_t s = m->stream;
+    SIND_TRY(w.I.up(oI[B], s)); SIND_TRY(w.Fin.up(oFi[B], s)); SIND_TRY(w.Din.up(oDi[B], s)); SIND_TRY(w.views.up(B, s));
+    SIND_TRY(sind::launch_essential_graph(w.views.d.p, B, maxMp, s));
+    SIND_TRY(w.head.down(oDo[B], s));
+    SIND_TRY(w.Fout.down(oFo[B], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) sind::ess_store(items[b], w.plan[b], &w.Fout.h[oFo[b]], &w.head.h[oDo[b]]);
     return SIND_OK;
 }
 

@@ -128,13 +128,14 @@ template <int N> struct DenseSystem {
 //   void   pop()                the estimates back from the stacks (the errors in the edges stay those of the trial)
 // On the device every lane runs this with the same values, so the flow is uniform over the workgroup and every barrier inside an operation is reached by all lanes.
 // Always inlined: each optimizer calls it from one place, and its phases stay in the caller's one function as they were when each optimizer had the loop written out.
-template <class Pr> SIND_HD inline __attribute__((always_inline)) int levenberg_optimize(Pr& pr, int iterations, double& chi2, double& lambdaOut) {
+// userLambdaInit: setUserLambdaInit; computeLambdaInit (:166-180) returns it when it is > 0 and never looks at the diagonal then.  The three optimizers above leave it 0
+template <class Pr> SIND_HD inline __attribute__((always_inline)) int levenberg_optimize(Pr& pr, int iterations, double& chi2, double& lambdaOut, double userLambdaInit = 0.0) {
     double lambda = -1.0, ni = 2.0, currentChi = 0.0;                // _currentLambda, _ni
     int cj = 0, nBadLM = 0; bool ok = true;
     for (int i = 0; i < iterations && ok; i++) {                     // sparse_optimizer.cpp:376-414
         currentChi = pr.linearize();
         double tempChi = currentChi; const double iniChi = currentChi;
-        if (i == 0) { lambda = 1e-5 * pr.max_diagonal(); ni = 2.0; nBadLM = 0; }      // computeLambdaInit (:166-180), _tau = 1e-5
+        if (i == 0) { lambda = (userLambdaInit > 0) ? userLambdaInit : 1e-5 * pr.max_diagonal(); ni = 2.0; nBadLM = 0; }      // computeLambdaInit (:166-180), _tau = 1e-5
         double rho = 0.0; int qmax = 0;
         do {
             pr.push();

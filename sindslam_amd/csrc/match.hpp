@@ -3,6 +3,7 @@
 #pragma once
 #include "common.hpp"
 #include "host/local_ba.hpp"
+#include "host/essential_graph.hpp"
 
 namespace sind {
 
@@ -122,6 +123,13 @@ int launch_sim3_optimize(const Sim3OptParams& p, const Sim3OptArrays& a, int B, 
 // Optimizer::LocalBundleAdjustment, whole, one workgroup per item (match_localba.hip, host/local_ba.hpp).  views [B]: device pointers throughout
 #define LBA_THREADS 512                                              // profiles/match_local_ba.txt: the compiler's resource report and the choice
 int launch_local_ba(const LbaView* views, int B, hipStream_t s);
+
+// Optimizer::OptimizeEssentialGraph, whole: k_ess_graph, one workgroup per item, then k_ess_points over the points of all items on the same stream (match_essgraph.hip,
+// host/essential_graph.hpp).  views [B]: device pointers throughout; maxMp: the largest n_mp of the call
+#define ESS_THREADS 512                                              // profiles/match_essential_graph.txt: the compiler's resource report and the choice
+#define ESS_PT_THREADS 256
+#define ESS_PT_BLOCKS 64                                             // per item: a full grid covers 16384 points in one pass, the lanes stride beyond it
+int launch_essential_graph(const EssView* views, int B, int maxMp, hipStream_t s);
 
 // Vocabulary-guided searches (match_bow.hip): SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation.  Side A is the one whose entries act
 // (the key frame / pKF1, capacity capLast), side B the one searched (the frame / pKF2, capacity capCur).

@@ -113,6 +113,13 @@ class _LocalBaItem(C.Structure):
                 ("stage_chi2", C.c_void_p), ("stage_lambda", C.c_void_p)]
 
 
+class _EssGraphItem(C.Structure):
+    _fields_ = [("n_kf", C.c_int), ("kf_id", C.c_void_p), ("Tcw", C.c_void_p), ("has_corrected", C.c_void_p), ("corrected", C.c_void_p), ("has_noncorrected", C.c_void_p),
+                ("noncorrected", C.c_void_p), ("fixed_kf", C.c_int), ("n_edges", C.c_int), ("edge_i", C.c_void_p), ("edge_j", C.c_void_p), ("edge_kind", C.c_void_p),
+                ("n_mp", C.c_int), ("x3Dw", C.c_void_p), ("mp_ref", C.c_void_p), ("Siw_out", C.c_void_p), ("Tiw_out", C.c_void_p), ("x3Dw_out", C.c_void_p),
+                ("n_iters", C.c_void_p), ("chi2", C.c_void_p), ("lambda_", C.c_void_p), ("n_active", C.c_void_p), ("solver_fail", C.c_void_p)]
+
+
 _f32 = lambda a: np.ascontiguousarray(a, np.float32)
 _u8 = lambda a: np.ascontiguousarray(a, np.uint8)
 _i32 = lambda a: np.ascontiguousarray(a, np.int32)
@@ -211,6 +218,29 @@ def localba_result(a):
                 **{k: a[k] for k in ("stage_iters", "stage_chi2", "stage_lambda")})
 
 
+def essgraph_items(items):
+    """the sind_essgraph_item array of ORBmatcher.OptimizeEssentialGraph's items, and the arrays it points to (which live as long as the caller keeps them)"""
+    arr = (_EssGraphItem * len(items))(); keep = []
+    for q, it in zip(arr, items):
+        n_kf = len(it["kf_id"])
+        a = dict(kf_id=np.ascontiguousarray(it["kf_id"], np.int64), Tcw=_f32(it["Tcw"]).reshape(n_kf, 16).copy(), has_corrected=_u8(it["has_corrected"]),
+                 corrected=np.ascontiguousarray(it["corrected"], np.float64).reshape(n_kf, 8), has_noncorrected=_u8(it["has_noncorrected"]),
+                 noncorrected=np.ascontiguousarray(it["noncorrected"], np.float64).reshape(n_kf, 8), edge_i=_i32(it["edge_i"]), edge_j=_i32(it["edge_j"]), edge_kind=_u8(it["edge_kind"]),
+                 x3Dw=_f32(it["x3Dw"]).reshape(-1, 3).copy(), mp_ref=_i32(it["mp_ref"]))
+        a.update(Siw_out=np.zeros((n_kf, 8), np.float64), Tiw_out=a["Tcw"].copy(), x3Dw_out=a["x3Dw"].copy(), n_iters=np.zeros(1, np.int32), chi2=np.zeros(1, np.float64),
+                 lambda_=np.zeros(1, np.float64), n_active=np.zeros(1, np.int32), solver_fail=np.zeros(1, np.int32))
+        for key, v in a.items():
+            setattr(q, key, v.ctypes.data if v.size else None)
+        q.n_kf = n_kf; q.n_edges = len(a["edge_i"]); q.n_mp = len(a["mp_ref"]); q.fixed_kf = int(it["fixed_kf"])
+        keep.append(a)
+    return arr, keep
+
+
+def essgraph_result(a):
+    return dict(Siw=a["Siw_out"], Tiw=a["Tiw_out"].reshape(-1, 4, 4), x3Dw=a["x3Dw_out"], n_iters=int(a["n_iters"][0]), chi2=np.float64(a["chi2"][0]), lambda_=np.float64(a["lambda_"][0]),
+                n_active=int(a["n_active"][0]), solver_fail=int(a["solver_fail"][0]))
+
+
 class ORBmatcher:
     """ORBmatcher(nnratio, checkOri) of the reference.  Provided: SearchByProjection(CurrentFrame, LastFrame, th, bMono) (TrackWithMotionModel),
     SearchLocalPoints = Frame::isInFrustum over the local map + SearchByProjection(F, vpMapPoints, th) (TrackLocalMap), and SearchByProjectionKF =
@@ -222,7 +252,8 @@ class ORBmatcher:
     Between SearchByBoW and SearchByProjectionKF in Tracking::Relocalization: the PnPsolver (src/PnPsolver.cc; PnPRansac, pnp_solvers, sindslam_amd/pnp.py).
     After every search of the tracking thread: Optimizer::PoseOptimization (src/Optimizer.cc:239-451; PoseOptimization, sindslam_amd/optimizer.py).
     After SearchBySim3 in LoopClosing::ComputeSim3: Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241; OptimizeSim3, sindslam_amd/optimizer.py).
-    After SearchInNeighbors in LocalMapping::Run: Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778; LocalBundleAdjustment, sindslam_amd/optimizer.py)."""
+    After SearchInNeighbors in LocalMapping::Run: Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778; LocalBundleAdjustment, sindslam_amd/optimizer.py).
+    After the loop fusion in LoopClosing::CorrectLoop: Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044; OptimizeEssentialGraph, sindslam_amd/optimizer.py)."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
 
     def __init__(self, fx, fy, cx, cy, bf, bounds, scale_factors, nnratio=0.6, checkOri=True, cap=4096, max_batch=1, device=0, cap_points=0):
@@ -463,6 +494,16 @@ class ORBmatcher:
         arr, keep = localba_items(items)
         check(lib().sind_match_local_ba(self._h, arr, len(items)), "sind_match_local_ba")
         return [localba_result(a) for a in keep]
+
+    def OptimizeEssentialGraph(self, items, fix_scale=True):
+        """sind_match_essential_graph: Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:787-1043) of every item: the pose graph in one launch, the points in a second one on
+        the same stream.  items: list of dicts: kf_id i64 [n_kf] strictly ascending, Tcw [n_kf, 4, 4], has_corrected u8 [n_kf], corrected f64 [n_kf, 8] (qx qy qz qw tx ty tz s),
+        has_noncorrected, noncorrected alike, fixed_kf (index of pLoopKF); edge_i, edge_j i32 [n_edges] (vertex 0, vertex 1), edge_kind u8 (0 LoopConnections, 1 normal) in the
+        order the edges are added; x3Dw [n_mp, 3], mp_ref i32 [n_mp] (index of the key frame of nIDr).  fix_scale as in the reference (mbFixScale: true for RGB-D).
+        -> list of dicts: Siw f64 [n_kf, 8], Tiw f32 [n_kf, 4, 4] (what SetPose gets), x3Dw f32 [n_mp, 3] (what SetWorldPos gets), n_iters, chi2, lambda_, n_active, solver_fail."""
+        arr, keep = essgraph_items(items)
+        check(lib().sind_match_essential_graph(self._h, arr, len(items), int(bool(fix_scale))), "sind_match_essential_graph")
+        return [essgraph_result(a) for a in keep]
 
     def last_rounds(self):
         return lib().sind_match_last_rounds(self._h)

@@ -3,7 +3,9 @@ one call of the tracking thread, over sind_match_pose_optimize, and the chain of
 callback of pnp.relocalization_pnp.  Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241), the one call of LoopClosing::ComputeSim3, over sind_match_sim3_optimize, and the
 rest of ComputeSim3 built on it (src/LoopClosing.cc:310-398): compute_sim3_accept, the `accept` callback of sim3.compute_sim3, loop_scw and loop_accept.
 Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778), the one call of LocalMapping::Run, over sind_match_local_ba: LocalBundleAdjustment collects the graph
-(:455-504) from a map of plain dicts, apply_local_ba writes the result back (:746-777).
+(:455-504) from a map of plain dicts, apply_local_ba writes the result back (:746-777).  Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044), the one
+call of LoopClosing::CorrectLoop, over sind_match_essential_graph: essential_graph_item collects the pose graph (:797-983), apply_essential_graph writes poses and
+points back, correct_loop is CorrectLoop around them (src/LoopClosing.cc:402-584).
 
 A frame is a dict of per-keypoint arrays: un_xy [N, 2] (mvKeysUn[i].pt), u_right [N] (mvuRight), inv_sigma2 [N] (mvInvLevelSigma2[mvKeysUn[i].octave]), mp i64 [N] (the id of
 mvpMapPoints[i], -1 for NULL), x3Dw [N, 3] (GetWorldPos() of that map point; rows without one are not read), Tcw [4, 4] (mTcw), and optionally outlier [N] (mvbOutlier).
@@ -318,3 +320,202 @@ def apply_local_ba(keyframes, mappoints, result):
         keyframes[k]["Tcw"] = np.array(T, np.float32).reshape(4, 4)
     for m, X in result["points"].items():
         mappoints[m]["x3Dw"] = np.array(X, np.float32)
+
+
+# ---------------------------------------------------------------- LoopClosing::CorrectLoop and Optimizer::OptimizeEssentialGraph
+def _D(v):
+    return [np.float64(x) for x in v]
+
+
+def _s3(q, t, s):
+    return (_D(q), _D(t), np.float64(s))
+
+
+def _s3_from_pose(T):
+    """g2o::Sim3(Rcw, tcw, 1.0) of a float pose: the quaternion of Eigen, not normalised (csrc/host/sim3_opt.hpp: s3_from_input)"""
+    T = np.asarray(T, np.float32).reshape(4, 4)
+    return (_quat_from_matrix([[np.float64(T[i, j]) for j in range(3)] for i in range(3)]), [np.float64(T[i, 3]) for i in range(3)], np.float64(1.0))
+
+
+def _s3_mul(A, B):
+    a, b = A[0], B[0]
+    q = [a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1], a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2], a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0],
+         a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2]]
+    rt = _quat_rotate(a, B[1])
+    return (q, [A[2] * rt[i] + A[1][i] for i in range(3)], A[2] * B[2])
+
+
+def _s3_inverse(S):
+    q = [-S[0][0], -S[0][1], -S[0][2], S[0][3]]
+    f = np.float64(-1.0) / S[2]
+    return (q, _quat_rotate(q, [f * S[1][0], f * S[1][1], f * S[1][2]]), np.float64(1.0) / S[2])
+
+
+def _s3_map(S, X):
+    r = _quat_rotate(S[0], X)
+    return [S[2] * r[i] + S[1][i] for i in range(3)]
+
+
+def _s3_to_se3(S):
+    """Converter::toCvSE3(q.toRotationMatrix(), t * (1. / s)) -> f32 [4, 4]"""
+    D = np.float64
+    q = S[0]
+    tx, ty, tz = D(2) * q[0], D(2) * q[1], D(2) * q[2]
+    twx, twy, twz = tx * q[3], ty * q[3], tz * q[3]
+    txx, txy, txz, tyy, tyz, tzz = tx * q[0], ty * q[0], tz * q[0], ty * q[1], tz * q[1], tz * q[2]
+    R = [[D(1) - (tyy + tzz), txy - twz, txz + twy], [txy + twz, D(1) - (txx + tzz), tyz - twx], [txz - twy, tyz + twx, D(1) - (txx + tyy)]]
+    f = D(1.0) / S[2]
+    T = np.eye(4, dtype=np.float32)
+    for i in range(3):
+        for j in range(3):
+            T[i, j] = np.float32(R[i][j])
+        T[i, 3] = np.float32(S[1][i] * f)
+    return T
+
+
+def _s3_row(S):
+    return np.array([*S[0], *S[1], S[2]], np.float64)
+
+
+def update_connections(k, keyframes, mappoints):
+    """KeyFrame::UpdateConnections (src/KeyFrame.cc) on the dicts: weights = the shared good map points with every other key frame; covisible = those with at least 15
+    (or the best one), most first; the other side gets AddConnection (its weight, and its list re-sorted over all of its weights).  Ties are broken by ascending id (the
+    reference: by pointer).  The first-connection parent is the map builder's: key frames come with `parent`."""
+    kf = keyframes[k]; counter = {}
+    for m in np.asarray(kf["mp"]).tolist():
+        if m < 0 or mappoints[m].get("bad"):
+            continue
+        for q in mappoints[m]["obs"]:
+            if q != k:
+                counter[q] = counter.get(q, 0) + 1
+    if not counter:
+        return
+    best = max(sorted(counter), key=lambda q: counter[q])
+    near = [q for q in counter if counter[q] >= 15] or [best]
+    for q in near:
+        o = keyframes[q]; o.setdefault("weights", {})[k] = counter[q]
+        o["covisible"] = sorted(o["weights"], key=lambda r: (-o["weights"][r], r))
+    kf["weights"] = dict(counter)
+    kf["covisible"] = sorted(near, key=lambda q: (-counter[q], q))
+
+
+def _replace(keyframes, mappoints, old, new):
+    """MapPoint::Replace (src/MapPoint.cc:163-200): the observations of `old` move to `new`, `old` goes bad"""
+    if old == new:
+        return
+    o, n = mappoints[old], mappoints[new]
+    obs = dict(o["obs"]); o["obs"] = {}; o["bad"] = True
+    for q in sorted(obs):
+        if q not in n["obs"]:
+            keyframes[q]["mp"][obs[q]] = new; n["obs"][q] = obs[q]
+        else:
+            keyframes[q]["mp"][obs[q]] = -1
+
+
+def essential_graph_item(keyframes, mappoints, loop_kf, cur_kf, non_corrected, corrected, loop_connections, min_feat=100):
+    """The graph collection of Optimizer::OptimizeEssentialGraph (:797-983, :1020-1029) over plain dicts.  keyframes {id: dict(Tcw [4, 4], bad, parent (id or None), children
+    (set of ids), loop_edges (set of ids), covisible (ids, most shared points first), weights {id: shared points})}; mappoints {id: dict(x3Dw [3], bad, ref_kf,
+    corrected_by_kf, corrected_reference)}; non_corrected / corrected {kf id: Sim3 as (q [4], t [3], s)}; loop_connections {kf id: set of ids}.
+    The reference walks GetAllKeyFrames, the LoopConnections map, its sets and GetLoopEdges in pointer order: here all four in ascending id.  GetCovisiblesByWeight(100)
+    stays in weight order.  Bad key frames and bad points are left out; an edge to a key frame that is not in the item is left out with it.
+    -> (item: the dict ORBmatcher.OptimizeEssentialGraph takes; kf ids; mp ids)"""
+    kfs = sorted(k for k in keyframes if not keyframes[k].get("bad"))
+    row = {k: i for i, k in enumerate(kfs)}
+    hasC = np.zeros(len(kfs), np.uint8); hasN = np.zeros(len(kfs), np.uint8); C8 = np.zeros((len(kfs), 8)); N8 = np.zeros((len(kfs), 8))
+    for k, i in row.items():
+        if k in corrected:
+            hasC[i] = 1; C8[i] = _s3_row(corrected[k])
+        if k in non_corrected:
+            hasN[i] = 1; N8[i] = _s3_row(non_corrected[k])
+    ei, ej, kind, inserted = [], [], [], set()
+    for i in sorted(loop_connections):                                  # :857-883
+        for j in sorted(loop_connections[i]):
+            if (i != cur_kf or j != loop_kf) and keyframes[i].get("weights", {}).get(j, 0) < min_feat:
+                continue
+            if i in row and j in row:
+                ei.append(row[i]); ej.append(row[j]); kind.append(0)
+            inserted.add((min(i, j), max(i, j)))
+    for i in kfs:                                                       # :886-979
+        kf = keyframes[i]; parent = kf.get("parent")
+        if parent is not None and parent in row:
+            ei.append(row[i]); ej.append(row[parent]); kind.append(1)
+        loops = set(kf.get("loop_edges", ()))
+        for l in sorted(loops):
+            if l < i and l in row:
+                ei.append(row[i]); ej.append(row[l]); kind.append(1)
+        for n in kf.get("covisible", ()):
+            if kf.get("weights", {}).get(n, 0) < min_feat:
+                continue                                                # GetCovisiblesByWeight(minFeat)
+            if n != parent and n not in kf.get("children", ()) and n not in loops and n in row and n < i:
+                if (min(i, n), max(i, n)) in inserted:
+                    continue
+                ei.append(row[i]); ej.append(row[n]); kind.append(1)
+    mps = sorted(m for m in mappoints if not mappoints[m].get("bad"))
+    ref = [row[mappoints[m]["corrected_reference"] if mappoints[m].get("corrected_by_kf", -1) == cur_kf else mappoints[m]["ref_kf"]] for m in mps]
+    item = dict(kf_id=np.array(kfs, np.int64), Tcw=np.array([np.asarray(keyframes[k]["Tcw"], np.float32).reshape(4, 4) for k in kfs], np.float32).reshape(len(kfs), 4, 4),
+                has_corrected=hasC, corrected=C8, has_noncorrected=hasN, noncorrected=N8, fixed_kf=row[loop_kf], edge_i=np.array(ei, np.int32), edge_j=np.array(ej, np.int32),
+                edge_kind=np.array(kind, np.uint8), x3Dw=np.array([np.asarray(mappoints[m]["x3Dw"], np.float32) for m in mps], np.float32).reshape(len(mps), 3), mp_ref=np.array(ref, np.int32))
+    return item, kfs, mps
+
+
+def apply_essential_graph(keyframes, mappoints, kfs, mps, result):
+    """:999-1040 on the dicts: SetPose(Tiw) of every key frame and SetWorldPos of every point.  UpdateNormalAndDepth is not in the library: the caller's step after this one."""
+    for i, k in enumerate(kfs):
+        keyframes[k]["Tcw"] = np.array(result["Tiw"][i], np.float32).reshape(4, 4)
+    for j, m in enumerate(mps):
+        mappoints[m]["x3Dw"] = np.array(result["x3Dw"][j], np.float32)
+
+
+def correct_loop(matcher, keyframes, mappoints, cur_kf, loop_kf, g2oScw, matched_points, fix_scale=True, fuse=None, trace=None):
+    """LoopClosing::CorrectLoop (src/LoopClosing.cc:402-584) on the dicts, from UpdateConnections of the current key frame to the loop edges; stopping local mapping, the
+    running global BA and the new one are the caller's.  g2oScw = mg2oScw as (q, t, s) or the dict loop_scw returns; matched_points i64 [N] = mvpCurrentMatchedPoints as
+    map-point ids (-1 for NULL).  matcher: an ORBmatcher or anything with OptimizeEssentialGraph(items, fix_scale).  fuse(corrected) is SearchAndFuse (:586-621): called
+    with CorrectedSim3 after the loop fusion, it returns a list of (point to replace, loop map point) from ORBmatcher.FuseSim3 on the caller's key frames, which are
+    replaced here; None: nothing to fuse.  The maps are walked in ascending id (the reference: by pointer).  trace: a dict that gets corrected, non_corrected,
+    loop_connections, item, kfs, mps and result.  The map IS modified."""
+    Scw = _s3(g2oScw["q"], g2oScw["t"], g2oScw["s"]) if isinstance(g2oScw, dict) else _s3(*g2oScw)
+    with np.errstate(all="ignore"):
+        update_connections(cur_kf, keyframes, mappoints)                # :429
+        connected = list(keyframes[cur_kf]["covisible"]) + [cur_kf]     # :432-433
+        corrected, non_corrected = {cur_kf: Scw}, {}
+        Tcw = np.asarray(keyframes[cur_kf]["Tcw"], np.float32).reshape(4, 4)
+        Twc = np.eye(4, dtype=np.float32); Twc[:3, :3] = Tcw[:3, :3].T; Twc[:3, 3] = -(Tcw[:3, :3].T @ Tcw[:3, 3])      # GetPoseInverse(), in float as SetPose forms it
+        for i in connected:                                             # :445-470
+            Tiw = np.asarray(keyframes[i]["Tcw"], np.float32).reshape(4, 4)
+            if i != cur_kf:
+                corrected[i] = _s3_mul(_s3_from_pose(Tiw @ Twc), Scw)   # g2oSic * mg2oScw, Tic = Tiw * Twc in float
+            non_corrected[i] = _s3_from_pose(Tiw)
+        for i in sorted(corrected):                                     # :473-517
+            Swi = _s3_inverse(corrected[i]); Siw = non_corrected[i]
+            for m in np.asarray(keyframes[i]["mp"]).tolist():
+                if m < 0 or mappoints[m].get("bad") or mappoints[m].get("corrected_by_kf", -1) == cur_kf:
+                    continue
+                P = _s3_map(Swi, _s3_map(Siw, _D(np.asarray(mappoints[m]["x3Dw"], np.float32))))
+                mappoints[m]["x3Dw"] = np.array(P, np.float64).astype(np.float32)
+                mappoints[m]["corrected_by_kf"] = cur_kf; mappoints[m]["corrected_reference"] = i
+            keyframes[i]["Tcw"] = _s3_to_se3(corrected[i])
+            update_connections(i, keyframes, mappoints)
+        cur = keyframes[cur_kf]
+        for slot, lm in enumerate(np.asarray(matched_points).tolist()):   # :521-537
+            if lm < 0:
+                continue
+            cm = int(cur["mp"][slot])
+            if cm >= 0:
+                _replace(keyframes, mappoints, cm, lm)
+            else:
+                cur["mp"][slot] = lm; mappoints[lm]["obs"][cur_kf] = slot
+        if fuse is not None:                                            # SearchAndFuse(CorrectedSim3)
+            for old, new in fuse(corrected):
+                _replace(keyframes, mappoints, old, new)
+        loop_connections = {}
+        for i in connected:                                             # :549-566
+            previous = list(keyframes[i].get("covisible", ()))
+            update_connections(i, keyframes, mappoints)
+            loop_connections[i] = set(keyframes[i].get("weights", {})) - set(previous) - set(connected)
+    item, kfs, mps = essential_graph_item(keyframes, mappoints, loop_kf, cur_kf, non_corrected, corrected, loop_connections)
+    result = matcher.OptimizeEssentialGraph([item], fix_scale)[0]
+    apply_essential_graph(keyframes, mappoints, kfs, mps, result)
+    keyframes[loop_kf].setdefault("loop_edges", set()).add(cur_kf); keyframes[cur_kf].setdefault("loop_edges", set()).add(loop_kf)   # :575-576
+    if trace is not None:
+        trace.update(corrected=corrected, non_corrected=non_corrected, loop_connections=loop_connections, item=item, kfs=kfs, mps=mps, result=result)
+    return result
