@@ -1,6 +1,6 @@
 // Host twin of sind_match_essential_graph (reference src/Optimizer.cc:781-1044): essential_graph.hpp with the plain sequential executor, and what the two entry
 // points share: the argument check, the digest of an item into the lists the phases walk (EssPlan) and the copy of one item's results.  Compiled into libsind_hip.so
-// (capi_match.cpp calls the shared part) and into libsind_host.so.
+// (capi_match_opt.cpp calls the shared part) and into libsind_host.so.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -85,19 +85,15 @@ int ess_plan(const ::sind_essgraph_item& q, EssPlan& pl) {
     pl.oPairStart = add(pairStart.data(), (size_t)nPair + 1); pl.oPairLo = add(pairLo.data(), nPair); pl.oPairHi = add(pairHi.data(), nPair); pl.oPairE = add(pairE.data(), pairE.size());
     pl.oFirst = add(first.data(), nAct); pl.oRowOff = add(rowOff.data(), nAct); pl.oBlkLast = add(blkLast.data(), nAct);
     pl.oIsc = room(ESS_IS_N);
-    pl.nI = pl.I.size();
     const size_t n = 7 * (size_t)nAct;
-    pl.nD = 8 + 8 * (size_t)nKf + ESS_SC_N + 4 * 8 * (size_t)nKf + 8 * (size_t)nE + 2 * 8 * SIM3OPT_TRANSFORMS * (size_t)nKf + (size_t)(ESS_NERR * 7 + 98 + ESS_C + 1) * nE +
-            ESS_V * (size_t)nAct + 49 * (size_t)nPair + nEnv + 4 * n;
+    pl.z.ints = pl.I.size(); pl.z.floatsIn = pl.z.floatsOut = 16 * (size_t)nKf + 3 * (size_t)nMp; pl.z.doublesIn = 16 * (size_t)nKf; pl.z.head = 8 + 8 * (size_t)nKf;
+    pl.z.work = 8 + 8 * (size_t)nKf + ESS_SC_N + 4 * 8 * (size_t)nKf + 8 * (size_t)nE + 2 * 8 * SIM3OPT_TRANSFORMS * (size_t)nKf + (size_t)(ESS_NERR * 7 + 98 + ESS_C + 1) * nE +
+                ESS_V * (size_t)nAct + 49 * (size_t)nPair + nEnv + 4 * n;
     return SIND_OK;
 }
 
-size_t ess_doubles_in(const EssPlan& pl) { return 16 * (size_t)pl.nKf; }
-size_t ess_floats_in(const EssPlan& pl) { return 16 * (size_t)pl.nKf + 3 * (size_t)pl.nMp; }
-size_t ess_floats_out(const EssPlan& pl) { return 16 * (size_t)pl.nKf + 3 * (size_t)pl.nMp; }
-size_t ess_doubles_out(const EssPlan& pl) { return 8 + 8 * (size_t)pl.nKf; }
-
-void ess_fill(const ::sind_essgraph_item& q, float* F, double* Din) {
+void ess_fill(const ::sind_essgraph_item& q, const ItemPtrs& p) {
+    float* F = p.Fin; double* Din = p.Din;
     if (q.n_kf) std::memcpy(F, q.Tcw, sizeof(float) * 16 * q.n_kf);
     if (q.n_mp) std::memcpy(F + 16 * (size_t)q.n_kf, q.x3Dw, sizeof(float) * 3 * q.n_mp);
     for (int i = 0; i < q.n_kf; i++) for (int k = 0; k < 8; k++) {                         // an entry that is not there is not read by the caller's leave, nor by the phases
@@ -106,7 +102,8 @@ void ess_fill(const ::sind_essgraph_item& q, float* F, double* Din) {
     }
 }
 
-void ess_bind(const EssPlan& pl, int fixScale, int* I, const float* Fin, const double* Din, float* Fout, double* D, EssView& v) {
+void ess_bind(const EssPlan& pl, int fixScale, const ItemPtrs& p, EssView& v) {
+    int* I = p.I; const float* Fin = p.Fin; const double* Din = p.Din; float* Fout = p.Fout;
     const size_t nKf = pl.nKf, nE = pl.nE, nAct = pl.nAct, n = 7 * nAct;
     v.nKf = pl.nKf; v.nE = pl.nE; v.nMp = pl.nMp; v.nAct = pl.nAct; v.nPair = pl.nPair; v.n = (int)n; v.fixScale = fixScale ? 1 : 0;
     v.Tcw = Fin; v.x3Dw = Fin + 16 * nKf; v.corr = Din; v.ncorr = Din + 8 * nKf;
@@ -114,8 +111,8 @@ void ess_bind(const EssPlan& pl, int fixScale, int* I, const float* Fin, const d
     v.vEdgeStart = I + pl.oVEdgeStart; v.vEdge = I + pl.oVEdge; v.pairStart = I + pl.oPairStart; v.pairLo = I + pl.oPairLo; v.pairHi = I + pl.oPairHi; v.pairE = I + pl.oPairE;
     v.first = I + pl.oFirst; v.rowOff = I + pl.oRowOff; v.blkLast = I + pl.oBlkLast; v.isc = I + pl.oIsc;
     static_assert(sizeof(EssDiag) <= 8 * sizeof(double) && sizeof(Sim3Q) == 8 * sizeof(double), "the layout of the working state");
-    double* d = D;
-    v.diag = (EssDiag*)d; d += 8; v.SiwOut = d; d += 8 * nKf; v.sc = d; d += ESS_SC_N;
+    double* d = p.D + 8 + 8 * nKf;                                   // the room of the head in the working state
+    v.diag = (EssDiag*)p.head; v.SiwOut = p.head + 8; v.sc = d; d += ESS_SC_N;
     v.vScw = (Sim3Q*)d; d += 8 * nKf; v.est = (Sim3Q*)d; d += 8 * nKf; v.bak = (Sim3Q*)d; d += 8 * nKf; v.Swc = (Sim3Q*)d; d += 8 * nKf; v.meas = (Sim3Q*)d; d += 8 * nE;
     v.T = (Sim3Q*)d; d += 8 * SIM3OPT_TRANSFORMS * nKf; v.Ti = (Sim3Q*)d; d += 8 * SIM3OPT_TRANSFORMS * nKf;
     v.E = d; d += ESS_NERR * 7 * nE; v.J = d; d += 98 * nE; v.C = d; d += ESS_C * nE; v.chiE = d; d += nE;
@@ -123,7 +120,8 @@ void ess_bind(const EssPlan& pl, int fixScale, int* I, const float* Fin, const d
     v.TiwOut = Fout; v.XOut = Fout + 16 * nKf;
 }
 
-void ess_store(const ::sind_essgraph_item& q, const EssPlan& pl, const float* Fout, const double* Dout) {
+void ess_store(const ::sind_essgraph_item& q, const EssPlan& pl, const ItemPtrs& p) {
+    const float* Fout = p.Fout; const double* Dout = p.head;
     EssDiag dg; std::memcpy(&dg, Dout, sizeof(dg));
     if (pl.nKf) { std::memcpy(q.Siw_out, Dout + 8, sizeof(double) * 8 * pl.nKf); std::memcpy(q.Tiw_out, Fout, sizeof(float) * 16 * pl.nKf); }
     if (pl.nMp) std::memcpy(q.x3Dw_out, Fout + 16 * (size_t)pl.nKf, sizeof(float) * 3 * pl.nMp);
@@ -134,24 +132,13 @@ void ess_store(const ::sind_essgraph_item& q, const EssPlan& pl, const float* Fo
     if (q.solver_fail) *q.solver_fail = dg.solverFail;
 }
 
-// the plain sequential executor (the host library's)
-struct EssSeq {
-    template <class F> void par(int n, F f) { for (int i = 0; i < n; i++) f(i); }
-    double rd(const double* p) { return *p; }
-    int rdi(const int* p) { return *p; }
-};
-
-// an item bound to host storage: plan() digests it (no workspace yet), bind() allocates the workspace
-struct EssHostItem {
-    EssPlan pl; std::vector<float> Fin, Fout; std::vector<double> Din, D; EssView v;
-    int plan(const ::sind_essgraph_item& q) { return ess_plan(q, pl); }
-    void bind(const ::sind_essgraph_item& q, int fixScale) {
-        Fin.assign(ess_floats_in(pl) + 1, 0.f); Fout.assign(ess_floats_out(pl) + 1, 0.f); Din.assign(ess_doubles_in(pl) + 1, 0.0); D.assign(pl.nD + 1, 0.0);
-        ess_fill(q, Fin.data(), Din.data());
-        ess_bind(pl, fixScale, pl.I.data(), Fin.data(), Din.data(), Fout.data(), D.data(), v);
-    }
-    int make(const ::sind_essgraph_item& q, int fixScale) { if (const int r = plan(q)) return r; bind(q, fixScale); return SIND_OK; }
-};
+using EssHost = HostItem<EssPlan, EssView>;
+// plan -> workspace, Fin, Din and the view
+static void ess_host_bind(EssHost& h, const ::sind_essgraph_item& q, int fixScale) {
+    h.store();
+    ess_fill(q, h.p);
+    ess_bind(h.pl, fixScale, h.p, h.v);
+}
 
 }  // namespace sind
 
@@ -161,15 +148,15 @@ extern "C" {
 int sindh_essential_graph(const sind_essgraph_item* items, int B, int fix_scale) {
     if (B < 0 || (B && !items)) return SIND_E_ARG;
     for (int b = 0; b < B; b++) if (sind::ess_check(items[b])) return SIND_E_ARG;
-    std::vector<sind::EssHostItem> h((size_t)B);
-    for (int b = 0; b < B; b++) if (const int r = h[b].plan(items[b])) return r;                    // every limit is checked before anything is written; only the lists are held
+    std::vector<sind::EssHost> h((size_t)B);
+    for (int b = 0; b < B; b++) if (const int r = sind::ess_plan(items[b], h[b].pl)) return r;                   // every limit is checked before anything is written; only the lists are held
     for (int b = 0; b < B; b++) {                                    // the workspace of one item at a time
-        h[b].bind(items[b], fix_scale);
-        sind::EssSeq ex; const sind::EssView& w = h[b].v;
+        sind::ess_host_bind(h[b], items[b], fix_scale);
+        sind::SeqExec ex; const sind::EssView& w = h[b].v;
         sind::essential_graph(ex, w);
         for (int j = 0; j < w.nMp; j++) sind::ess_point(w, j);
-        sind::ess_store(items[b], h[b].pl, h[b].Fout.data(), h[b].D.data());
-        h[b] = sind::EssHostItem();
+        sind::ess_store(items[b], h[b].pl, h[b].p);
+        h[b] = sind::EssHost();
     }
     return SIND_OK;
 }
@@ -185,13 +172,14 @@ void sindh_ess_sim3_exp(const double* u7, double* S) { sind::Sim3Q q; sind::s3_e
 // entries; any of H, b, x may be NULL (to ask for n first).  -> 0, SIND_E_ARG, SIND_E_CAPACITY, or 1: the factorisation failed
 int sindh_essgraph_linear(const sind_essgraph_item* item, int fix_scale, double* H, double* b, double* x, double* lambda, long long* env) {
     if (!item || sind::ess_check(*item)) return SIND_E_ARG;
-    sind::EssHostItem h;
-    if (const int r = h.make(*item, fix_scale)) return r;
-    sind::EssSeq ex; const sind::EssView& w = h.v; const int n = w.n;
+    sind::EssHost h;
+    if (const int r = sind::ess_plan(*item, h.pl)) return r;
+    sind::ess_host_bind(h, *item, fix_scale);
+    sind::SeqExec ex; const sind::EssView& w = h.v; const int n = w.n;
     if (env) { env[0] = n; env[1] = (long long)h.pl.nEnv; }
     if (!H || !b || !x) return 0;
     sind::ess_init(ex, w);
-    sind::EssLm<sind::EssSeq> lm{ex, w, 0};
+    sind::EssLm<sind::SeqExec> lm{ex, w, 0};
     lm.linearize();
     const double lam = 1e-16; if (lambda) *lambda = lam;
     for (int i = 0; i < n; i++) { w.x[i] = 0.0; b[i] = w.Hd[(i / 7) * ESS_V + 28 + i % 7]; }

@@ -459,20 +459,18 @@ SIND_HD inline void ess_point(const EssView& w, int j) {
 struct EssPlan {
     int nKf = 0, nE = 0, nMp = 0, nAct = 0, nPair = 0; size_t nEnv = 0;
     std::vector<int> I;
-    size_t oHasC, oHasN, oMpRef, oEI, oEJ, oEKind, oVIdx, oIdxV, oVEdgeStart, oVEdge, oPairStart, oPairLo, oPairHi, oPairE, oFirst, oRowOff, oBlkLast, oIsc, nI;
-    size_t nD;                                                       // doubles of the working state: EssDiag, SiwOut, then the rest
+    size_t oHasC, oHasN, oMpRef, oEI, oEJ, oEKind, oVIdx, oIdxV, oVEdgeStart, oVEdge, oPairStart, oPairLo, oPairHi, oPairE, oFirst, oRowOff, oBlkLast, oIsc;
+    ItemSizes z;                                                     // no ints come back; doubles in: corr, ncorr; the head: EssDiag, SiwOut
 };
 // -> 0, or what is wrong with the item (ess_check_text)
 int ess_check(const ::sind_essgraph_item& q);
 extern const char* const ess_check_text[];
 // -> SIND_OK or SIND_E_CAPACITY; the item has passed ess_check
 int ess_plan(const ::sind_essgraph_item& q, EssPlan& pl);
-size_t ess_doubles_in(const EssPlan& pl);                            // corr, ncorr
-size_t ess_floats_in(const EssPlan& pl);                             // Tcw, x3Dw
-size_t ess_floats_out(const EssPlan& pl);                            // TiwOut, XOut
-size_t ess_doubles_out(const EssPlan& pl);                           // the head of the working state that comes back: EssDiag and SiwOut
-void ess_fill(const ::sind_essgraph_item& q, float* Fin, double* Din);
-void ess_bind(const EssPlan& pl, int fixScale, int* I, const float* Fin, const double* Din, float* Fout, double* D, EssView& v);
-void ess_store(const ::sind_essgraph_item& q, const EssPlan& pl, const float* Fout, const double* Dout);
+// the view of an item over its share of the streams (Fin: Tcw, x3Dw; Din: corr, ncorr, both filled by ess_fill; Fout: TiwOut, XOut; the head: EssDiag, SiwOut)
+void ess_fill(const ::sind_essgraph_item& q, const ItemPtrs& p);
+void ess_bind(const EssPlan& pl, int fixScale, const ItemPtrs& p, EssView& v);
+// an item's outputs from what came back (p: host storage)
+void ess_store(const ::sind_essgraph_item& q, const EssPlan& pl, const ItemPtrs& p);
 
 }  // namespace sind

@@ -13,9 +13,12 @@
 //   - after a rejected trial the edges still hold the errors of the REJECTED estimate: pop() restores the vertices, nobody recomputes the errors, and the callers'
 //     classifications read those.  The problem notes the estimate its stored errors belong to whenever it evaluates;
 //   - _currentLambda is -1 until computeLambdaInit has run, which is what a call with no iteration reports.
+// At the end, host only: what the host layers of local BA and the essential graph share (SeqExec, ItemSizes, ItemPtrs, HostItem).
 #pragma once
 #include <cmath>
 #include <cfloat>
+#include <cstddef>
+#include <vector>
 #include "peac_fit.hpp"                                              // SIND_HD
 
 namespace sind {
@@ -169,5 +172,33 @@ template <class Pr> SIND_HD inline __attribute__((always_inline)) int levenberg_
     chi2 = currentChi; lambdaOut = lambda;
     return cj;
 }
+
+// ---------------------------------------------------------------- what LocalBundleAdjustment and OptimizeEssentialGraph share of their host layer: a call's items lie
+// one after the other in a few streams (the device call, ../match_handle.hpp: PackedItems) or each in vectors of its own (the host twins: HostItem)
+// The plain sequential executor of the host twins (the device's is WgExec, ../match_device.hpp)
+struct SeqExec {
+    template <class F> void par(int n, F f) { for (int i = 0; i < n; i++) f(i); }
+    double rd(const double* p) { return *p; }
+    int rdi(const int* p) { return *p; }
+};
+
+// What one item takes of each stream, in elements: LbaPlan and EssPlan report it in this shape
+struct ItemSizes {
+    size_t ints = 0, intsOutAt = 0, intsOut = 0;                     // every int array; [intsOutAt, intsOutAt + intsOut) of them comes back (local BA's erase flags)
+    size_t floatsIn = 0, floatsOut = 0, doublesIn = 0;               // doublesIn: the Sim3 maps of the essential graph
+    size_t head = 0, work = 0;                                       // doubles that come back (the diagnostics first); doubles of the working state, room for the head included
+};
+// where an item's share of each stream starts, host or device alike.  The host twins keep the head where the working state has room for it: head == D
+struct ItemPtrs { int* I; float* Fin; float* Fout; double* Din; double* head; double* D; };
+
+// an item bound to host storage: the caller digests it into pl (no workspace yet), store() allocates the workspace
+template <class Plan, class View> struct HostItem {
+    Plan pl; std::vector<float> Fin, Fout; std::vector<double> Din, D; ItemPtrs p{}; View v;
+    void store() {
+        const ItemSizes& z = pl.z;
+        Fin.assign(z.floatsIn + 1, 0.f); Fout.assign(z.floatsOut + 1, 0.f); Din.assign(z.doublesIn + 1, 0.0); D.assign(z.work + 1, 0.0);
+        p = ItemPtrs{pl.I.data(), Fin.data(), Fout.data(), Din.data(), D.data(), D.data()};
+    }
+};
 
 }  // namespace sind

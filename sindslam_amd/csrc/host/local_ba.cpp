@@ -1,5 +1,5 @@
 // Host twin of sind_match_local_ba (reference src/Optimizer.cc:506-778): local_ba.hpp with the plain sequential executor, and what the two entry points share: the
-// argument check, the digest of an item into the lists the phases walk (LbaPlan) and the copy of one item's results.  Compiled into libsind_hip.so (capi_match.cpp
+// argument check, the digest of an item into the lists the phases walk (LbaPlan) and the copy of one item's results.  Compiled into libsind_hip.so (capi_match_opt.cpp
 // calls the shared part) and into libsind_host.so.
 #include <algorithm>
 #include <cmath>
@@ -92,17 +92,15 @@ int lba_plan(const ::sind_localba_item& q, LbaPlan& pl) {
     pl.oPtNF = add(ptNF.data(), nMp); pl.oPtSorted = add(ptSorted.data(), nObs); pl.oPairStart = add(pairStart.data(), (size_t)nPair + 1); pl.oPairKey = add(pairKey.data(), nPair);
     pl.oPairE = add(pairE.data(), pairE.size()); pl.oDiagPair = add(diagPair.data(), P);
     pl.oLevel = room(nObs); pl.oPoseIdx = room(P); pl.oPtAct = room(nMp); pl.oIsc = room(LBA_IS_N); pl.oErase = room(nObs);
-    pl.nI = pl.I.size();
     const size_t n = 6 * (size_t)P;
-    pl.nD = 8 + LBA_SC_N + 14 * (size_t)nKf + 6 * (size_t)nMp + (size_t)(LBA_C + 18) * nObs + 27 * (size_t)P + 21 * (size_t)nMp + 2 * n * n + 2 * n + 2 * (n + 3 * (size_t)nMp) + nObs;
+    pl.z.ints = pl.I.size(); pl.z.intsOutAt = pl.oErase; pl.z.intsOut = nObs;
+    pl.z.floatsIn = 16 * (size_t)nKf + 3 * (size_t)nMp + 4 * (size_t)nObs; pl.z.floatsOut = 16 * (size_t)nKf + 3 * (size_t)nMp; pl.z.head = 8;
+    pl.z.work = 8 + LBA_SC_N + 14 * (size_t)nKf + 6 * (size_t)nMp + (size_t)(LBA_C + 18) * nObs + 27 * (size_t)P + 21 * (size_t)nMp + 2 * n * n + 2 * n + 2 * (n + 3 * (size_t)nMp) + nObs;
     return SIND_OK;
 }
 
-size_t lba_floats_in(const LbaPlan& pl) { return 16 * (size_t)pl.nKf + 3 * (size_t)pl.nMp + 4 * (size_t)pl.nObs; }
-size_t lba_floats_out(const LbaPlan& pl) { return 16 * (size_t)pl.nKf + 3 * (size_t)pl.nMp; }
-
-void lba_fill_floats(const ::sind_localba_item& q, float* F) {
-    const int nObs = q.n_mp ? q.obs_start[q.n_mp] : 0;
+void lba_fill(const ::sind_localba_item& q, const ItemPtrs& p) {
+    const int nObs = q.n_mp ? q.obs_start[q.n_mp] : 0; float* F = p.Fin;
     if (q.n_kf) std::memcpy(F, q.Tcw, sizeof(float) * 16 * q.n_kf);
     F += 16 * (size_t)q.n_kf;
     if (q.n_mp) std::memcpy(F, q.x3Dw, sizeof(float) * 3 * q.n_mp);
@@ -110,7 +108,8 @@ void lba_fill_floats(const ::sind_localba_item& q, float* F) {
     for (int e = 0; e < nObs; e++) { F[4 * e] = q.obs_xy[2 * e]; F[4 * e + 1] = q.obs_xy[2 * e + 1]; F[4 * e + 2] = q.u_right[e]; F[4 * e + 3] = q.inv_sigma2[e]; }
 }
 
-void lba_bind(const LbaPlan& pl, int doMore, const PoseOptCam& K, int* I, const float* Fin, float* Fout, double* D, LbaView& v) {
+void lba_bind(const LbaPlan& pl, int doMore, const PoseOptCam& K, const ItemPtrs& p, LbaView& v) {
+    int* I = p.I; const float* Fin = p.Fin; float* Fout = p.Fout;
     const size_t nKf = pl.nKf, nMp = pl.nMp, nObs = pl.nObs, P = pl.P, n = 6 * P;
     v.nKf = pl.nKf; v.nMp = pl.nMp; v.nObs = pl.nObs; v.P = pl.P; v.nPair = pl.nPair; v.doMore = doMore; v.K = K;
     v.Tcw = Fin; v.x3Dw = Fin + 16 * nKf; v.eObs = v.x3Dw + 3 * nMp;
@@ -119,14 +118,16 @@ void lba_bind(const LbaPlan& pl, int doMore, const PoseOptCam& K, int* I, const 
     v.pairE = I + pl.oPairE; v.diagPair = I + pl.oDiagPair;
     v.level = I + pl.oLevel; v.poseIdx = I + pl.oPoseIdx; v.ptAct = I + pl.oPtAct; v.isc = I + pl.oIsc; v.erase = I + pl.oErase;
     static_assert(sizeof(LbaDiag) <= 8 * sizeof(double) && sizeof(PoseQ) == 7 * sizeof(double), "the layout of the working state");
-    double* d = D;
-    v.diag = (LbaDiag*)d; d += 8; v.sc = d; d += LBA_SC_N; v.est = (PoseQ*)d; d += 7 * nKf; v.bak = (PoseQ*)d; d += 7 * nKf; v.X = d; d += 3 * nMp; v.Xbak = d; d += 3 * nMp;
+    double* d = p.D + 8;                                             // the room of the head in the working state
+    v.diag = (LbaDiag*)p.head; v.sc = d; d += LBA_SC_N; v.est = (PoseQ*)d; d += 7 * nKf; v.bak = (PoseQ*)d; d += 7 * nKf; v.X = d; d += 3 * nMp; v.Xbak = d; d += 3 * nMp;
     v.C = d; d += LBA_C * nObs; v.BD = d; d += 18 * nObs; v.Hpp = d; d += 27 * P; v.Hll = d; d += 9 * nMp; v.Dinv = d; d += 9 * nMp; v.db = d; d += 3 * nMp;
     v.Hs = d; d += n * n; v.Lm = d; d += n * n; v.Dg = d; d += n; v.y = d; d += n; v.x = d; d += n + 3 * nMp; v.term = d; d += n + 3 * nMp; v.rho = d; d += nObs;
     v.TcwOut = Fout; v.XOut = Fout + 16 * nKf;
 }
 
-void lba_store(const ::sind_localba_item& q, const LbaPlan& pl, const int* erase, const float* Fout, const LbaDiag& dg) {
+void lba_store(const ::sind_localba_item& q, const LbaPlan& pl, const ItemPtrs& p) {
+    const int* erase = p.I + pl.oErase; const float* Fout = p.Fout;
+    LbaDiag dg; std::memcpy(&dg, p.head, sizeof(dg));
     if (pl.nKf) std::memcpy(q.Tcw_out, Fout, sizeof(float) * 16 * pl.nKf);
     if (pl.nMp) std::memcpy(q.x3Dw_out, Fout + 16 * (size_t)pl.nKf, sizeof(float) * 3 * pl.nMp);
     for (int e = 0; e < pl.nObs; e++) q.erase[e] = (uint8_t)erase[e];
@@ -137,24 +138,13 @@ void lba_store(const ::sind_localba_item& q, const LbaPlan& pl, const int* erase
     if (q.stage_lambda) std::memcpy(q.stage_lambda, dg.lambda, sizeof(dg.lambda));
 }
 
-// the plain sequential executor (the host library's)
-struct LbaSeq {
-    template <class F> void par(int n, F f) { for (int i = 0; i < n; i++) f(i); }
-    double rd(const double* p) { return *p; }
-    int rdi(const int* p) { return *p; }
-};
-
-// an item bound to host storage
-struct LbaHostItem {
-    LbaPlan pl; std::vector<float> Fin, Fout; std::vector<double> D; LbaView v;
-    int make(const ::sind_localba_item& q, const float* K5) {
-        if (const int r = lba_plan(q, pl)) return r;
-        Fin.assign(lba_floats_in(pl) + 1, 0.f); Fout.assign(lba_floats_out(pl) + 1, 0.f); D.assign(pl.nD, 0.0);
-        lba_fill_floats(q, Fin.data());
-        lba_bind(pl, q.do_more, {(double)K5[0], (double)K5[1], (double)K5[2], (double)K5[3], (double)K5[4]}, pl.I.data(), Fin.data(), Fout.data(), D.data(), v);
-        return SIND_OK;
-    }
-};
+using LbaHost = HostItem<LbaPlan, LbaView>;
+// plan -> workspace, Fin and the view
+static void lba_host_bind(LbaHost& h, const ::sind_localba_item& q, const float* K5) {
+    h.store();
+    lba_fill(q, h.p);
+    lba_bind(h.pl, q.do_more, {(double)K5[0], (double)K5[1], (double)K5[2], (double)K5[3], (double)K5[4]}, h.p, h.v);
+}
 
 }  // namespace sind
 
@@ -164,12 +154,14 @@ extern "C" {
 int sindh_local_ba(const sind_localba_item* items, int B, const float* K5) {
     if (B < 0 || (B && !items) || !K5) return SIND_E_ARG;
     for (int b = 0; b < B; b++) if (sind::lba_check(items[b])) return SIND_E_ARG;
-    std::vector<sind::LbaHostItem> h((size_t)B);
-    for (int b = 0; b < B; b++) if (const int r = h[b].make(items[b], K5)) return r;
-    for (int b = 0; b < B; b++) {
-        sind::LbaSeq ex;
+    std::vector<sind::LbaHost> h((size_t)B);
+    for (int b = 0; b < B; b++) if (const int r = sind::lba_plan(items[b], h[b].pl)) return r;     // every limit is checked before anything is written; only the lists are held
+    for (int b = 0; b < B; b++) {                                    // the workspace of one item at a time
+        sind::lba_host_bind(h[b], items[b], K5);
+        sind::SeqExec ex;
         sind::local_ba(ex, h[b].v);
-        sind::lba_store(items[b], h[b].pl, h[b].v.erase, h[b].Fout.data(), *h[b].v.diag);
+        sind::lba_store(items[b], h[b].pl, h[b].p);
+        h[b] = sind::LbaHost();
     }
     return SIND_OK;
 }
@@ -184,9 +176,10 @@ void sindh_localba_edge(const double* qt, const double* X, const float* ob4, con
 // contributions, x [6 P + 3 n_mp] by pose rank (kind 0 in ascending kf_id) and item point, lambda [1].  -> 0, SIND_E_ARG, SIND_E_CAPACITY, or 1: the factorisation failed
 int sindh_localba_linear(const sind_localba_item* item, const float* K5, double* C, double* x, double* lambda) {
     if (!item || !K5 || sind::lba_check(*item)) return SIND_E_ARG;
-    sind::LbaHostItem h;
-    if (const int r = h.make(*item, K5)) return r;
-    sind::LbaSeq ex; const sind::LbaView& w = h.v;
+    sind::LbaHost h;
+    if (const int r = sind::lba_plan(*item, h.pl)) return r;
+    sind::lba_host_bind(h, *item, K5);
+    sind::SeqExec ex; const sind::LbaView& w = h.v;
     ex.par(w.nKf, [&](int i) { sind::po_from_tcw(&w.Tcw[16 * i], w.est[i]); });
     for (int k = 0; k < 3 * w.nMp; k++) w.X[k] = (double)w.x3Dw[k];
     sind::lba_activate(ex, w); sind::lba_eval(ex, w, true, true); sind::lba_sums(ex, w, true); sind::lba_maxdiag(ex, w);

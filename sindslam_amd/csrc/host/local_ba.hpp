@@ -404,8 +404,8 @@ template <class Ex> SIND_HD inline void local_ba(Ex& ex, const LbaView& w) {
 struct LbaPlan {
     int nKf = 0, nMp = 0, nObs = 0, P = 0, nPair = 0, nPairE = 0;
     std::vector<int> I;
-    size_t oKfKind, oKfPose, oPoseKf, oPtOrder, oObsStart, oEPt, oEKf, oPoseEdgeStart, oPoseEdge, oPtNF, oPtSorted, oPairStart, oPairKey, oPairE, oDiagPair, oLevel, oPoseIdx, oPtAct, oIsc, oErase, nI;
-    size_t nD;                                                       // doubles of the working state (LbaDiag first)
+    size_t oKfKind, oKfPose, oPoseKf, oPtOrder, oObsStart, oEPt, oEKf, oPoseEdgeStart, oPoseEdge, oPtNF, oPtSorted, oPairStart, oPairKey, oPairE, oDiagPair, oLevel, oPoseIdx, oPtAct, oIsc, oErase;
+    ItemSizes z;                                                     // the ints that come back: erase; no doubles go in; the head: LbaDiag
 };
 // -> 0, or what is wrong with the item: 1 a negative count, 2 a NULL array, 3 ids that repeat, 4 an obs_kf out of range, 5 a key frame twice in one point's observations,
 // 6 a non-monotone obs_start, 7 an inv_sigma2 that is negative or not finite, 8 a pose or point that is not finite, 9 no key frame of kind 0, 10 a kind outside 0..2
@@ -413,12 +413,10 @@ int lba_check(const ::sind_localba_item& q);
 extern const char* const lba_check_text[];
 // -> SIND_OK or SIND_E_CAPACITY (a limit above); the item has passed lba_check
 int lba_plan(const ::sind_localba_item& q, LbaPlan& pl);
-// the view of an item over its int, float and double storage (Fin: Tcw, x3Dw, eObs in this order; Fout: TcwOut, XOut); Fin filled by lba_fill_floats
-void lba_bind(const LbaPlan& pl, int doMore, const PoseOptCam& K, int* I, const float* Fin, float* Fout, double* D, LbaView& v);
-size_t lba_floats_in(const LbaPlan& pl);
-size_t lba_floats_out(const LbaPlan& pl);
-void lba_fill_floats(const ::sind_localba_item& q, float* Fin);
-// an item's outputs from the int (from oErase: erase, then nothing), float and LbaDiag results
-void lba_store(const ::sind_localba_item& q, const LbaPlan& pl, const int* erase, const float* Fout, const LbaDiag& dg);
+// the view of an item over its share of the streams (Fin: Tcw, x3Dw, eObs in this order, filled by lba_fill; Fout: TcwOut, XOut; the head: LbaDiag)
+void lba_fill(const ::sind_localba_item& q, const ItemPtrs& p);
+void lba_bind(const LbaPlan& pl, int doMore, const PoseOptCam& K, const ItemPtrs& p, LbaView& v);
+// an item's outputs from what came back (p: host storage)
+void lba_store(const ::sind_localba_item& q, const LbaPlan& pl, const ItemPtrs& p);
 
 }  // namespace sind

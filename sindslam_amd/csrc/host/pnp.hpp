@@ -1,5 +1,5 @@
 // Host half of PnPsolver (reference src/PnPsolver.cc) around epnp.hpp: SetRansacParameters, the list of Refine problems of a candidate, and the
-// test entries of libsind_host.so.  Plain C++: compiled into libsind_hip.so (capi_match.cpp calls it) and into libsind_host.so.
+// test entries of libsind_host.so.  Plain C++: compiled into libsind_hip.so (capi_match_ransac.cpp calls it) and into libsind_host.so.
 #pragma once
 #include <cstdint>
 

@@ -1,5 +1,5 @@
 // Host twin of sind_match_pose_optimize (reference src/Optimizer.cc:239-451): pose_opt.hpp with the plain sequential evaluator, and what the two entry points share:
-// the argument check and the copy of one item's results.  Compiled into libsind_hip.so (capi_match.cpp calls the shared part) and into libsind_host.so.
+// the argument check and the copy of one item's results.  Compiled into libsind_hip.so (capi_match_opt.cpp calls the shared part) and into libsind_host.so.
 #include <cmath>
 #include <cstring>
 #include <vector>

@@ -11,7 +11,7 @@
 //   C = C / P.cols                       MatExpr with alpha = 1. / 3 (double), assigned by convertTo: c * (float)alpha + 0.0f in FP32                 [R]
 //   Pr.col(i) = P.col(i) - C             cv::subtract in FP32                                                                                    [R]
 //   M = Pr2 * Pr1.t()                    cv::gemm with GEMM_2_T: not the small-matrix path (it needs flags == 0); the generic kernel accumulates the
-//                                        products in FP64, k ascending, and stores (float)(s * alpha), alpha = 1                                    [R, as capi_match.cpp camera_centre]
+//                                        products in FP64, k ascending, and stores (float)(s * alpha), alpha = 1                                    [R, as match_handle.hpp camera_centre]
 //   N11 .. N44                           FP32 expressions of M's elements, left to right, widened to double and narrowed again by Mat_<float> <<    [R]
 //   cv::eigen(N, eval, evec)             symmetric 4x4 CV_32F -> JacobiImpl_<float>: V = I; the pivot is the off-diagonal element of largest magnitude, tracked
 //                                        per row (indR) and per column (indC); stop at |p| <= FLT_EPSILON or after 30 n^2 rotations; y = (W[l] - W[k]) * 0.5,

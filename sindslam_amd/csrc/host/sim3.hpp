@@ -1,5 +1,5 @@
 // Host half of Sim3Solver (reference src/Sim3Solver.cc): the closed-form hypothesis of one sampled triple and the constructor's per-correspondence
-// arithmetic.  Plain C++, no device code: compiled into libsind_hip.so (capi_match.cpp calls it) and into libsind_host.so (sindh_sim3_horn, for the CPU tests).
+// arithmetic.  Plain C++, no device code: compiled into libsind_hip.so (capi_match_ransac.cpp calls it) and into libsind_host.so (sindh_sim3_horn, for the CPU tests).
 #pragma once
 #include <cstddef>
 

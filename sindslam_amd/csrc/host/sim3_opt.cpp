@@ -1,5 +1,5 @@
 // Host twin of sind_match_sim3_optimize (reference src/Optimizer.cc:1046-1241): sim3_opt.hpp with the plain sequential evaluator, and what the two entry points share:
-// the argument check and the copy of one item's results.  Compiled into libsind_hip.so (capi_match.cpp calls the shared part) and into libsind_host.so.
+// the argument check and the copy of one item's results.  Compiled into libsind_hip.so (capi_match_opt.cpp calls the shared part) and into libsind_host.so.
 #include <cmath>
 #include <cstring>
 #include <vector>

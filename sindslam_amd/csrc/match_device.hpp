@@ -1,6 +1,7 @@
 // Device functions shared by the matcher's searches (match_kernels.hip, match_local.hip, match_bow.hip, bow_kernels.hip): DescriptorDistance
 // (reference src/ORBmatcher.cc:1647-1665), and the tail every search with an orientation check ends on -- assignments ->
-// CurrentFrame.mvpMapPoints (the later point wins), rotation histogram, ComputeThreeMaxima (:1601-1642), removal.
+// CurrentFrame.mvpMapPoints (the later point wins), rotation histogram, ComputeThreeMaxima (:1601-1642), removal.  And the workgroup executor of the two graph
+// optimizers (match_localba.hip, match_essgraph.hip).
 #pragma once
 #include "common.hpp"
 
@@ -8,6 +9,18 @@ namespace sind {
 
 #define MT_NT 1024
 #define HISTO_LENGTH 30
+
+// The executor of local_ba and essential_graph for one workgroup of THREADS lanes (host/local_ba.hpp: Ex; the host twins' is SeqExec, host/g2o_lm.hpp): the lanes stride
+// over the elements of a phase, then one barrier; a scalar of the control flow is read by every lane, then a barrier, so the next phase may rewrite it
+template <int THREADS> struct WgExec {
+    int tid;
+    template <class F> __device__ void par(int n, F f) {
+        for (int i = tid; i < n; i += THREADS) f(i);
+        __syncthreads();
+    }
+    __device__ double rd(const double* p) { const double v = *p; __syncthreads(); return v; }
+    __device__ int rdi(const int* p) { const int v = *p; __syncthreads(); return v; }
+};
 
 struct MatchTailShared { int hist[HISTO_LENGTH], keep[HISTO_LENGTH], nmatch; };
 

@@ -2,7 +2,8 @@
 hold valid|has_obs, kf_valid or has_mp1; the taken array of the searched side holds cur_taken or has_mp2), so every call here finds staging left
 behind by a different kind, by a larger batch or by a longer frame, and must still equal the restatement its own test file uses (oracle_lib,
 localmap_ref, bow_ref).  All equalities; floats are compared as uint32 bit patterns.  The "plenty of matches" guards are half of what the restatement
-finds on these scenes (the found values stand beside them)."""
+finds on these scenes (the found values stand beside them).  The last test does the same for the two graph optimizers, which pack their items into streams
+of the handle that grow between calls, against their host twins."""
 import numpy as np
 import pytest
 
@@ -104,4 +105,32 @@ def test_five_searches_interleaved_on_one_handle():
     # 7. BoW once more, the full pair
     (m, n), = mt.SearchByBoW([(kf, bcur)], nnratio=0.75)
     assert n == bow_full[1] and np.array_equal(m, bow_full[0])
+    mt.close()
+
+
+def test_local_ba_and_essential_graph_alternate_on_one_handle_with_items_of_changing_size():
+    """The two graph optimizers pack their items one after the other into streams that grow between calls (csrc/match_handle.hpp: PackedItems), each call kind its own.
+    On one handle: a small item, a larger one (the streams grow), a batch of two unequal items (the second item's offsets are not the first's), the small one again
+    (nothing of the larger calls is read).  Every output of every call equals the host twin's bit for bit.  The scenes are checked on the host first: both stages of
+    local BA run with planted outliers erased, the essential graph iterates and its factorisation never fails."""
+    import essgraph_scene as E
+    import localba_scene as LB
+    from sindslam_amd.matcher import ORBmatcher
+
+    lb = {"small": LB.scene(61, 2, 1, 6, kind="mixed", outliers=1), "big": LB.scene(61, 5, 3, 40, kind="mixed", outliers=3)}
+    es = {"small": E.scene(61, 4, window=1, loop=1, n_mp=8), "big": E.scene(61, 12, window=3, loop=2, n_mp=40)}
+    assert [len(es[k]["edge_i"]) for k in ("small", "big")] == [5, 38] and [len(lb[k]["obs_kf"]) for k in ("small", "big")] == [18, 320]
+    lb_ref = {k: LB.HostBA().LocalBundleAdjustment([v], K=LB.K5)[0] for k, v in lb.items()}
+    es_ref = {k: E.HostEss().OptimizeEssentialGraph([v], True)[0] for k, v in es.items()}
+    for r in lb_ref.values():
+        assert r["n_stages"] == 2 and min(r["stage_iters"]) >= 2 and r["erase"].sum() >= 1
+    for r in es_ref.values():
+        assert r["solver_fail"] == 0 and r["n_iters"] >= 2
+
+    mt = ORBmatcher(*[float(k) for k in LB.K5], (0.0, 640.0, 0.0, 480.0), [1.2 ** k for k in range(8)], cap=512, max_batch=2)
+    for step, (lb_names, es_names) in enumerate(((["small"], ["small"]), (["big"], ["big"]), (["small", "big"], ["big", "small"]), (["small"], ["small"]))):
+        for k, g in zip(lb_names, mt.LocalBundleAdjustment([lb[k] for k in lb_names])):
+            LB.assert_same(g, lb_ref[k], ("local BA", step, k))
+        for k, g in zip(es_names, mt.OptimizeEssentialGraph([es[k] for k in es_names], True)):
+            E.assert_same(g, es_ref[k], ("essential graph", step, k))
     mt.close()
