@@ -853,8 +853,7 @@ int sindh_local_ba(const sind_localba_item* items, int B, const float* K5);   /*
  * optimised), n_active = the vertices with a Hessian index, solver_fail = the factorisations that failed.
  * Valid: B = 0; n_edges = 0 (the empty graph: nothing is optimised, the outputs are the conversions alone); n_mp = 0; free vertices without edges.
  * Unpinned: parity with a real g2o / Eigen build: the linear system (a natural-order envelope LDL^T here, SimplicialLDLT under AMD ordering there), W.lu().solve(t) of
- * Sim3::log, std::log and acos (restated from fdlibm), the reference's iteration by pointer value; see the head of essential_graph.hpp.  Not offered: a stop flag,
- * global bundle adjustment.
+ * Sim3::log, std::log and acos (restated from fdlibm), the reference's iteration by pointer value; see the head of essential_graph.hpp.  Not offered: a stop flag.
  * Limits: 4096 key frames, 65536 edges, 2^20 points, 2^24 stored entries of the factor's envelope (sum over the free key frames with an edge, in ascending mnId with
  * rank I, of 49 (I - first(I) + 1), first(I) the smallest rank among I and its neighbours), B <= max_batch: beyond them SIND_E_CAPACITY.  The workspace lives on the
  * handle, grows between calls to the largest call seen and is freed with the handle.
@@ -873,6 +872,54 @@ typedef struct sind_essgraph_item {
 } sind_essgraph_item;
 int sind_match_essential_graph(sind_match* m, const sind_essgraph_item* items, int B, int fix_scale);
 int sindh_essential_graph(const sind_essgraph_item* items, int B, int fix_scale);   /* host twin (libsind_host.so too) */
+
+/* sind_match_global_ba.  Replaces the whole of
+ *   void Optimizer::BundleAdjustment(const vector<KeyFrame *> &vpKFs, const vector<MapPoint *> &vpMP, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF,
+ *                                    const bool bRobust)
+ * from the optimizer's set-up on (src/Optimizer.cc:49-191; GlobalBundleAdjustemnt forwards to it; LoopClosing::RunGlobalBundleAdjustment, src/LoopClosing.cc:645): one
+ * VertexSE3Expmap per key frame (fixed iff mnId == 0), one marginalised VertexSBAPointXYZ per point, one EdgeSE3ProjectXYZ or EdgeStereoSE3ProjectXYZ per observation,
+ * Huber kernels only if robust (deltas the floats sqrt(5.99) and sqrt(7.815): the monocular one is not local BA's sqrt(5.991)), BlockSolver_6_3's Schur complement under
+ * OptimizationAlgorithmLevenberg, initializeOptimization(), ONE optimize(iterations); no levels and no classification.  A global BA is one large item, so the phases
+ * of the algorithm are KERNELS OVER THE WHOLE GRID, one element per lane, on the handle's stream (csrc/match_globalba.hip), stream order the only synchronisation, and
+ * the Levenberg-Marquardt control flow runs on the host with one wait per linearisation and one per trial; no cooperative launch, no grid-wide flags, no atomics.
+ * csrc/host/global_ba.hpp is one FP64 source for host and device and states the order of every sum: it is local BA's contract, with the reduced camera system stored and
+ * factored as a natural-order envelope in 6 x 6 block rows.  The B items of a call run one after the other.  Calibration is the handle's fx fy cx cy bf.
+ * What stays with the caller: the collection of the graph (:68-184; sindslam_amd/optimizer.py mirrors it) and what follows the optimize (:193-235: SetPose / SetWorldPos
+ * or mTcwGBA / mPosGBA), and the tail of RunGlobalBundleAdjustment (sindslam_amd/optimizer.py: run_global_bundle_adjustment).
+ * Inputs: the key frames that are not bad in ascending mnId (kf_id), Tcw = GetPose(); the points that are not bad, x3Dw = GetWorldPos(); the observations of point j are
+ * obs_start[j] .. obs_start[j + 1] - 1 in the order the edges are added, those in bad key frames or in key frames the call does not hold left out (:109): obs_kf the
+ * index of the key frame, obs_xy = mvKeysUn[slot].pt, u_right = mvuRight[slot] (< 0: the monocular edge), inv_sigma2 = mvInvLevelSigma2[octave].  iterations: the
+ * reference passes 10 (loop closing) or 20 (the default); 0 is the stop flag already set at entry (no iteration; the outputs are the conversions alone).
+ * Outputs: Tcw_out = toCvMat(estimate) of every key frame (a round trip through the quaternion, for the fixed one and for one without edges too); x3Dw_out = the float of
+ * the estimate, the input for a point without observations (vbNotIncludedMP, :175-179); included[j] = 0 exactly for those points.  The diagnostics may be NULL: n_iters
+ * = optimize's return (-1 where nothing was optimised), chi2 = activeRobustChi2 after the last accepted step, lambda = _currentLambda at the end (-1 before
+ * computeLambdaInit), n_active_poses = the key frames with a Hessian index, solver_fail = the factorisations that failed, env_entries = the stored entries of the
+ * factor's envelope, env_dense_entries = those of the dense lower triangle in 6 x 6 blocks, 36 n (n + 1) / 2.
+ * Valid: B = 0; no key frame but mnId 0 (only the points move); no observations (nothing is optimised); n_mp = 0; no key frame with mnId 0 (nothing is fixed).
+ * Unpinned: parity with a real g2o / Eigen build, above all the reduced system (a natural-order envelope LDL^T here, SimplicialLDLT under AMD ordering there) and the
+ * order of a point's observations (a std::map keyed by pointers there); see the heads of global_ba.hpp and local_ba.hpp.  Not offered: a stop flag that flips in the
+ * middle of the optimize.
+ * Limits: 4096 key frames, 2^20 points, 2^22 observations, 2^26 entries of the co-observation lists (sum over the points of k (k + 1) / 2, k = its observations in key
+ * frames with mnId != 0), 2^25 stored entries of the envelope (sum over the key frames with a Hessian index I of 36 (I - first(I) + 1), first(I) the smallest index among
+ * I and the key frames that share a point with it), B <= max_batch: beyond them SIND_E_CAPACITY, decided before anything is allocated or launched.  The workspace lives
+ * on the handle, grows between calls to the largest call seen and is freed with the handle.
+ * SIND_E_ARG: a NULL array with a non-zero count, a negative count or iteration count, kf_id not strictly ascending, point ids that repeat, an obs_kf out of range, the
+ * same key frame twice in one point's observations, an obs_start that does not start at 0 or decreases, an inv_sigma2 that is negative or not finite, a pose or point
+ * that is not finite.  On an error nothing is launched and the outputs are untouched.
+ */
+typedef struct sind_globalba_item {
+    int n_kf; const int64_t* kf_id; const float* Tcw;         /* [n_kf] strictly ascending; [n_kf][16] GetPose() */
+    int n_mp; const int64_t* mp_id; const float* x3Dw;        /* [n_mp], [n_mp][3] */
+    const int* obs_start;                                     /* [n_mp + 1]: the observations of point j, in the order the edges are added */
+    const int* obs_kf;                                        /* [n_obs] index into 0..n_kf-1 */
+    const float* obs_xy; const float* u_right; const float* inv_sigma2;   /* [n_obs][2], [n_obs] (< 0: mono), [n_obs] */
+    float* Tcw_out; float* x3Dw_out; uint8_t* included;       /* [n_kf][16], [n_mp][3], [n_mp] */
+    int* n_iters; double* chi2; double* lambda; int* n_active_poses; int* solver_fail;   /* diagnostics, may be NULL: [1] each */
+    long long* env_entries; long long* env_dense_entries;     /* [1] each */
+} sind_globalba_item;
+int sind_match_global_ba(sind_match* m, const sind_globalba_item* items, int B, int iterations, int robust);
+int sind_match_global_ba_counts(sind_match* m, long long* launches, long long* waits);   /* of the last sind_match_global_ba on the handle: kernel launches, host waits */
+int sindh_global_ba(const sind_globalba_item* items, int B, int iterations, int robust, const float* K5);   /* host twin (libsind_host.so too): K5 = fx fy cx cy bf */
 
 /* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of

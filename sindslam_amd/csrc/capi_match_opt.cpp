@@ -1,4 +1,4 @@
-// C ABI: the optimizers on the matcher handle: PoseOptimization, OptimizeSim3, LocalBundleAdjustment, OptimizeEssentialGraph (include/sind_hip.h, "sind_match_*").
+// C ABI: the optimizers on the matcher handle: PoseOptimization, OptimizeSim3, LocalBundleAdjustment, OptimizeEssentialGraph, BundleAdjustment (include/sind_hip.h, "sind_match_*").
 #include "match_handle.hpp"
 #include "host/pose_opt.hpp"
 #include "host/sim3_opt.hpp"
@@ -147,6 +147,41 @@ int sind_match_essential_graph(sind_match* m, const sind_essgraph_item* items, i
     SIND_TRY(w.download(B, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (int b = 0; b < B; b++) sind::ess_store(items[b], w.plan[b], w.host(b));
+    return SIND_OK;
+}
+
+// global BA: check, plan, pack, then item after item: the phases of host/global_ba.hpp as launches over the whole grid, the Levenberg-Marquardt driver here on the host
+int sind_match_global_ba(sind_match* m, const sind_globalba_item* items, int B, int iterations, int robust) {
+    const char* who = "sind_match_global_ba: item";
+    SIND_TRY(solver_prologue("sind_match_global_ba", m, items, B, iterations >= 0));
+    for (int b = 0; b < B; b++) if (const int bad = sind::gba_check(items[b])) { sind_set_error("%s %d: %s", who, b, sind::gba_check_text[bad]); return SIND_E_ARG; }
+    if (!B) return SIND_OK;
+    auto& w = m->globalba;
+    w.plan.resize((size_t)m->maxB);
+    for (int b = 0; b < B; b++) if (sind::gba_plan(items[b], w.plan[b])) {
+        sind_set_error("%s %d is beyond a limit: %d key frames, %d points, %d observations, %d co-observation entries, %d entries of the factor's envelope", who, b, GBA_MAX_KF, GBA_MAX_MP, GBA_MAX_OBS, GBA_MAX_PAIRS, GBA_MAX_ENV);
+        return SIND_E_CAPACITY;
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    SIND_TRY(w.reserve(B, (size_t)m->maxB)); SIND_TRY(m->gbaSc.alloc(sind::GBA_SC_N));
+    const sind::MatchParams& c = m->prm;
+    const sind::PoseOptCam K{(double)c.fx, (double)c.fy, (double)c.cx, (double)c.cy, (double)c.bf};
+    for (int b = 0; b < B; b++) { sind::gba_fill(items[b], w.host(b)); sind::gba_bind(w.plan[b], K, w.dev(b), w.views.h[b]); }
+    hipStream_t s = m->stream;
+    SIND_TRY(w.I.up(w.at[B].ints, s)); SIND_TRY(w.Fin.up(w.at[B].floatsIn, s));
+    std::vector<sind::GbaDiag> dg((size_t)B);
+    m->gbaCount = sind::GbaCounters{};
+    for (int b = 0; b < B; b++) SIND_TRY(sind::launch_global_ba(w.views.h[b], w.plan[b].cs.data(), iterations, robust != 0, m->gbaSc.p, s, dg[b], m->gbaCount));
+    SIND_TRY(w.Fout.down(w.at[B].floatsOut, s));
+    HIP_TRY(hipStreamSynchronize(s)); m->gbaCount.waits++;
+    for (int b = 0; b < B; b++) sind::gba_store(items[b], w.plan[b], w.host(b), dg[b]);
+    return SIND_OK;
+}
+
+// the launches and host waits of the last sind_match_global_ba on the handle (profiles/match_global_ba_timing.py)
+int sind_match_global_ba_counts(sind_match* m, long long* launches, long long* waits) {
+    if (!m || !launches || !waits) return SIND_E_ARG;
+    *launches = m->gbaCount.launches; *waits = m->gbaCount.waits;
     return SIND_OK;
 }
 

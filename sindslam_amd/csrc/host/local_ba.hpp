@@ -114,14 +114,15 @@ SIND_HD inline void lba_inv3(const double m[3][3], double inv[3][3]) {
 
 // One edge: computeError (+ robustify); full: linearizeOplus (types_six_dof_expmap.cpp:103-139, :188-234, as written: divisions by z and z_2) and
 // constructQuadraticForm.  poseFree: vertex 1 is not fixed.  c: see LBA_C; not full: c[54] and c[55] alone; !poseFree: the pose entries and Hpl stay unwritten.
-// jac (the tests'): _jacobianOplusXi [3][3], _jacobianOplusXj [3][6] and the error [3]
-SIND_HD inline void lba_edge(const PoseQ& P, const PoseOptCam& K, const double X[3], const float* ob, bool robust, bool full, bool poseFree, double* c, double* jac = nullptr) {
+// jac (the tests'): _jacobianOplusXi [3][3], _jacobianOplusXj [3][6] and the error [3].  delta: the Huber deltas [mono, stereo] of a caller whose are not po_delta's
+// (global_ba.hpp: Optimizer::BundleAdjustment's sqrt(5.99)); NULL: po_delta, local BA's
+SIND_HD inline void lba_edge(const PoseQ& P, const PoseOptCam& K, const double X[3], const float* ob, bool robust, bool full, bool poseFree, double* c, double* jac = nullptr, const double* delta = nullptr) {
     const bool stereo = !(ob[2] < 0.0f);                             // if(pKFi->mvuRight[mit->second]<0) mono (Optimizer.cc:594)
     const double s = (double)ob[3];
     double e[3], Xc[3];
     const double chi2 = po_edge_error(P, K, X, (double)ob[0], (double)ob[1], (double)ob[2], stereo, s, e, Xc);
     double rho0 = chi2, rho1 = 1.0;
-    if (robust) po_huber(chi2, po_delta(stereo), &rho0, &rho1);
+    if (robust) po_huber(chi2, delta ? delta[stereo ? 1 : 0] : po_delta(stereo), &rho0, &rho1);
     c[54] = rho0; c[55] = chi2;
     if (!full) return;
     double R[3][3]; po_quat_to_matrix(P.q, R);

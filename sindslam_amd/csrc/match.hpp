@@ -4,6 +4,7 @@
 #include "common.hpp"
 #include "host/local_ba.hpp"
 #include "host/essential_graph.hpp"
+#include "host/global_ba.hpp"
 
 namespace sind {
 
@@ -130,6 +131,12 @@ int launch_local_ba(const LbaView* views, int B, hipStream_t s);
 #define ESS_PT_THREADS 256
 #define ESS_PT_BLOCKS 64                                             // per item: a full grid covers 16384 points in one pass, the lanes stride beyond it
 int launch_essential_graph(const EssView* views, int B, int maxMp, hipStream_t s);
+
+// Optimizer::BundleAdjustment, the optimize of a global BA: kernels per phase over the whole grid on stream s, the Levenberg-Marquardt driver on the host
+// (match_globalba.hip, host/global_ba.hpp).  w: device pointers throughout; cs: GbaPlan::cs; pinned: [GBA_SC_N] page-locked.  Returns after the last phase is enqueued
+#define GBA_THREADS 256                                              // profiles/match_global_ba.txt: the compiler's resource report of the edge kernel and the choice
+struct GbaCounters { long long launches = 0, waits = 0; };
+int launch_global_ba(const GbaView& w, const int* cs, int iterations, bool robust, double* pinned, hipStream_t s, GbaDiag& dg, GbaCounters& cnt);
 
 // Vocabulary-guided searches (match_bow.hip): SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation.  Side A is the one whose entries act
 // (the key frame / pKF1, capacity capLast), side B the one searched (the frame / pKF2, capacity capCur).

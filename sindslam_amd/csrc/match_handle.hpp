@@ -187,6 +187,8 @@ struct sind_match {
     } sim3opt;
     // sind_match_local_ba (match_localba.hip) and sind_match_essential_graph (match_essgraph.hip): each its own streams, grown by its own calls
     PackedItems<sind::LbaPlan, sind::LbaView> localba; PackedItems<sind::EssPlan, sind::EssView> ess;
+    // sind_match_global_ba (match_globalba.hip): the same streams, the items run one after the other; the scalars of the control flow come back through gbaSc
+    PackedItems<sind::GbaPlan, sind::GbaView> globalba; PinnedBuf<double> gbaSc; sind::GbaCounters gbaCount;       // gbaCount: launches and host waits of the last call
     int reserve_bow() {
         const size_t B = maxB, nl = B * prm.capLast, nc = B * prm.capCur; int r = SIND_OK;
         (r = last.node.alloc(nl)) || (r = last.xy.alloc(nl * 2)) || (r = last.uRight.alloc(nl)) || (r = cur.node.alloc(nc)) || (r = choice.alloc(nl)) || (r = bow.pose.alloc(B)) ||

@@ -120,6 +120,13 @@ class _EssGraphItem(C.Structure):
                 ("n_iters", C.c_void_p), ("chi2", C.c_void_p), ("lambda_", C.c_void_p), ("n_active", C.c_void_p), ("solver_fail", C.c_void_p)]
 
 
+class _GlobalBaItem(C.Structure):
+    _fields_ = [("n_kf", C.c_int), ("kf_id", C.c_void_p), ("Tcw", C.c_void_p), ("n_mp", C.c_int), ("mp_id", C.c_void_p), ("x3Dw", C.c_void_p),
+                ("obs_start", C.c_void_p), ("obs_kf", C.c_void_p), ("obs_xy", C.c_void_p), ("u_right", C.c_void_p), ("inv_sigma2", C.c_void_p),
+                ("Tcw_out", C.c_void_p), ("x3Dw_out", C.c_void_p), ("included", C.c_void_p), ("n_iters", C.c_void_p), ("chi2", C.c_void_p), ("lambda_", C.c_void_p),
+                ("n_active_poses", C.c_void_p), ("solver_fail", C.c_void_p), ("env_entries", C.c_void_p), ("env_dense_entries", C.c_void_p)]
+
+
 _f32 = lambda a: np.ascontiguousarray(a, np.float32)
 _u8 = lambda a: np.ascontiguousarray(a, np.uint8)
 _i32 = lambda a: np.ascontiguousarray(a, np.int32)
@@ -218,6 +225,29 @@ def localba_result(a):
                 **{k: a[k] for k in ("stage_iters", "stage_chi2", "stage_lambda")})
 
 
+def globalba_items(items):
+    """the sind_globalba_item array of ORBmatcher.GlobalBundleAdjustment's items, and the arrays it points to (which live as long as the caller keeps them)"""
+    arr = (_GlobalBaItem * len(items))(); keep = []
+    for q, it in zip(arr, items):
+        n_kf, n_mp = len(it["kf_id"]), len(it["mp_id"])
+        a = dict(kf_id=np.ascontiguousarray(it["kf_id"], np.int64), Tcw=_f32(it["Tcw"]).reshape(n_kf, 16).copy(), mp_id=np.ascontiguousarray(it["mp_id"], np.int64),
+                 x3Dw=_f32(it["x3Dw"]).reshape(n_mp, 3).copy(), obs_start=_i32(it["obs_start"]), obs_kf=_i32(it["obs_kf"]), obs_xy=_f32(it["obs_xy"]), u_right=_f32(it["u_right"]),
+                 inv_sigma2=_f32(it["inv_sigma2"]))
+        a.update(Tcw_out=a["Tcw"].copy(), x3Dw_out=a["x3Dw"].copy(), included=np.full(n_mp, 255, np.uint8), n_iters=np.zeros(1, np.int32), chi2=np.zeros(1, np.float64),
+                 lambda_=np.zeros(1, np.float64), n_active_poses=np.zeros(1, np.int32), solver_fail=np.zeros(1, np.int32), env_entries=np.zeros(1, np.int64),
+                 env_dense_entries=np.zeros(1, np.int64))
+        for key, v in a.items():
+            setattr(q, key, v.ctypes.data if v.size else None)
+        q.n_kf = n_kf; q.n_mp = n_mp
+        keep.append(a)
+    return arr, keep
+
+
+def globalba_result(a):
+    return dict(Tcw=a["Tcw_out"].reshape(-1, 4, 4), x3Dw=a["x3Dw_out"], included=a["included"], n_iters=int(a["n_iters"][0]), chi2=np.float64(a["chi2"][0]), lambda_=np.float64(a["lambda_"][0]),
+                n_active_poses=int(a["n_active_poses"][0]), solver_fail=int(a["solver_fail"][0]), env_entries=int(a["env_entries"][0]), env_dense_entries=int(a["env_dense_entries"][0]))
+
+
 def essgraph_items(items):
     """the sind_essgraph_item array of ORBmatcher.OptimizeEssentialGraph's items, and the arrays it points to (which live as long as the caller keeps them)"""
     arr = (_EssGraphItem * len(items))(); keep = []
@@ -253,7 +283,8 @@ class ORBmatcher:
     After every search of the tracking thread: Optimizer::PoseOptimization (src/Optimizer.cc:239-451; PoseOptimization, sindslam_amd/optimizer.py).
     After SearchBySim3 in LoopClosing::ComputeSim3: Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241; OptimizeSim3, sindslam_amd/optimizer.py).
     After SearchInNeighbors in LocalMapping::Run: Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778; LocalBundleAdjustment, sindslam_amd/optimizer.py).
-    After the loop fusion in LoopClosing::CorrectLoop: Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044; OptimizeEssentialGraph, sindslam_amd/optimizer.py)."""
+    After the loop fusion in LoopClosing::CorrectLoop: Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044; OptimizeEssentialGraph, sindslam_amd/optimizer.py).
+    After CorrectLoop, in LoopClosing::RunGlobalBundleAdjustment: Optimizer::BundleAdjustment (src/Optimizer.cc:49-237; GlobalBundleAdjustment, sindslam_amd/optimizer.py)."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
 
     def __init__(self, fx, fy, cx, cy, bf, bounds, scale_factors, nnratio=0.6, checkOri=True, cap=4096, max_batch=1, device=0, cap_points=0):
@@ -504,6 +535,23 @@ class ORBmatcher:
         arr, keep = essgraph_items(items)
         check(lib().sind_match_essential_graph(self._h, arr, len(items), int(bool(fix_scale))), "sind_match_essential_graph")
         return [essgraph_result(a) for a in keep]
+
+    def GlobalBundleAdjustment(self, items, iterations=10, robust=False):
+        """sind_match_global_ba: Optimizer::BundleAdjustment (src/Optimizer.cc:49-191, what GlobalBundleAdjustemnt forwards to) of every item, one after the other, each as
+        kernels per phase over the whole grid.  items: list of dicts: kf_id i64 [n_kf] strictly ascending (the key frame with id 0 is fixed), Tcw [n_kf, 4, 4]; mp_id i64 [n_mp],
+        x3Dw [n_mp, 3]; obs_start i32 [n_mp + 1], and per observation in the order the edges are added obs_kf i32 (index into the key frames), obs_xy [n_obs, 2], u_right [n_obs]
+        (< 0: monocular edge), inv_sigma2 [n_obs].  iterations: 10 in loop closing, 20 the reference's default, 0 = the stop flag set at entry.  robust: bRobust.
+        -> list of dicts: Tcw f32 [n_kf, 4, 4], x3Dw f32 [n_mp, 3], included u8 [n_mp] (0: a point without observations, vbNotIncludedMP), n_iters, chi2, lambda_,
+        n_active_poses, solver_fail, env_entries, env_dense_entries."""
+        arr, keep = globalba_items(items)
+        check(lib().sind_match_global_ba(self._h, arr, len(items), int(iterations), int(bool(robust))), "sind_match_global_ba")
+        return [globalba_result(a) for a in keep]
+
+    def global_ba_counts(self):
+        """-> (kernel launches, host waits) of the last GlobalBundleAdjustment on this handle"""
+        a, b = C.c_longlong(), C.c_longlong()
+        check(lib().sind_match_global_ba_counts(self._h, C.byref(a), C.byref(b)), "sind_match_global_ba_counts")
+        return a.value, b.value
 
     def last_rounds(self):
         return lib().sind_match_last_rounds(self._h)

@@ -5,7 +5,9 @@ rest of ComputeSim3 built on it (src/LoopClosing.cc:310-398): compute_sim3_accep
 Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778), the one call of LocalMapping::Run, over sind_match_local_ba: LocalBundleAdjustment collects the graph
 (:455-504) from a map of plain dicts, apply_local_ba writes the result back (:746-777).  Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044), the one
 call of LoopClosing::CorrectLoop, over sind_match_essential_graph: essential_graph_item collects the pose graph (:797-983), apply_essential_graph writes poses and
-points back, correct_loop is CorrectLoop around them (src/LoopClosing.cc:402-584).
+points back, correct_loop is CorrectLoop around them (src/LoopClosing.cc:402-584).  Optimizer::BundleAdjustment (src/Optimizer.cc:49-237), the global bundle adjustment that
+follows CorrectLoop, over sind_match_global_ba: global_ba_item, GlobalBundleAdjustment, apply_global_ba, and run_global_bundle_adjustment, which is
+LoopClosing::RunGlobalBundleAdjustment around them (src/LoopClosing.cc:645-749).
 
 A frame is a dict of per-keypoint arrays: un_xy [N, 2] (mvKeysUn[i].pt), u_right [N] (mvuRight), inv_sigma2 [N] (mvInvLevelSigma2[mvKeysUn[i].octave]), mp i64 [N] (the id of
 mvpMapPoints[i], -1 for NULL), x3Dw [N, 3] (GetWorldPos() of that map point; rows without one are not read), Tcw [4, 4] (mTcw), and optionally outlier [N] (mvbOutlier).
@@ -472,7 +474,8 @@ def correct_loop(matcher, keyframes, mappoints, cur_kf, loop_kf, g2oScw, matched
     map-point ids (-1 for NULL).  matcher: an ORBmatcher or anything with OptimizeEssentialGraph(items, fix_scale).  fuse(corrected) is SearchAndFuse (:586-621): called
     with CorrectedSim3 after the loop fusion, it returns a list of (point to replace, loop map point) from ORBmatcher.FuseSim3 on the caller's key frames, which are
     replaced here; None: nothing to fuse.  The maps are walked in ascending id (the reference: by pointer).  trace: a dict that gets corrected, non_corrected,
-    loop_connections, item, kfs, mps and result.  The map IS modified."""
+    loop_connections, item, kfs, mps and result.  The map IS modified.  The reference's next call is the global bundle adjustment in a thread of its own
+    (:579): run_global_bundle_adjustment below."""
     Scw = _s3(g2oScw["q"], g2oScw["t"], g2oScw["s"]) if isinstance(g2oScw, dict) else _s3(*g2oScw)
     with np.errstate(all="ignore"):
         update_connections(cur_kf, keyframes, mappoints)                # :429
@@ -519,3 +522,117 @@ def correct_loop(matcher, keyframes, mappoints, cur_kf, loop_kf, g2oScw, matched
     if trace is not None:
         trace.update(corrected=corrected, non_corrected=non_corrected, loop_connections=loop_connections, item=item, kfs=kfs, mps=mps, result=result)
     return result
+
+
+# ---------------------------------------------------------------- Optimizer::GlobalBundleAdjustemnt / BundleAdjustment and LoopClosing::RunGlobalBundleAdjustment
+def _mat44(A, B):
+    """A * B of two 4 x 4 cv::Mat in FP32, per entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3, as _to_camera treats cv::Mat products"""
+    A = np.asarray(A, np.float32).reshape(4, 4); B = np.asarray(B, np.float32).reshape(4, 4)
+    return np.array([[((A[r, 0] * B[0, c] + A[r, 1] * B[1, c]) + A[r, 2] * B[2, c]) + A[r, 3] * B[3, c] for c in range(4)] for r in range(4)], np.float32)
+
+
+def _pose_inverse(Tcw):
+    """GetPoseInverse(), in float as SetPose forms it"""
+    Tcw = np.asarray(Tcw, np.float32).reshape(4, 4)
+    Twc = np.eye(4, dtype=np.float32); Twc[:3, :3] = Tcw[:3, :3].T; Twc[:3, 3] = -(Tcw[:3, :3].T @ Tcw[:3, 3])
+    return Twc
+
+
+def global_ba_item(keyframes, mappoints):
+    """The graph collection of Optimizer::BundleAdjustment (:68-184) over the plain dicts of local_ba_graph: every key frame and every point that is not bad, the key frames
+    in ascending id; a point's observations in ascending key-frame id (the reference walks a std::map keyed by pointers), those in bad key frames left out (:109).
+    -> item: the dict ORBmatcher.GlobalBundleAdjustment takes, with kfs and mps = the ids of its key frames and points"""
+    kfs = sorted(k for k in keyframes if not keyframes[k].get("bad"))
+    mps = sorted(m for m in mappoints if not mappoints[m].get("bad"))
+    row = {k: i for i, k in enumerate(kfs)}
+    obs_start, obs_kf, xy, ur, s2 = [0], [], [], [], []
+    for m in mps:
+        for k in sorted(mappoints[m]["obs"]):
+            if k not in row:
+                continue
+            slot = mappoints[m]["obs"][k]; f = keyframes[k]
+            obs_kf.append(row[k]); xy.append(np.asarray(f["un_xy"], np.float32)[slot]); ur.append(np.float32(f["u_right"][slot])); s2.append(np.float32(f["inv_sigma2"][slot]))
+        obs_start.append(len(obs_kf))
+    item = dict(kf_id=np.array(kfs, np.int64), Tcw=np.array([np.asarray(keyframes[k]["Tcw"], np.float32).reshape(4, 4) for k in kfs], np.float32).reshape(len(kfs), 4, 4),
+                mp_id=np.array(mps, np.int64), x3Dw=np.array([np.asarray(mappoints[m]["x3Dw"], np.float32) for m in mps], np.float32).reshape(len(mps), 3),
+                obs_start=np.array(obs_start, np.int32), obs_kf=np.array(obs_kf, np.int32), obs_xy=np.array(xy, np.float32).reshape(len(obs_kf), 2), u_right=np.array(ur, np.float32),
+                inv_sigma2=np.array(s2, np.float32), kfs=kfs, mps=mps)
+    return item
+
+
+def GlobalBundleAdjustment(matcher, keyframes, mappoints, iterations=20, robust=True):
+    """Optimizer::GlobalBundleAdjustemnt(pMap, nIterations, pbStopFlag, nLoopKF, bRobust) up to the recovery (:39-188): global_ba_item, then matcher.GlobalBundleAdjustment
+    (an ORBmatcher or anything with that method).  The defaults are the reference's.  The map is not modified: apply_global_ba does that.
+    -> dict(poses {kf id: Tcw f32 [4, 4]}, points {mp id: x3Dw f32 [3]} of the points the graph included, item, result = the call's raw result)"""
+    item = global_ba_item(keyframes, mappoints)
+    r = matcher.GlobalBundleAdjustment([item], iterations, robust)[0]
+    return dict(poses={k: np.array(r["Tcw"][i], np.float32) for i, k in enumerate(item["kfs"])},
+                points={m: np.array(r["x3Dw"][j], np.float32) for j, m in enumerate(item["mps"]) if r["included"][j]}, item=item, result=r)
+
+
+def apply_global_ba(keyframes, mappoints, result, nLoopKF):
+    """:193-235 on the dicts, result = what GlobalBundleAdjustment above returns.  nLoopKF == 0: SetPose and SetWorldPos (UpdateNormalAndDepth is not in the library: the
+    caller's step).  Else TcwGBA / PosGBA and ba_global_for_kf = nLoopKF (mTcwGBA, mPosGBA, mnBAGlobalForKF).  A point the graph did not include (no observation) is left
+    alone; a key frame or point that became bad meanwhile too."""
+    for k, T in result["poses"].items():
+        if keyframes[k].get("bad"):
+            continue
+        T = np.array(T, np.float32).reshape(4, 4)
+        if nLoopKF == 0:
+            keyframes[k]["Tcw"] = T
+        else:
+            keyframes[k]["TcwGBA"] = T; keyframes[k]["ba_global_for_kf"] = nLoopKF
+    for m, X in result["points"].items():
+        if mappoints[m].get("bad"):
+            continue
+        X = np.array(X, np.float32)
+        if nLoopKF == 0:
+            mappoints[m]["x3Dw"] = X
+        else:
+            mappoints[m]["PosGBA"] = X; mappoints[m]["ba_global_for_kf"] = nLoopKF
+
+
+def propagate_global_ba(keyframes, mappoints, nLoopKF, origins):
+    """LoopClosing::RunGlobalBundleAdjustment after the optimizer (src/LoopClosing.cc:676-737) on the dicts: the correction goes through the spanning tree, breadth first
+    from `origins` (mvpKeyFrameOrigins), to the key frames the BA did not hold (created while it ran): Tchildc = Tcw_child * Twc and TcwGBA = Tchildc * parent's TcwGBA, both
+    products in FP32; every key frame keeps TcwBefGBA and takes TcwGBA.  A point the BA held takes PosGBA; another one is moved with its reference key frame (ref_kf), into
+    the camera of TcwBefGBA and back out through the corrected pose, in FP32.  Children are walked in ascending id (the reference: a std::set of pointers)."""
+    queue = list(origins)
+    while queue:
+        k = queue.pop(0); kf = keyframes[k]
+        Twc = _pose_inverse(kf["Tcw"])
+        for c in sorted(kf.get("children", ())):
+            ch = keyframes[c]
+            if ch.get("ba_global_for_kf", 0) != nLoopKF:
+                ch["TcwGBA"] = _mat44(_mat44(ch["Tcw"], Twc), kf["TcwGBA"])
+                ch["ba_global_for_kf"] = nLoopKF
+            queue.append(c)
+        kf["TcwBefGBA"] = np.array(kf["Tcw"], np.float32).reshape(4, 4)
+        kf["Tcw"] = np.array(kf["TcwGBA"], np.float32).reshape(4, 4)
+    for m in sorted(mappoints):
+        mp = mappoints[m]
+        if mp.get("bad"):
+            continue
+        if mp.get("ba_global_for_kf", 0) == nLoopKF:
+            mp["x3Dw"] = np.array(mp["PosGBA"], np.float32)
+        else:
+            ref = keyframes[mp["ref_kf"]]
+            if ref.get("ba_global_for_kf", 0) != nLoopKF:
+                continue
+            Xc = _to_camera(ref["TcwBefGBA"], mp["x3Dw"])
+            mp["x3Dw"] = _to_camera(_pose_inverse(ref["Tcw"]), Xc)[0]
+
+
+def run_global_bundle_adjustment(matcher, keyframes, mappoints, nLoopKF, origins, iterations=10, robust=False, during=None, trace=None):
+    """LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:645-749) on the dicts: GlobalBundleAdjustment above (matcher: an ORBmatcher or anything with its
+    GlobalBundleAdjustment; the reference passes 10 iterations and no kernels), apply_global_ba, propagate_global_ba.  during(keyframes, mappoints): called between the collection and the
+    update, where local mapping adds key frames and points in the reference.  The stop flag, the idx check and the two mutexes are the caller's.  The map IS modified."""
+    result = GlobalBundleAdjustment(matcher, keyframes, mappoints, iterations, robust)
+    if during is not None:
+        during(keyframes, mappoints)
+    apply_global_ba(keyframes, mappoints, result, nLoopKF)
+    if nLoopKF != 0:
+        propagate_global_ba(keyframes, mappoints, nLoopKF, origins)
+    if trace is not None:
+        trace.update(result)
+    return result["result"]
