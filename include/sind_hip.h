@@ -796,7 +796,7 @@ int sind_match_sim3_optimize(sind_match* m, const sind_sim3opt_item* items, int 
  * the order of every sum).  Calibration is the handle's fx fy cx cy bf, as for sind_match_pose_optimize.
  * What stays with the caller: the graph collection (:455-504: lLocalKeyFrames, lLocalMapPoints, lFixedCameras; sindslam_amd/optimizer.py mirrors it), and after the
  * call, under the map mutex, EraseMapPointMatch and EraseObservation for every erased observation (:748-757), SetPose (:762-768), SetWorldPos and
- * UpdateNormalAndDepth (:771-777).
+ * UpdateNormalAndDepth (:771-777; sind_match_update_points below does the latter for all points in one call).
  * Inputs: kf_kind 0 = a local key frame, 1 = a local key frame that is fixed (mnId == 0), 2 = a fixed camera; Tcw = GetPose(); the points in lLocalMapPoints order
  * with x3Dw = GetWorldPos(); the observations of point j are obs_start[j] .. obs_start[j + 1] - 1 in the order the edges are added (key frames that are bad left out):
  * obs_kf the index of the key frame in 0 .. n_kf - 1, obs_xy = mvKeysUn[slot].pt, u_right = mvuRight[slot] (< 0: the monocular edge), inv_sigma2 =
@@ -840,7 +840,8 @@ int sindh_local_ba(const sind_localba_item* items, int B, const float* K5);   /*
  * (csrc/match_essgraph.hip: k_ess_graph, one workgroup per item, then k_ess_points over the points of all items; csrc/host/essential_graph.hpp is one FP64 source for
  * host and device and states the order of every sum).
  * What stays with the caller: which edges exist (:853-983: the minFeat = 100 weights and the (cur, loop) exception, sInsertedEdges, parent, hasChild, sLoopEdges and
- * the mnId comparisons; sindslam_amd/optimizer.py mirrors the collection) and, under the map mutex, SetPose, SetWorldPos and UpdateNormalAndDepth with the outputs.
+ * the mnId comparisons; sindslam_amd/optimizer.py mirrors the collection) and, under the map mutex, SetPose, SetWorldPos and UpdateNormalAndDepth with the outputs
+ * (sind_match_update_points below does the latter for all points in one call).
  * Inputs: the key frames in ascending mnId (kf_id), Tcw = GetPose(); has_corrected / corrected = the CorrectedSim3 entry of the key frame (qx qy qz qw tx ty tz s),
  * has_noncorrected / noncorrected = its NonCorrectedSim3 entry; fixed_kf = the index of pLoopKF.  vScw[i] is the corrected entry if present, else Sim3(Rcw, tcw, 1.0).
  * The edges in the order the reference adds them: edge_i is vertex 0 and edge_j vertex 1; edge_kind 0 = a LoopConnections edge, its measurement Sjw * Swi from vScw of
@@ -885,7 +886,8 @@ int sindh_essential_graph(const sind_essgraph_item* items, int B, int fix_scale)
  * csrc/host/global_ba.hpp is one FP64 source for host and device and states the order of every sum: it is local BA's contract, with the reduced camera system stored and
  * factored as a natural-order envelope in 6 x 6 block rows.  The B items of a call run one after the other.  Calibration is the handle's fx fy cx cy bf.
  * What stays with the caller: the collection of the graph (:68-184; sindslam_amd/optimizer.py mirrors it) and what follows the optimize (:193-235: SetPose / SetWorldPos
- * or mTcwGBA / mPosGBA), and the tail of RunGlobalBundleAdjustment (sindslam_amd/optimizer.py: run_global_bundle_adjustment).
+ * or mTcwGBA / mPosGBA, and UpdateNormalAndDepth, which sind_match_update_points below does for all points in one call), and the tail of RunGlobalBundleAdjustment
+ * (sindslam_amd/optimizer.py: run_global_bundle_adjustment).
  * Inputs: the key frames that are not bad in ascending mnId (kf_id), Tcw = GetPose(); the points that are not bad, x3Dw = GetWorldPos(); the observations of point j are
  * obs_start[j] .. obs_start[j + 1] - 1 in the order the edges are added, those in bad key frames or in key frames the call does not hold left out (:109): obs_kf the
  * index of the key frame, obs_xy = mvKeysUn[slot].pt, u_right = mvuRight[slot] (< 0: the monocular edge), inv_sigma2 = mvInvLevelSigma2[octave].  iterations: the
@@ -920,6 +922,84 @@ typedef struct sind_globalba_item {
 int sind_match_global_ba(sind_match* m, const sind_globalba_item* items, int B, int iterations, int robust);
 int sind_match_global_ba_counts(sind_match* m, long long* launches, long long* waits);   /* of the last sind_match_global_ba on the handle: kernel launches, host waits */
 int sindh_global_ba(const sind_globalba_item* items, int B, int iterations, int robust, const float* K5);   /* host twin (libsind_host.so too): K5 = fx fy cx cy bf */
+
+/* Map-point upkeep on the matcher handle (csrc/capi_match_map.cpp, csrc/match_mappoints.hip; csrc/host/map_points.hpp is one source for host and device and states
+ * the type of every step).
+ *
+ * sind_match_triangulate.  Replaces, for B (current key frame, neighbour) pairs at once, the per-match loop of
+ *   void LocalMapping::CreateNewMapPoints()                                                             src/LocalMapping.cc:284-431
+ *   cv::Mat KeyFrame::UnprojectStereo(int i)                                                            src/KeyFrame.cc:615-631
+ * from the ray parallax to the scale-consistency test: ONE launch, one lane per match over the matches of all pairs (k_tri_points), everything of a match in registers.
+ * fx fy cx cy bf, scale_factors and nlevels are the handle's: invfx = 1.0f / fx, mb = bf / fx, mvLevelSigma2[l] = scale[l] * scale[l], ratioFactor = 1.5f * scale[1],
+ * all in FP32.  Capacities: kf1.n <= cap_last, kf2.n <= cap_cur, B <= max_batch.
+ * What stays with the caller: the neighbours and the baseline test (:213-261), ComputeF12 and sind_match_for_triangulation before the call; after it, for every
+ * status 0 in (pair, idx1) order, new MapPoint, both AddObservation, both AddMapPoint and the list (:434-449), then sind_match_update_points over the new points
+ * (sindslam_amd/mapping.py: create_new_map_points does all of it on plain dicts).
+ * Inputs: Tcw1 / Twc1 = GetPose() / GetPoseInverse() of the current key frame, Tcw2 / Twc2 of the neighbour, 4x4 row-major, rows 0..2 are read (Ow = column 3 of Twc;
+ * Rwc of the rays = the transpose of Tcw's rotation, the rotation of UnprojectStereo = Twc's, as there); per key frame and keypoint xy = mvKeys[i].pt (the distorted
+ * key, read by UnprojectStereo), un_xy = mvKeysUn[i].pt, octave = mvKeysUn[i].octave, u_right = mvuRight, depth = mvDepth; match12 [kf1.n] exactly as
+ * sind_match_for_triangulation writes it.  The matches are walked in ascending idx1, the order of vMatchedIndices.
+ * Outputs, [kf1.n] like match12: x3D (the point where one was formed, else zeros), how (0 triangulated by the 4x4 SVD, 1 UnprojectStereo of key frame 1, 2 of key
+ * frame 2, -1 none), status: 0 a new point; 1 no stereo and low parallax (:349); 2 w == 0 (:333); 3 z1 <= 0; 4 z2 <= 0; 5 reprojection in key frame 1; 6 in key frame 2;
+ * 7 a zero distance; 8 scale inconsistency; -1 where match12 < 0 (x3D zeros, how -1).  *nnew = the entries with status 0.
+ * cos(2 * atan2(mb / 2, depth)) is evaluated with the float overloads of the C library ON THE HOST inside the call, once per match with a stereo side, and never on the
+ * device; the kernel receives the cosine.
+ * Valid: B = 0; pairs without matches; kf1.n = 0.
+ * Unpinned: parity with a real OpenCV build (the 4x4 SVD is OpenCV 4.2's JacobiSVDImpl_<float> restated; the small-matrix conventions of csrc/match_local.hip).
+ * SIND_E_CAPACITY beyond the capacities.  SIND_E_ARG: a NULL array with a non-zero count, a match12 entry outside [-1, kf2.n), an octave outside [0, nlevels), a pose
+ * that is not finite, a matched keypoint with u_right >= 0 and depth <= 0 (the reference's UnprojectStereo returns an empty matrix there and the loop goes on to read
+ * it).  On an error nothing is launched and the outputs are untouched.
+ */
+typedef struct sind_tri_side { int n; const float* xy; const float* un_xy; const int* octave; const float* u_right; const float* depth; } sind_tri_side;   /* [n][2] x2, [n] x3 */
+typedef struct sind_tri_pair {
+    const float* Tcw1; const float* Twc1; const float* Tcw2; const float* Twc2;      /* [16] each */
+    sind_tri_side kf1, kf2;
+    const int* match12;                                                               /* [kf1.n]: idx2 or -1 */
+    float* x3D; int* how; int* status; int* nnew;                                     /* outputs (host): [kf1.n][3], [kf1.n], [kf1.n], [1] */
+} sind_tri_pair;
+int sind_match_triangulate(sind_match* m, const sind_tri_pair* pairs, int B);
+/* host twin (libsind_host.so too): K5 = fx fy cx cy bf; no capacities */
+int sindh_triangulate(const sind_tri_pair* pairs, int B, const float* K5, const float* scale_factors, int nlevels);
+
+/* sind_match_update_points.  Replaces, for every point of B lists at once,
+ *   void MapPoint::ComputeDistinctiveDescriptors()                                                      src/MapPoint.cc:242-307
+ *   void MapPoint::UpdateNormalAndDepth()                                                               src/MapPoint.cc:330-371
+ * the pair the reference calls for every point of a new key frame (LocalMapping.cc:152-153), for every new point (:442-444), after Fuse (:526-527), after local BA
+ * (Optimizer.cc:776), after the essential graph (:1042) and a global BA (:227) and in LoopClosing.cc:500, :532.  Its outputs are what sind_match_local_map, sind_match_fuse,
+ * sind_match_by_projection_sim3 and sind_match_by_sim3 take per map point: desc, normal, max_dist, min_dist.  TWO launches on the handle's stream with one host wait:
+ * k_mp_descriptor, one wave per point (all-pairs Hamming distances row by row, the row's median by bisection with wave ballots, nothing stored or sorted), and
+ * k_mp_normal, one lane per point, which walks its list in order.  scale_factors and nlevels are the handle's.
+ * What stays with the caller: isBad() of the point (a bad point is not passed), the locks, and writing the outputs to the map.
+ * Inputs: Ow [n_kf][3] = GetCameraCenter() of the key frames the item's observations name; x3Dw [n_mp][3] = GetWorldPos(); the observations of point j are obs_start[j]
+ * .. obs_start[j + 1] - 1 (the layout of sind_localba_item) in the order the caller's map iterates (the reference: a std::map keyed by pointers; the Python mirror:
+ * ascending mnId): obs_kf the index into Ow, obs_bad = pKF->isBad(), obs_octave = mvKeysUn[slot].octave, obs_desc = the 32 bytes of mDescriptors.row(slot); ref_obs[j] =
+ * the position of mpRefKF within point j's own list (0 .. count - 1; -1: not in it).  do_descriptor, do_normal: which of the two functions run.
+ * Outputs.  Descriptor: only observations in key frames that are not bad enter, N their number; the median of a row is entry (int)(0.5 * (N - 1)) of its N sorted distances
+ * (the zero to itself included); the FIRST row with the strictly smallest median wins.  best_obs[j] = its position in the point's list, desc_out[j] = its 32 bytes; where
+ * the reference returns early (no observations, or every observer bad) best_obs[j] = -1 and desc_out[j] is untouched.  Normal: ALL observations enter the sum, those in bad
+ * key frames too, as there; sequential FP32 in list order.  normal_out = mNormalVector, max_dist = mfMaxDistance, min_dist = mfMinDistance: the members, before the
+ * 1.2f / 0.8f of GetMaxDistanceInvariance / GetMinDistanceInvariance, as the searches take them; updated[j] = 1, or 0 where the reference returns on empty observations
+ * and the three are untouched.  With do_descriptor = 0 desc_out and best_obs are untouched (and may be NULL), with do_normal = 0 the other four.
+ * Valid: B = 0; n_mp = 0; points without observations.
+ * Unpinned: cv::norm and the MatExpr scalings (the conventions of csrc/match_local.hip).
+ * Limits: 4096 key frames, 65536 points, 2^20 observations per item, B <= max_batch: beyond them SIND_E_CAPACITY.  No limit on the observations of one point below
+ * these.  The workspace lives on the handle, grows between calls to the largest call seen and is freed with the handle.
+ * SIND_E_ARG: a NULL array with a non-zero count, a negative count, an obs_start that does not start at 0 or decreases, an obs_kf, an obs_octave or a ref_obs out of
+ * range, ref_obs = -1 on a point that has observations while do_normal is set (the reference would index a map entry that does not exist), a position or camera centre
+ * that is not finite.  On an error nothing is launched and the outputs are untouched.
+ */
+typedef struct sind_mappoints_item {
+    int n_kf; const float* Ow;                                                        /* [n_kf][3] */
+    int n_mp; const float* x3Dw;                                                      /* [n_mp][3] */
+    const int* obs_start;                                                             /* [n_mp + 1] */
+    const int* obs_kf; const uint8_t* obs_bad; const int* obs_octave; const uint8_t* obs_desc;   /* [n_obs], [n_obs], [n_obs], [n_obs][32] */
+    const int* ref_obs;                                                               /* [n_mp] */
+    int do_descriptor, do_normal;
+    uint8_t* desc_out; int* best_obs;                                                 /* outputs (host): [n_mp][32], [n_mp] */
+    float* normal_out; float* max_dist; float* min_dist; uint8_t* updated;            /* [n_mp][3], [n_mp] x3 */
+} sind_mappoints_item;
+int sind_match_update_points(sind_match* m, const sind_mappoints_item* items, int B);
+int sindh_update_points(const sind_mappoints_item* items, int B, const float* scale_factors, int nlevels);   /* host twin (libsind_host.so too); no limits */
 
 /* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of

@@ -1,7 +1,8 @@
 // CPU-only test shim over the product's HOST stages (bit-image morphology, border following, homography, PEAC graph,
 // octree).  Built with plain g++ into libsind_host.so so that `pytest -m "not gpu"` can exercise the host logic against
 // the oracle without a GPU.  Not part of libsind_hip.so's ABI and never used by the product path.
-// The entry points of the solvers live with their sources: sindh_sim3_* in sim3.cpp, sindh_pnp_* in pnp.cpp, sindh_pose_optimize in pose_opt.cpp, sindh_sim3_optimize in sim3_opt.cpp, sindh_local_ba in local_ba.cpp.
+// The entry points of the solvers live with their sources: sindh_sim3_* in sim3.cpp, sindh_pnp_* in pnp.cpp, sindh_pose_optimize in pose_opt.cpp, sindh_sim3_optimize in sim3_opt.cpp, sindh_local_ba in local_ba.cpp,
+// sindh_essential_graph in essential_graph.cpp, sindh_global_ba in global_ba.cpp, sindh_triangulate and sindh_update_points in map_points.cpp.
 #include <cstring>
 #include "host.hpp"
 #include "peac_fit4.hpp"

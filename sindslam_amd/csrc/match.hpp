@@ -5,6 +5,7 @@
 #include "host/local_ba.hpp"
 #include "host/essential_graph.hpp"
 #include "host/global_ba.hpp"
+#include "host/map_points.hpp"
 
 namespace sind {
 
@@ -137,6 +138,16 @@ int launch_essential_graph(const EssView* views, int B, int maxMp, hipStream_t s
 #define GBA_THREADS 256                                              // profiles/match_global_ba.txt: the compiler's resource report of the edge kernel and the choice
 struct GbaCounters { long long launches = 0, waits = 0; };
 int launch_global_ba(const GbaView& w, const int* cs, int iterations, bool robust, double* pinned, hipStream_t s, GbaDiag& dg, GbaCounters& cnt);
+
+// Map-point upkeep (match_mappoints.hip, host/map_points.hpp).  k_tri_points: the loop of LocalMapping::CreateNewMapPoints, one lane per match over the n matches of all
+// pairs of a call.  k_mp_descriptor: MapPoint::ComputeDistinctiveDescriptors, one wave per point; k_mp_normal: MapPoint::UpdateNormalAndDepth, one lane per point.
+// Device pointers throughout; profiles/match_map_points.txt has the compiler's resource report
+#define TRI_THREADS 64
+#define MPD_THREADS 256                                              // four waves, four points
+#define MPN_THREADS 64
+int launch_tri_points(const TriCam& c, const TriPair* pairs, const TriMatch* matches, TriOut* out, int n, hipStream_t s);
+int launch_mp_descriptor(const MpArrays& a, int nPts, hipStream_t s);
+int launch_mp_normal(const MpCam& c, const MpArrays& a, int nPts, hipStream_t s);
 
 // Vocabulary-guided searches (match_bow.hip): SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation.  Side A is the one whose entries act
 // (the key frame / pKF1, capacity capLast), side B the one searched (the frame / pKF2, capacity capCur).

@@ -1,6 +1,7 @@
 // The matcher handle behind the C ABI "sind_match_*" (include/sind_hip.h) and what more than one family of its entry points uses.  The entry points: capi_match.cpp
 // (create, destroy, the projection searches), capi_match_kf.cpp (projections into a key frame), capi_match_bow.cpp (the vocabulary searches), capi_match_ransac.cpp
-// (Sim3 and PnP RANSAC), capi_match_opt.cpp (the four optimizers).  What one family alone uses stays in its file.
+// (Sim3 and PnP RANSAC), capi_match_opt.cpp (the optimizers), capi_match_map.cpp (map-point upkeep: triangulation, descriptor, normal and depth).  What one family
+// alone uses stays in its file.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -189,6 +190,19 @@ struct sind_match {
     PackedItems<sind::LbaPlan, sind::LbaView> localba; PackedItems<sind::EssPlan, sind::EssView> ess;
     // sind_match_global_ba (match_globalba.hip): the same streams, the items run one after the other; the scalars of the control flow come back through gbaSc
     PackedItems<sind::GbaPlan, sind::GbaView> globalba; PinnedBuf<double> gbaSc; sind::GbaCounters gbaCount;       // gbaCount: launches and host waits of the last call
+    // sind_match_triangulate (match_mappoints.hip): the pairs and the matches of a call, grown to the largest call seen
+    struct TriSide { Staged<sind::TriPair> pair; Staged<sind::TriMatch> match; Staged<sind::TriOut> out; std::vector<sind::TriMatch> list; } tri;
+    // sind_match_update_points (match_mappoints.hip): the items of a call one after the other, grown to the largest call seen
+    struct MapSide {
+        Staged<int> obsFirst, obsCount, refObs, obsKf, obsOctave, bestObs; Staged<uint8_t> todo, obsBad, updated; Staged<float> x3Dw, Ow, normal, maxDist, minDist; Staged<uint32_t> obsDesc, descOut;
+        int reserve(size_t nKf, size_t nPts, size_t nObs) {
+            int r = SIND_OK;
+            (r = obsFirst.alloc(nPts)) || (r = obsCount.alloc(nPts)) || (r = refObs.alloc(nPts)) || (r = bestObs.alloc(nPts)) || (r = todo.alloc(nPts)) || (r = updated.alloc(nPts)) ||
+                (r = x3Dw.alloc(3 * nPts)) || (r = normal.alloc(3 * nPts)) || (r = maxDist.alloc(nPts)) || (r = minDist.alloc(nPts)) || (r = descOut.alloc(DESC_WORDS * nPts)) ||
+                (r = obsKf.alloc(nObs)) || (r = obsOctave.alloc(nObs)) || (r = obsBad.alloc(nObs)) || (r = obsDesc.alloc(DESC_WORDS * nObs)) || (r = Ow.alloc(3 * nKf));
+            return r;
+        }
+    } mapPts;
     int reserve_bow() {
         const size_t B = maxB, nl = B * prm.capLast, nc = B * prm.capCur; int r = SIND_OK;
         (r = last.node.alloc(nl)) || (r = last.xy.alloc(nl * 2)) || (r = last.uRight.alloc(nl)) || (r = cur.node.alloc(nc)) || (r = choice.alloc(nl)) || (r = bow.pose.alloc(B)) ||

@@ -7,7 +7,8 @@ Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778), the one call of Loc
 call of LoopClosing::CorrectLoop, over sind_match_essential_graph: essential_graph_item collects the pose graph (:797-983), apply_essential_graph writes poses and
 points back, correct_loop is CorrectLoop around them (src/LoopClosing.cc:402-584).  Optimizer::BundleAdjustment (src/Optimizer.cc:49-237), the global bundle adjustment that
 follows CorrectLoop, over sind_match_global_ba: global_ba_item, GlobalBundleAdjustment, apply_global_ba, and run_global_bundle_adjustment, which is
-LoopClosing::RunGlobalBundleAdjustment around them (src/LoopClosing.cc:645-749).
+LoopClosing::RunGlobalBundleAdjustment around them (src/LoopClosing.cc:645-749).  MapPoint::UpdateNormalAndDepth after the three graph optimizers (:776, :1042, :227), over
+sind_match_update_points: update_after_local_ba, update_after_essential_graph, update_after_global_ba (sindslam_amd/mapping.py has the call).
 
 A frame is a dict of per-keypoint arrays: un_xy [N, 2] (mvKeysUn[i].pt), u_right [N] (mvuRight), inv_sigma2 [N] (mvInvLevelSigma2[mvKeysUn[i].octave]), mp i64 [N] (the id of
 mvpMapPoints[i], -1 for NULL), x3Dw [N, 3] (GetWorldPos() of that map point; rows without one are not read), Tcw [4, 4] (mTcw), and optionally outlier [N] (mvbOutlier).
@@ -307,7 +308,7 @@ def LocalBundleAdjustment(matcher, kf_id, keyframes, mappoints, do_more=True):
 def apply_local_ba(keyframes, mappoints, result):
     """:746-777 on the dicts: for every pair of vToErase EraseMapPointMatch (the slot's map point becomes -1) and EraseObservation (the observation goes; with two or
     fewer observations left, a stereo one counting twice, the point gets its bad flag and loses the rest, src/MapPoint.cc:118-146), then SetPose and SetWorldPos.
-    UpdateNormalAndDepth is not in the library: it stays the caller's step after this one."""
+    UpdateNormalAndDepth is the step after this one: update_after_local_ba."""
     for k, m in result["erase"]:
         mp = mappoints[m]
         if k not in mp["obs"]:
@@ -322,6 +323,13 @@ def apply_local_ba(keyframes, mappoints, result):
         keyframes[k]["Tcw"] = np.array(T, np.float32).reshape(4, 4)
     for m, X in result["points"].items():
         mappoints[m]["x3Dw"] = np.array(X, np.float32)
+
+
+def update_after_local_ba(matcher, keyframes, mappoints, result):
+    """:771-777, the step after apply_local_ba: UpdateNormalAndDepth of every local map point (lLocalMapPoints; a point that became bad is left alone, as the function
+    returns on mbBad), in one call of matcher.UpdateMapPoints (mapping.update_map_points).  result = what LocalBundleAdjustment above returns.  -> the updated ids"""
+    from .mapping import update_map_points
+    return update_map_points(matcher, result["map_points"], keyframes, mappoints, descriptor=False)
 
 
 # ---------------------------------------------------------------- LoopClosing::CorrectLoop and Optimizer::OptimizeEssentialGraph
@@ -461,11 +469,18 @@ def essential_graph_item(keyframes, mappoints, loop_kf, cur_kf, non_corrected, c
 
 
 def apply_essential_graph(keyframes, mappoints, kfs, mps, result):
-    """:999-1040 on the dicts: SetPose(Tiw) of every key frame and SetWorldPos of every point.  UpdateNormalAndDepth is not in the library: the caller's step after this one."""
+    """:999-1040 on the dicts: SetPose(Tiw) of every key frame and SetWorldPos of every point.  UpdateNormalAndDepth is the step after this one: update_after_essential_graph."""
     for i, k in enumerate(kfs):
         keyframes[k]["Tcw"] = np.array(result["Tiw"][i], np.float32).reshape(4, 4)
     for j, m in enumerate(mps):
         mappoints[m]["x3Dw"] = np.array(result["x3Dw"][j], np.float32)
+
+
+def update_after_essential_graph(matcher, keyframes, mappoints, mps):
+    """:1042, the step after apply_essential_graph: UpdateNormalAndDepth of every map point the graph corrected (mps = the ids essential_graph_item returned: the points
+    of the map that are not bad), in one call of matcher.UpdateMapPoints.  -> the updated ids"""
+    from .mapping import update_map_points
+    return update_map_points(matcher, mps, keyframes, mappoints, descriptor=False)
 
 
 def correct_loop(matcher, keyframes, mappoints, cur_kf, loop_kf, g2oScw, matched_points, fix_scale=True, fuse=None, trace=None):
@@ -571,8 +586,8 @@ def GlobalBundleAdjustment(matcher, keyframes, mappoints, iterations=20, robust=
 
 
 def apply_global_ba(keyframes, mappoints, result, nLoopKF):
-    """:193-235 on the dicts, result = what GlobalBundleAdjustment above returns.  nLoopKF == 0: SetPose and SetWorldPos (UpdateNormalAndDepth is not in the library: the
-    caller's step).  Else TcwGBA / PosGBA and ba_global_for_kf = nLoopKF (mTcwGBA, mPosGBA, mnBAGlobalForKF).  A point the graph did not include (no observation) is left
+    """:193-235 on the dicts, result = what GlobalBundleAdjustment above returns.  nLoopKF == 0: SetPose and SetWorldPos (UpdateNormalAndDepth is the step
+    after this one: update_after_global_ba).  Else TcwGBA / PosGBA and ba_global_for_kf = nLoopKF (mTcwGBA, mPosGBA, mnBAGlobalForKF).  A point the graph did not include (no observation) is left
     alone; a key frame or point that became bad meanwhile too."""
     for k, T in result["poses"].items():
         if keyframes[k].get("bad"):
@@ -590,6 +605,13 @@ def apply_global_ba(keyframes, mappoints, result, nLoopKF):
             mappoints[m]["x3Dw"] = X
         else:
             mappoints[m]["PosGBA"] = X; mappoints[m]["ba_global_for_kf"] = nLoopKF
+
+
+def update_after_global_ba(matcher, keyframes, mappoints, result):
+    """:227, the step after apply_global_ba with nLoopKF == 0: UpdateNormalAndDepth of every point the graph included, in one call of matcher.UpdateMapPoints.  result =
+    what GlobalBundleAdjustment above returns.  -> the updated ids"""
+    from .mapping import update_map_points
+    return update_map_points(matcher, list(result["points"]), keyframes, mappoints, descriptor=False)
 
 
 def propagate_global_ba(keyframes, mappoints, nLoopKF, origins):
