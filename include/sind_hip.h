@@ -76,7 +76,8 @@ int sind_flow_set_wave_solver(sind_flow* f, int on, int target_items, int bands)
 /* how k_sor_wave cuts a w x h level of B pairs (host arithmetic only, no GPU needed): out = {column strips, kept columns per strip, row bands, kept rows per band}.  A strip works on
  * 128 columns -- its kept ones plus 10 on every side that is not an image border --, a band on its kept rows plus 10 on every cut side. */
 int sind_flow_wave_layout(int w, int h, int B, int target_items, int bands, int out[4]);
-/* coefficient kernel: 1 = k_coef_lanes (neighbours from lanes, short correctly rounded sqrt / quotient forms; default), 2 = k_coef_lanes with the compiler's IEEE forms,
+/* coefficient kernel: 1 = k_coef_lanes (neighbours from lanes, short sqrt / c / sqrt forms that are correctly rounded for arguments >= 2^-96; default), 2 = k_coef_lanes with the compiler's IEEE sqrt and c / sqrt
+ * (every variant divides by the gradient norms through their reciprocals: correctly rounded for numerators >= 2^-100 or zero, the IEEE division below; sind_debug_div_scan),
  * 0 = k_coef (neighbours from memory), 3 = variant 1 with its tiles in plain grid order over the XCDs (A/B timing: by default the tiles of a pair share an XCD's L2).  Same results. */
 int sind_flow_set_coef_kernel(sind_flow* f, int variant);
 /* HIP-event timing of everything enqueued on the handle's stream between begin and end (bench.py roofline leg) */
@@ -160,6 +161,12 @@ int sind_debug_coef_math_scan(int device, int exp_lo, int exp_hi, const float nu
  * estimate + one Newton step) that differ from the correctly rounded 1 / a, out[1] = quotients through that reciprocal (Markstein) that differ
  * from the IEEE division (16 numerators per divisor), out[2] = smallest failing significand (all ones if none) */
 int sind_debug_rcp_scan(int device, int exp_lo, int exp_hi, unsigned long long out[3]);
+/* the same two quotients (sor_div of the solver kernels, kc_div of the coefficient kernels) against the IEEE division BELOW the range of the two scans above, where the
+ * residual of Markstein's correction is no longer exact: every divisor significand x the divisor exponents -7 .. 14 x one numerator of random sign and significand per binary
+ * exponent from -149 (the smallest denormal) up to the divisor's exponent - 40, and the numerators +0 and -0.  counts[0] / counts[1] = quotients of sor_div / kc_div that differ,
+ * counts[2] = those of them with a zero numerator, *max_exp = the largest numerator exponent of a mismatch (-1000: none), by_exp (optional) = mismatches of both helpers at the
+ * numerator exponents -149 .. -26 */
+int sind_debug_div_scan(int device, unsigned long long counts[3], int* max_exp, unsigned long long by_exp[124]);
 
 /* parity-test access to the residual-threshold kernel (Otsu + Triangle of cv::threshold and the clamping of DynaDetect.cc:1309-1367 from a 256-bin
  * histogram): hist = n blocks of 257 words (counts, then the float bits of the maximal residual), res = n blocks of 261 words (the 257 input words,

@@ -108,6 +108,20 @@ int sind_debug_rcp_scan(int device, int exp_lo, int exp_hi, unsigned long long o
     HIP_TRY(hipMemcpy(out, d.p, sizeof(init), hipMemcpyDeviceToHost));
     return SIND_OK;
 }
+int sind_debug_div_scan(int device, unsigned long long counts[3], int* max_exp, unsigned long long by_exp[124]) {
+    if (!counts || !max_exp) { sind_set_error("sind_debug_div_scan: null argument"); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(device));
+    unsigned long long host[164];
+    DevBuf<unsigned long long> d; SIND_TRY(d.alloc(164));
+    HIP_TRY(hipMemset(d.p, 0, sizeof(host)));
+    SIND_TRY(sind::debug_div_scan(nullptr, d.p));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(host, d.p, sizeof(host), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; i++) counts[i] = host[i];
+    *max_exp = host[3] ? (int)host[3] - 200 : -1000;
+    if (by_exp) for (int i = 0; i < 124; i++) by_exp[i] = host[4 + i];
+    return SIND_OK;
+}
 int sind_debug_coef_math_scan(int device, int exp_lo, int exp_hi, const float numer[3], unsigned long long out[2]) {
     if (!out || !numer || exp_lo < -96 || exp_hi > 100 || exp_lo > exp_hi) { sind_set_error("sind_debug_coef_math_scan: bad arguments (exponents -96 .. 100)"); return SIND_E_ARG; }
     HIP_TRY(hipSetDevice(device));

@@ -46,6 +46,7 @@ int launch_resize_u8(hipStream_t s, const uint8_t* src, uint8_t* dst, int sw, in
 int launch_roll_history(hipStream_t s, uint8_t* pool, int S, int T, size_t frame_bytes);      // history slots 0, 1 <- slots T, T + 1 of every stream's T + 2 pool slots
 int launch_bgr2gray(hipStream_t s, const uint8_t* bgr, uint8_t* gray, size_t npix, bool swap_rb);
 int debug_rcp_scan(hipStream_t s, int exp_lo, int exp_hi, unsigned long long* out_dev);
+int debug_div_scan(hipStream_t s, unsigned long long* out_dev);          // out_dev: 164 words, zeroed (k_debug_div_scan)
 int debug_coef_math_scan(hipStream_t s, int exp_lo, int exp_hi, const float numer[3], unsigned long long* out_dev);
 struct SolverCfg;
 int sor_iterations(hipStream_t s, FlowPlanes& P, int w, int h, int B, int total, float omega, long long* nlaunch, const SolverCfg& C, int* streamed = nullptr);

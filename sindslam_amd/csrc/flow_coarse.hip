@@ -112,8 +112,7 @@ __device__ __forceinline__ void coarse_sor(float* lds, int w, int h, int SW, int
                 const float sigmaU = wl * ul + wp[i] * ur + wu[i] * uu[k] + wp[i] * ud[k];                                        \
                 const float sigmaV = wl * vl + wp[i] * vr + wu[i] * vu[k] + wp[i] * vd[k];                                        \
                 float nu = du[i], nv = dv[i];                                                                                     \
-                nu += omega * (sor_div(sigmaU + b1[i] - nv * a12[i], a11[i], r11[i]) - nu);                                       \
-                nv += omega * (sor_div(sigmaV + b2[i] - nu * a12[i], a22[i], r22[i]) - nv);                                       \
+                sor_update(nu, nv, sigmaU + b1[i], sigmaV + b2[i], a12[i], a11[i], r11[i], a22[i], r22[i], omega);                \
                 du[i] = nu; dv[i] = nv;                                                                                           \
             }                                                                                                                     \
             *reinterpret_cast<VT*>(rM + (2 * (Q) + 0) * CL_PL) = cl_pack<P>(du + (START));                                        \
@@ -270,8 +269,7 @@ __global__ void __launch_bounds__(1024) k_sor_tile(int w, int h, int IW, int IH,
                 const float sigmaU = wl * ul + wp[i] * ur + wu[i] * uu[k] + wp[i] * ud[k];                                        \
                 const float sigmaV = wl * vl + wp[i] * vr + wu[i] * vu[k] + wp[i] * vd[k];                                        \
                 float nu = du[i], nv = dv[i];                                                                                     \
-                nu += omega * (sor_div(sigmaU + b1[i] - nv * a12[i], a11[i], r11[i]) - nu);                                       \
-                nv += omega * (sor_div(sigmaV + b2[i] - nu * a12[i], a22[i], r22[i]) - nv);                                       \
+                sor_update(nu, nv, sigmaU + b1[i], sigmaV + b2[i], a12[i], a11[i], r11[i], a22[i], r22[i], omega);                \
                 du[i] = nu; dv[i] = nv;                                                                                           \
             }                                                                                                                     \
             *reinterpret_cast<VT*>(rM + (2 * (Q) + 0) * ST_PL) = cl_pack<P>(du + (START));                                        \

@@ -43,10 +43,29 @@ __device__ __forceinline__ void warp_px(const float* __restrict__ S, float i0, f
 }
 
 // Divisions that share a divisor (the three gradient norms of a pixel divide 14 numerators) go through the divisor's reciprocal: hardware estimate +
-// one Newton step = exactly RN(1 / a) for every float significand, then Markstein's correction = the correctly rounded quotient (sor_rcp / sor_div
-// below the solver kernels; checked exhaustively by sind_debug_rcp_scan) -- 3 instructions per quotient instead of the 10 of an IEEE division.
+// one Newton step = exactly RN(1 / a) for every float significand, then Markstein's correction q0 = n * r; e = fma(-a, q0, n); q = fma(e, r, q0) -- 3 instructions per
+// quotient instead of the 10 of an IEEE division.  The correction gives RN(n / a) only WHILE ITS RESIDUAL e IS EXACT: a * q0 carries 48 bits down to 2^(E - 47) for a
+// numerator of binary exponent E, so e is representable for E >= -102 and is rounded as a denormal below (sind_debug_div_scan on the unguarded form: mismatches at every
+// numerator exponent from -103 down, one quotient in eleven near 2^-128; none from -102 up; sind_debug_rcp_scan / sind_debug_coef_math_scan: none for quotients of
+// 2^-40 .. 2^40).  And for n = -0 it returns +0: e is +0 and +0 * r + -0 is +0.  The flow reaches all of that on sparse content: the increment that spreads from texture
+// into a flat field passes through 2^-103, the denormals and the zeros, and the next fixed-point iteration squares it (tests/test_flow_sparse_gpu.py: before the guards
+// below the solver kernels differed from the oracle there).  Hence two additions, after which the result is n / a for every finite n whose quotient does not overflow,
+// with divisors in [2^-7, 2^15) (the gradient norms and the system's diagonals):
+//   * a numerator that is NOT ZERO and below 2^-100 in any lane sends the whole wave to the compiler's IEEE division (a wave-uniform branch that replaces the short
+//     form's result, so the common path stays a straight line);
+//   * zeros stay on the short path and take their sign from q0 = n * r, whose sign is the quotient's for every input (one v_bfi).  Zeros are common, tiny numerators
+//     are not: squares and products of second derivatives of 8-bit images are exactly zero at a few pixels of EVERY wave of the coefficient kernels, a tenth of them
+//     -0; the solver's numerators are zero on flat and on static content and in every lane that overhangs the image.
+// Both kc_div (the coefficient kernels) and sor_div / sor_update (the solver kernels, below) are built from these two pieces.
+constexpr int DIV_TINY_FREXP = -99;  // v_frexp_exp of 2^-100; the instruction returns 0 for a zero, an infinity and a NaN: none of them is "tiny"
+__device__ __forceinline__ float div_short(float n, float a, float r) { const float q0 = n * r; const float e = fmaf(-a, q0, n); return __builtin_copysignf(fmaf(e, r, q0), q0); }
+__device__ __forceinline__ int div_exp(float n) { return __builtin_amdgcn_frexp_expf(n); }
 __device__ __forceinline__ float kc_rcp(float a) { const float y0 = __builtin_amdgcn_rcpf(a); const float e = fmaf(-a, y0, 1.f); return fmaf(e, y0, y0); }
-__device__ __forceinline__ float kc_div(float n, float a, float r) { const float q0 = n * r; const float e = fmaf(-a, q0, n); return fmaf(e, r, q0); }
+__device__ __forceinline__ float kc_div(float n, float a, float r) {
+    float q = div_short(n, a, r);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(div_exp(n) < DIV_TINY_FREXP) != 0, 0)) q = n / a;
+    return q;
+}
 // RN(sqrt(x)) for 2^-96 <= x < inf: the compiler's own correctly rounded sequence (hardware estimate within 1 ulp, then the neighbour whose residual says so) without its
 // guards for tiny, zero and infinite arguments -- 8 instructions instead of 15.  c / sqrt(x) then goes through the root's reciprocal like every other quotient of the kernel
 // (kc_rcp + kc_div: 6 instructions instead of the IEEE division's 11).  sind_debug_coef_math_scan checks both against sqrtf and the IEEE division for EVERY float in a range
@@ -70,7 +89,7 @@ template <bool FAST> __device__ __forceinline__ float kc_over_sqrt(float c, floa
 // 64 consecutive columns of KL_ROWS rows and loads each plane's rows ONCE (one dword per lane and row: 8 rows of the average, 6 of Iz and of each of the four flow planes for four
 // output rows: 9.5 loads per pixel); x +- 1 and x +- 2 come from the lanes to the left and right with whole-wave DPP shifts (gfx9 wave_shl / wave_shr, VALU rate), y +- 1 and
 // y +- 2 from the rows held in registers.  The two lanes at either end only feed their neighbours (60 of 64 lanes store).  Values and the order of every float operation are
-// those of kc_rows -- except that sqrt and c / sqrt take their short correctly rounded forms (kc_sqrt / kc_over_sqrt above: the same VALUES for every float) --: the results are
+// those of kc_rows -- except that sqrt and c / sqrt take their short correctly rounded forms (kc_sqrt / kc_over_sqrt above: the same VALUES for every float of the ranges stated there) --: the results are
 // bit-identical (tests/test_flow_gpu.py compares the kernels, with and without the short forms, and all of them with the oracle).
 #define KL_ROWS 4
 #define KL_COLS 60
@@ -177,9 +196,41 @@ __device__ __forceinline__ void kc_lanes(const VarParams& P, int w, int h, int c
 }
 
 struct __attribute__((packed, aligned(4))) F4u { float x, y, z, w; };     // 4-byte aligned 16-byte load (gfx950 allows unaligned dwordx4)
-__device__ __forceinline__ float sor_div(float n, float a, float r) { const float q0 = n * r; const float e = fmaf(-a, q0, n); return fmaf(e, r, q0); }
+// The solver's quotient, the same two pieces.  A lane whose pixel lies outside the image has n = 0 in every solver kernel, so it never sends its wave to the division;
+// its divisor is r = 0 in k_sor_wave, k_sor_stream, k_sor_tile and the coarse kernels (the short form gives n * 0, and the guarded branch keeps that: its a is whatever
+// the lane holds) and a = r = 1 in k_sor_fused.  Inside the image r = RN(1 / a) > 0.  (sind_debug_div_scan scans this function.)
+__device__ __forceinline__ float sor_div(float n, float a, float r) {
+    float q = div_short(n, a, r);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(div_exp(n) < DIV_TINY_FREXP) != 0, 0)) q = r != 0.f ? n / a : q;
+    return q;
+}
+// One SOR update of a pixel, sU = sigmaU + b1 and sV = sigmaV + b2: the ONE statement of the update for the solver kernels whose workgroups share their state (k_sor_fused,
+// k_sor_stream, k_sor_tile, the coarse kernels); each quotient carries its own test.
+__device__ __forceinline__ void sor_update(float& nu, float& nv, float sU, float sV, float a12, float a11, float r11, float a22, float r22, float omega) {
+    nu += omega * (sor_div(sU - nv * a12, a11, r11) - nu);
+    nv += omega * (sor_div(sV - nu * a12, a22, r22) - nv);
+}
+// The same update for a kernel that can run its whole launch again (k_sor_wave: nothing it writes is read before it ends).  First on the short form alone, with no test
+// and no branch: `lo` collects the smallest v_frexp_exp of the numerators it met (a zero counts as exponent 0).  If lo < DIV_TINY_FREXP in any lane at the end, a quotient of
+// that wave may have been wrong, and the wave runs again with sor_update_ieee, the compiler's division throughout (a pixel outside the image, r = 0, keeps its 0).
+__device__ __forceinline__ void sor_update_short(float& nu, float& nv, float sU, float sV, float a12, float a11, float r11, float a22, float r22, float omega, int& lo) {
+    // (the bare three operations, without the sign of q0: a zero quotient enters the update only through q - nu, and +0 - nu and -0 - nu differ only for nu = +0, where
+    // omega * +-0 is then added to +0 and gives +0 either way)
+    const float n1 = sU - nv * a12; const float p1 = n1 * r11;
+    nu += omega * (fmaf(fmaf(-a11, p1, n1), r11, p1) - nu);
+    const float n2 = sV - nu * a12; const float p2 = n2 * r22;
+    nv += omega * (fmaf(fmaf(-a22, p2, n2), r22, p2) - nv);
+    lo = min(lo, min(div_exp(n1), div_exp(n2)));
+}
+__device__ __forceinline__ void sor_update_ieee(float& nu, float& nv, float sU, float sV, float a12, float a11, float r11, float a22, float r22, float omega) {
+    const float n1 = sU - nv * a12;
+    nu += omega * ((r11 != 0.f ? n1 / a11 : n1 * r11) - nu);
+    const float n2 = sV - nu * a12;
+    nv += omega * ((r22 != 0.f ? n2 / a22 : n2 * r22) - nv);
+}
 // RN(1 / a) without the IEEE division sequence: hardware reciprocal (<= 1 ulp) + one Newton step in FMA arithmetic.  sind_debug_rcp_scan checks it
-// against the correctly rounded division for EVERY float significand (the step is invariant under scaling by powers of two while nothing is denormal).
+// against the correctly rounded division for EVERY float significand at the binary exponents -24 .. 24 (the step is invariant under scaling by powers of two
+// while neither a nor 1 / a is denormal; the system's diagonals lie in [2^-7, 2^14]).
 // (volatile asm: the compiler must not hoist the loop-invariant reciprocals out of the solver loop, where they would cost 16 registers and spill;
 // s_nop: the transcendental unit's result needs one wait state before a VALU read, which the hazard pass cannot see through inline asm)
 __device__ __forceinline__ float sor_rcp(float a) {

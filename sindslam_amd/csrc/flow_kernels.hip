@@ -349,6 +349,48 @@ __global__ void k_debug_coef_math_scan(int exp_lo, int exp_hi, float n0, float n
     if (bad_s) atomicAdd(&out[0], bad_s);
     if (bad_q) atomicAdd(&out[1], bad_q);
 }
+// sor_div and kc_div against the IEEE division BELOW the quotients of the two scans above: every divisor significand x the divisor exponents -7 .. 14 (the data term's and
+// the solver's diagonals) x one numerator of random sign and significand per binary exponent from -149 (the smallest denormal) up to the divisor's exponent - 40, then +0 and -0.
+// out[0] / out[1] = quotients of sor_div / kc_div that differ, out[2] = those among them whose numerator is a zero, out[3] = 200 + the largest numerator exponent of a
+// mismatch (0: none), out[4 + 149 + e] = mismatches at the numerator exponent e (both helpers)
+#define DIV_SCAN_EA_LO (-7)
+#define DIV_SCAN_EA_HI 14
+__global__ void __launch_bounds__(256) k_debug_div_scan(unsigned long long* __restrict__ out) {
+    __shared__ unsigned by_exp[160];
+    for (int i = threadIdx.x; i < 160; i += blockDim.x) by_exp[i] = 0;
+    __syncthreads();
+    const unsigned m = blockIdx.x * blockDim.x + threadIdx.x;           // all 2^23 significands
+    unsigned long long bad_s = 0, bad_k = 0, bad_z = 0; unsigned rng = m * 2654435761u + 977u;
+    for (int en = -149; en <= DIV_SCAN_EA_HI - 40; en++) {
+        unsigned bad = 0;
+        for (int ea = max(DIV_SCAN_EA_LO, en + 40); ea <= DIV_SCAN_EA_HI; ea++) {
+            const float a = __uint_as_float(((unsigned)(127 + ea) << 23) | m);
+            rng = rng * 1664525u + 1013904223u;
+            const unsigned mag = en >= -126 ? (((unsigned)(127 + en) << 23) | ((rng >> 8) & 0x7fffffu)) : ((1u << (en + 149)) | ((rng >> 8) & ((1u << (en + 149)) - 1u)));
+            const float n = __uint_as_float(mag | (rng & 0x80000000u)), ref = n / a;
+            if (__float_as_uint(sor_div(n, a, sor_rcp(a))) != __float_as_uint(ref)) { bad_s++; bad++; }
+            if (__float_as_uint(kc_div(n, a, kc_rcp(a))) != __float_as_uint(ref)) { bad_k++; bad++; }
+        }
+        if (bad) atomicAdd(&by_exp[en + 149], bad);
+    }
+    for (int ea = DIV_SCAN_EA_LO; ea <= DIV_SCAN_EA_HI; ea++) {
+        const float a = __uint_as_float(((unsigned)(127 + ea) << 23) | m);
+        for (unsigned z = 0; z < 2; z++) {
+            const float n = __uint_as_float(z << 31), ref = n / a;
+            if (__float_as_uint(sor_div(n, a, sor_rcp(a))) != __float_as_uint(ref)) { bad_s++; bad_z++; }
+            if (__float_as_uint(kc_div(n, a, kc_rcp(a))) != __float_as_uint(ref)) { bad_k++; bad_z++; }
+        }
+    }
+    if (bad_s) atomicAdd(&out[0], bad_s);
+    if (bad_k) atomicAdd(&out[1], bad_k);
+    if (bad_z) atomicAdd(&out[2], bad_z);
+    __syncthreads();
+    for (int i = threadIdx.x; i < 160; i += blockDim.x) if (by_exp[i]) { atomicAdd(&out[4 + i], (unsigned long long)by_exp[i]); atomicMax(&out[3], (unsigned long long)(200 + i - 149)); }
+}
+int debug_div_scan(hipStream_t s, unsigned long long* out_dev) {
+    hipLaunchKernelGGL(k_debug_div_scan, dim3((1u << 23) / 256), dim3(256), 0, s, out_dev);
+    HIP_TRY(hipGetLastError()); return SIND_OK;
+}
 int debug_coef_math_scan(hipStream_t s, int exp_lo, int exp_hi, const float numer[3], unsigned long long* out_dev) {
     hipLaunchKernelGGL(k_debug_coef_math_scan, dim3((1u << 23) / 256), dim3(256), 0, s, exp_lo, exp_hi, numer[0], numer[1], numer[2], out_dev);
     HIP_TRY(hipGetLastError()); return SIND_OK;
@@ -358,7 +400,7 @@ int debug_rcp_scan(hipStream_t s, int exp_lo, int exp_hi, unsigned long long* ou
     HIP_TRY(hipGetLastError()); return SIND_OK;
 }
 // Fused register-resident SOR over one extended tile: the two divisions of a pixel update are Markstein's three-operation sequence on a reciprocal formed
-// on the fly (sor_rcp / sor_div: the correctly rounded quotient).  MAXT threads per workgroup, WPE waves per SIMD.
+// on the fly (sor_rcp / sor_div: the correctly rounded quotient for |n| >= 2^-100, the IEEE division below; flow_dev.hpp).  MAXT threads per workgroup, WPE waves per SIMD.
 // CEW x CNR: extended tile known at compile time (0 = run-time sizes, the one-workgroup levels): every LDS address then is one base register plus an
 // immediate offset instead of a dozen address registers held across the loop.
 template <int MAXT, int WPE, int CEW, int CNR>
@@ -474,8 +516,7 @@ k_sor_fused(int w, int h, int EW, int EH, int IW, int IH, int halo_x, int halo, 
                 const float sigmaU = wl * ul + wp[i] * ur + wu[k] * uu[k] + wp[i] * ud[k];                                        \
                 const float sigmaV = wl * vl + wp[i] * vr + wu[k] * vu[k] + wp[i] * vd[k];                                        \
                 float nu = du[i], nv = dv[i];                                                                                     \
-                nu += omega * (sor_div(sigmaU + b1[i] - nv * a12[i], a11[i], sor_rcp(a11[i])) - nu);                              \
-                nv += omega * (sor_div(sigmaV + b2[i] - nu * a12[i], a22[i], sor_rcp(a22[i])) - nv);                              \
+                sor_update(nu, nv, sigmaU + b1[i], sigmaV + b2[i], a12[i], a11[i], sor_rcp(a11[i]), a22[i], sor_rcp(a22[i]), omega);     \
                 const bool ok = (valid >> i) & 1u;                                                                                \
                 du[i] = ok ? nu : 0.f; dv[i] = ok ? nv : 0.f;                                                                     \
             }                                                                                                                     \
@@ -642,8 +683,7 @@ __device__ __forceinline__ void ss_item(float* lds, const int strip, const int i
                 const float sigmaU = wl * ula[k] + R.wp[i] * ura[k] + wua[k] * uua[k] + R.wp[i] * uda[k];                          \
                 const float sigmaV = wl * vla[k] + R.wp[i] * vra[k] + wua[k] * vua[k] + R.wp[i] * vda[k];                          \
                 float nu = R.du[i], nv = R.dv[i];                                                                                  \
-                nu += omega * (sor_div(sigmaU + R.b1[i] - nv * R.a12[i], R.a11[i], R.r11[i]) - nu);                                \
-                nv += omega * (sor_div(sigmaV + R.b2[i] - nu * R.a12[i], R.a22[i], R.r22[i]) - nv);                                \
+                sor_update(nu, nv, sigmaU + R.b1[i], sigmaV + R.b2[i], R.a12[i], R.a11[i], R.r11[i], R.a22[i], R.r22[i], omega);          \
                 R.du[i] = nu; R.dv[i] = nv;                                                                                        \
             }                                                                                                                      \
             /* (one 8-byte vector store each: as HIP float2 structs the stores were split into scalars, sunk below the two colours' code and came out as four ds_write_b32 with four address adds) */ \

@@ -34,16 +34,17 @@ struct SwvRow { float a11[2], a22[2], r11[2], r22[2], wp[2], du[2], dv[2]; };
 typedef unsigned swv_u2 __attribute__((ext_vector_type(2)));
 
 // half-sweep of pixel I of row R (U: the row above, D: the row below); a12, b1, b2: the pixel's entries of the row's LDS record
-template <int I>
-__device__ __forceinline__ void swv_update(SwvRow& R, const SwvRow& U, const SwvRow& D, float a12, float b1, float b2, float omega) {
+// IEEE: the second run of a wave whose first run met a numerator below 2^-100 (sor_update_short / sor_update_ieee, flow_dev.hpp); lo: the first run's smallest exponent
+template <int I, bool IEEE>
+__device__ __forceinline__ void swv_update(SwvRow& R, const SwvRow& U, const SwvRow& D, float a12, float b1, float b2, float omega, int& lo) {
     float lu, lv, ru, rv;            // weight x value of the left and right neighbours
     if (I == 0) { lu = lane_prev(R.wp[1] * R.du[1]); lv = lane_prev(R.wp[1] * R.dv[1]); ru = R.wp[0] * R.du[1]; rv = R.wp[0] * R.dv[1]; }
     else        { lu = R.wp[0] * R.du[0]; lv = R.wp[0] * R.dv[0]; ru = R.wp[1] * lane_next(R.du[0]); rv = R.wp[1] * lane_next(R.dv[0]); }
     const float sigmaU = lu + ru + U.wp[I] * U.du[I] + R.wp[I] * D.du[I];
     const float sigmaV = lv + rv + U.wp[I] * U.dv[I] + R.wp[I] * D.dv[I];
     float nu = R.du[I], nv = R.dv[I];
-    nu += omega * (sor_div(sigmaU + b1 - nv * a12, R.a11[I], R.r11[I]) - nu);
-    nv += omega * (sor_div(sigmaV + b2 - nu * a12, R.a22[I], R.r22[I]) - nv);
+    if (IEEE) sor_update_ieee(nu, nv, sigmaU + b1, sigmaV + b2, a12, R.a11[I], R.r11[I], R.a22[I], R.r22[I], omega);
+    else sor_update_short(nu, nv, sigmaU + b1, sigmaV + b2, a12, R.a11[I], R.r11[I], R.a22[I], R.r22[I], omega, lo);
     R.du[I] = nu; R.dv[I] = nv;
 }
 
@@ -67,8 +68,8 @@ __device__ __forceinline__ SwvRec swv_record(const SwvCtx& C) {
 // half-sweeps S .. 9 of step K of the loop body (t = t0 + K): every window index is a compile-time constant.  Every stage tests its row against the band (scalar
 // compare and branch).  An instance without the tests for the steady state -- twelve steps in one basic block -- was measured: same time (the kernel waits for memory, see
 // DESIGN.md), twice the code.
-template <int K, int S>
-__device__ __forceinline__ void swv_stages(SwvRow (&win)[SWV_NW], const SwvCtx& C, int t, SwvRec rec) {
+template <int K, int S, bool IEEE>
+__device__ __forceinline__ void swv_stages(SwvRow (&win)[SWV_NW], const SwvCtx& C, int t, SwvRec rec, int& lo) {
     if constexpr (S < SWV_NS) {
         const int y = t - S;
         SwvRec next{};
@@ -78,7 +79,7 @@ __device__ __forceinline__ void swv_stages(SwvRow (&win)[SWV_NW], const SwvCtx& 
 #ifdef SWV_SKIP       /* timing experiment (wrong results): only the first SWV_SKIP half-sweeps compute; loads, stores and the pipeline stay */
             if (S < SWV_SKIP)
 #endif
-            swv_update<K & 1>(win[sl], win[up], win[dn], rec.a12, rec.b1, rec.b2, C.omega);
+            swv_update<K & 1, IEEE>(win[sl], win[up], win[dn], rec.a12, rec.b1, rec.b2, C.omega, lo);
             if (S == SWV_NS - 1 && y >= C.by0 && y < C.by1) {                   // the row is through: its kept pixels go to memory
                 const unsigned ro = (unsigned)y * C.row_bytes;
                 const SwvRow& R = win[sl];
@@ -92,12 +93,12 @@ __device__ __forceinline__ void swv_stages(SwvRow (&win)[SWV_NW], const SwvCtx& 
             }
         }
         __builtin_amdgcn_sched_barrier(0);              // (the next stage's LDS reads stay where they were issued: a stage ahead of their use)
-        swv_stages<K, S + 1>(win, C, t, next);
+        swv_stages<K, S + 1, IEEE>(win, C, t, next, lo);
     }
 }
 // steps K .. 11 of the loop body
-template <int K, int PF>
-__device__ __forceinline__ void swv_steps(SwvRow (&win)[SWV_NW], SwvFlight (&FL)[PF], const SwvCtx& C, int t0) {
+template <int K, int PF, bool IEEE>
+__device__ __forceinline__ void swv_steps(SwvRow (&win)[SWV_NW], SwvFlight (&FL)[PF], const SwvCtx& C, int t0, int& lo) {
     if constexpr (K < SWV_NW) {
         const int t = t0 + K;
         const SwvRec rec0 = swv_record<K, 0>(C);                            // (row t's record was written a step ago)
@@ -129,8 +130,8 @@ __device__ __forceinline__ void swv_steps(SwvRow (&win)[SWV_NW], SwvFlight (&FL)
         }
         // (3) the ten half-sweeps of this step
         __builtin_amdgcn_sched_barrier(0);
-        swv_stages<K, 0>(win, C, t, rec0);
-        swv_steps<K + 1, PF>(win, FL, C, t0);
+        swv_stages<K, 0, IEEE>(win, C, t, rec0, lo);
+        swv_steps<K + 1, PF, IEEE>(win, FL, C, t0, lo);
     }
 }
 
@@ -158,10 +159,20 @@ k_sor_wave(int strips, int bands, int items, int w, int h, int IW, int BH, float
     auto rs = [&](const float* plane) { return __builtin_amdgcn_make_buffer_rsrc((void*)(plane + base), 0, plane_bytes, 0x00020000); };
     const SwvCtx C{rs(gA11), rs(gA12), rs(gA22), rs(gB1), rs(gB2), rs(gW), rs(gU), rs(gV), rs(gUo), rs(gVo),
                    swv_lds + lane, omega, (unsigned)x0 * 4u, (unsigned)w * 4u, ys, nrows, by0, by1, in0, in1, keep0, keep1};
-    SwvRow win[SWV_NW] = {};
-    SwvFlight FL[PF] = {};
     const int Tb = (ys - 1 - PF) & ~1, Tend = ye + SWV_NS - 1;    // steps Tb .. Tend - 1 (Tb even: step K of the loop body updates pixel K & 1; row ys is requested in step ys - 1 - PF)
-    for (int t0 = Tb; t0 < Tend; t0 += SWV_NW) swv_steps<0, PF>(win, FL, C, t0);
+    int lo = 0;
+    {
+        SwvRow win[SWV_NW] = {};
+        SwvFlight FL[PF] = {};
+        for (int t0 = Tb; t0 < Tend; t0 += SWV_NW) swv_steps<0, PF, false>(win, FL, C, t0, lo);
+    }
+    // a numerator below 2^-100 somewhere in this wave's strip: the short quotient may have been off by an ulp there.  The wave runs again from its inputs (which no wave
+    // writes) with the IEEE division and overwrites what it stored.  Rare: the flow's increment has to be that small and not zero.
+    if (__builtin_amdgcn_ballot_w64(lo < DIV_TINY_FREXP) != 0) {
+        SwvRow win[SWV_NW] = {};
+        SwvFlight FL[PF] = {};
+        for (int t0 = Tb; t0 < Tend; t0 += SWV_NW) swv_steps<0, PF, true>(win, FL, C, t0, lo);
+    }
 }
 
 // Column strips and row bands of a w x h level.  One strip: w <= 128; two: the kept width + 10 <= 128; more: + 20.  The bands are the launch's parallelism knob: every cut
