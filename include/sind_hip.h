@@ -174,6 +174,13 @@ int sind_debug_div_scan(int device, unsigned long long counts[3], int* max_exp, 
  * kernel, 1 = one-wave kernel, 2 = one-wave kernel in its production form, which clears the working histogram: the first 257 words of every result
  * block then hold the cleared words.  mu1 (optional, variants 1 / 2): n x 256 values of Otsu's running class mean, the one rounding chain with a division. */
 int sind_debug_flow_thresholds(const int* hist, int n, int width, int height, int variant, int device, int* res, double* mu1);
+/* parity-test access to the batched flow-mask stage (csrc/flow_kernels.hip: k_residual_mag_frames, k_mag_hist_frames, k_flow_thresholds_frames,
+ * k_flow_mask_bits_frames): n frames of dense flow (host f32 [n][height][width] each) and n homographies (row-major 3 x 3 doubles) go through the four
+ * batched launches and, in the same call, frame by frame through the per-frame kernels.  Both sets come back: masks as u8 [n][height * width] (low: 0 / 128,
+ * high: 0 / 255; the batched bit masks are expanded on the host) and result blocks [n][261] (256 histogram counts, the float bits of the maximal residual,
+ * lo, hi, otsu, triangle as floats).  width must be a multiple of 64. */
+int sind_debug_flow_masks_batch(const float* u, const float* v, const double* homographies, int n, int width, int height, int device,
+                                uint8_t* low_batch, uint8_t* high_batch, int* res_batch, uint8_t* low_frame, uint8_t* high_frame, int* res_frame);
 
 /* parity-test access to the GPU region grow of the PEAC plane refinement (AHCPlaneFitter.hpp:546-601 floodFill; csrc/peac_kernels.hip): n depth frames
  * (host u16 [n][height][width]) -> membership map per pixel (plane index or -1) from ONE kernel launch over all frames (member_gpu) and from the host
@@ -314,6 +321,13 @@ int sind_pipe_get_grow_share(sind_pipe* p, int* quarters);
  * chosen by the same controller (one more while steps wait for the host although every region grow already runs on the GPU).  Results do not depend on it. */
 int sind_pipe_set_kmeans_groups(sind_pipe* p, int groups);      /* 1 .. min(4, streams / 8), or -1 = adaptive (default); takes effect with the next step */
 int sind_pipe_get_kmeans_groups(sind_pipe* p, int* groups);
+/* Flow-mask stage of the tails (DynaDetect.cc:1252-1367: residual against the homography, histogram, Otsu / Triangle thresholds, both masks) batched per round:
+ * where a step runs as rounds whose k-means waits for whole tails (more streams than pool workers), the homographies of one frame of every stream of a group are
+ * computed on the pool while the batched k-means runs, and the stage's kernels run once for the group instead of once per frame; the masks come back bit-packed.
+ * Same results.  on = 0 runs the stage per frame everywhere (default 1).  Setting the switch resets the counter: frames_batched = frames whose masks came from a
+ * batch since then.  Not while a submitted step is pending. */
+int sind_pipe_set_flow_mask_batch(sind_pipe* p, int on);
+int sind_pipe_get_flow_mask_batch(sind_pipe* p, int* on, long long* frames_batched);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Frame post-ORB steps: what the reference's RGB-D Frame constructor does with the extractor's output

@@ -1,5 +1,6 @@
 // C ABI: dense flow stage (include/sind_hip.h).
 #include "../../include/sind_hip.h"
+#include <cstring>
 #include "flow.hpp"
 
 struct sind_flow {
@@ -145,6 +146,43 @@ int sind_debug_flow_thresholds(const int* hist, int n, int width, int height, in
     if (variant == 2) {                                 // the working histograms must have been cleared: hand them back in the first words of every result block
         std::vector<int> back((size_t)n * 257); HIP_TRY(hipMemcpy(back.data(), dh.p, back.size() * sizeof(int), hipMemcpyDeviceToHost));
         for (int i = 0; i < n; i++) for (int k = 0; k < 257; k++) res[(size_t)i * 261 + k] = back[(size_t)i * 257 + k];
+    }
+    return SIND_OK;
+}
+int sind_debug_flow_masks_batch(const float* u, const float* v, const double* hm, int n, int width, int height, int device,
+                                uint8_t* low_batch, uint8_t* high_batch, int* res_batch, uint8_t* low_frame, uint8_t* high_frame, int* res_frame) {
+    if (!u || !v || !hm || !low_batch || !high_batch || !res_batch || !low_frame || !high_frame || !res_frame || n < 1 || n > 64 || width < 64 || width % 64 != 0 || height < 1 || height > 4096 || width > 4096) {
+        sind_set_error("sind_debug_flow_masks_batch: bad arguments (1..64 frames, width a multiple of 64)"); return SIND_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(device));
+    const size_t np = (size_t)width * height, words = np / 64, slot = sind::flow_mask_slot_words(width, height), res_off = (2 * np + 15) / 16 * 16;
+    DevBuf<float> du, dv, dmag; DevBuf<uint8_t> dq, dmask; DevBuf<int> dh; DevBuf<unsigned long long> dout; DevBuf<sind::FlowMaskRec> drec;
+    SIND_TRY(du.alloc(np * n)); SIND_TRY(dv.alloc(np * n)); SIND_TRY(dmag.alloc(np * n)); SIND_TRY(dq.alloc(np * n)); SIND_TRY(dh.alloc((size_t)264 * n)); SIND_TRY(dout.alloc(slot * n)); SIND_TRY(drec.alloc(n));
+    SIND_TRY(dmask.alloc(res_off + 1088));
+    HIP_TRY(hipMemcpy(du.p, u, np * n * sizeof(float), hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dv.p, v, np * n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dh.p, 0, (size_t)264 * n * sizeof(int))); HIP_TRY(hipMemset(dout.p, 0, slot * n * 8));
+    // ---- batched: one record per frame, every frame with workspaces and a working histogram of its own (264 words apart: 16-byte aligned)
+    std::vector<sind::FlowMaskRec> recs(n);
+    for (int i = 0; i < n; i++) { sind::FlowMaskRec& R = recs[i]; R.U = du.p + np * i; R.V = dv.p + np * i; std::copy(hm + 9 * i, hm + 9 * i + 9, R.H);
+                                  R.mag = dmag.p + np * i; R.magu8 = dq.p + np * i; R.hist = dh.p + (size_t)264 * i; R.out = dout.p + slot * i; }
+    HIP_TRY(hipMemcpy(drec.p, recs.data(), n * sizeof(sind::FlowMaskRec), hipMemcpyHostToDevice));
+    SIND_TRY(sind::launch_flow_masks_frames(nullptr, drec.p, recs.data(), n, n, width, height));
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<unsigned long long> out(slot * n);
+    HIP_TRY(hipMemcpy(out.data(), dout.p, out.size() * 8, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) {
+        const unsigned long long* o = out.data() + slot * i;
+        for (size_t k = 0; k < np; k++) { low_batch[np * i + k] = ((o[k >> 6] >> (k & 63)) & 1) ? 128 : 0; high_batch[np * i + k] = ((o[words + (k >> 6)] >> (k & 63)) & 1) ? 255 : 0; }
+        std::memcpy(res_batch + (size_t)261 * i, o + 2 * words, 261 * sizeof(int));
+    }
+    // ---- frame by frame: the kernels of DynaTail::flow_masks_gpu (the batched run left every working histogram zeroed; frame 0's serves all)
+    for (int i = 0; i < n; i++) {
+        int* res = reinterpret_cast<int*>(dmask.p + res_off);
+        SIND_TRY(sind::launch_residual(nullptr, du.p + np * i, dv.p + np * i, hm + 9 * i, dmag.p, reinterpret_cast<unsigned*>(dh.p + 256), dh.p, dq.p, width, height, false));
+        SIND_TRY(sind::launch_flow_thresholds_and_masks(nullptr, dh.p, width, height, res, dq.p, dmask.p, dmask.p + np));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(low_frame + np * i, dmask.p, np, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(high_frame + np * i, dmask.p + np, np, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(res_frame + (size_t)261 * i, res, 261 * sizeof(int), hipMemcpyDeviceToHost));
     }
     return SIND_OK;
 }

@@ -84,6 +84,32 @@ private:
     std::vector<KmFrameResult> res;
 };
 
+// masks of one frame made ahead of its tail by the batched flow-mask stage: bit-packed in BitImg's layout, and the 261-word result block
+// (histogram, maximum, thresholds lo / hi / otsu / triangle); page-locked host memory of the FlowMaskBatch that made them
+struct FlowMasksReady { const uint64_t* low; const uint64_t* high; const int* res; };
+
+class DynaTail;
+// ---- GPU part of the flow-mask stage (DD:1252-1367: residual against the homography, u8 normalisation + histogram, Otsu / Triangle thresholds, both masks) for one
+// frame of EVERY stream of a k-means group in four launches and one D2H: per frame it was four launches of 3.7 MB passes, a 615 KB copy and
+// a stream wait, 512 times a step.  The masks come back bit-packed (77.8 KB per 640 x 480 frame), so the host packing is gone too.  Same arithmetic, same kernels'
+// device functions; the residual workspaces and the working histogram stay the tails' own.
+class FlowMaskBatch {
+public:
+    int init(const DynaConfig& c, int cap, hipStream_t s);
+    ~FlowMaskBatch();
+    int set(int b, DynaTail* tail, const float* U, const float* V, const double Hm[9]);      // record b (host side only; any thread, one per slot)
+    int enqueue(int n);                       // records 0 .. n - 1: table upload, four launches, one D2H, the event
+    int wait();                               // until the results are on the host; they stay valid until the next enqueue
+    FlowMasksReady result(int b) const { const uint64_t* o = reinterpret_cast<const uint64_t*>(out_h.p) + slot_words * b; const size_t words = (size_t)H * (W / 64);
+                                          return FlowMasksReady{o, o + words, reinterpret_cast<const int*>(o + 2 * words)}; }
+    int capacity() const { return cap; }
+    hipStream_t stream = nullptr;
+private:
+    DynaConfig cfg; int W = 0, H = 0, cap = 0, pending = 0; size_t slot_words = 0;
+    PinnedBuf<FlowMaskRec> recs_h; DevBuf<FlowMaskRec> recs_d; DevBuf<unsigned long long> out_d; PinnedBuf<unsigned long long> out_h;
+    std::vector<DynaTail*> tails; hipEvent_t done = nullptr;
+};
+
 class DynaTail {
 public:
     DynaConfig cfg; hipStream_t stream = nullptr; DynaDebug dbg; bool keep_debug = false;
@@ -95,14 +121,18 @@ public:
     // dyna_out / label_out: host H x W u8 (0 invalid / 125 static / 255 dynamic ; 0 invalid, 1..n clusters).
     // depth_half: the tail object that carries the depth half's state and workspaces (nullptr = this one)
     int process(const uint16_t* depth_host, const uint16_t* depth_dev, const float* U, const float* V, uint8_t* dyna_out, uint8_t* label_out,
-                const OccResult* precomputed = nullptr, DynaTail* depth_half = nullptr, const KmFrameResult* km = nullptr);
+                const OccResult* precomputed = nullptr, DynaTail* depth_half = nullptr, const KmFrameResult* km = nullptr, const FlowMasksReady* fm = nullptr);
+    // host part of the flow-mask stage (DD:1163-1250): sample weights from the state the previous frame left, PROSAC order, pairs, homography.  The batched
+    // stage calls it for every stream of a group before ONE set of launches (FlowMaskBatch); fills dbg.nPairs / dbg.H
+    int flow_masks_homography(const float* U, const float* V, const float* gridFlowPre, double Hm[9]);
     // the k-means warm labels of the next frame (nullptr before the first frame of a stream): what KMeansBatch::run wants as prev[b]
     const uint8_t* prev_km_labels() const { return kmLabelLastAny ? kmLabelLast.data() : nullptr; }
     // process() = depth_stage() + flow_stage().  The two halves keep separate state (the k-means warm labels belong to the depth half,
     // the sample weights / previous masks to the flow half), so the depth half of the next frames may run ahead of the flow half.
     // km: this frame's k-means result when it was computed by the batched chain (else the stage runs its own)
     int depth_stage(const uint16_t* depth_host, const uint16_t* depth_dev, const OccResult* precomputed, DepthStageOut& out, const KmFrameResult* km = nullptr);
-    int flow_stage(const float* U, const float* V, const DepthStageOut& d, uint8_t* dyna_out, uint8_t* label_out, const float* gridFlowPre = nullptr);
+    // fm: this frame's masks when the batched flow-mask stage made them (else the stage runs its own launches)
+    int flow_stage(const float* U, const float* V, const DepthStageOut& d, uint8_t* dyna_out, uint8_t* label_out, const float* gridFlowPre = nullptr, const FlowMasksReady* fm = nullptr);
     // CalOccluded (DD:429-642) depends on the depth frame only: the pipeline runs it on this tail's stream while the dense flow
     // of the step is still on the GPU and the host cores are idle
     int compute_occluded(const uint16_t* depth_host, const uint16_t* depth_dev, OccResult& out, const OccGpuOut* pre = nullptr);
@@ -124,6 +154,7 @@ public:
     double t_stage[6] = {0, 0, 0, 0, 0, 0}; long n_frames = 0;
     double t_fine[40] = {0};       // cal_occluded: gpu+d2h, pack, endpoints, peac, contour filter, close | seg_merge: pieces, planes+h2d, rag gpu, merge    // flow masks, k-means, label prep, CalOccluded, SegAndMerge, fusion (ms, SIND_TAIL_TIMING=1)
 private:
+    friend class FlowMaskBatch;       // its records point at this tail's residual workspaces (mag, magu8, hist_d) and it keeps hist_clean
     int W = 0, H = 0, N = 0, zInvalidFrom = 65536; float invDepthScale = 0.f;
     std::vector<uint8_t> dynaLast, labelLast; BitImg highLast;       // host state images (DynaDetect.h:172-178) as seen by the flow half
     int lastCnt[256] = {0}, lastDyn[256] = {0};
@@ -136,6 +167,9 @@ private:
     PinnedBuf<float> h_grid; PinnedBuf<int> h_hist, h_rag; PinnedBuf<uint8_t> h_ab, h_lab8; PinnedBuf<KmState> h_kstate; PinnedBuf<PeacBlockStats> h_blocks;
     PinnedBuf<unsigned long long> h_planes;
     int flow_masks(const float* U, const float* V, BitImg& low, BitImg& high, const float* gridFlowPre = nullptr);
+    int flow_masks_gpu(const float* U, const float* V, const double Hm[9]);      // residual, histogram, thresholds, u8 masks; one D2H into h_ab, one wait
+    void flow_masks_result(const int* res261);
+    void flow_masks_ready(const FlowMasksReady& fm, BitImg& low, BitImg& high);
     int fuse(const BitImg& maskLow, const BitImg& maskHigh, const DepthStageOut& d, uint8_t* dyna_out, uint8_t* label_out);
     int kmeans(const uint16_t* depth_dev, std::vector<uint8_t>& label8, float centers[KM_K][3], int counts[KM_K]);
     bool hist_clean = false;      // hist_d's working block is known to be zero (left so by k_flow_thresholds)

@@ -158,7 +158,34 @@ void DynaTail::load_state(const uint8_t* buf, bool flow_half, bool depth_half) {
 }
 
 // ---- DD:1163-1367: sample weights -> PROSAC pairs -> homography -> residual -> Otsu / Triangle thresholds -> masks
+// Three parts: the host part up to the homography (flow_masks_homography), the GPU part (flow_masks_gpu, or FlowMaskBatch for one frame of every stream of a
+// k-means group) and the part that turns the results into the two masks and the debug fields (flow_masks_result / flow_masks_ready).
 int DynaTail::flow_masks(const float* U, const float* V, BitImg& low, BitImg& high, const float* gridFlowPre) {
+    double Hm[9];
+    SIND_TRY(flow_masks_homography(U, V, gridFlowPre, Hm));
+    SIND_TRY(flow_masks_gpu(U, V, Hm));
+    const size_t res_off = ((size_t)2 * N + 15) / 16 * 16;
+    flow_masks_result(reinterpret_cast<const int*>(h_ab.p + res_off));
+    const double tq = tick_ms();
+    low = BitImg::from_u8(h_ab.p, W, H, W); high = BitImg::from_u8((h_ab.p + N), W, H, W);
+    t_fine[23] += tick_ms() - tq;
+    if (keep_debug) { dbg.maskLow.assign(h_ab.p, h_ab.p + N); dbg.maskHigh.assign((h_ab.p + N), (h_ab.p + N) + N); }
+    return SIND_OK;
+}
+// masks that the batched stage made (bit-packed already): nothing to pack on the host
+void DynaTail::flow_masks_ready(const FlowMasksReady& fm, BitImg& low, BitImg& high) {
+    flow_masks_result(fm.res);
+    const size_t words = (size_t)H * (W / 64);
+    low.create(W, H); high.create(W, H);
+    std::memcpy(low.d.data(), fm.low, words * 8); std::memcpy(high.d.data(), fm.high, words * 8);
+    if (keep_debug) { dbg.maskLow.resize(N); low.to_u8(dbg.maskLow.data(), W, 128); dbg.maskHigh.resize(N); high.to_u8(dbg.maskHigh.data(), W, 255); }
+}
+void DynaTail::flow_masks_result(const int* hh) {
+    float f[5]; std::memcpy(&f[0], hh + 256, 4); std::memcpy(&f[1], hh + 257, 16);
+    dbg.maxError = f[0]; dbg.thr_low = f[1]; dbg.thr_high = f[2]; dbg.otsu = f[3]; dbg.triangle = f[4];
+    std::copy(hh, hh + 256, dbg.hist);
+}
+int DynaTail::flow_masks_homography(const float* U, const float* V, const float* gridFlowPre, double Hm[9]) {
     const int numCluster = KM_K;
     const int gx = (W - 1) / 10, gy = (H - 1) / 10;
     const float* gridFlow = gridFlowPre;                      // the pipeline gathers the sample grid of all frames right after the dense flow
@@ -193,10 +220,14 @@ int DynaTail::flow_masks(const float* U, const float* V, BitImg& low, BitImg& hi
         const int r = (int)(ptRow - fyv), c = (int)(ptCol - fxv);
         if ((unsigned)r <= (unsigned)H && (unsigned)c <= (unsigned)W) { in.push_back({ptCol, ptRow}); inLast.push_back({ptCol - fxv, ptRow - fyv}); }
     }
-    double Hm[9];
     tq = tick_ms();
     find_homography_rho(in, inLast, Hm);
     QLAP(22)
+    #undef QLAP
+    dbg.nPairs = (int)in.size(); std::copy(Hm, Hm + 9, dbg.H);
+    return SIND_OK;
+}
+int DynaTail::flow_masks_gpu(const float* U, const float* V, const double Hm[9]) {
     // working histogram hist_d[0..256] (+ maximum): zero whenever the previous frame's threshold kernel completed (it clears what it read); a frame that
     // failed in between leaves it unknown, hence the flag
     SIND_TRY(launch_residual(stream, U, V, Hm, mag.p, (unsigned*)(hist_d.p + 256), hist_d.p, magu8.p, W, H, hist_clean));
@@ -209,17 +240,43 @@ int DynaTail::flow_masks(const float* U, const float* V, BitImg& low, BitImg& hi
     HIP_TRY(hipMemcpyAsync(h_ab.p, low_d.p, res_off + 261 * sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(sind_stream_wait(stream));
     hist_clean = true;
-    {
-        const int* hh = reinterpret_cast<const int*>(h_ab.p + res_off);
-        float f[5]; std::memcpy(&f[0], hh + 256, 4); std::memcpy(&f[1], hh + 257, 16);
-        dbg.maxError = f[0]; dbg.thr_low = f[1]; dbg.thr_high = f[2]; dbg.otsu = f[3]; dbg.triangle = f[4];
-        dbg.nPairs = (int)in.size(); std::copy(Hm, Hm + 9, dbg.H); std::copy(hh, hh + 256, dbg.hist);
-    }
-    tq = tick_ms();
-    low = BitImg::from_u8(h_ab.p, W, H, W); high = BitImg::from_u8((h_ab.p + N), W, H, W);
-    QLAP(23)
-    #undef QLAP
-    if (keep_debug) { dbg.maskLow.assign(h_ab.p, h_ab.p + N); dbg.maskHigh.assign((h_ab.p + N), (h_ab.p + N) + N); }
+    return SIND_OK;
+}
+
+// ---- the GPU part of the flow-mask stage for one frame of every stream of a k-means group (see dyna.hpp)
+int FlowMaskBatch::init(const DynaConfig& c, int cap_, hipStream_t s) {
+    cfg = c; W = c.W; H = c.H; cap = cap_; stream = s; slot_words = flow_mask_slot_words(W, H);
+    if (W % 64 != 0) { sind_set_error("FlowMaskBatch: width must be a multiple of 64 (got %d)", W); return SIND_E_ARG; }
+    SIND_TRY(recs_h.alloc(cap)); SIND_TRY(recs_d.alloc(cap)); SIND_TRY(out_d.alloc(slot_words * cap)); SIND_TRY(out_h.alloc(slot_words * cap));
+    tails.assign(cap, nullptr);
+    if (!done) HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    return SIND_OK;
+}
+FlowMaskBatch::~FlowMaskBatch() { if (done) (void)hipEventDestroy(done); }
+int FlowMaskBatch::set(int b, DynaTail* tail, const float* U, const float* V, const double Hm[9]) {
+    if (b < 0 || b >= cap || !tail) { sind_set_error("FlowMaskBatch::set: slot %d outside [0,%d)", b, cap); return SIND_E_ARG; }
+    FlowMaskRec& R = recs_h.p[b];
+    R.U = U; R.V = V; std::copy(Hm, Hm + 9, R.H); R.mag = tail->mag.p; R.magu8 = tail->magu8.p; R.hist = tail->hist_d.p; R.out = out_d.p + slot_words * b;
+    tails[b] = tail;
+    return SIND_OK;
+}
+int FlowMaskBatch::enqueue(int n) {
+    if (n < 1 || n > cap) { sind_set_error("FlowMaskBatch::enqueue: %d frames (capacity %d)", n, cap); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(cfg.device));
+    // a working histogram is zero whenever the threshold kernel that read it last completed; a frame that failed in between leaves it unknown
+    for (int b = 0; b < n; b++) { if (!tails[b]->hist_clean) HIP_TRY(hipMemsetAsync(tails[b]->hist_d.p, 0, 257 * sizeof(int), stream)); tails[b]->hist_clean = false; }
+    HIP_TRY(hipMemcpyAsync(recs_d.p, recs_h.p, (size_t)n * sizeof(FlowMaskRec), hipMemcpyHostToDevice, stream));
+    SIND_TRY(launch_flow_masks_frames(stream, recs_d.p, recs_h.p, n, cap, W, H));
+    HIP_TRY(hipMemcpyAsync(out_h.p, out_d.p, slot_words * n * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(done, stream));
+    pending = n;
+    return SIND_OK;
+}
+int FlowMaskBatch::wait() {
+    if (pending < 1) { sind_set_error("FlowMaskBatch::wait: nothing was enqueued"); return SIND_E_STATE; }
+    HIP_TRY(sind_event_wait(done));
+    for (int b = 0; b < pending; b++) tails[b]->hist_clean = true;
+    pending = 0;
     return SIND_OK;
 }
 
@@ -651,12 +708,12 @@ int DynaTail::finish_occluded(OccResult& out, const OccGpuOut* pre) {
 }
 
 int DynaTail::process(const uint16_t* depth_host, const uint16_t* depth_dev, const float* U, const float* V, uint8_t* dyna_out, uint8_t* label_out,
-                      const OccResult* pre, DynaTail* depth_half, const KmFrameResult* km) {
+                      const OccResult* pre, DynaTail* depth_half, const KmFrameResult* km, const FlowMasksReady* fm) {
     // same stage order as the reference (flow masks, clustering, fusion); the order also matters for throughput: a pool of tails that
     // all start with the 50-launch k-means chain was measured 20 ms per step slower than one that starts with the host-side pair sorting
     HIP_TRY(hipSetDevice(cfg.device));
     BitImg maskLow, maskHigh; n_frames++;
-    { const double t0 = tick_ms(); SIND_TRY(flow_masks(U, V, maskLow, maskHigh, pre ? pre->gridFlow : nullptr)); t_stage[0] += tick_ms() - t0; }
+    { const double t0 = tick_ms(); if (fm) flow_masks_ready(*fm, maskLow, maskHigh); else SIND_TRY(flow_masks(U, V, maskLow, maskHigh, pre ? pre->gridFlow : nullptr)); t_stage[0] += tick_ms() - t0; }
     DepthStageOut d;
     SIND_TRY((depth_half ? depth_half : this)->depth_stage(depth_host, depth_dev, pre, d, km));
     return fuse(maskLow, maskHigh, d, dyna_out, label_out);
@@ -704,11 +761,11 @@ int DynaTail::depth_stage(const uint16_t* depth_host, const uint16_t* depth_dev,
 }
 
 // flow-dependent half: flow masks (DD:1163-1367) and fusion (DD:1553-1636), then the state roll (DD:1660-1664)
-int DynaTail::flow_stage(const float* U, const float* V, const DepthStageOut& d, uint8_t* dyna_out, uint8_t* label_out, const float* gridFlowPre) {
+int DynaTail::flow_stage(const float* U, const float* V, const DepthStageOut& d, uint8_t* dyna_out, uint8_t* label_out, const float* gridFlowPre, const FlowMasksReady* fm) {
     HIP_TRY(hipSetDevice(cfg.device));
     if (!d.ready) { sind_set_error("DynaTail::flow_stage: the depth stage of this frame has not run"); return SIND_E_STATE; }
     BitImg maskLow, maskHigh; n_frames++;
-    { const double t0 = tick_ms(); SIND_TRY(flow_masks(U, V, maskLow, maskHigh, gridFlowPre)); t_stage[0] += tick_ms() - t0; }
+    { const double t0 = tick_ms(); if (fm) flow_masks_ready(*fm, maskLow, maskHigh); else SIND_TRY(flow_masks(U, V, maskLow, maskHigh, gridFlowPre)); t_stage[0] += tick_ms() - t0; }
     return fuse(maskLow, maskHigh, d, dyna_out, label_out);
 }
 

@@ -9,6 +9,9 @@ struct VarParams {      // cv::VariationalRefinement parameters (variational_ref
     float alpha = 20.0f, delta = 5.0f, gamma = 10.0f, omega = 1.6f, zeta = 0.1f, epsilon = 0.001f;
 };
 struct HMat { double h[9]; };
+// One frame of the batched flow-mask stage (launch_flow_masks_frames): the frame's flow, its homography, its residual workspaces, the working histogram
+// (256 counts + the maximum's bit pattern, zero on entry and on exit) and its result slot: [low words | high words | 261-word result block]
+struct FlowMaskRec { const float* U; const float* V; double H[9]; float* mag; uint8_t* magu8; int* hist; unsigned long long* out; };
 
 // per-level working planes (16), each [B][h][w] float, allocated once for the finest level
 struct FlowPlanes {
@@ -88,6 +91,9 @@ int launch_mag_stats(hipStream_t s, const float* u, const float* v, float* mag, 
 int launch_residual(hipStream_t s, const float* u, const float* v, const double H[9], float* mag, unsigned* maxbits, int* hist, uint8_t* magu8, int w, int h, bool already_zero = false);
 // hist: 257 working words (zeroed again by the kernel), res: 261 words = histogram, maximum, lo / hi / otsu / triangle
 int launch_flow_thresholds_and_masks(hipStream_t s, int* hist, int W, int H, int* res, const uint8_t* magu8, uint8_t* low, uint8_t* high);
+// result slot of one frame in 8-byte words: two bit masks of W * H / 64 words and the result block, rounded up to 16 bytes
+static inline size_t flow_mask_slot_words(int W, int H) { return (2 * ((size_t)W * H / 64) + (261 * sizeof(int) + 7) / 8 + 1) / 2 * 2; }
+int launch_flow_masks_frames(hipStream_t s, const FlowMaskRec* recs_dev, const FlowMaskRec* recs_host, int n, int capacity, int W, int H);
 int debug_flow_thresholds(hipStream_t s, int* hist, int n, int W, int H, int variant, int* res, double* mu1);
 int launch_threshold_masks(hipStream_t s, const uint8_t* magu8, float lo, float hi, uint8_t* low, uint8_t* high, int n);
 int launch_gather_grid(hipStream_t s, const float* u, const float* v, float* out, int w, int h, int step, int B = 1);

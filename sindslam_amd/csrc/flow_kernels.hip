@@ -950,33 +950,41 @@ __global__ void k_mag_max(const float* __restrict__ u, const float* __restrict__
 }
 // Pass 2: histogram of saturate_cast<uchar>(mag * (float)(255.0/max)); LDS histogram per workgroup, one global
 // atomic per bin per workgroup.  Optionally stores the u8 image (residual stage).
+__device__ __forceinline__ void mag_hist_plane(const float* __restrict__ mag, const unsigned* __restrict__ maxbits, int* __restrict__ hist,
+                                               uint8_t* __restrict__ out_u8, int n, int* lh) {
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) lh[i] = 0;
+    __syncthreads();
+    const float a = (float)(255.0 / (double)__uint_as_float(*maxbits));
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        int q = d_cvRound(mag[i] * a);
+        q = min(max(q, 0), 255);
+        if (out_u8) out_u8[i] = (uint8_t)q;
+        atomicAdd(&lh[q], 1);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) if (lh[i]) atomicAdd(&hist[i], lh[i]);
+}
 __global__ void k_mag_hist(const float* __restrict__ mag, const unsigned* __restrict__ maxbits, int* __restrict__ hist,
                            uint8_t* __restrict__ out_u8, int n) {
     __shared__ int lh[256];
     const int b = blockIdx.y;
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) lh[i] = 0;
-    __syncthreads();
-    const float a = (float)(255.0 / (double)__uint_as_float(maxbits[b]));
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        int q = d_cvRound(mag[(size_t)b * n + i] * a);
-        q = min(max(q, 0), 255);
-        if (out_u8) out_u8[(size_t)b * n + i] = (uint8_t)q;
-        atomicAdd(&lh[q], 1);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) if (lh[i]) atomicAdd(&hist[b * 256 + i], lh[i]);
+    mag_hist_plane(mag + (size_t)b * n, maxbits + b, hist + b * 256, out_u8 ? out_u8 + (size_t)b * n : nullptr, n, lh);
+}
+// the same for the frames of a record table (flow-mask stage of a whole k-means group): blockIdx.y = record
+__global__ void k_mag_hist_frames(const FlowMaskRec* __restrict__ recs, int n) {
+    __shared__ int lh[256];
+    const FlowMaskRec& R = recs[blockIdx.y];
+    mag_hist_plane(R.mag, reinterpret_cast<const unsigned*>(R.hist + 256), R.hist, R.magu8, n, lh);
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // Residual stage, reference DynaDetect.cc:1252-1271: flow - (p - H p), homography part in FP64 then cast to FP32.
 // A thread takes RM_ROWS pixels of one column (2 400 workgroups of one row segment each were mostly workgroup turnover: 11 us of the whole GPU per 640 x 480 frame, 512 times a step)
 #define RM_ROWS 4
-__global__ void k_residual_mag(const float* __restrict__ u, const float* __restrict__ v, HMat Hm, float* __restrict__ mag,
-                               unsigned* __restrict__ maxbits, int w, int h) {
-    const int col = blockIdx.x * blockDim.x + threadIdx.x, row0 = blockIdx.y * RM_ROWS;
+__device__ __forceinline__ void residual_mag_rows(const float* __restrict__ u, const float* __restrict__ v, const double* __restrict__ H, float* __restrict__ mag,
+                                                  unsigned* __restrict__ maxbits, int w, int h, int col, int row0) {
     float m = 0.f;
     if (col < w) {
-        const double* H = Hm.h;
         #pragma unroll
         for (int r = 0; r < RM_ROWS; r++) {
             const int row = row0 + r;
@@ -993,6 +1001,15 @@ __global__ void k_residual_mag(const float* __restrict__ u, const float* __restr
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     // thousands of waves hitting one address serialise in L2: a wave only issues the atomic when it can still raise the maximum
     if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > *(volatile unsigned*)maxbits) atomicMax(maxbits, __float_as_uint(m));
+}
+__global__ void k_residual_mag(const float* __restrict__ u, const float* __restrict__ v, HMat Hm, float* __restrict__ mag,
+                               unsigned* __restrict__ maxbits, int w, int h) {
+    residual_mag_rows(u, v, Hm.h, mag, maxbits, w, h, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y * RM_ROWS);
+}
+// the same for the frames of a record table: blockIdx.z = record, the homography comes from the record
+__global__ void k_residual_mag_frames(const FlowMaskRec* __restrict__ recs, int w, int h) {
+    const FlowMaskRec& R = recs[blockIdx.z];
+    residual_mag_rows(R.U, R.V, R.H, R.mag, reinterpret_cast<unsigned*>(R.hist + 256), w, h, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y * RM_ROWS);
 }
 // masks from the u8 residual: low -> 128, high -> 255 (stImgMasks), thresholds decided on the host from the histogram
 __global__ void k_threshold_masks(const uint8_t* __restrict__ magu8, float thr_low, float thr_high, uint8_t* __restrict__ low,
@@ -1080,10 +1097,8 @@ __device__ __forceinline__ int wave_max_i32(int v) { for (int o = 32; o > 0; o >
 __device__ __forceinline__ void wave_argmax_f64(double& v, int& idx) {
     for (int o = 32; o > 0; o >>= 1) { const double ov = __shfl_xor(v, o); const int oi = __shfl_xor(idx, o); if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; } }
 }
-__global__ void __launch_bounds__(64) k_flow_thresholds(int* __restrict__ hist, int W, int H, int* __restrict__ res, double* __restrict__ dbg_mu1, int keep_hist) {
-    hist += (size_t)blockIdx.x * 257; res += (size_t)blockIdx.x * 261; if (dbg_mu1) dbg_mu1 += (size_t)blockIdx.x * 256;
-    __shared__ double s_p[256];
-    __shared__ double4 s_c[256];                        // per bin: q1_i, i * p_i, y_i, skip flag
+__device__ __forceinline__ void flow_thresholds_wave(int* __restrict__ hist, int W, int H, int* __restrict__ res, double* __restrict__ dbg_mu1, int keep_hist,
+                                                     double* s_p, double4* s_c) {
     const int lane = threadIdx.x, N = W * H;
     const int4 h4 = *reinterpret_cast<const int4*>(hist + 4 * lane);
     const int hmax_bits = hist[256];
@@ -1216,6 +1231,31 @@ __global__ void __launch_bounds__(64) k_flow_thresholds(int* __restrict__ hist, 
     }
     if (lane == 0) { float* out = reinterpret_cast<float*>(res + 257); out[0] = lo; out[1] = hi; out[2] = otsu_f; out[3] = tri_f; }
     if (!keep_hist) { *reinterpret_cast<int4*>(hist + 4 * lane) = make_int4(0, 0, 0, 0); if (lane == 0) hist[256] = 0; }
+}
+__global__ void __launch_bounds__(64) k_flow_thresholds(int* __restrict__ hist, int W, int H, int* __restrict__ res, double* __restrict__ dbg_mu1, int keep_hist) {
+    __shared__ double s_p[256];
+    __shared__ double4 s_c[256];                        // per bin: q1_i, i * p_i, y_i, skip flag
+    flow_thresholds_wave(hist + (size_t)blockIdx.x * 257, W, H, res + (size_t)blockIdx.x * 261, dbg_mu1 ? dbg_mu1 + (size_t)blockIdx.x * 256 : nullptr, keep_hist, s_p, s_c);
+}
+// one block = the histogram of one record; the result block sits behind the record's two bit masks
+__global__ void __launch_bounds__(64) k_flow_thresholds_frames(const FlowMaskRec* __restrict__ recs, int W, int H, int mask_words) {
+    __shared__ double s_p[256];
+    __shared__ double4 s_c[256];
+    const FlowMaskRec& R = recs[blockIdx.x];
+    flow_thresholds_wave(R.hist, W, H, reinterpret_cast<int*>(R.out + 2 * (size_t)mask_words), nullptr, 0, s_p, s_c);
+}
+// both masks of every record, bit-packed in BitImg's layout (row-major, W / 64 words per row, bit x & 63 of word x >> 6): the width is a multiple of 64, so
+// 64 consecutive pixels are one word and one wave ballot makes it.  Same comparison as k_threshold_masks_dev (q > (double)thr); blockIdx.y = record.
+__global__ void __launch_bounds__(256) k_flow_mask_bits_frames(const FlowMaskRec* __restrict__ recs, int mask_words) {
+    const FlowMaskRec& R = recs[blockIdx.y];
+    const float* thr = reinterpret_cast<const float*>(reinterpret_cast<const int*>(R.out + 2 * (size_t)mask_words) + 257);
+    const double tl = (double)thr[0], th = (double)thr[1];
+    const int lane = threadIdx.x & 63;
+    for (int word = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); word < mask_words; word += gridDim.x * (blockDim.x >> 6)) {
+        const double q = (double)R.magu8[(size_t)word * 64 + lane];
+        const unsigned long long lo = __ballot(q > tl), hi = __ballot(q > th);
+        if (lane == 0) { R.out[word] = lo; R.out[(size_t)mask_words + word] = hi; }
+    }
 }
 // (16 pixels per thread where the planes allow 16-byte accesses: one pixel per thread was 1 200 workgroups of turnover per 640 x 480 frame)
 __global__ void k_threshold_masks_dev(const uint8_t* __restrict__ magu8, const float* __restrict__ thr, uint8_t* __restrict__ low, uint8_t* __restrict__ high, int n, int wide) {
@@ -1543,6 +1583,22 @@ int launch_flow_thresholds_and_masks(hipStream_t s, int* hist, int W, int H, int
     hipLaunchKernelGGL(k_flow_thresholds, dim3(1), dim3(64), 0, s, hist, W, H, res, (double*)nullptr, 0);
     const int wide = ((((uintptr_t)magu8 | (uintptr_t)low | (uintptr_t)high) & 15) == 0) ? 1 : 0;
     hipLaunchKernelGGL(k_threshold_masks_dev, dim3(divup(wide ? divup(W * H, 16) : W * H, 256)), dim3(256), 0, s, magu8, reinterpret_cast<const float*>(res + 257), low, high, W * H, wide);
+    return SIND_OK;
+}
+// The flow-mask stage for the n frames of a record table (device copy of `host`, which is checked here: a bad record is a wild device access) in four launches.
+// Every record's working histogram must be zero on entry and is left zeroed.
+int launch_flow_masks_frames(hipStream_t s, const FlowMaskRec* recs_dev, const FlowMaskRec* host, int n, int capacity, int W, int H) {
+    if (n < 1 || n > capacity || !recs_dev || !host || W < 64 || W % 64 != 0 || H < 1) { sind_set_error("launch_flow_masks_frames: %d records (capacity %d), %d x %d", n, capacity, W, H); return SIND_E_ARG; }
+    for (int i = 0; i < n; i++) {
+        const FlowMaskRec& R = host[i];
+        if (!R.U || !R.V || !R.mag || !R.magu8 || !R.hist || !R.out || ((uintptr_t)R.hist & 15) || ((uintptr_t)R.out & 15)) { sind_set_error("launch_flow_masks_frames: record %d has a null or misaligned pointer", i); return SIND_E_ARG; }
+    }
+    const int np = W * H, words = np / 64;
+    hipLaunchKernelGGL(k_residual_mag_frames, dim3(divup(W, 128), divup(H, RM_ROWS), n), dim3(128), 0, s, recs_dev, W, H);
+    hipLaunchKernelGGL(k_mag_hist_frames, dim3(std::min(divup(np, 256), 64), n), dim3(256), 0, s, recs_dev, np);
+    hipLaunchKernelGGL(k_flow_thresholds_frames, dim3(n), dim3(64), 0, s, recs_dev, W, H, words);
+    hipLaunchKernelGGL(k_flow_mask_bits_frames, dim3(std::min(divup(words, 16), 64), n), dim3(256), 0, s, recs_dev, words);
+    HIP_TRY(hipGetLastError());
     return SIND_OK;
 }
 // test entry: n histograms (257 words each, device) through the one-wave kernel (variant 1; mu1 chain optionally dumped) or the serial reference (variant 0)

@@ -215,6 +215,15 @@ int sind_pipe_set_kmeans_groups(sind_pipe* p, int groups) {
     p->km_groups_fixed = groups; if (groups > 0) p->km_groups = groups; return SIND_OK;
 }
 int sind_pipe_get_kmeans_groups(sind_pipe* p, int* groups) { if (!p || !groups) { sind_set_error("sind_pipe_get_kmeans_groups: null argument"); return SIND_E_ARG; } *groups = p->batch_km ? p->km_groups : 0; return SIND_OK; }
+int sind_pipe_set_flow_mask_batch(sind_pipe* p, int on) {
+    if (!p) { sind_set_error("sind_pipe_set_flow_mask_batch: null handle"); return SIND_E_ARG; }
+    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_set_flow_mask_batch: a submitted step is still pending"); return SIND_E_STATE; }
+    p->fm_batch = on != 0; p->fm_frames = 0; return SIND_OK;
+}
+int sind_pipe_get_flow_mask_batch(sind_pipe* p, int* on, long long* frames_batched) {
+    if (!p || !on || !frames_batched) { sind_set_error("sind_pipe_get_flow_mask_batch: null argument"); return SIND_E_ARG; }
+    *on = p->fm_batch ? 1 : 0; *frames_batched = p->fm_frames.load(); return SIND_OK;
+}
 // several handles on one GPU (sindslam_amd.pipeline.PipelineGroup: the streams of a small step cut into independent pipelines whose launch chains interleave):
 // each takes its part of the process's CPU share -- the tokens of its pool tasks and its CalOccluded runners follow
 int sind_pipe_set_cpu_share(sind_pipe* p, int cores) {

@@ -72,6 +72,10 @@ struct sind_pipe {
     // then the S tails of that frame on the pool); used when there are several streams and the depth half is not run ahead
     static constexpr int KM_GROUPS = 4;
     KMeansBatch kmb[KM_GROUPS]; int km_groups = 1, km_groups_max = 1, km_groups_fixed = -1; hipStream_t km_stream = nullptr, km_streams[KM_GROUPS] = {nullptr}; bool batch_km = false;
+    // flow-mask stage of a round, batched the same way (FlowMaskBatch, dyna.hpp): in the non-split rounds every stream of a group holds the state its homography needs
+    // once the round thread has waited for the previous round's tails, so the homographies are computed on the pool WHILE the batched k-means runs and the stage's
+    // kernels run once for the group.  One set per handle: phase B of two steps is never in flight together (a submit finishes the previous step's tails before it returns).
+    FlowMaskBatch fmb[KM_GROUPS]; bool fm_batch = true; std::atomic<long long> fm_frames{0};
     std::vector<std::thread> round_threads; std::mutex km_stat_mu; double km_round_ms = 0; long km_rounds = 0;
     std::vector<std::unique_ptr<PinnedBuf<uint8_t>>> upload_stage;        // page-locked staging of sind_pipe_process (host-buffer entry point), two 4 MB buffers per uploading worker
     std::vector<std::unique_ptr<DynaTail>> occ_tails;     // CalOccluded workspaces, one per pool worker (state free)
@@ -99,6 +103,7 @@ struct sind_pipe {
         // and a gate per frame that opens when both its CalOccluded result and the stream's previous depth stage are there
         bool depth_ahead = false; std::vector<DepthStageOut> dout; std::unique_ptr<std::atomic<int>[]> gate; TaskGroup depth_group;
         std::vector<int> depth_rc; std::vector<std::string> depth_err;
+        TaskGroup fm_group[4];                                         // per k-means group: the homography tasks of a round's batched flow-mask stage
         TaskGroup occ_group, tail_group, km_tails[4]; int km_groups = 1, km_first[5] = {0, 0, 0, 0, 0};       /* (4 = sind_pipe::KM_GROUPS) the step's own partition of the streams */ std::vector<int> occ_rc, tail_rc, dchain_rc; std::vector<std::string> occ_err, tail_err, dchain_err;      /* dchain_*: the depth chain of a stream in two-chain mode (its flow chain writes tail_*: two workers, two slots) */
         std::vector<int> active, first; std::vector<uint64_t> state_hash;      // tails of stream s run for first[s] <= t < active[s] (empty: 0 / all T); per-frame state fingerprints [S][T][2]
         bool few_chain = false;                                        // this step runs a handful of streams as per-stream chains (see phase_b_start)

@@ -18,16 +18,16 @@ void depth_task(sind_pipe* p, sind_pipe::StepBuf* sb, int k, int worker) {
         p->workers.push(sb->depth_group, [p, sb, k](int w) { depth_task(p, sb, k + 1, w); }); return;
     }
 }
-static bool tail_one(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int t, int worker, const KmFrameResult* km) {
+static bool tail_one(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int t, int worker, const KmFrameResult* km, const FlowMasksReady* fm = nullptr) {
     SindRange range_t("sind tail: flow masks, SegAndMerge, fusion, dilation, ORB mask filter");
     p->tails[s]->stream = p->worker_streams[worker];
     const int T = p->T, W = p->c.width, H = p->c.height; const size_t np = (size_t)W * H;
     static thread_local std::vector<uint8_t> dy, lb, dil;
     dy.resize(np); lb.resize(np); dil.resize(np);
     const int k = s * T + t;
-    int r = (sb->depth_ahead || sb->two_chain) ? p->tails[s]->flow_stage(sb->U.p + np * k, sb->V.p + np * k, sb->dout[k], dy.data(), lb.data(), sb->occ[k].gridFlow)
+    int r = (sb->depth_ahead || sb->two_chain) ? p->tails[s]->flow_stage(sb->U.p + np * k, sb->V.p + np * k, sb->dout[k], dy.data(), lb.data(), sb->occ[k].gridFlow, fm)
                             : p->tails[s]->process(sb->depth_h.data() + np * k, sb->depth_dev.p + np * k, sb->U.p + np * k, sb->V.p + np * k, dy.data(), lb.data(), &sb->occ[k],
-                                                   p->dtails.empty() ? nullptr : (p->dtails[s]->stream = p->worker_streams[worker], p->dtails[s].get()), km);
+                                                   p->dtails.empty() ? nullptr : (p->dtails[s]->stream = p->worker_streams[worker], p->dtails[s].get()), km, fm);
     if (r != SIND_OK) { sb->tail_rc[s] = r; sb->tail_err[s] = sind_last_error(); return false; }
     if (p->hashing) { sb->state_hash[2 * (size_t)k] = p->tails[s]->state_hash[0]; sb->state_hash[2 * (size_t)k + 1] = p->tails[s]->state_hash[1]; }
     double* tf = p->tails[s]->t_fine; double t0 = now_ms();
@@ -46,11 +46,11 @@ static bool tail_one(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int
     if (o.desc) std::memcpy(o.desc + (size_t)k * o.cap * 32, dd.data(), dd.size());
     return true;
 }
-static void tail_task(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int t, int worker, const KmFrameResult* km = nullptr, bool chain = true) {
+static void tail_task(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int t, int worker, const KmFrameResult* km = nullptr, bool chain = true, const FlowMasksReady* fm = nullptr) {
     struct Spin { int keep; explicit Spin(bool on) : keep(t_sind_spin_us) { if (on) t_sind_spin_us = 400; } ~Spin() { t_sind_spin_us = keep; } } spin(sb->few_chain);      // few chains, idle host: poll before sleeping (common.hpp)
     for (;;) {
-        if (!tail_one(p, sb, o, s, t, worker, km) || !chain || t + 1 >= (sb->active.empty() ? p->T : std::min(p->T, sb->active[s]))) return;
-        if (p->S == 1 || sb->few_chain) { t++; km = nullptr; continue; }      // one stream / a few chains: the next frame's chain link right here (no hand-over to another worker)
+        if (!tail_one(p, sb, o, s, t, worker, km, fm) || !chain || t + 1 >= (sb->active.empty() ? p->T : std::min(p->T, sb->active[s]))) return;
+        if (p->S == 1 || sb->few_chain) { t++; km = nullptr; fm = nullptr; continue; }      // one stream / a few chains: the next frame's chain link right here (no hand-over to another worker)
         p->workers.push(sb->tail_group, [p, sb, o, s, t](int w) { tail_task(p, sb, o, s, t + 1, w); }); return;
     }
 }
@@ -76,6 +76,13 @@ static void depth_chain(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, 
         if (sb->fgate[k].fetch_add(1) == 1) p->workers.push(sb->tail_group, [p, sb, o, s, t, t1](int w) { flow_chain(p, sb, o, s, t, t1, w); });
     }
 }
+// a round's batched flow-mask stage as its round thread sees it: the slot of every stream of the group in the batch (-1: no frame in this round), the homography
+// tasks still out, the first failure, and the masks handed to the tails
+struct FmRound {
+    std::vector<int> slot; std::vector<FlowMasksReady> ready; int n = 0; std::atomic<int> left{0};
+    std::mutex m; int rc = SIND_OK; std::string err;
+    void fail(int r, const std::string& e) { std::lock_guard<std::mutex> lk(m); if (rc == SIND_OK) { rc = r; err = e; } }
+};
 void phase_b_start(sind_pipe* p, sind_pipe::StepBuf& sb, const PipeOut& o) {
     const int S = p->S;
     sb.tail_rc.assign(S, SIND_OK); sb.tail_err.assign(S, std::string()); sb.dchain_rc.assign(S, SIND_OK); sb.dchain_err.assign(S, std::string());
@@ -117,21 +124,47 @@ void phase_b_start(sind_pipe* p, sind_pipe::StepBuf& sb, const PipeOut& o) {
             (void)pthread_setname_np(pthread_self(), "sind-rounds"); (void)hipSetDevice(p->c.device);
             const size_t np = (size_t)p->c.width * p->c.height;
             const int s0 = sbp->km_first[g], ns = sbp->km_first[g + 1] - s0; std::vector<const uint8_t*> prev(ns);
+            FmRound fm; fm.slot.assign(ns, -1); fm.ready.resize(ns);
             for (int t = 0; t < p->T; t++) {
                 bool any = false;                                        // ragged / replayed steps: rounds in which no stream of the group has a frame are passed over
                 for (int s = s0; s < s0 + ns && !any; s++) any = (sbp->first.empty() || t >= sbp->first[s]) && (sbp->active.empty() || t < sbp->active[s]);
                 if (!any) continue;
                 if (t > 0) WorkerPool::wait(sbp->km_tails[g]);           // this group's tails (split: their depth halves) of frame t - 1: their merged labels start this round's k-means
                 for (int s = 0; s < ns; s++) prev[s] = depth_half(p, s0 + s)->prev_km_labels();
+                // Batched flow-mask stage of this round (non-split rounds only: with split rounds the flow half of frame t - 1 may still be running here, and its state is
+                // what the homography starts from).  One homography task per stream with a frame in this round; whichever finishes last enqueues the group's launches.
+                fm.n = 0; fm.rc = SIND_OK;
+                if (p->fm_batch && !split) for (int s = s0; s < s0 + ns; s++)
+                    if (sbp->tail_rc[s] == SIND_OK && (sbp->first.empty() || t >= sbp->first[s]) && (sbp->active.empty() || t < sbp->active[s])) fm.slot[s - s0] = fm.n++; else fm.slot[s - s0] = -1;
+                if (fm.n > 0) {
+                    fm.left.store(fm.n);
+                    FmRound* f = &fm;
+                    for (int s = s0; s < s0 + ns; s++) if (fm.slot[s - s0] >= 0) p->workers.push(sbp->fm_group[g], [p, sbp, f, s, t, g, s0, np](int w) {
+                        const int k = s * p->T + t; double Hm[9];
+                        DynaTail* tl = p->tails[s].get(); tl->stream = p->worker_streams[w];
+                        int r = tl->flow_masks_homography(sbp->U.p + np * k, sbp->V.p + np * k, sbp->occ[k].gridFlow, Hm);
+                        if (r == SIND_OK) r = p->fmb[g].set(f->slot[s - s0], tl, sbp->U.p + np * k, sbp->V.p + np * k, Hm);
+                        if (r != SIND_OK) f->fail(r, sind_last_error());
+                        if (f->left.fetch_sub(1) != 1) return;
+                        if (f->rc == SIND_OK && (r = p->fmb[g].enqueue(f->n)) != SIND_OK) f->fail(r, sind_last_error());
+                    });
+                }
                 const double tk = now_ms();
                 int rc;
                 { SindRange range_km("sind round: batched k-means of frame t of one group of streams");
                   rc = p->kmb[g].run(sbp->depth_dev.p + np * ((size_t)s0 * p->T + t), np * p->T, ns, prev.data()); }
                 { std::lock_guard<std::mutex> lk(p->km_stat_mu); p->km_round_ms += now_ms() - tk; p->km_rounds++; }
+                if (fm.n > 0) {              // (also when the k-means failed: the tasks point at this thread's round state)
+                    WorkerPool::wait(sbp->fm_group[g]);
+                    if (fm.rc == SIND_OK) { const int r = p->fmb[g].wait(); if (r != SIND_OK) fm.fail(r, sind_last_error()); }
+                    if (fm.rc == SIND_OK) { for (int s = 0; s < ns; s++) if (fm.slot[s] >= 0) fm.ready[s] = p->fmb[g].result(fm.slot[s]); p->fm_frames += fm.n; }
+                }
                 if (rc != SIND_OK) { const std::string e = sind_last_error(); for (int s = s0; s < s0 + ns; s++) if (sbp->tail_rc[s] == SIND_OK) { sbp->tail_rc[s] = rc; sbp->tail_err[s] = "batched k-means: " + e; } return; }
+                if (fm.rc != SIND_OK) { for (int s = s0; s < s0 + ns; s++) if (sbp->tail_rc[s] == SIND_OK) { sbp->tail_rc[s] = fm.rc; sbp->tail_err[s] = "batched flow masks: " + fm.err; } return; }
                 for (int s = s0; s < s0 + ns; s++) {
                     if (!(sbp->tail_rc[s] == SIND_OK && (sbp->first.empty() || t >= sbp->first[s]) && (sbp->active.empty() || t < sbp->active[s]))) continue;
-                    if (!split) { p->workers.push(sbp->km_tails[g], [p, sbp, o, s, t, g, s0](int w) { tail_task(p, sbp, o, s, t, w, &p->kmb[g].result(s - s0), false); }); continue; }
+                    if (!split) { const bool have = fm.n > 0; const FlowMasksReady fr = have ? fm.ready[s - s0] : FlowMasksReady{nullptr, nullptr, nullptr};      // (by value: this thread may be gone when the task runs; the masks themselves stay until the group's next enqueue)
+                                  p->workers.push(sbp->km_tails[g], [p, sbp, o, s, t, g, s0, fr, have](int w) { tail_task(p, sbp, o, s, t, w, &p->kmb[g].result(s - s0), false, have ? &fr : nullptr); }); continue; }
                     p->workers.push(sbp->km_tails[g], [p, sbp, o, s, t, g, s0, np](int w) {
                         const int k = s * p->T + t, t1 = sbp->active.empty() ? p->T : std::min(p->T, sbp->active[s]);
                         DynaTail* dt = p->dtails[s].get(); dt->stream = p->worker_streams[w];      // (on the chain that the next round waits for: the pool's high-priority stream)

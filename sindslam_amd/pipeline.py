@@ -99,6 +99,15 @@ class Pipeline:
         """groups of streams whose batched k-means rounds run as independent chains right now (0: no batched k-means)"""
         q = C.c_int(); check(lib().sind_pipe_get_kmeans_groups(self._h, C.byref(q)), "sind_pipe_get_kmeans_groups"); return q.value
 
+    def set_flow_mask_batch(self, on: bool):
+        """flow-mask stage of the tails batched per k-means round (non-split rounds; default on; same results); resets the frames_batched counter"""
+        check(lib().sind_pipe_set_flow_mask_batch(self._h, int(bool(on))), "sind_pipe_set_flow_mask_batch")
+
+    def flow_mask_batch(self):
+        """(switch, frames whose masks came from a batched flow-mask stage since the switch was last set)"""
+        on = C.c_int(); n = C.c_longlong()
+        check(lib().sind_pipe_get_flow_mask_batch(self._h, C.byref(on), C.byref(n)), "sind_pipe_get_flow_mask_batch"); return bool(on.value), int(n.value)
+
     def host_info(self) -> dict:
         a = np.zeros(6, np.int32); check(lib().sind_pipe_host_info(self._h, ptr(a)), "sind_pipe_host_info")
         return dict(cpu_share=int(a[0]), workers=int(a[1]), cpu_tokens_max=int(a[2]), cores_usable=int(a[3]), cgroup_quota_cores=(int(a[4]) if a[4] >= 0 else None), local_world=int(a[5]))
@@ -250,6 +259,8 @@ class PipelineGroup:
     def keypoints(self, s, t): k = s * self.T + t; n = self.nkp[k]; return self.kps[k, :n], self.desc[k, :n]
     def grow_share(self): return self.pipes[0].grow_share()
     def kmeans_groups(self): return self.pipes[0].kmeans_groups()
+    def set_flow_mask_batch(self, on): [p.set_flow_mask_batch(on) for p in self.pipes]
+    def flow_mask_batch(self): r = [p.flow_mask_batch() for p in self.pipes]; return r[0][0], sum(x[1] for x in r)
     def host_info(self): h = self.pipes[0].host_info(); h["pipelines"] = len(self.pipes); return h
 
     def set_active_frames(self, a):
