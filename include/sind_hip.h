@@ -1023,6 +1023,74 @@ int sind_match_update_points(sind_match* m, const sind_mappoints_item* items, in
 int sindh_update_points(const sind_mappoints_item* items, int B, const float* scale_factors, int nlevels);   /* host twin (libsind_host.so too); no limits */
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Covisibility: the observations of the map on the device and the three walks over them.  Replaces the counting in
+ *   void KeyFrame::UpdateConnections()                                                                  src/KeyFrame.cc:289-320
+ *   void Tracking::UpdateLocalKeyFrames()                                                               src/Tracking.cc:1268-1288
+ *   void LocalMapping::KeyFrameCulling()                                                                src/LocalMapping.cc:645-691
+ * each of which copies every point's std::map<KeyFrame*, size_t> and counts per key frame.  A handle of its own (its own stream, fixed capacity from create), as
+ * sind_bowdb: the state lives on the device and a query uploads point ids alone.  All arithmetic is integer: the results are the literal loops' in any order of
+ * evaluation, and nothing here is unpinned but the order in which the CALLER walks pointer-keyed containers (the Python layer: ascending id).
+ * State.  The point side of the map (MapPoint::mObservations) stored key-frame-major: cell (kf, idx), kf in [0, cap_kf), idx in [0, cap_feat), holds `point`
+ * (-1: empty), `octave` = mvKeysUn[idx].octave and `stereo` = (mvuRight[idx] >= 0).  A point has at most one cell per key frame (AddObservation ignores a second
+ * one): that is the caller's contract and is not checked.  Per point the handle keeps n_obs (the reference's nObs: a stereo cell counts 2) and a histogram of its
+ * cells by octave, [nlevels].
+ *   apply   n ops {kf, idx, point, octave, stereo} in ONE launch (k_covis_apply, one lane per op): the lane exchanges the cell and moves the two aggregates of the
+ *           old and the new point with integer atomics.  point = -1 clears the cell (octave and stereo are not read); setting an occupied cell replaces its
+ *           content; clearing an empty cell does nothing; n = 0 is valid.  A call may hold at most ONE op per cell (checked on the host), which keeps the
+ *           exchange free of races.  The caller's array is free again on return.
+ *   count   Q queries {self_kf, n, points, count} at once: count[k], k in [0, cap_kf), = the number of list entries whose point has a cell in key frame k.  An entry
+ *           -1 is skipped (NULL, or a point the caller found isBad(): that filter is the caller's, as for sind_match_update_points).  count[self_kf] = 0 is the
+ *           mnId == mnId skip of UpdateConnections; self_kf = -1 (the tracker's vote) skips nothing.  The list is a MULTISET: a point listed twice counts twice, as
+ *           the loop over mvpMapPoints does.  THREE launches and one host wait for any Q: k_covis_tag (one lane per entry; every query owns as many consecutive bits
+ *           of a per-point tag as its list names one point most often, bit t tagging the points named more than t times), k_covis_count (one wave per key-frame row
+ *           and 64 bits: the row read coalesced, the tags gathered, one ballot and popcount per bit; no atomics), k_covis_untag (clears exactly the bits that were set;
+ *           the tags are never cleared wholesale).  The bits of a query are added on the host.  The cost is one pass over rows * cap_feat cells per 64 bits, rows =
+ *           the highest key frame ever set + 1, whatever the observation counts.
+ *   cull    B items {kf, n, points, octave, close, n_mps, n_redundant, redundant} at once, each the body of the loop over one key frame's points in KeyFrameCulling,
+ *           entry i = feature i of key frame kf.  An entry is skipped if its point is -1 or close[i] is 0 (close carries the mvDepth test of :660, which the caller
+ *           evaluates; all 1 for monocular).  Otherwise *n_mps is incremented, and the entry is redundant if n_obs(point) > th_obs and the point has at least th_obs
+ *           cells in OTHER key frames with octave <= octave[i] + 1: the histogram's prefix up to min(octave[i] + 1, nlevels - 1), minus the point's own cell in kf
+ *           if it has one there that qualifies.  The own cell is (kf, i) where that holds the point; otherwise the row is searched (an inconsistent map may hold
+ *           the point at another index, or at none).  The reference's early break makes its verdict depend on that count alone.  redundant[i] = 0 / 1 per
+ *           entry (skipped: 0; may be NULL), *n_redundant their sum.  ONE launch (k_covis_cull, one lane per entry, the counts reduced per item) and one wait.
+ *           What stays with the caller: nRedundantObservations > 0.9 * nMPs (:693, FP64) and SetBadFlag.
+ *   read_row, read_points   the state back, for tests and tools: a row's cells (octave and stereo 0 where empty), and n_obs and the histogram of n points.
+ * Limits, decided in create: cap_kf * cap_feat <= 2^28, cap_points <= 2^24, nlevels <= 16, max_queries <= 4096: beyond them SIND_E_CAPACITY.  Per call: a list or an
+ * item of more than cap_feat entries, Q or B > max_queries, or more tag bits in one count than 64 * ceil(max_queries / 64): SIND_E_CAPACITY.
+ * SIND_E_ARG: a NULL handle, a NULL array with a non-zero count, a NULL output, a negative count, a key frame, index, point or octave out of range (a point: [-1,
+ * cap_points); self_kf: [-1, cap_kf); the octave of a skipped cull entry is not read), two ops on one cell.  On any error nothing is launched, the state and the outputs
+ * are untouched.
+ * sindh_covis_* are the host twins (libsind_host.so too): the same per-element source (csrc/host/covis.hpp), the state in host memory, none of the per-call limits.
+ */
+typedef struct sind_covis sind_covis;
+typedef struct sind_covis_op { int kf, idx, point, octave, stereo; } sind_covis_op;
+typedef struct sind_covis_query {
+    int self_kf, n; const int* points;                                                /* [n] */
+    int* count;                                                                       /* output (host), [cap_kf] */
+} sind_covis_query;
+typedef struct sind_covis_cull_item {
+    int kf, n; const int* points; const uint8_t* octave; const uint8_t* close;        /* [n] x3 */
+    int* n_mps; int* n_redundant; uint8_t* redundant;                                 /* outputs (host): [1], [1], [n] or NULL */
+} sind_covis_cull_item;
+int sind_covis_create(int cap_kf, int cap_feat, int cap_points, int nlevels, int max_queries, int device, sind_covis** out);
+int sind_covis_destroy(sind_covis* c);
+int sind_covis_clear(sind_covis* c);
+int sind_covis_apply(sind_covis* c, const sind_covis_op* ops, int n);
+int sind_covis_read_row(sind_covis* c, int kf, int* point, uint8_t* octave, uint8_t* stereo);          /* [cap_feat] x3 */
+int sind_covis_read_points(sind_covis* c, const int* points, int n, int* n_obs, int* hist);           /* [n], [n], [n][nlevels] */
+int sind_covis_count(sind_covis* c, const sind_covis_query* q, int Q);
+int sind_covis_cull(sind_covis* c, const sind_covis_cull_item* items, int B, int th_obs);
+typedef struct sindh_covis sindh_covis;
+int sindh_covis_create(int cap_kf, int cap_feat, int cap_points, int nlevels, int max_queries, int device, sindh_covis** out);   /* max_queries and device are not used */
+int sindh_covis_destroy(sindh_covis* c);
+int sindh_covis_clear(sindh_covis* c);
+int sindh_covis_apply(sindh_covis* c, const sind_covis_op* ops, int n);
+int sindh_covis_read_row(sindh_covis* c, int kf, int* point, uint8_t* octave, uint8_t* stereo);
+int sindh_covis_read_points(sindh_covis* c, const int* points, int n, int* n_obs, int* hist);
+int sindh_covis_count(sindh_covis* c, const sind_covis_query* q, int Q);
+int sindh_covis_cull(sindh_covis* c, const sind_covis_cull_item* items, int B, int th_obs);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Mapping consumer.  Replaces, for B key frames at once, the body of
  *   generatePointCloud(imgRGB, imgDepth, imgDepthLast, imgDynaMask, imgDynaMaskLast, imgLabel, poseRelative, Twc)
  *                                                                              octomap_pub/src/pubPointCloud.cc:471-668
