@@ -189,6 +189,14 @@ int sind_debug_flow_masks_batch(const float* u, const float* v, const double* ho
 int sind_debug_peac_grow(const uint16_t* depth, int n, int width, int height, float fx, float fy, float cx, float cy, float depth_scale, int device,
                          int8_t* member_gpu, int8_t* member_host, uint8_t* pair_gpu, uint8_t* pair_host, int* status);
 
+/* parity-test access to the GPU front of CalOccluded (DynaDetect.cc:429-482) and the depth normalisation of the region-adjacency stage (DynaDetect.cc:765-768) through the
+ * production launchers (csrc/depth_kernels.hip: k_median5_u16, k_max_u16, k_grad_edge, k_morph_e4, k_depth_norm): n depth frames (host u16 [n][height][width], 1 <= n <= 64,
+ * 7 <= width, height <= 4096).  n == 1 takes the single-frame forms of the drop-in path, n >= 2 the batched forms of the pipeline.  Per frame: filt = medianBlur(5) (u16),
+ * maxima [n][2] = {maximum of filt, maximum of the raw frame}, edge_pre / edge = the gradient edge before / after MORPH_OPEN with the 4 x 4 ellipse, total_area, depth_n = the
+ * 8-bit normalised depth; images are [n][height][width]. */
+int sind_debug_depth_front(const uint16_t* depth, int n, int width, int height, float depth_scale, int device,
+                           uint16_t* filt, unsigned* maxima, uint8_t* edge_pre, uint8_t* edge, uint8_t* total_area, uint8_t* depth_n);
+
 /* parity-test access to the bit-plane dilation used by the region-adjacency stage (7x7 ellipse on 64-pixel words, cv::dilate semantics):
  * planes / out are host arrays [nplanes][height][ceil(width / 64)] of 64-bit words, bit i of word k = pixel 64 k + i. */
 int sind_debug_dilate_planes(const unsigned long long* planes, int nplanes, int width, int height, int n, int device, unsigned long long* out);

@@ -207,6 +207,47 @@ int sind_debug_dilate_planes(const unsigned long long* planes, int nplanes, int 
     return SIND_OK;
 }
 
+// parity-test access to the GPU front of CalOccluded and the depth normalisation of the RAG statistics: n depth frames (host, [n][height][width] u16) through the production
+// launchers with the arguments dyna_engine.cpp gives them -- n == 1: the single-frame forms of DynaTail::cal_occluded_p1 / seg_and_merge (maxima in slots 0 and 1 of one
+// two-word buffer), n >= 2: the batched forms of OccBatch::run (per-frame maxima slots, stride 1; the raw maxima n words behind the filtered ones).  The maxima are cleared
+// by launch_max_u16 itself, as in production.  maxima [n][2] = {of the filtered frame, of the raw frame}; edge_pre = the gradient edge before the 4 x 4 opening.
+int sind_debug_depth_front(const uint16_t* depth, int n, int width, int height, float depth_scale, int device,
+                           uint16_t* filt_out, unsigned* maxima, uint8_t* edge_pre, uint8_t* edge_out, uint8_t* total_area, uint8_t* depth_n) {
+    if (!depth || !filt_out || !maxima || !edge_pre || !edge_out || !total_area || !depth_n || n < 1 || n > 64 || width < 7 || height < 7 || width > 4096 || height > 4096 || !(depth_scale > 0)) {
+        sind_set_error("sind_debug_depth_front: bad arguments (1..64 frames of 7 x 7 to 4096 x 4096)"); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(device));
+    const int W = width, H = height, N = W * H, B = n; const size_t NB = (size_t)N * B;
+    DevBuf<uint16_t> dd, filt; DevBuf<uint8_t> edge, edgeTmp, total, depthN; DevBuf<unsigned> umax;
+    SIND_TRY(dd.alloc(NB)); SIND_TRY(filt.alloc(NB)); SIND_TRY(edge.alloc(NB)); SIND_TRY(edgeTmp.alloc(NB)); SIND_TRY(total.alloc(NB)); SIND_TRY(depthN.alloc(NB)); SIND_TRY(umax.alloc((size_t)2 * B));
+    HIP_TRY(hipMemcpy(dd.p, depth, NB * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(umax.p, 0xff, (size_t)2 * B * sizeof(unsigned)));      // a slot a launch forgets to clear shows
+    hipStream_t s = nullptr;
+    if (B == 1) {
+        SIND_TRY(sind::launch_median5(s, dd.p, filt.p, W, H));
+        SIND_TRY(sind::launch_max_u16(s, filt.p, N, umax.p));
+        SIND_TRY(sind::launch_grad_edge(s, filt.p, umax.p, edge.p, total.p, W, H, depth_scale));
+        HIP_TRY(hipMemcpy(edge_pre, edge.p, NB, hipMemcpyDeviceToHost));
+        SIND_TRY(sind::launch_morph(s, edge.p, edgeTmp.p, W, H, 4, false));
+        SIND_TRY(sind::launch_morph(s, edgeTmp.p, edge.p, W, H, 4, true));
+        SIND_TRY(sind::launch_max_u16(s, dd.p, N, umax.p + 1)); SIND_TRY(sind::launch_depth_norm(s, dd.p, umax.p + 1, depthN.p, N));
+    } else {
+        SIND_TRY(sind::launch_max_u16(s, dd.p, N, umax.p + B, B, 1)); SIND_TRY(sind::launch_depth_norm(s, dd.p, umax.p + B, depthN.p, N, B, 1));
+        SIND_TRY(sind::launch_median5(s, dd.p, filt.p, W, H, B));
+        SIND_TRY(sind::launch_max_u16(s, filt.p, N, umax.p, B, 1));
+        SIND_TRY(sind::launch_grad_edge(s, filt.p, umax.p, edge.p, total.p, W, H, depth_scale, B, 1));
+        HIP_TRY(hipMemcpy(edge_pre, edge.p, NB, hipMemcpyDeviceToHost));
+        SIND_TRY(sind::launch_morph(s, edge.p, edgeTmp.p, W, H, 4, false, B));
+        SIND_TRY(sind::launch_morph(s, edgeTmp.p, edge.p, W, H, 4, true, B));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<unsigned> mh((size_t)2 * B);
+    HIP_TRY(hipMemcpy(mh.data(), umax.p, mh.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; b++) { maxima[2 * b] = mh[B == 1 ? 0 : b]; maxima[2 * b + 1] = mh[B == 1 ? 1 : B + b]; }
+    HIP_TRY(hipMemcpy(filt_out, filt.p, NB * 2, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(edge_out, edge.p, NB, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(total_area, total.p, NB, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(depth_n, depthN.p, NB, hipMemcpyDeviceToHost));
+    return SIND_OK;
+}
+
 // parity-test access to the GPU region grow of the PEAC refinement (k_peac_grow): n depth frames (host, [n][height][width] u16) go through the block
 // statistics kernel and the host graph clustering (PeacFitter::part1); then ONE launch grows all frames on the GPU and the host statement of the same
 // FIFO grows them one by one.  member_* [n][height*width] int8 (plane or -1), pair_* [n][127*127] (row stride = the frame's plane count), status [n][4] =

@@ -66,3 +66,19 @@ class DynaDetect:
                 "total_area", "grad_edge", "plane_contours", "info"]
         check(lib().sind_dyna_debug(self._h, *[ptr(d[k]) for k in keys]), "sind_dyna_debug")
         d["H"] = d["H"].reshape(3, 3); return d
+
+
+def depth_front(depth: np.ndarray, depth_scale: float, device: int = 0) -> dict:
+    """parity-test access (sind_debug_depth_front): depth u16 [n, h, w] or [h, w] -> the GPU front of CalOccluded and the normalised depth of every frame:
+    filt (medianBlur 5), max_filt / max_raw [n], edge_pre / edge (gradient edge before / after the 4 x 4 opening), total_area, depth_n.  One frame takes the
+    single-frame launches of the drop-in path, more take the batched launches of the pipeline."""
+    d = np.ascontiguousarray(depth, np.uint16)
+    if d.ndim == 2:
+        d = d[None]
+    n, h, w = d.shape
+    out = dict(filt=np.empty((n, h, w), np.uint16), maxima=np.empty((n, 2), np.uint32), edge_pre=np.empty((n, h, w), np.uint8), edge=np.empty((n, h, w), np.uint8),
+               total_area=np.empty((n, h, w), np.uint8), depth_n=np.empty((n, h, w), np.uint8))
+    check(lib().sind_debug_depth_front(ptr(d), n, w, h, C.c_float(depth_scale), device, *[ptr(out[k]) for k in ("filt", "maxima", "edge_pre", "edge", "total_area", "depth_n")]),
+          "sind_debug_depth_front")
+    out["max_filt"] = out["maxima"][:, 0].copy(); out["max_raw"] = out["maxima"][:, 1].copy(); del out["maxima"]
+    return out
