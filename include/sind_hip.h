@@ -76,6 +76,12 @@ int sind_flow_set_wave_solver(sind_flow* f, int on, int target_items, int bands)
 /* how k_sor_wave cuts a w x h level of B pairs (host arithmetic only, no GPU needed): out = {column strips, kept columns per strip, row bands, kept rows per band}.  A strip works on
  * 128 columns -- its kept ones plus 10 on every side that is not an image border --, a band on its kept rows plus 10 on every cut side. */
 int sind_flow_wave_layout(int w, int h, int B, int target_items, int bands, int out[4]);
+/* which kernel solves a w x h level of B pairs with `total` SOR iterations under the given settings (host arithmetic only, no GPU needed; for tests of the policy).  The settings are
+ * the setters' arguments: mode / fuse / tile_w / tile_h as in sind_flow_set_sor_tiled, wave as `on` of sind_flow_set_wave_solver, stream_min_b = images per launch from which the
+ * large levels get their own solver (80 in every handle), latency_tiles and coarse_chain as in their setters.  out[0] = kernel: 0 k_coarse_chain (the whole level in one launch),
+ * 1 k_sor_color (two launches per iteration), 2 k_sor_tile, 3 k_sor_fused on the whole level in one workgroup, 4 k_sor_wave, 5 k_sor_stream, 6 k_sor_fused on tiles; out[1] = n = number
+ * of launches (iterations for kernel 1); out[2 .. 2 + n) = iterations of each.  SIND_E_ARG: bad arguments, cap < 2 + n, or a level / tile that k_sor_fused cannot hold. */
+int sind_flow_sor_plan(int mode, int fuse, int tile_w, int tile_h, int wave, int stream_min_b, int latency_tiles, int coarse_chain, int w, int h, int B, int total, int* out, int cap);
 /* coefficient kernel: 1 = k_coef_lanes (neighbours from lanes, short sqrt / c / sqrt forms that are correctly rounded for arguments >= 2^-96; default), 2 = k_coef_lanes with the compiler's IEEE sqrt and c / sqrt
  * (every variant divides by the gradient norms through their reciprocals: correctly rounded for numerators >= 2^-100 or zero, the IEEE division below; sind_debug_div_scan),
  * 0 = k_coef (neighbours from memory), 3 = variant 1 with its tiles in plain grid order over the XCDs (A/B timing: by default the tiles of a pair share an XCD's L2).  Same results. */
@@ -174,7 +180,7 @@ int sind_debug_div_scan(int device, unsigned long long counts[3], int* max_exp, 
  * kernel, 1 = one-wave kernel, 2 = one-wave kernel in its production form, which clears the working histogram: the first 257 words of every result
  * block then hold the cleared words.  mu1 (optional, variants 1 / 2): n x 256 values of Otsu's running class mean, the one rounding chain with a division. */
 int sind_debug_flow_thresholds(const int* hist, int n, int width, int height, int variant, int device, int* res, double* mu1);
-/* parity-test access to the batched flow-mask stage (csrc/flow_kernels.hip: k_residual_mag_frames, k_mag_hist_frames, k_flow_thresholds_frames,
+/* parity-test access to the batched flow-mask stage (csrc/flow_mask.hip: k_residual_mag_frames, k_mag_hist_frames, k_flow_thresholds_frames,
  * k_flow_mask_bits_frames): n frames of dense flow (host f32 [n][height][width] each) and n homographies (row-major 3 x 3 doubles) go through the four
  * batched launches and, in the same call, frame by frame through the per-frame kernels.  Both sets come back: masks as u8 [n][height * width] (low: 0 / 128,
  * high: 0 / 255; the batched bit masks are expanded on the host) and result blocks [n][261] (256 histogram counts, the float bits of the maximal residual,
@@ -282,15 +288,15 @@ int sind_pipe_release_retained(sind_pipe* p, int tag);
  * runners of a repair: 1.10 -> 0.70 s on the Bonn-shaped stream, profiles/r04/repair_latency.txt). */
 int sind_pipe_set_chain_max_streams(sind_pipe* p, int n);
 /* per-stage wall times of the last step in milliseconds: {front_gray, dense_flow, orb_front, host_upload (sind_pipe_process only, else 0), tails, total},
- * plus HIP-event statistics of the flow solver: sor_launches, sor_ms (sum of event-bracketed SOR launch groups),
+ * plus HIP-event statistics of the flow solver of the large levels (see sind_pipe_sor_other_stats): sor_launches, sor_ms (sum of event-bracketed SOR launch groups),
  * sor_alg_bytes (algorithmic bytes those launches cover: 44 B per pixel per red+black iteration) */
 int sind_pipe_stats(sind_pipe* p, double* stage_ms6, long long* sor_launches, double* sor_ms, double* sor_alg_bytes);
 /* flow-solver statistics of the last step when the batch is cut into concurrent slices (one HIP stream each): launches and algorithmic
  * bytes of all slices, sum_ms = sum of the event-bracketed launch groups, union_ms = time during which at least one slice had solver
  * launches in flight (union of those intervals on a common event time base), slices = number of concurrent streams */
 int sind_pipe_sor_stats(sind_pipe* p, long long* launches, double* sum_ms, double* union_ms, double* alg_bytes, int* slices);
-/* since round 5 the two calls above count the launch groups of the STREAMING solver only (k_sor_stream: the kernel of slices of 80 pairs and more, the one bench.py's roofline
- * object describes); this one reports the other solver launches of the step (tiles, one-workgroup levels outside k_coarse_chain, whose solver phases are not separate launches) */
+/* since round 5 the two calls above count the launch groups of the solver of the LARGE levels only, at 80 images per launch and more (k_sor_wave by default, k_sor_stream with
+ * sind_flow_set_wave_solver(f, 0, ...) / flow_opts_off bit 3: the kernel bench.py's roofline object describes); this one reports the other solver launches of the step (tiles, one-workgroup levels outside k_coarse_chain, whose solver phases are not separate launches) */
 int sind_pipe_sor_other_stats(sind_pipe* p, long long* launches, double* sum_ms, double* alg_bytes);
 /* last sind_pipe_submit(_dev): time the call still waited for the previous step's tails after its own phase A had finished (0 = hidden) */
 int sind_pipe_tail_wait_ms(sind_pipe* p, double* ms);

@@ -12,9 +12,9 @@ struct sind_flow {
 extern "C" {
 
 int sind_flow_set_max_levels(sind_flow* f, int n) { if (!f || n < 0) return SIND_E_ARG; f->eng.max_levels = n; return SIND_OK; }
-int sind_flow_set_coarse_chain(sind_flow* f, int on) { if (!f) return SIND_E_ARG; f->eng.coarse_chain = on != 0; return SIND_OK; }
-int sind_flow_set_level_up(sind_flow* f, int on) { if (!f) return SIND_E_ARG; f->eng.level_up = on != 0; return SIND_OK; }
-int sind_flow_set_latency_tiles(sind_flow* f, int on) { if (!f) return SIND_E_ARG; f->eng.latency_tiles = on != 0; return SIND_OK; }
+int sind_flow_set_coarse_chain(sind_flow* f, int on) { if (!f) return SIND_E_ARG; f->eng.solver.coarse_chain = on != 0; return SIND_OK; }
+int sind_flow_set_level_up(sind_flow* f, int on) { if (!f) return SIND_E_ARG; f->eng.solver.level_up = on != 0; return SIND_OK; }
+int sind_flow_set_latency_tiles(sind_flow* f, int on) { if (!f) return SIND_E_ARG; f->eng.solver.latency_tiles = on != 0; return SIND_OK; }
 int sind_device_count(int* count) { if (!count) return SIND_E_ARG; HIP_TRY(hipGetDeviceCount(count)); return SIND_OK; }
 
 int sind_flow_create(int fw, int fh, int max_batch, int device, sind_flow** out) {
@@ -186,14 +186,25 @@ int sind_debug_flow_masks_batch(const float* u, const float* v, const double* hm
     }
     return SIND_OK;
 }
+static bool sor_tiled_ok(int mode, int fuse, int tile_w, int tile_h) {
+    const int nt = tile_w * tile_h / 8;
+    return (mode == 0 || mode == 4 || mode == 5 || mode == 6) && fuse >= 1 && fuse <= 12 && tile_w >= 16 && tile_w % 8 == 0 && tile_h >= 8 && tile_h % 2 == 0 && nt % 128 == 0 && nt <= 1024 &&
+           4 * fuse < tile_w && 4 * fuse < tile_h;
+}
 int sind_flow_set_sor_tiled(sind_flow* f, int mode, int fuse, int tile_w, int tile_h) {
     if (!f) { sind_set_error("sind_flow_set_sor_tiled: null handle"); return SIND_E_ARG; }
-    const int nt = tile_w * tile_h / 8;
-    if ((mode != 0 && mode != 4 && mode != 5 && mode != 6) || fuse < 1 || fuse > 12 || tile_w < 16 || tile_w % 8 || tile_h < 8 || tile_h % 2 || nt % 128 || nt > 1024 ||
-        4 * fuse >= tile_w || 4 * fuse >= tile_h) {
-        sind_set_error("sind_flow_set_sor_tiled: bad arguments (mode %d, fuse %d, tile %d x %d)", mode, fuse, tile_w, tile_h); return SIND_E_ARG;
-    }
+    if (!sor_tiled_ok(mode, fuse, tile_w, tile_h)) { sind_set_error("sind_flow_set_sor_tiled: bad arguments (mode %d, fuse %d, tile %d x %d)", mode, fuse, tile_w, tile_h); return SIND_E_ARG; }
     sind::SolverCfg& C = f->eng.solver; C.mode = mode; C.fuse = fuse; C.tile_w = tile_w; C.tile_h = tile_h; return SIND_OK;
+}
+int sind_flow_sor_plan(int mode, int fuse, int tile_w, int tile_h, int wave, int stream_min_b, int latency_tiles, int coarse_chain, int w, int h, int B, int total, int* out, int cap) {
+    if (!out || cap < 2 || w < 1 || h < 1 || B < 1 || total < 1 || stream_min_b < 1 || !sor_tiled_ok(mode, fuse, tile_w, tile_h)) { sind_set_error("sind_flow_sor_plan: bad arguments"); return SIND_E_ARG; }
+    sind::SolverCfg C; C.mode = mode; C.fuse = fuse; C.tile_w = tile_w; C.tile_h = tile_h; C.wave = wave ? 1 : 0; C.stream_min_b = stream_min_b; C.latency_tiles = latency_tiles != 0; C.coarse_chain = coarse_chain != 0;
+    sind::SorPlan plan;
+    SIND_TRY(sind::sor_plan(w, h, B, total, sind::VarParams().epsilon, C, &plan));
+    const int n = (int)plan.iters.size();
+    if (cap < 2 + n) { sind_set_error("sind_flow_sor_plan: %d launches, room for %d", n, cap - 2); return SIND_E_ARG; }
+    out[0] = (int)plan.kernel; out[1] = n; std::copy(plan.iters.begin(), plan.iters.end(), out + 2);
+    return SIND_OK;
 }
 int sind_flow_set_solver_workgroups(sind_flow* f, int cap) { if (!f || cap < 0) return SIND_E_ARG; f->eng.solver.stream_wg_cap = cap; return SIND_OK; }
 int sind_flow_set_wave_solver(sind_flow* f, int on, int target_items, int bands) {

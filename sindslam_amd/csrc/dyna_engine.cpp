@@ -1,7 +1,7 @@
 // DynaDetect engine: orchestration of the HIP stages and the serial host stages.
 // Reference walk: ORB_SLAM2/src/DynaDetect.cc DetectDynaArea :1377-1666, DetectDynaByDenseOpticalFLow :1023-1374,
 // SegByKmeans :315-420, CalOccluded :429-642, SegAndMergeV2 :653-1018, cal_hist :1685-1739.
-// Per-pixel work runs in flow_kernels.hip / depth_kernels.hip; contour / graph / flood-fill logic is serial, tiny and
+// Per-pixel work runs in flow_prep.hip / flow_mask.hip / depth_kernels.hip; contour / graph / flood-fill logic is serial, tiny and
 // order-defined and runs on bit-packed masks on the host (DESIGN.md "host stages").  No CPU fallback exists for any
 // device stage: every launch error is returned to the caller.
 #include <algorithm>

@@ -1,4 +1,4 @@
-// Flow engine interface (host side of flow_kernels.hip).
+// Flow engine interface (host side of flow_prep.hip, flow_level.hip, flow_sor.hip, flow_stream.hip, flow_wave.hip, flow_coarse.hip and flow_mask.hip).
 #pragma once
 #include "common.hpp"
 
@@ -25,7 +25,8 @@ struct FlowPlanes {
 // stream the kernels run on; collect() sums the elapsed times after the stream has been synchronised.
 struct SorTimer {
     std::vector<hipEvent_t> ev; std::vector<char> kind; size_t used = 0; bool enabled = false;
-    // kind 0: launch groups of the STREAMING solver (k_sor_stream, the kernel the roofline object describes); kind 1: every other solver kernel (tiles, one-workgroup levels)
+    // kind 0: launch groups of the solver of the LARGE levels at SolverCfg::stream_min_b images per launch and more (k_sor_wave by default, k_sor_stream with wave = 0: the kernel the
+    // roofline object describes); kind 1: every other solver kernel (tiles, one-workgroup levels).  sor_timer_kind() maps the plan's kernel to the kind.
     double alg_bytes = 0, alg_bytes_other = 0; long long launches = 0, launches_other = 0;
     void begin(hipStream_t s) { if (!enabled) return; if (used + 2 > ev.size()) { hipEvent_t a, b; (void)hipEventCreate(&a); (void)hipEventCreate(&b); ev.push_back(a); ev.push_back(b); kind.push_back(0); } (void)hipEventRecord(ev[used], s); }
     void end(hipStream_t s, long long n_launches, double bytes, int k = 0) {
@@ -51,20 +52,15 @@ int launch_bgr2gray(hipStream_t s, const uint8_t* bgr, uint8_t* gray, size_t npi
 int debug_rcp_scan(hipStream_t s, int exp_lo, int exp_hi, unsigned long long* out_dev);
 int debug_div_scan(hipStream_t s, unsigned long long* out_dev);          // out_dev: 164 words, zeroed (k_debug_div_scan)
 int debug_coef_math_scan(hipStream_t s, int exp_lo, int exp_hi, const float numer[3], unsigned long long* out_dev);
-struct SolverCfg;
-int sor_iterations(hipStream_t s, FlowPlanes& P, int w, int h, int B, int total, float omega, long long* nlaunch, const SolverCfg& C, int* streamed = nullptr);
-#define FLOW_OPT_COARSE_CHAIN 1      /* levels of <= 4096 pixels: the whole level (all of them, in a pyramid) in one launch (flow_coarse.hip) */
-#define FLOW_OPT_LATENCY_TILES 2
-#define FLOW_OPT_LEVEL_UP 4          /* W += dW, the up-sampling and the next level's warp in one launch (k_level_up) instead of three */     /* tiled levels with a compute unit per tile (few images): 1024-thread tiles, up to 13 iterations per launch (k_sor_tile) */
-// Solver settings of ONE flow handle (every variant returns the same bits; sind_flow_set_sor_tiled / _solver_workgroups / _coef_kernel / _coarse_chain / _latency_tiles).
+// Solver settings of ONE flow handle (every variant returns the same bits; sind_flow_set_sor_tiled / _solver_workgroups / _coef_kernel / _coarse_chain / _latency_tiles / _level_up).
 struct SolverCfg {
     int mode = 4;              // 4 = fused register-resident SOR with 1x8 strips, divisions through a reciprocal formed on the fly (hardware estimate + Newton step, then
                                // Markstein's correction; default), 5 = the streaming kernel on every level it fits, 6 = the one-wave pipeline (k_sor_wave) on every level beyond
                                // one workgroup, 0 = one launch per colour (cross-check)
     int fuse = 5;              // iterations per launch on the tiled levels (>= 1)
     int tile_w = 64, tile_h = 64;      // extended tile (multiple of 8 wide, even height, tile_w * tile_h / 8 threads)
-    int stream_min_b = 80;     // mode 4: tiled levels go to the streaming kernel (one workgroup per image and column strip) from this many images per launch on
-                               // (profiles/r05/stream_min_batch.txt: 48 images per launch 907 pairs/s streamed vs 1093-1110 tiled; 112 images 1356 vs 1237; 170 images 1514 vs 1296)
+    int stream_min_b = 80;     // mode 4: the large levels leave the tiled kernel for their own solver (k_sor_wave; k_sor_stream with wave = 0) from this many images per launch on
+                               // (profiles/r05/stream_min_batch.txt, k_sor_stream: 48 images per launch 907 pairs/s streamed vs 1093-1110 tiled; 112 images 1356 vs 1237; 170 images 1514 vs 1296)
     int stream_wg_cap = 0;     // k_sor_stream: at most this many (persistent) workgroups per launch (0 = one per item)
     int wave = 1;              // mode 4: levels that would go to the streaming kernel go to the one-wave pipeline instead (k_sor_wave, flow_wave.hip); 0 = k_sor_stream (cross-check, A/B timing)
     int wave_items = 1024;     // k_sor_wave: row bands are cut while a launch has fewer waves than this (2048 fill the chip; every cut recomputes 20 rows, and the slices of a step run side by side:
@@ -73,8 +69,19 @@ struct SolverCfg {
     int wave_prefetch = 2;     // k_sor_wave: steps between a row's request and its take-over (1 .. 3; 16 registers per row in flight)
     int coef_kernel = 1;       // 1: k_coef_lanes (neighbours from lanes; short forms of sqrt and c / sqrt), 2: k_coef_lanes with the IEEE forms, 0: k_coef (neighbours from memory)
     int coef_xcd = 1;          // k_coef_lanes: the tiles of a pair go to one XCD (1) or round-robin over the eight in grid order (0: A/B timing)
-    int opts = FLOW_OPT_COARSE_CHAIN | FLOW_OPT_LATENCY_TILES | FLOW_OPT_LEVEL_UP;
+    bool coarse_chain = true;  // levels that are one workgroup's work (<= 4096 pixels): the whole level (all of them, in a pyramid) in ONE launch (k_coarse_chain, flow_coarse.hip);
+                               // false: per-stage kernels everywhere (cross-check, A/B timing)
+    bool latency_tiles = true; // tiled levels with a compute unit per tile (few images): 1024-thread tiles, up to 13 iterations per launch on deeper halos (k_sor_tile)
+    bool level_up = true;      // W += dW, the up-sampling and the next level's warp in one launch (k_level_up) instead of three (cross-check)
 };
+// Which kernel solves a level, and the iterations of each of its launches: the ONE statement of the policy (flow_sor.hip).  The values are sind_flow_sor_plan's.
+enum SorKernel { SOR_COARSE_CHAIN = 0, SOR_COLOR = 1, SOR_LATENCY_TILES = 2, SOR_ONE_WORKGROUP = 3, SOR_WAVE = 4, SOR_STREAM = 5, SOR_FUSED_TILES = 6 };
+struct SorPlan { SorKernel kernel = SOR_COLOR; std::vector<int> iters; };      // SOR_COARSE_CHAIN: one launch for the whole level; SOR_COLOR: two kernels per entry
+static inline int sor_timer_kind(SorKernel k) { return k == SOR_WAVE || k == SOR_STREAM ? 0 : 1; }      // SorTimer's kinds
+// host arithmetic only; SIND_E_ARG (error text set) for a level or a tile that k_sor_fused cannot hold
+int sor_plan(int w, int h, int B, int total, float epsilon, const SolverCfg& C, SorPlan* plan);
+bool chain_takes_level(int w, int h, float epsilon, const SolverCfg& C);       // the chain's part of the plan, whatever the mode: FlowEngine::deepflow walks the pyramid with it
+int sor_iterations(hipStream_t s, FlowPlanes& P, int w, int h, int B, float omega, const SorPlan& plan, const SolverCfg& C, long long* nlaunch);
 int varref_level(hipStream_t s, FlowPlanes& P, const float* I0, const float* I1, int w, int h, int B, const VarParams& V, SorTimer* timer, const SolverCfg& C,
                  bool have_buffers = false, bool leave_increment = false);
 int launch_level_up(hipStream_t s, FlowPlanes& P, int sw, int sh, const float* I0_next, const float* I1_next, int dw, int dh, int B, float post);
@@ -85,6 +92,9 @@ int launch_sor_tile(hipStream_t s, FlowPlanes& P, int w, int h, int B, int iters
 int launch_sor_wave(hipStream_t s, FlowPlanes& P, int w, int h, int B, float omega, int target_items, int force_bands, int prefetch);
 void sor_wave_layout(int w, int h, int B, int target_items, int force_bands, int* strips, int* IW, int* bands, int* BH);
 int sor_tile_count(int w, int h, int iters);
+// flow_stream.hip: 5 iterations of a level of h >= 4 rows as one workgroup per (column strip, image); the result is in P.dWu / P.dWv (swapped with their partners)
+int launch_sor_stream(hipStream_t s, FlowPlanes& P, int w, int h, int B, float omega, int wg_cap);
+bool sor_stream_fits(int h, int total);
 int launch_coarse_chain(hipStream_t s, FlowPlanes& Pl, const float* pyr0, const float* pyr1, const std::vector<std::pair<int, int>>& levels, const std::vector<size_t>& level_off,
                         int first, int last, int B, const VarParams& V, bool init_zero, bool upsample_last, float post, float* out_u, float* out_v);
 int launch_mag_stats(hipStream_t s, const float* u, const float* v, float* mag, unsigned* maxbits, int* hist, uint8_t* out_u8, int n, int B);
@@ -120,10 +130,6 @@ public:
                                                  // effective -- OpenCV 4.2 never increments its layer counter; BASELINE.json config 5 "3-level flow pyramid"); 0 = all levels
     int launch_ahead = 3;                        // pyramid levels the launching thread may be ahead of the GPU (0 = unbounded)
     SolverCfg solver;                            // this handle's solver settings
-    bool latency_tiles = true;                   // tiled levels of few images: 1024-thread tiles and deep halos (k_sor_tile) where every tile has a compute unit to itself
-    bool level_up = true;                        // W += dW, up-sampling and the next level's warp in one launch (k_level_up); false: the three kernels (cross-check)
-    const SolverCfg& opts() { solver.opts = (coarse_chain ? FLOW_OPT_COARSE_CHAIN : 0) | (latency_tiles ? FLOW_OPT_LATENCY_TILES : 0) | (level_up ? FLOW_OPT_LEVEL_UP : 0); return solver; }
-    bool coarse_chain = true;                    // the one-workgroup levels (<= ~8 k pixels) run in ONE launch (k_coarse_chain); false: per-stage kernels everywhere (cross-check, A/B timing)
     ~FlowEngine() { for (hipEvent_t e : level_done) (void)hipEventDestroy(e); }
 private:
     DevBuf<float> plane_store, pyr0, pyr1;

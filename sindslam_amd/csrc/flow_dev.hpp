@@ -1,4 +1,4 @@
-// Device-side pieces of the dense-flow path that more than one translation unit needs (flow_kernels.hip: the per-stage kernels; flow_coarse.hip: the one-launch
+// Device-side pieces of the dense-flow path that more than one translation unit needs (flow_prep.hip, flow_level.hip, flow_sor.hip, flow_stream.hip, flow_wave.hip: the per-stage kernels; flow_coarse.hip: the one-launch
 // chain over the one-workgroup pyramid levels).  Every function here is the ONE statement of its arithmetic: both units evaluate the same float operations in the
 // same order (-ffp-contract=off), which is what keeps them bit-identical to each other and to the oracle.
 #pragma once

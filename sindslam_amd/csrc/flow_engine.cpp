@@ -2,7 +2,6 @@
 // call structure, opencv_contrib 4.2.0 deepflow.cpp / opencv 4.2.0 variational_refinement.cpp; call sites in the
 // reference: DynaDetect.cc:1031, 1075, 1127, 1133-1143).  All work is enqueued on one HIP stream; nothing here syncs.
 #include <cmath>
-#include <cstdarg>
 #include "flow.hpp"
 
 namespace sind {
@@ -55,7 +54,7 @@ int FlowEngine::deepflow(const uint8_t* g0, const uint8_t* g1, int B, float* u, 
     FlowPlanes& P = planes;
     // the coarsest levels that are one workgroup's work each go through ONE launch (flow_coarse.hip), which leaves the flow up-sampled to the first level above them
     int lc = L;
-    if (coarse_chain && V.epsilon >= 1e-12f) while (lc > 0 && L - lc < 32 && coarse_level_P(levels[lc - 1].first, levels[lc - 1].second)) lc--;
+    while (lc > 0 && L - lc < 32 && chain_takes_level(levels[lc - 1].first, levels[lc - 1].second, V.epsilon, solver)) lc--;
     while ((int)level_done.size() < L) { hipEvent_t ev; HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); level_done.push_back(ev); }
     if (lc < L) {
         SIND_TRY(launch_coarse_chain(stream, P, pyr0.p, pyr1.p, levels, level_off, L - 1, lc, B, V, true, lc > 0, inv_scale, P.dWu2, P.dWv2));
@@ -73,8 +72,8 @@ int FlowEngine::deepflow(const uint8_t* g0, const uint8_t* g1, int B, float* u, 
     for (int l = lc - 1; l >= 0; --l) {
         const int w = levels[l].first, h = levels[l].second;
         if (launch_ahead > 0 && l + launch_ahead < L) HIP_TRY(sind_event_wait(level_done[l + launch_ahead]));
-        const bool fuse_up = level_up && l > 0 && solver.mode != 0;
-        SIND_TRY(varref_level(stream, P, level_ptr(pyr0, l, B), level_ptr(pyr1, l, B), w, h, B, V, &sor_timer, opts(), have_buffers, fuse_up));
+        const bool fuse_up = solver.level_up && l > 0 && solver.mode != 0;
+        SIND_TRY(varref_level(stream, P, level_ptr(pyr0, l, B), level_ptr(pyr1, l, B), w, h, B, V, &sor_timer, solver, have_buffers, fuse_up));
         HIP_TRY(hipEventRecord(level_done[l], stream));
         have_buffers = false;
         if (l > 0) {
@@ -105,52 +104,10 @@ int FlowEngine::varref_f32(const float* I0, const float* I1, int w, int h, int B
     const size_t n = (size_t)w * h * B;
     HIP_TRY(hipMemcpyAsync(planes.Wu, u, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(planes.Wv, v, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    SIND_TRY(varref_level(stream, planes, I0, I1, w, h, B, V, &sor_timer, opts()));
+    SIND_TRY(varref_level(stream, planes, I0, I1, w, h, B, V, &sor_timer, solver));
     HIP_TRY(hipMemcpyAsync(u, planes.Wu, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(v, planes.Wv, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
     return SIND_OK;
 }
 
 }  // namespace sind
-
-// ---------------------------------------------------------------- process set-up
-// HIP streams are multiplexed onto GPU_MAX_HW_QUEUES hardware queues (runtime default 4).  A pipeline handle drives ~45 streams; with four queues its flow slices share queues
-// with the tail streams and a stand-alone sequence job runs 17 % slower, six keep them apart, ten and more are catastrophic (profiles/r04/hw_queues.txt).  The runtime reads
-// the variable when it initialises (the first HIP call of the process), so the library sets it when it is LOADED -- for the C++ integrator who links libsind_hip.so as much
-// as for the Python mirror.  An explicit setting in the environment wins; a process whose HIP runtime is already up keeps what it started with.
-__attribute__((constructor)) static void sind_process_setup() { setenv("GPU_MAX_HW_QUEUES", "6", 0); }
-
-// ---------------------------------------------------------------- error string (shared by the whole library)
-static thread_local char g_err[512] = "";
-std::atomic<long long> g_sind_wait_ns{0}, g_sind_wait_calls{0};
-thread_local SindHostGate* t_sind_gate = nullptr;
-thread_local int t_sind_spin_us = 0;
-
-#include <dlfcn.h>
-#include <cstring>
-#include <cstdlib>
-namespace {
-struct Roctx { int (*push)(const char*) = nullptr; int (*pop)() = nullptr;
-    // The marker library is only looked for when a profiler is attached (rocprofv3 preloads librocprofiler-sdk-tool / sets ROCP_TOOL_LIBRARIES) or SIND_ROCTX=1
-    // asks for it: a production process does not dlopen profiler libraries.
-    static bool wanted() {
-        if (const char* e = getenv("SIND_ROCTX")) return atoi(e) != 0;
-        for (const char* v : {"ROCP_TOOL_LIBRARIES", "ROCPROFILER_REGISTER_FORCE_LOAD", "ROCPROF_OUTPUT_PATH"}) if (getenv(v)) return true;
-        const char* pre = getenv("LD_PRELOAD"); return pre && strstr(pre, "rocprofiler");
-    }
-    Roctx() {
-        if (!wanted()) return;
-        for (const char* lib : {"librocprofiler-sdk-roctx.so.1", "librocprofiler-sdk-roctx.so", "libroctx64.so.4", "libroctx64.so"}) {
-            if (void* so = dlopen(lib, RTLD_NOW | RTLD_LOCAL)) {
-                push = (int (*)(const char*))dlsym(so, "roctxRangePushA"); pop = (int (*)())dlsym(so, "roctxRangePop");
-                if (push && pop) return;
-                push = nullptr; pop = nullptr; (void)dlclose(so);
-            }
-        }
-    } };
-Roctx& roctx() { static Roctx r; return r; }
-}  // namespace
-void sind_range_push(const char* name) { if (roctx().push) (void)roctx().push(name); }
-void sind_range_pop() { if (roctx().pop) (void)roctx().pop(); }
-void sind_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap); }
-extern "C" const char* sind_last_error() { return g_err; }

@@ -1,7 +1,7 @@
 // k_sor_wave: the red-black SOR iterations of one launch (5 iterations = 10 half-sweeps) as a row pipeline in time that lives in ONE WAVE.
 // (VariationalRefinementImpl::RedBlackSOR_ParBody of OpenCV's variational_refinement.cpp, the solver under the reference's DeepFlow call, DynaDetect.cc:1031 / 1075.)
 //
-// k_sor_stream (flow_kernels.hip) spreads the same pipeline over the 512 threads of a workgroup: a thread owns two rows of a four-pixel column strip, du / dv / weights
+// k_sor_stream (flow_stream.hip) spreads the same pipeline over the 512 threads of a workgroup: a thread owns two rows of a four-pixel column strip, du / dv / weights
 // travel between threads through LDS rings, and every step -- two half-sweeps of two rows, ~150 instructions -- ends in a workgroup barrier.  Measured there: 54 % of the wave
 // cycles wait, the VALU issues 0.14 - 0.19 of its peak by counts.  Here nothing is shared between waves, so there is no barrier at all:
 //   * a wave owns a column strip of 128 columns (lane l: the pixels ex0 + 2 l, ex0 + 2 l + 1) of a band of rows of one image and walks down it one row per step;

@@ -1,5 +1,5 @@
 // ORBextractor device stages for gfx950 (reference ORB_SLAM2/src/ORBextractor.cc):
-//   ComputePyramid (:1166-1191)  -> k_resize_u8 (flow_kernels.hip) + k_pad_reflect101
+//   ComputePyramid (:1166-1191)  -> k_resize_u8 (flow_prep.hip) + k_pad_reflect101
 //   cell-wise cv::FAST + NMS (:789-828, OpenCV features2d fast.cpp / fast_score.cpp) -> k_fast_cells
 //   IC_Angle (:77-104) + cv::fastAtan2 -> k_ic_angle
 //   GaussianBlur 7x7 sigma 2, 8U fixed point (:1145) -> k_blur7_h / k_blur7_v
