@@ -1113,8 +1113,31 @@ int sindh_covis_cull(sindh_covis* c, const sind_covis_cull_item* items, int B, i
  * Images are dense [B][height][width] (bgr x3), host or device pointers (inputs_on_device); pose_relative / Twc: [B][16] row-major
  * doubles (Eigen::Matrix4d values).  points [B][cap] receives tempCloudOneFrame in the reference's order (cluster 0, then the kept
  * clusters 1..11, raster order inside a cluster; masked / out-of-range pixels are NaN points, the cloud is not dense), n_points [B];
- * occlusion / label_count / kept: [B][12], may be NULL.  The statistical outlier filter and the octree insertion that follow in the
- * ROS node (:291-309) are PCL / octomap library calls and stay with the caller.
+ * occlusion / label_count / kept: [B][12], may be NULL.  The statistical outlier filter that follows in the ROS node (:291-296) is
+ * sind_cloud_filter_outliers below; the octree insertion after it (:297-309, octomap's serial insertRay) stays with the caller.
+ *
+ * sind_cloud_filter_outliers replaces pcl::StatisticalOutlierRemoval (setMeanK(mean_k), setStddevMulThresh(stddev_mul), filter(*temp1); the reference uses 100
+ * and 1.0) for B clouds at once.  The contract is restated from PCL 1.10's applyFilterIndices over KdTreeFLANN / flann::L2_Simple<float>; parity with a real PCL /
+ * FLANN build is UNPINNED.  Per cloud (csrc/host/cloud_filter.hpp holds the arithmetic, one source for host and device):
+ *   - a point is finite if x, y, z are; only finite points are neighbours; a non-finite point gets distance 0, is not counted in valid and is never removed;
+ *   - squared distances are FP32, uncontracted (d = 0; d += dx*dx; d += dy*dy; d += dz*dz);
+ *   - distances[i] = (float)(sum / mean_k), sum (FP64) of sqrt((double)d) over the mean_k + 1 smallest squared distances to the finite points (i itself
+ *     included), ascending, the first dropped: a function of the multiset, so ties between neighbours cannot change a bit;
+ *   - sum and sq_sum (FP64) run over all points in index order (sq_sum adds the FP32 product d * d); mean = sum / valid, variance = (sq_sum - sum * sum / valid) /
+ *     (valid - 1.0), stddev = sqrt(variance), threshold = mean + stddev_mul * stddev, literally (a negative variance gives a NaN threshold and nothing is removed;
+ *     a NaN in stddev or threshold is reported with the bits 0x7ff8000000000000, since its sign and payload are the processor's choice);
+ *   - point i is removed iff distances[i] > threshold; the rest keeps its input order.
+ *   The one deliberate divergence: with fewer than mean_k + 1 finite points the reference reads past its neighbour arrays; here the cloud comes back unchanged with
+ *   degenerate = 1, valid = the finite count, mean = stddev = threshold = 0 and all distances 0.
+ * points is [B][stride] with n_points[b] used (n_points is a host array; points is a device pointer if inputs_on_device); n_points[b] = 0 is legal.  points == NULL
+ * means the clouds that the last sind_cloud_generate on this handle left on the device (B at most that call's B; n_points is not read): the reference's pair of calls
+ * then costs one upload of images and one download of the filtered cloud.  Outputs are host arrays: out [B][out_cap] with n_out [B] (a cloud that keeps more than
+ * out_cap points -> SIND_E_CAPACITY, n_out filled, as sind_cloud_generate does; out may be NULL to get the counts only), distances [B][stride] (may be NULL; with
+ * points == NULL stride only lays out this array), stats [B] (may be NULL): n_ring and n_brute count the finite points answered by the grid search and by the
+ * brute-force launch (0 in the host twin).  Limits: B <= max_batch, 1 <= mean_k <= 128, a finite stddev_mul (SIND_E_ARG otherwise); a cloud of more than
+ * sind_cloud_max_points points -> SIND_E_CAPACITY.  The workspace is allocated on the handle at the first filter call and reused; sind_cloud_generate is not affected.
+ * Ten launches and one memset whatever B, and two host waits: one for the counts, one for the copies sized by them.
+ * sindh_cloud_filter_outliers is the host twin (libsind_host.so too): the same arithmetic, its own exact search, host arrays only, no handle.
  */
 typedef struct sind_cloud sind_cloud;
 typedef struct sind_cloud_point { float x, y, z; uint8_t b, g, r, a; } sind_cloud_point;       /* pcl::PointXYZRGB payload */
@@ -1124,6 +1147,12 @@ int sind_cloud_max_points(sind_cloud* c);                    /* ceil(width / 2) 
 int sind_cloud_generate(sind_cloud* c, int B, const uint8_t* bgr, const uint16_t* depth, const uint16_t* depth_last, const uint8_t* dyna, const uint8_t* dyna_last,
                         const uint8_t* label, const double* pose_relative, const double* Twc, int inputs_on_device, sind_cloud_point* points, int cap, int* n_points,
                         int* occlusion, int* label_count, int* kept);
+typedef struct sind_cloud_filter_stats { double mean, stddev, threshold; int valid, degenerate, n_ring, n_brute; } sind_cloud_filter_stats;
+int sind_cloud_filter_outliers(sind_cloud* c, int B, const sind_cloud_point* points, int stride, const int* n_points, int inputs_on_device, int mean_k,
+                               double stddev_mul, sind_cloud_point* out, int out_cap, int* n_out, float* distances, sind_cloud_filter_stats* stats);
+int sind_cloud_filter_max_mean_k(void);                      /* the built maximum of mean_k: 128 */
+int sindh_cloud_filter_outliers(int B, const sind_cloud_point* points, int stride, const int* n_points, int mean_k, double stddev_mul, sind_cloud_point* out,
+                                int out_cap, int* n_out, float* distances, sind_cloud_filter_stats* stats);
 
 /* helper of the rgbd_tum_noros-shaped harness (sindslam_amd/harness.py): PNG scanline reconstruction, raw = h x (1 + stride) bytes */
 int sind_png_unfilter(const uint8_t* raw, int h, int stride, int bytes_per_pixel, uint8_t* out);
