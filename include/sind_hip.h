@@ -206,6 +206,12 @@ int sind_debug_depth_front(const uint16_t* depth, int n, int width, int height, 
 /* parity-test access to the bit-plane dilation used by the region-adjacency stage (7x7 ellipse on 64-pixel words, cv::dilate semantics):
  * planes / out are host arrays [nplanes][height][ceil(width / 64)] of 64-bit words, bit i of word k = pixel 64 k + i. */
 int sind_debug_dilate_planes(const unsigned long long* planes, int nplanes, int width, int height, int n, int device, unsigned long long* out);
+/* parity-test access to the batched RAG stage against the per-frame one: n frames (1..64, width a multiple of 64) with pieces[i] pieces each (1..254).  planes: host
+ * words, frame after frame, per frame [2][pieces[i]][height][width / 64] (piece planes, then connection planes); occ2 / depth_n: [n][height][width] u8.  Both forms
+ * write, frame after frame, the stage's five outputs [overlap C*C][overlapPlane C*C][ljOverlap C*C][ljArea C][hist C*256] (C = pieces[i]) into out_batch / out_frame:
+ * the batched one through launch_rag_frames as ONE chunk, the per-frame one through the kernels of the unbatched tail. */
+int sind_debug_rag_batch(const unsigned long long* planes, const int* pieces, const uint8_t* occ2, const uint8_t* depth_n, int n, int width, int height, int device,
+                         int* out_batch, int* out_frame);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Batched multi-stream pipeline: S independent camera streams x T consecutive frames per step through
@@ -342,6 +348,16 @@ int sind_pipe_get_kmeans_groups(sind_pipe* p, int* groups);
  * batch since then.  Not while a submitted step is pending. */
 int sind_pipe_set_flow_mask_batch(sind_pipe* p, int on);
 int sind_pipe_get_flow_mask_batch(sind_pipe* p, int* on, long long* frames_batched);
+/* Region-adjacency (RAG) stage of SegAndMerge in the tails (the 7 x 7 dilation of every piece and the overlap / connection / histogram counts over the pieces' bit planes)
+ * batched in the same rounds: a frame's tail runs up to the packed planes, joins the round's batch of its k-means group, and continues from the returned counters; a
+ * chunk of frames costs one plane upload, one record upload, two launches and one copy back instead of that per frame.  Same results (integer counts).  on = 0 runs the
+ * stage per frame everywhere (default 1).  Setting the switch resets the counters: frames_batched = frames of batched rounds that did not take the per-frame stage
+ * (a frame without pieces needs no counts and is one of them), frames_fallback = frames the slab had no room for, which took the per-frame stage.
+ * chunk_frames: frames per set of launches (< 1: a whole group; default 32).  slab_planes_per_frame: the page-locked and device slabs hold that many input planes (two
+ * per piece) times the frames of a group (default 64; < 0: keep).  Not while a submitted step is pending. */
+int sind_pipe_set_rag_batch(sind_pipe* p, int on);
+int sind_pipe_get_rag_batch(sind_pipe* p, int* on, long long* frames_batched, long long* frames_fallback);
+int sind_pipe_set_rag_batch_chunk(sind_pipe* p, int chunk_frames, int slab_planes_per_frame);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Frame post-ORB steps: what the reference's RGB-D Frame constructor does with the extractor's output

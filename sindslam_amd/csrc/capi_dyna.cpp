@@ -207,6 +207,43 @@ int sind_debug_dilate_planes(const unsigned long long* planes, int nplanes, int 
     return SIND_OK;
 }
 
+// parity-test access to the batched RAG stage (launch_rag_frames, one chunk) against the per-frame kernels as DynaTail::seg_rag_gpu runs them
+int sind_debug_rag_batch(const unsigned long long* planes, const int* pieces, const uint8_t* occ2, const uint8_t* depth_n, int n, int width, int height, int device,
+                         int* out_batch, int* out_frame) {
+    if (!planes || !pieces || !occ2 || !depth_n || !out_batch || !out_frame || n < 1 || n > 64 || width < 64 || width % 64 != 0 || width > 4096 || height < 1 || height > 4096) {
+        sind_set_error("sind_debug_rag_batch: bad arguments (1..64 frames, width a multiple of 64)"); return SIND_E_ARG; }
+    const int wpr = width / 64; const size_t pw = (size_t)height * wpr, np = (size_t)width * height;
+    size_t in_words = 0, res_ints = 0; int maxC = 0;
+    std::vector<sind::RagRec> recs(n);
+    for (int i = 0; i < n; i++) {
+        if (pieces[i] < 1 || pieces[i] > 254) { sind_set_error("sind_debug_rag_batch: frame %d has %d pieces (1..254)", i, pieces[i]); return SIND_E_ARG; }
+        recs[i].plane_off = in_words; recs[i].res_off = res_ints; recs[i].C = pieces[i]; recs[i].pad = 0;
+        in_words += (size_t)2 * pieces[i] * pw; res_ints += sind::rag_result_ints(pieces[i]); maxC = std::max(maxC, pieces[i]);
+    }
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<unsigned long long> din, ddil, dpl; DevBuf<uint8_t> docc, ddn; DevBuf<int> dres, drag; DevBuf<sind::RagRec> drec;
+    SIND_TRY(din.alloc(in_words)); SIND_TRY(ddil.alloc(in_words / 2)); SIND_TRY(docc.alloc(np * n)); SIND_TRY(ddn.alloc(np * n)); SIND_TRY(dres.alloc(res_ints)); SIND_TRY(drec.alloc(n));
+    SIND_TRY(dpl.alloc((size_t)3 * maxC * pw)); SIND_TRY(drag.alloc(sind::rag_result_ints(maxC)));
+    HIP_TRY(hipMemcpy(din.p, planes, in_words * 8, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(docc.p, occ2, np * n, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(ddn.p, depth_n, np * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dres.p, 0xff, res_ints * sizeof(int)));                       // (the stage clears its result blocks itself)
+    for (int i = 0; i < n; i++) { recs[i].occ2 = docc.p + np * i; recs[i].depthN = ddn.p + np * i; }
+    HIP_TRY(hipMemcpy(drec.p, recs.data(), n * sizeof(sind::RagRec), hipMemcpyHostToDevice));
+    SIND_TRY(sind::launch_rag_frames(nullptr, drec.p, recs.data(), n, din.p, in_words, ddil.p, dres.p, res_ints, width, height));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out_batch, dres.p, res_ints * sizeof(int), hipMemcpyDeviceToHost));
+    // ---- frame by frame: two uploads into the [3][C] plane block, the dilation (which clears the accumulators), the statistics
+    for (int i = 0; i < n; i++) {
+        const int Cn = pieces[i]; const unsigned long long* src = planes + recs[i].plane_off;
+        HIP_TRY(hipMemcpy(dpl.p, src, (size_t)Cn * pw * 8, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dpl.p + (size_t)2 * Cn * pw, src + (size_t)Cn * pw, (size_t)Cn * pw * 8, hipMemcpyHostToDevice));
+        SIND_TRY(sind::launch_dilate_planes(nullptr, dpl.p, dpl.p + (size_t)Cn * pw, Cn, width, height, 7, drag.p, (int)sind::rag_result_ints(Cn)));
+        int* ov = drag.p; int* ovp = ov + Cn * Cn; int* lj = ovp + Cn * Cn; int* la = lj + Cn * Cn; int* hs = la + Cn;
+        SIND_TRY(sind::launch_rag_stats(nullptr, dpl.p, Cn, width, height, wpr, docc.p + np * i, ddn.p + np * i, ov, ovp, lj, la, hs, true));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(out_frame + recs[i].res_off, drag.p, sind::rag_result_ints(Cn) * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    return SIND_OK;
+}
+
 // parity-test access to the GPU front of CalOccluded and the depth normalisation of the RAG statistics: n depth frames (host, [n][height][width] u16) through the production
 // launchers with the arguments dyna_engine.cpp gives them -- n == 1: the single-frame forms of DynaTail::cal_occluded_p1 / seg_and_merge (maxima in slots 0 and 1 of one
 // two-word buffer), n >= 2: the batched forms of OccBatch::run (per-frame maxima slots, stride 1; the raw maxima n words behind the filtered ones).  The maxima are cleared

@@ -42,5 +42,12 @@ int launch_depth_norm(hipStream_t s, const uint16_t* depth, const unsigned* dmax
 int launch_dilate_planes(hipStream_t s, const unsigned long long* src, unsigned long long* dst, int nplanes, int w, int h, int n, int* zero = nullptr, int nzero = 0);
 int launch_rag_stats(hipStream_t s, const unsigned long long* planes, int C, int w, int h, int wpr, const uint8_t* occ2, const uint8_t* depthN,
                      int* overlap, int* overlapPlane, int* ljOverlap, int* ljArea, int* hist, bool already_zero = false);
+// One frame of the batched RAG stage (launch_rag_frames).  plane_off: words from the start of the input slab to the frame's 2 C planes ([0, C) pieces, [C, 2 C) connection
+// areas); its C dilated planes lie plane_off / 2 words into the dilation slab.  res_off: ints from the start of the result slab to the frame's block
+// [overlap C*C][overlapPlane C*C][ljOverlap C*C][ljArea C][hist C*256] -- the per-frame stage's layout.
+struct RagRec { unsigned long long plane_off, res_off; const uint8_t* occ2; const uint8_t* depthN; int C, pad; };
+static inline size_t rag_result_ints(int C) { return (size_t)3 * C * C + C + (size_t)C * 256; }
+// n records: the 7 x 7 dilation of every piece (which also clears the result blocks), then the statistics; two launches.  in_words / res_ints: the slabs' sizes (checked against every record)
+int launch_rag_frames(hipStream_t s, const RagRec* recs_dev, const RagRec* recs_host, int n, const unsigned long long* in, size_t in_words, unsigned long long* dil, int* res, size_t res_ints, int w, int h);
 
 }  // namespace sind

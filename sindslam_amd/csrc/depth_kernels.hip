@@ -847,12 +847,13 @@ __global__ void k_depth_norm(const uint16_t* __restrict__ depth, const unsigned*
 // membership words.  One pass produces overlap[i][j] = |dil_i & dil_j|, overlapPlane[i][j] = |dil_i & dil_j & occ2|,
 // ljOverlap[i][j], ljArea[i] and hist[i][v] = 256-bin histogram of the normalised depth over img_i (value 255 dropped:
 // calcHist ranges {0,255}).  Counters are privatised in LDS when they fit (C <= 64) and flushed once per workgroup.
+// (body shared by the per-frame kernel and the frame-indexed one: the three plane sets as pointers of their own, the workgroup's index and count among
+// those of its frame, and the LDS block)
 template <bool USE_LDS>
-__global__ void __launch_bounds__(256) k_rag_stats(const unsigned long long* __restrict__ planes, int C, int w, int h, int wpr,
-                                                   const uint8_t* __restrict__ occ2, const uint8_t* __restrict__ depthN,
-                                                   int* __restrict__ overlap, int* __restrict__ overlapPlane, int* __restrict__ ljOverlap,
-                                                   int* __restrict__ ljArea, int* __restrict__ hist) {
-    extern __shared__ int sm[];
+__device__ __forceinline__ void rag_stats_body(const unsigned long long* __restrict__ p_img, const unsigned long long* __restrict__ p_dil, const unsigned long long* __restrict__ p_lj,
+                                               int C, int w, int h, int wpr, const uint8_t* __restrict__ occ2, const uint8_t* __restrict__ depthN,
+                                               int* __restrict__ overlap, int* __restrict__ overlapPlane, int* __restrict__ ljOverlap,
+                                               int* __restrict__ ljArea, int* __restrict__ hist, int* sm, int block, int nblocks) {
     int *lh = hist, *lo = overlap, *lp = overlapPlane, *ll = ljOverlap, *la = ljArea;
     if (USE_LDS) {
         lh = sm; lo = lh + C * 256; lp = lo + C * C; ll = lp + C * C; la = ll + C * C;
@@ -863,7 +864,7 @@ __global__ void __launch_bounds__(256) k_rag_stats(const unsigned long long* __r
     const int NW = (C + 63) >> 6;
     const size_t pw = (size_t)h * wpr;           // words per plane
     const int n = w * h;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    for (int i = block * 256 + threadIdx.x; i < n; i += nblocks * 256) {
         const int y = i / w, x = i - y * w; const size_t widx = (size_t)y * wpr + (x >> 6); const int bit = x & 63;
         // The 64 lanes of a wave sit on the 64 pixels of ONE plane word (w % 64 == 0 and every stride is a multiple of 64): lane c fetches
         // the three words of piece c once, and each lane then picks its own bit out of the words broadcast with readlane -- 3 loads per
@@ -875,7 +876,7 @@ __global__ void __launch_bounds__(256) k_rag_stats(const unsigned long long* __r
             if (q >= NW) break;
             const int c = (q << 6) + lane;
             unsigned long long wi = 0, wd = 0, wl = 0;
-            if (c < C) { wi = planes[((size_t)0 * C + c) * pw + widx]; wd = planes[((size_t)1 * C + c) * pw + widx]; wl = planes[((size_t)2 * C + c) * pw + widx]; }
+            if (c < C) { wi = p_img[(size_t)c * pw + widx]; wd = p_dil[(size_t)c * pw + widx]; wl = p_lj[(size_t)c * pw + widx]; }
             const int cnt = min(64, C - (q << 6));
             // lane `bit` wants bit `bit` of piece cc's words as bit cc of its own: the half of the word the lane's pixel lies in is fixed per lane, the half of the result per cc --
             // 32-bit operations throughout (three instead of six per plane and piece: the 64-bit shifts by a lane-varying and by a uniform count were two passes each)
@@ -919,18 +920,34 @@ __global__ void __launch_bounds__(256) k_rag_stats(const unsigned long long* __r
         for (int i = threadIdx.x; i < C; i += 256) if (la[i]) atomicAdd(&ljArea[i], la[i]);
     }
 }
+template <bool USE_LDS>
+__global__ void __launch_bounds__(256) k_rag_stats(const unsigned long long* __restrict__ planes, int C, int w, int h, int wpr,
+                                                   const uint8_t* __restrict__ occ2, const uint8_t* __restrict__ depthN,
+                                                   int* __restrict__ overlap, int* __restrict__ overlapPlane, int* __restrict__ ljOverlap,
+                                                   int* __restrict__ ljArea, int* __restrict__ hist) {
+    extern __shared__ int sm[];
+    const size_t pw = (size_t)h * wpr;
+    rag_stats_body<USE_LDS>(planes, planes + (size_t)C * pw, planes + (size_t)2 * C * pw, C, w, h, wpr, occ2, depthN, overlap, overlapPlane, ljOverlap, ljArea, hist, sm, blockIdx.x, gridDim.x);
+}
+// One frame of every stream of a k-means group: blockIdx.y = the frame's record (depth.hpp), blockIdx.x = one of the few workgroups of that frame -- the
+// parallelism comes from the frames, so a frame's counters are zeroed and flushed by 8 - 32 workgroups instead of 128.  The launch's dynamic LDS holds the counters
+// of the chunk's largest C <= 64; a frame with more pieces counts in global memory (uniform per workgroup).  Counts are integers: any partition gives the same numbers.
+__global__ void __launch_bounds__(256) k_rag_stats_frames(const RagRec* __restrict__ recs, const unsigned long long* __restrict__ in, const unsigned long long* __restrict__ dil,
+                                                          int* __restrict__ res, int w, int h, int wpr) {
+    extern __shared__ int sm[];
+    const RagRec R = recs[blockIdx.y];
+    const int C = R.C; const size_t pw = (size_t)h * wpr;
+    const unsigned long long* p_img = in + R.plane_off; const unsigned long long* p_lj = p_img + (size_t)C * pw; const unsigned long long* p_dil = dil + R.plane_off / 2;
+    int* ov = res + R.res_off; int* ovp = ov + C * C; int* lj = ovp + C * C; int* la = lj + C * C; int* hs = la + C;
+    if (C <= 64) rag_stats_body<true>(p_img, p_dil, p_lj, C, w, h, wpr, R.occ2, R.depthN, ov, ovp, lj, la, hs, sm, blockIdx.x, gridDim.x);
+    else rag_stats_body<false>(p_img, p_dil, p_lj, C, w, h, wpr, R.occ2, R.depthN, ov, ovp, lj, la, hs, sm, blockIdx.x, gridDim.x);
+}
 
 // Elliptical dilation of bit planes (64 pixels per word), dst(x, y) = OR over the element of src(x + j - ax, y + i - ay) with positions
 // outside the image ignored: the 7x7 dilation of every piece of SegAndMergeV2 (DD:760-ish "imgEachClusterDilate") for the region-adjacency
 // statistics.  One thread per output word; a row of the element is a run of <= 15 shifts over a three-word window.
 // zero / nzero (optional): a block of ints cleared on the way -- the accumulators of k_rag_stats, which follows on the same stream (one fill launch less per frame).
-__global__ void k_dilate_planes(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst, int nplanes, int wpr, int H, MorphElem e,
-                                unsigned long long tail_mask, int* __restrict__ zero, int nzero) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, pw = (size_t)wpr * H;
-    for (size_t z = idx; z < (size_t)nzero; z += (size_t)gridDim.x * blockDim.x) zero[z] = 0;
-    if (idx >= pw * nplanes) return;
-    const int c = (int)(idx / pw), rem = (int)(idx - (size_t)c * pw), y = rem / wpr, k = rem - y * wpr;
-    const unsigned long long* sp = src + (size_t)c * pw;
+__device__ __forceinline__ unsigned long long dilate_plane_word(const unsigned long long* __restrict__ sp, int y, int k, int wpr, int H, const MorphElem& e, unsigned long long tail_mask) {
     unsigned long long acc = 0ull;
     for (int i = 0; i < e.n; i++) {
         const int ys = y + i - e.ay;
@@ -945,7 +962,29 @@ __global__ void k_dilate_planes(const unsigned long long* __restrict__ src, unsi
         }
     }
     if (k == wpr - 1) acc &= tail_mask;
-    dst[idx] = acc;
+    return acc;
+}
+__global__ void k_dilate_planes(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst, int nplanes, int wpr, int H, MorphElem e,
+                                unsigned long long tail_mask, int* __restrict__ zero, int nzero) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, pw = (size_t)wpr * H;
+    for (size_t z = idx; z < (size_t)nzero; z += (size_t)gridDim.x * blockDim.x) zero[z] = 0;
+    if (idx >= pw * nplanes) return;
+    const int c = (int)(idx / pw), rem = (int)(idx - (size_t)c * pw), y = rem / wpr, k = rem - y * wpr;
+    dst[idx] = dilate_plane_word(src + (size_t)c * pw, y, k, wpr, H, e, tail_mask);
+}
+// the same for one frame of every stream of a group: blockIdx.y = the frame's record, the grid's x extent covers the chunk's largest C; every frame's
+// result block is cleared on the way
+__global__ void k_dilate_planes_frames(const RagRec* __restrict__ recs, const unsigned long long* __restrict__ in, unsigned long long* __restrict__ dil, int* __restrict__ res,
+                                       int wpr, int H, MorphElem e, unsigned long long tail_mask) {
+    const RagRec R = recs[blockIdx.y];
+    const int C = R.C;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, pw = (size_t)wpr * H;
+    const size_t nzero = (size_t)3 * C * C + C + (size_t)C * 256;
+    int* zero = res + R.res_off;
+    for (size_t z = idx; z < nzero; z += (size_t)gridDim.x * blockDim.x) zero[z] = 0;
+    if (idx >= pw * C) return;
+    const int c = (int)(idx / pw), rem = (int)(idx - (size_t)c * pw), y = rem / wpr, k = rem - y * wpr;
+    dil[R.plane_off / 2 + idx] = dilate_plane_word(in + R.plane_off + (size_t)c * pw, y, k, wpr, H, e, tail_mask);
 }
 int launch_dilate_planes(hipStream_t s, const unsigned long long* src, unsigned long long* dst, int nplanes, int w, int h, int n, int* zero, int nzero) {
     const int wpr = (w + 63) / 64; const size_t total = (size_t)wpr * h * nplanes;
@@ -1056,6 +1095,26 @@ int launch_rag_stats(hipStream_t s, const unsigned long long* planes, int C, int
     } else {
         hipLaunchKernelGGL(k_rag_stats<false>, dim3(256), dim3(256), 0, s, planes, C, w, h, wpr, occ2, depthN, overlap, overlapPlane, ljOverlap, ljArea, hist);
     }
+    return SIND_OK;
+}
+int launch_rag_frames(hipStream_t s, const RagRec* recs_dev, const RagRec* host, int n, const unsigned long long* in, size_t in_words, unsigned long long* dil, int* res, size_t res_ints, int w, int h) {
+    if (n < 1 || n > 65535 || !recs_dev || !host || !in || !dil || !res || w < 64 || w % 64 != 0 || h < 1) { sind_set_error("launch_rag_frames: %d records, %d x %d", n, w, h); return SIND_E_ARG; }
+    const int wpr = w / 64; const size_t pw = (size_t)h * wpr;
+    int maxC = 0, maxLds = 0;
+    for (int i = 0; i < n; i++) {
+        const RagRec& R = host[i];
+        if (R.C < 1 || R.C > 254 || !R.occ2 || !R.depthN || (R.plane_off & 1) || R.plane_off + (size_t)2 * R.C * pw > in_words || R.res_off + rag_result_ints(R.C) > res_ints) {
+            sind_set_error("launch_rag_frames: record %d (%d pieces) has a null pointer or leaves its slab", i, R.C); return SIND_E_ARG; }
+        maxC = std::max(maxC, R.C); if (R.C <= 64) maxLds = std::max(maxLds, R.C);
+    }
+    hipLaunchKernelGGL(k_dilate_planes_frames, dim3((unsigned)((pw * maxC + 255) / 256), n), dim3(256), 0, s, recs_dev, in, dil, res, wpr, h, make_ellipse(7), ~0ull);
+    // workgroups per frame: the frame's counters (C = 20: 6 340) are zeroed and flushed once per workgroup, each of which should have many more pixels than that --
+    // 8 at 64 frames (150 pixels per thread at 640 x 480), up to 32 for a small chunk, no more than the frame has 256-pixel groups
+    const int per_frame = std::max(1, std::min(std::max(8, std::min(32, 512 / n)), (int)((size_t)w * h / 256)));
+    const size_t shm = rag_result_ints(maxLds) * sizeof(int);
+    static SindPerDeviceInit attr_init;
+    HIP_TRY(attr_init.run([] { return hipFuncSetAttribute((const void*)k_rag_stats_frames, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024); }));
+    hipLaunchKernelGGL(k_rag_stats_frames, dim3(per_frame, n), dim3(256), shm, s, recs_dev, in, dil, res, w, h, wpr);
     return SIND_OK;
 }
 

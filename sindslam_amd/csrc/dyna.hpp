@@ -1,7 +1,9 @@
 // DynaDetect engine interface: state-free GPU front (gray, 0.6 resize, dense flow, up-scale) and the stateful
 // per-stream tail (k-means, depth edges, PEAC, split/merge re-clustering, residual thresholds, mask fusion).
 #pragma once
+#include <algorithm>
 #include <memory>
+#include <mutex>
 #include <vector>
 #include "common.hpp"
 #include "depth.hpp"
@@ -110,6 +112,39 @@ private:
     std::vector<DynaTail*> tails; hipEvent_t done = nullptr;
 };
 
+// ---- GPU stage of SegAndMerge (DD:760-ish: the region-adjacency statistics over the pieces' bit planes) for one frame of EVERY stream of a k-means group, in chunks:
+// per frame it was two plane uploads, two small launches of 128 workgroups that mostly zero and flush their counters, a copy back and a stream wait, 512 times a
+// step.  A frame reserves a slot and plane space (any pool thread), packs its planes straight into the page-locked slab and joins; slots are handed out in order and
+// chunk c holds slots [c * chunk, (c + 1) * chunk), so a chunk's planes, records and results are contiguous: one H2D of the planes, one of the records, two launches
+// (launch_rag_frames), one D2H, one event.  Same kernels' device functions as the per-frame stage, integer counts: the same numbers.
+class RagBatch {
+public:
+    int init(const DynaConfig& c, int max_frames, hipStream_t s);      // (cheap: the slabs are made by the first round that uses them)
+    ~RagBatch();
+    // chunk: frames per set of launches; planes_per_frame: the slabs hold max_frames * planes_per_frame input planes (2 per piece).  Not while a round is running.
+    void set_limits(int chunk, int planes_per_frame) { chunk_n = chunk < 1 ? cap : std::min(chunk, cap); planes_frame = std::max(0, planes_per_frame); }      // (chunk < 1: the whole group)
+    int chunk_frames() const { return chunk_n; }
+    int begin_round();                                                 // forget the previous round's slots (whose results are no longer needed)
+    // a slot and plane space for a frame of C pieces: *pieces and *conn take C planes each.  false: the slabs are full (the frame takes the per-frame stage)
+    bool reserve(int C, int* slot, unsigned long long** pieces, unsigned long long** conn);
+    void set_inputs(int slot, const uint8_t* occ2, const uint8_t* depthN, hipEvent_t occ2_event);      // occ2_event: recorded behind the frame's occ2 upload on another stream (or nullptr)
+    int chunk_of(int slot) const { return slot / chunk_n; }
+    int chunk_first(int chunk) const { return chunk * chunk_n; }
+    int chunk_count(int chunk) const { return std::max(0, std::min(chunk_n, n_slots - chunk * chunk_n)); }      // (of the slots handed out so far)
+    int slots() const { return n_slots; }
+    int enqueue(int chunk);                   // every slot of the chunk has been packed
+    int wait(int chunk);                      // until the chunk's results are on the host; they stay valid until the next begin_round
+    const int* result(int slot) const { return res_h.p + recs_h.p[slot].res_off; }
+    hipStream_t stream = nullptr;
+private:
+    DynaConfig cfg; int W = 0, H = 0, cap = 0, chunk_n = 32, planes_frame = 64, n_slots = 0; size_t pw = 0, in_used = 0, res_used = 0, in_cap = 0, res_cap = 0;
+    std::mutex m, enq;
+    PinnedBuf<unsigned long long> in_h; DevBuf<unsigned long long> in_d, dil_d; PinnedBuf<RagRec> recs_h; DevBuf<RagRec> recs_d; DevBuf<int> res_d; PinnedBuf<int> res_h;
+    std::vector<hipEvent_t> occ2_ev, done;
+};
+
+struct SegPiece { BitImg img, lianjie; bool hasLianjie = false; float area = 0, score = -10, cz = 0; };      // a piece of SegAndMerge (DD:668-760)
+
 class DynaTail {
 public:
     DynaConfig cfg; hipStream_t stream = nullptr; DynaDebug dbg; bool keep_debug = false;
@@ -127,6 +162,18 @@ public:
     int flow_masks_homography(const float* U, const float* V, const float* gridFlowPre, double Hm[9]);
     // the k-means warm labels of the next frame (nullptr before the first frame of a stream): what KMeansBatch::run wants as prev[b]
     const uint8_t* prev_km_labels() const { return kmLabelLastAny ? kmLabelLast.data() : nullptr; }
+    // process() in two parts around the batched RAG stage (RagBatch): process_begin runs the frame up to SegAndMerge's pieces, process_end takes the counters and does
+    // the rest.  Between them, on the depth-half object (rag_half()): rag_pieces() pieces (0: nothing to count, process_end(nullptr)); rag_batchable(): occ2 and the
+    // normalised depth are on the device already; rag_pack() writes the piece and connection planes; rag_own() is the per-frame stage.  Same arithmetic in the same order.
+    int process_begin(const uint16_t* depth_host, const uint16_t* depth_dev, const float* U, const float* V, const OccResult* precomputed, DynaTail* depth_half,
+                      const KmFrameResult* km, const FlowMasksReady* fm);
+    int process_end(const int* rag, uint8_t* dyna_out, uint8_t* label_out);
+    DynaTail* rag_half() { return pendHalf ? pendHalf : this; }
+    int rag_pieces() const { return (int)segAll.size(); }
+    bool rag_batchable() const { return segPre && segPre->occ2_dev && segPre->depthN_dev; }
+    const OccResult* rag_pre() const { return segPre; }
+    void rag_pack(unsigned long long* pieces, unsigned long long* conn) const;
+    int rag_own(const int** rag);
     // process() = depth_stage() + flow_stage().  The two halves keep separate state (the k-means warm labels belong to the depth half,
     // the sample weights / previous masks to the flow half), so the depth half of the next frames may run ahead of the flow half.
     // km: this frame's k-means result when it was computed by the batched chain (else the stage runs its own)
@@ -181,8 +228,16 @@ private:
     int finish_occluded(OccResult& out, const OccGpuOut* pre);
     struct OwnGrow { PeacGrowBatch batch; PinnedBuf<uint8_t> in_h, pair_h; PinnedBuf<int8_t> member_h; PinnedBuf<int> status_h; };
     std::unique_ptr<OwnGrow> own_grow;         // one-frame grow workspace, created on first use (single-frame API, unbatched pipeline steps)
-    int seg_and_merge(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& occ2, const BitImg& labelForSegEdge,
-                      const uint16_t* depth_host, const uint16_t* depth_dev, std::vector<uint8_t>& labelNew, const OccResult* pre = nullptr);
+    // SegAndMerge (DD:644-1031) in three parts: the host part up to the sorted pieces and pieceOf (seg_pieces), the GPU stage (rag_pack + seg_rag_gpu per frame, or a
+    // RagBatch), the host part from the counters on (seg_finish).  The pieces (areas, hasLianjie, images until they are packed), pieceOf and what the per-frame stage
+    // needs live here in between; depth_stage() = depth_stage_begin + seg_rag_gpu + depth_stage_end
+    std::vector<SegPiece> segAll; std::vector<uint8_t> segPieceOf; BitImg segOcc1, segOcc2; const uint16_t* segDepthDev = nullptr; const OccResult* segPre = nullptr;
+    BitImg pendLow, pendHigh; DepthStageOut pendD; DynaTail* pendHalf = nullptr;      // process_begin -> process_end
+    int depth_stage_begin(const uint16_t* depth_host, const uint16_t* depth_dev, const OccResult* precomputed, DepthStageOut& out, const KmFrameResult* km);
+    int depth_stage_end(DepthStageOut& out, const int* rag);
+    int seg_pieces(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& labelForSegEdge, const uint16_t* depth_host);
+    int seg_rag_gpu(const int** rag);
+    void seg_finish(const int* rag, std::vector<uint8_t>& labelNew);
 };
 
 }  // namespace sind

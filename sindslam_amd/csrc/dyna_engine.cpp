@@ -280,6 +280,59 @@ int FlowMaskBatch::wait() {
     return SIND_OK;
 }
 
+// ---- the GPU stage of SegAndMerge for one frame of every stream of a k-means group, in chunks (see dyna.hpp)
+int RagBatch::init(const DynaConfig& c, int max_frames, hipStream_t s) {
+    cfg = c; W = c.W; H = c.H; cap = max_frames; stream = s; pw = (size_t)H * (W / 64);
+    if (W % 64 != 0 || max_frames < 1) { sind_set_error("RagBatch: width must be a multiple of 64 (got %d), %d frames", W, max_frames); return SIND_E_ARG; }
+    SIND_TRY(recs_h.alloc(cap)); SIND_TRY(recs_d.alloc(cap));
+    occ2_ev.assign(cap, nullptr); done.resize(cap, nullptr);
+    for (hipEvent_t& e : done) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return SIND_OK;
+}
+RagBatch::~RagBatch() { for (hipEvent_t e : done) if (e) (void)hipEventDestroy(e); }
+int RagBatch::begin_round() {
+    HIP_TRY(hipSetDevice(cfg.device));
+    // result blocks: 16 K ints per frame hold 40 pieces (3 C^2 + 257 C); a frame that does not fit takes the per-frame stage
+    in_cap = (size_t)cap * planes_frame * pw; res_cap = (size_t)cap * 16384;
+    SIND_TRY(in_h.alloc(std::max<size_t>(in_cap, 2))); SIND_TRY(in_d.alloc(std::max<size_t>(in_cap, 2))); SIND_TRY(dil_d.alloc(std::max<size_t>(in_cap / 2, 1)));
+    SIND_TRY(res_d.alloc(res_cap)); SIND_TRY(res_h.alloc(res_cap));
+    std::lock_guard<std::mutex> lk(m);
+    n_slots = 0; in_used = 0; res_used = 0;
+    return SIND_OK;
+}
+bool RagBatch::reserve(int C, int* slot, unsigned long long** pieces, unsigned long long** conn) {
+    if (C < 1 || C > 254) return false;
+    const size_t words = (size_t)2 * C * pw, ints = rag_result_ints(C);
+    std::lock_guard<std::mutex> lk(m);
+    if (n_slots >= cap || in_used + words > in_cap || res_used + ints > res_cap) return false;
+    RagRec& R = recs_h.p[n_slots];
+    R.plane_off = in_used; R.res_off = res_used; R.C = C; R.pad = 0; R.occ2 = nullptr; R.depthN = nullptr;
+    *pieces = in_h.p + in_used; *conn = *pieces + (size_t)C * pw; *slot = n_slots++;
+    in_used += words; res_used += ints;
+    return true;
+}
+void RagBatch::set_inputs(int slot, const uint8_t* occ2, const uint8_t* depthN, hipEvent_t ev) { recs_h.p[slot].occ2 = occ2; recs_h.p[slot].depthN = depthN; occ2_ev[slot] = ev; }
+int RagBatch::enqueue(int chunk) {
+    HIP_TRY(hipSetDevice(cfg.device));
+    int first, n; { std::lock_guard<std::mutex> lk(m); first = chunk_first(chunk); n = chunk_count(chunk); }
+    if (chunk < 0 || n < 1) { sind_set_error("RagBatch::enqueue: chunk %d holds no frame", chunk); return SIND_E_ARG; }
+    const RagRec& A = recs_h.p[first]; const RagRec& Z = recs_h.p[first + n - 1];
+    const size_t w0 = A.plane_off, w1 = Z.plane_off + (size_t)2 * Z.C * pw, r0 = A.res_off, r1 = Z.res_off + rag_result_ints(Z.C);
+    std::lock_guard<std::mutex> lk(enq);      // (two chunks of a round may be enqueued by two pool threads: one chunk's calls stay together on the stream)
+    for (int b = first; b < first + n; b++) if (occ2_ev[b]) HIP_TRY(hipStreamWaitEvent(stream, occ2_ev[b], 0));       // occ2 uploaded on the CalOccluded runner's stream without a host wait
+    HIP_TRY(hipMemcpyAsync(in_d.p + w0, in_h.p + w0, (w1 - w0) * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(recs_d.p + first, recs_h.p + first, (size_t)n * sizeof(RagRec), hipMemcpyHostToDevice, stream));
+    SIND_TRY(launch_rag_frames(stream, recs_d.p + first, recs_h.p + first, n, in_d.p, in_cap, dil_d.p, res_d.p, res_cap, W, H));
+    HIP_TRY(hipMemcpyAsync(res_h.p + r0, res_d.p + r0, (r1 - r0) * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(done[chunk], stream));
+    return SIND_OK;
+}
+int RagBatch::wait(int chunk) {
+    if (chunk < 0 || chunk >= cap) { sind_set_error("RagBatch::wait: chunk %d", chunk); return SIND_E_ARG; }
+    HIP_TRY(sind_event_wait(done[chunk]));
+    return SIND_OK;
+}
+
 // ---- DD:315-420: 4-level k-means, K = 12, criteria (EPS+COUNT, 4, 0.07), KMEANS_USE_INITIAL_LABELS.
 // The whole loop is enqueued without a host round trip: the centre step, empty-cluster repair and the stop test of cv::kmeans
 // run in k_km_update (one workgroup) on the device; one D2H of the level-0 state + labels at the end.
@@ -481,10 +534,10 @@ int DynaTail::cal_occluded(const uint16_t* depth_host, const uint16_t* depth_dev
 }
 
 // ---- DD:653-1018: split every depth cluster on edges into pieces, region-adjacency statistics on the GPU, greedy merge on the host
-int DynaTail::seg_and_merge(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& occ2, const BitImg& labelForSegEdge,
-                            const uint16_t* depth_host, const uint16_t* depth_dev, std::vector<uint8_t>& labelNew, const OccResult* pre) {
-    struct Piece { BitImg img, lianjie; bool hasLianjie = false; float area = 0, score = -10, cz = 0; };
-    std::vector<Piece> all;
+// host part up to the pieces in score order and pieceOf; they stay in segAll / segPieceOf (no pieces: segAll is empty and the frame's labels are all 0)
+int DynaTail::seg_pieces(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& labelForSegEdge, const uint16_t* depth_host) {
+    typedef SegPiece Piece;
+    std::vector<Piece>& all = segAll; all.clear();
     double tf = tick_ms();
     #define FLAP(i) { const double t_ = tick_ms(); t_fine[i] += t_ - tf; tf = t_; }
     const EllipseElem e4(4), e9(9), e10(10);
@@ -542,23 +595,35 @@ int DynaTail::seg_and_merge(const std::vector<BitImg>& allLabels, const BitImg& 
     FLAP(6)
     const int C = (int)all.size();
     dbg.nClusters = C;
-    labelNew.assign(N, 0);
     if (C == 0) return SIND_OK;
-    if (C > 254) { sind_set_error("seg_and_merge: %d pieces exceed the 8-bit label range of the reference", C); return SIND_E_CAPACITY; }
+    if (C > 254) { all.clear(); sind_set_error("seg_and_merge: %d pieces exceed the 8-bit label range of the reference", C); return SIND_E_CAPACITY; }
     for (Piece& p : all) p.score = (float)(p.area * 0.0003f - p.cz);
     std::sort(all.begin(), all.end(), [](const Piece& a, const Piece& b) { return a.score > b.score; });
-    std::vector<uint8_t> pieceOf(N, (uint8_t)(C + 1));       // index of the piece that owns a pixel (the reference paints the pieces in score order)
-    for (int i = 0; i < C; i++) all[i].img.paint_u8(pieceOf.data(), W, (uint8_t)i);
-    // ---- RAG statistics on the GPU: upload the 3*C bit planes, one pass over the frame
+    segPieceOf.assign(N, (uint8_t)(C + 1));       // index of the piece that owns a pixel (the reference paints the pieces in score order)
+    for (int i = 0; i < C; i++) all[i].img.paint_u8(segPieceOf.data(), W, (uint8_t)i);
+    FLAP(10)
+    #undef FLAP
+    return SIND_OK;
+}
+// the pieces' planes and their connection areas' (zeros for a piece without one), C planes of H * W / 64 words each
+void DynaTail::rag_pack(unsigned long long* pieces, unsigned long long* conn) const {
+    const int C = (int)segAll.size(); const size_t pw = (size_t)H * (W / 64);
+    for (int i = 0; i < C; i++) {
+        std::memcpy(pieces + (size_t)i * pw, segAll[i].img.d.data(), pw * 8);
+        if (segAll[i].hasLianjie) std::memcpy(conn + (size_t)i * pw, segAll[i].lianjie.d.data(), pw * 8); else std::memset(conn + (size_t)i * pw, 0, pw * 8);
+    }
+}
+int DynaTail::rag_own(const int** rag) { HIP_TRY(hipSetDevice(cfg.device)); const double t0 = tick_ms(); const int r = seg_rag_gpu(rag); t_stage[4] += tick_ms() - t0; return r; }
+// ---- the GPU stage for this frame alone (every path that is not batched): upload the 2*C bit planes, dilation, one pass over the frame, the counters back, one wait
+int DynaTail::seg_rag_gpu(const int** rag_out) {
+    const int C = (int)segAll.size(); const BitImg& occ2 = segOcc2; const OccResult* pre = segPre; const uint16_t* depth_dev = segDepthDev;
+    double tf = tick_ms();
+    #define FLAP(i) { const double t_ = tick_ms(); t_fine[i] += t_ - tf; tf = t_; }
     const int wpr = W / 64; const size_t pw = (size_t)H * wpr;
     SIND_TRY(h_planes.alloc((size_t)3 * C * pw)); SIND_TRY(h_rag.alloc((size_t)3 * C * C + C + (size_t)C * 256));
     unsigned long long* planes = h_planes.p; const size_t planes_n = (size_t)3 * C * pw;
     // plane sets: [0, C) pieces, [C, 2C) their 7x7 dilations (formed on the GPU from the first set), [2C, 3C) connection areas
-    for (int i = 0; i < C; i++) if (!all[i].hasLianjie) std::memset(&planes[((size_t)2 * C + i) * pw], 0, pw * 8);
-    for (int i = 0; i < C; i++) {
-        std::memcpy(&planes[((size_t)0 * C + i) * pw], all[i].img.d.data(), pw * 8);
-        if (all[i].hasLianjie) std::memcpy(&planes[((size_t)2 * C + i) * pw], all[i].lianjie.d.data(), pw * 8);
-    }
+    rag_pack(planes, planes + (size_t)2 * C * pw);
     FLAP(10)
     SIND_TRY(planes_d.alloc(planes_n)); SIND_TRY(rag_d.alloc((size_t)3 * C * C + C + (size_t)C * 256));
     FLAP(11)
@@ -577,7 +642,16 @@ int DynaTail::seg_and_merge(const std::vector<BitImg>& allLabels, const BitImg& 
     HIP_TRY(hipMemcpyAsync(rag.data(), rag_d.p, ((size_t)3 * C * C + C + (size_t)C * 256) * sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(sind_stream_wait(stream));
     FLAP(8)
-    const int* ov = rag.data(); const int* ovp = ov + C * C; const int* ljo = ovp + C * C; const int* lja = ljo + C * C; const int* hst = lja + C;
+    #undef FLAP
+    *rag_out = rag.data();
+    return SIND_OK;
+}
+// host part from the counters on: cal_hist, merge matrix, folds, labelNew
+void DynaTail::seg_finish(const int* rag, std::vector<uint8_t>& labelNew) {
+    const std::vector<SegPiece>& all = segAll; const std::vector<uint8_t>& pieceOf = segPieceOf; const int C = (int)all.size();
+    double tf = tick_ms();
+    #define FLAP(i) { const double t_ = tick_ms(); t_fine[i] += t_ - tf; tf = t_; }
+    const int* ov = rag; const int* ovp = ov + C * C; const int* ljo = ovp + C * C; const int* lja = ljo + C * C; const int* hst = lja + C;
     // cal_hist (DD:1685-1739) from the two masked histograms
     auto cal_hist = [&](int a, int b, double out[3]) {
         float h1[256], h2[256]; double m1 = 0, m2 = 0, mn1 = DBL_MAX, mn2 = DBL_MAX;
@@ -652,7 +726,6 @@ int DynaTail::seg_and_merge(const std::vector<BitImg>& allLabels, const BitImg& 
     for (int k = 0; k < N; k++) labelNew[k] = lut[pieceOf[k]];
     FLAP(9)
     #undef FLAP
-    return SIND_OK;
 }
 
 // ---- DD:1377-1666
@@ -718,9 +791,29 @@ int DynaTail::process(const uint16_t* depth_host, const uint16_t* depth_dev, con
     SIND_TRY((depth_half ? depth_half : this)->depth_stage(depth_host, depth_dev, pre, d, km));
     return fuse(maskLow, maskHigh, d, dyna_out, label_out);
 }
+// the same in two parts around the batched RAG stage (dyna.hpp)
+int DynaTail::process_begin(const uint16_t* depth_host, const uint16_t* depth_dev, const float* U, const float* V, const OccResult* pre, DynaTail* depth_half,
+                            const KmFrameResult* km, const FlowMasksReady* fm) {
+    HIP_TRY(hipSetDevice(cfg.device));
+    n_frames++; pendHalf = depth_half;
+    { const double t0 = tick_ms(); if (fm) flow_masks_ready(*fm, pendLow, pendHigh); else SIND_TRY(flow_masks(U, V, pendLow, pendHigh, pre ? pre->gridFlow : nullptr)); t_stage[0] += tick_ms() - t0; }
+    pendD = DepthStageOut();
+    return rag_half()->depth_stage_begin(depth_host, depth_dev, pre, pendD, km);
+}
+int DynaTail::process_end(const int* rag, uint8_t* dyna_out, uint8_t* label_out) {
+    HIP_TRY(hipSetDevice(cfg.device));
+    SIND_TRY(rag_half()->depth_stage_end(pendD, rag));
+    return fuse(pendLow, pendHigh, pendD, dyna_out, label_out);
+}
 
 // flow-independent half: k-means (DD:1410-1414), cluster order (DD:1428-1491), CalOccluded (DD:1493), SegAndMerge (DD:1495-1551)
 int DynaTail::depth_stage(const uint16_t* depth_host, const uint16_t* depth_dev, const OccResult* pre, DepthStageOut& out, const KmFrameResult* km) {
+    SIND_TRY(depth_stage_begin(depth_host, depth_dev, pre, out, km));
+    const int* rag = nullptr;
+    if (!segAll.empty()) SIND_TRY(rag_own(&rag));
+    return depth_stage_end(out, rag);
+}
+int DynaTail::depth_stage_begin(const uint16_t* depth_host, const uint16_t* depth_dev, const OccResult* pre, DepthStageOut& out, const KmFrameResult* km) {
     HIP_TRY(hipSetDevice(cfg.device));
     double tk = tick_ms();
     #define LAP(i) { const double t_ = tick_ms(); t_stage[i] += t_ - tk; tk = t_; }
@@ -744,15 +837,25 @@ int DynaTail::depth_stage(const uint16_t* depth_host, const uint16_t* depth_dev,
         if (count0 <= 5 && ratioArea < 0.6f) { labelForSegEdge |= labelMask[idx]; ++count0; }
     }
     labelForSegEdge = labelForSegEdge.dilated(EllipseElem(7));
-    BitImg occ1, occ2;
+    BitImg& occ1 = segOcc1; BitImg& occ2 = segOcc2;
     LAP(2)
     if (pre && pre->ready) { out.totalArea = pre->totalArea; occ1 = pre->occ1; occ2 = pre->occ2; }
     else SIND_TRY(cal_occluded(depth_host, depth_dev, out.totalArea, occ1, occ2));
     LAP(3)
     out.label3.assign(N, 0);
-    if (!allLabels.empty()) SIND_TRY(seg_and_merge(allLabels, occ1, occ2, labelForSegEdge, depth_host, depth_dev, out.label3, pre && pre->ready ? pre : nullptr));
+    segAll.clear(); segDepthDev = depth_dev; segPre = pre && pre->ready ? pre : nullptr;
+    if (!allLabels.empty()) SIND_TRY(seg_pieces(allLabels, occ1, labelForSegEdge, depth_host));
     LAP(4)
     #undef LAP
+    return SIND_OK;
+}
+int DynaTail::depth_stage_end(DepthStageOut& out, const int* rag) {
+    const BitImg& occ1 = segOcc1; const BitImg& occ2 = segOcc2;
+    if (!segAll.empty()) {
+        if (!rag) { sind_set_error("DynaTail::depth_stage_end: the RAG counters of this frame are missing"); return SIND_E_STATE; }
+        const double t0 = tick_ms(); seg_finish(rag, out.label3); t_stage[4] += tick_ms() - t0;
+    }
+    segAll.clear();
     int maxNum = 0; for (uint8_t v : out.label3) maxNum = std::max<int>(maxNum, v);
     out.maxNum = maxNum; out.ready = true;
     if (keep_debug) { dbg.occ1.resize(N); occ1.to_u8(dbg.occ1.data(), W, 255); dbg.occ2.resize(N); occ2.to_u8(dbg.occ2.data(), W, 255); dbg.totalArea.resize(N); out.totalArea.to_u8(dbg.totalArea.data(), W, 255); }

@@ -220,6 +220,21 @@ int sind_pipe_set_flow_mask_batch(sind_pipe* p, int on) {
     if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_set_flow_mask_batch: a submitted step is still pending"); return SIND_E_STATE; }
     p->fm_batch = on != 0; p->fm_frames = 0; return SIND_OK;
 }
+int sind_pipe_set_rag_batch(sind_pipe* p, int on) {
+    if (!p) { sind_set_error("sind_pipe_set_rag_batch: null handle"); return SIND_E_ARG; }
+    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_set_rag_batch: a submitted step is still pending"); return SIND_E_STATE; }
+    p->rag_batch = on != 0; p->rag_frames = 0; p->rag_fallback = 0; return SIND_OK;
+}
+int sind_pipe_get_rag_batch(sind_pipe* p, int* on, long long* frames_batched, long long* frames_fallback) {
+    if (!p || !on || !frames_batched || !frames_fallback) { sind_set_error("sind_pipe_get_rag_batch: null argument"); return SIND_E_ARG; }
+    *on = p->rag_batch ? 1 : 0; *frames_batched = p->rag_frames.load(); *frames_fallback = p->rag_fallback.load(); return SIND_OK;
+}
+int sind_pipe_set_rag_batch_chunk(sind_pipe* p, int chunk_frames, int slab_planes_per_frame) {
+    if (!p) { sind_set_error("sind_pipe_set_rag_batch_chunk: null handle"); return SIND_E_ARG; }
+    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_set_rag_batch_chunk: a submitted step is still pending"); return SIND_E_STATE; }
+    if (slab_planes_per_frame > 1024) { sind_set_error("sind_pipe_set_rag_batch_chunk: %d planes per frame (at most 1024)", slab_planes_per_frame); return SIND_E_ARG; }
+    p->rag_chunk = chunk_frames < 1 ? 0 : chunk_frames; if (slab_planes_per_frame >= 0) p->rag_planes = slab_planes_per_frame; return SIND_OK;
+}
 int sind_pipe_get_flow_mask_batch(sind_pipe* p, int* on, long long* frames_batched) {
     if (!p || !on || !frames_batched) { sind_set_error("sind_pipe_get_flow_mask_batch: null argument"); return SIND_E_ARG; }
     *on = p->fm_batch ? 1 : 0; *frames_batched = p->fm_frames.load(); return SIND_OK;

@@ -76,6 +76,10 @@ struct sind_pipe {
     // once the round thread has waited for the previous round's tails, so the homographies are computed on the pool WHILE the batched k-means runs and the stage's
     // kernels run once for the group.  One set per handle: phase B of two steps is never in flight together (a submit finishes the previous step's tails before it returns).
     FlowMaskBatch fmb[KM_GROUPS]; bool fm_batch = true; std::atomic<long long> fm_frames{0};
+    // RAG stage of SegAndMerge in the same rounds, batched per chunk of the group's frames (RagBatch, dyna.hpp; pipeline_tails.cpp: tail_rag_begin) on the group's k-means
+    // stream, which is idle while the round's tails run.  rag_chunk: frames per set of launches (< 1: the whole group); rag_planes: input planes of slab per frame
+    struct RagRound { std::mutex m; int expected = 0, arrived = 0; std::vector<int> joined, stream_of_slot; };      // frames of the round / through their first task, packed slots per chunk, whose slot
+    RagBatch ragb[KM_GROUPS]; RagRound ragr[KM_GROUPS]; bool rag_batch = true; int rag_chunk = 32, rag_planes = 64; std::atomic<long long> rag_frames{0}, rag_fallback{0};
     std::vector<std::thread> round_threads; std::mutex km_stat_mu; double km_round_ms = 0; long km_rounds = 0;
     std::vector<std::unique_ptr<PinnedBuf<uint8_t>>> upload_stage;        // page-locked staging of sind_pipe_process (host-buffer entry point), two 4 MB buffers per uploading worker
     std::vector<std::unique_ptr<DynaTail>> occ_tails;     // CalOccluded workspaces, one per pool worker (state free)

@@ -18,17 +18,12 @@ void depth_task(sind_pipe* p, sind_pipe::StepBuf* sb, int k, int worker) {
         p->workers.push(sb->depth_group, [p, sb, k](int w) { depth_task(p, sb, k + 1, w); }); return;
     }
 }
-static bool tail_one(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int t, int worker, const KmFrameResult* km, const FlowMasksReady* fm = nullptr) {
-    SindRange range_t("sind tail: flow masks, SegAndMerge, fusion, dilation, ORB mask filter");
-    p->tails[s]->stream = p->worker_streams[worker];
+// what follows the fusion of a frame: state hash, dilation, the outputs, the keypoint filter (dy / lb: the frame's dynamic-area codes and labels)
+static bool tail_finish(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int t, std::vector<uint8_t>& dy, std::vector<uint8_t>& lb) {
     const int T = p->T, W = p->c.width, H = p->c.height; const size_t np = (size_t)W * H;
-    static thread_local std::vector<uint8_t> dy, lb, dil;
-    dy.resize(np); lb.resize(np); dil.resize(np);
+    static thread_local std::vector<uint8_t> dil;
+    dil.resize(np);
     const int k = s * T + t;
-    int r = (sb->depth_ahead || sb->two_chain) ? p->tails[s]->flow_stage(sb->U.p + np * k, sb->V.p + np * k, sb->dout[k], dy.data(), lb.data(), sb->occ[k].gridFlow, fm)
-                            : p->tails[s]->process(sb->depth_h.data() + np * k, sb->depth_dev.p + np * k, sb->U.p + np * k, sb->V.p + np * k, dy.data(), lb.data(), &sb->occ[k],
-                                                   p->dtails.empty() ? nullptr : (p->dtails[s]->stream = p->worker_streams[worker], p->dtails[s].get()), km, fm);
-    if (r != SIND_OK) { sb->tail_rc[s] = r; sb->tail_err[s] = sind_last_error(); return false; }
     if (p->hashing) { sb->state_hash[2 * (size_t)k] = p->tails[s]->state_hash[0]; sb->state_hash[2 * (size_t)k + 1] = p->tails[s]->state_hash[1]; }
     double* tf = p->tails[s]->t_fine; double t0 = now_ms();
     dilate15_codes(dy.data(), W, H, dil.data());
@@ -45,6 +40,75 @@ static bool tail_one(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int
     if (o.kps) std::memcpy(o.kps + (size_t)k * o.cap, kk.data(), kk.size() * sizeof(sind_keypoint));
     if (o.desc) std::memcpy(o.desc + (size_t)k * o.cap * 32, dd.data(), dd.size());
     return true;
+}
+static bool tail_one(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int t, int worker, const KmFrameResult* km, const FlowMasksReady* fm = nullptr) {
+    SindRange range_t("sind tail: flow masks, SegAndMerge, fusion, dilation, ORB mask filter");
+    p->tails[s]->stream = p->worker_streams[worker];
+    const size_t np = (size_t)p->c.width * p->c.height;
+    static thread_local std::vector<uint8_t> dy, lb;
+    dy.resize(np); lb.resize(np);
+    const int k = s * p->T + t;
+    int r = (sb->depth_ahead || sb->two_chain) ? p->tails[s]->flow_stage(sb->U.p + np * k, sb->V.p + np * k, sb->dout[k], dy.data(), lb.data(), sb->occ[k].gridFlow, fm)
+                            : p->tails[s]->process(sb->depth_h.data() + np * k, sb->depth_dev.p + np * k, sb->U.p + np * k, sb->V.p + np * k, dy.data(), lb.data(), &sb->occ[k],
+                                                   p->dtails.empty() ? nullptr : (p->dtails[s]->stream = p->worker_streams[worker], p->dtails[s].get()), km, fm);
+    if (r != SIND_OK) { sb->tail_rc[s] = r; sb->tail_err[s] = sind_last_error(); return false; }
+    return tail_finish(p, sb, o, s, t, dy, lb);
+}
+// ---- a frame's tail in two tasks around the round's batched RAG stage (RagBatch, dyna.hpp; non-split rounds).  The first runs the frame up to SegAndMerge's pieces, takes
+// a slot of the group's batch, packs its planes into the slab and joins.  Slots are handed out in the order the frames get there, a chunk is a run of slots: the frame
+// that packs the last slot of a chunk -- or the last frame of the round, for the partial chunk at the end -- enqueues the chunk, waits once for its event and queues the
+// second tasks of the chunk's frames (its own it runs itself).  A frame without pieces, or one the slab has no room for (it takes the per-frame stage), goes straight on.
+static void tail_rag_end(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int t, int worker, const int* rag) {
+    SindRange range_t("sind tail: SegAndMerge from the counters on, fusion, dilation, ORB mask filter");
+    p->tails[s]->stream = p->worker_streams[worker]; if (!p->dtails.empty()) p->dtails[s]->stream = p->worker_streams[worker];
+    const size_t np = (size_t)p->c.width * p->c.height;
+    static thread_local std::vector<uint8_t> dy, lb;
+    dy.resize(np); lb.resize(np);
+    const int r = p->tails[s]->process_end(rag, dy.data(), lb.data());
+    if (r != SIND_OK) { sb->tail_rc[s] = r; sb->tail_err[s] = sind_last_error(); return; }
+    tail_finish(p, sb, o, s, t, dy, lb);
+}
+static void tail_rag_begin(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int t, int g, int worker, const KmFrameResult* km, const FlowMasksReady* fm) {
+    RagBatch& rb = p->ragb[g]; sind_pipe::RagRound& rr = p->ragr[g];
+    int slot = -1; const int* own = nullptr; int r;
+    { SindRange range_t("sind tail: flow masks, SegAndMerge up to the packed planes");
+      DynaTail* tl = p->tails[s].get(); tl->stream = p->worker_streams[worker];
+      const size_t np = (size_t)p->c.width * p->c.height; const int k = s * p->T + t;
+      r = tl->process_begin(sb->depth_h.data() + np * k, sb->depth_dev.p + np * k, sb->U.p + np * k, sb->V.p + np * k, &sb->occ[k],
+                            p->dtails.empty() ? nullptr : (p->dtails[s]->stream = p->worker_streams[worker], p->dtails[s].get()), km, fm);
+      DynaTail* h = tl->rag_half();
+      if (r == SIND_OK && h->rag_pieces() > 0) {
+          unsigned long long *pieces = nullptr, *conn = nullptr;
+          if (h->rag_batchable() && rb.reserve(h->rag_pieces(), &slot, &pieces, &conn)) {
+              const double tp = now_ms(); h->rag_pack(pieces, conn); h->t_fine[10] += now_ms() - tp; const OccResult* pre = h->rag_pre(); rb.set_inputs(slot, pre->occ2_dev, pre->depthN_dev, pre->occ2_event);
+          } else { slot = -1; p->rag_fallback++; r = h->rag_own(&own); }
+      }
+      if (r != SIND_OK) { sb->tail_rc[s] = r; sb->tail_err[s] = sind_last_error(); } }
+    int flush[2] = {-1, -1}, flush_n[2] = {0, 0}, nf = 0;      // (two when this frame fills its chunk and is also the round's last, behind frames of the partial chunk at the end)
+    { std::lock_guard<std::mutex> lk(rr.m);
+      if (slot >= 0) { rr.stream_of_slot[slot] = s; const int c = rb.chunk_of(slot); if (++rr.joined[c] == rb.chunk_frames()) { flush[nf] = c; flush_n[nf++] = rb.chunk_frames(); } }
+      if (++rr.arrived == rr.expected && rb.slots() > 0) {                 // the last frame of the round: the partial chunk at the end, if there is one
+          const int lc = rb.chunk_of(rb.slots() - 1), n = rb.chunk_count(lc);
+          if (n < rb.chunk_frames()) { flush[nf] = lc; flush_n[nf++] = n; }
+      } }
+    bool mine = false;
+    for (int f = 0; f < nf; f++) {
+        const double te = now_ms();
+        int rc = rb.enqueue(flush[f]); if (rc == SIND_OK) rc = rb.wait(flush[f]);
+        p->tails[s]->t_fine[8] += now_ms() - te;      // (SIND_TAIL_TIMING's "rag": with the batch, the enqueuing frame's enqueue and wait for its whole chunk)
+        const std::string e = rc == SIND_OK ? std::string() : "batched RAG statistics: " + std::string(sind_last_error());
+        for (int b = rb.chunk_first(flush[f]); b < rb.chunk_first(flush[f]) + flush_n[f]; b++) {
+            const int s2 = rr.stream_of_slot[b];
+            if (rc != SIND_OK) { sb->tail_rc[s2] = rc; sb->tail_err[s2] = e; continue; }
+            p->rag_frames++;
+            if (s2 == s) { mine = true; continue; }
+            const int* res = rb.result(b);
+            p->workers.push(sb->km_tails[g], [p, sb, o, s2, t, res](int w) { tail_rag_end(p, sb, o, s2, t, w, res); });
+        }
+    }
+    if (r != SIND_OK || sb->tail_rc[s] != SIND_OK) return;
+    if (slot < 0) { if (!own) p->rag_frames++; tail_rag_end(p, sb, o, s, t, worker, own); }      // (no pieces: nothing to count, the frame did not leave the batched path)
+    else if (mine) tail_rag_end(p, sb, o, s, t, worker, rb.result(slot));
 }
 static void tail_task(sind_pipe* p, sind_pipe::StepBuf* sb, PipeOut o, int s, int t, int worker, const KmFrameResult* km = nullptr, bool chain = true, const FlowMasksReady* fm = nullptr) {
     struct Spin { int keep; explicit Spin(bool on) : keep(t_sind_spin_us) { if (on) t_sind_spin_us = 400; } ~Spin() { t_sind_spin_us = keep; } } spin(sb->few_chain);      // few chains, idle host: poll before sleeping (common.hpp)
@@ -161,8 +225,20 @@ void phase_b_start(sind_pipe* p, sind_pipe::StepBuf& sb, const PipeOut& o) {
                 }
                 if (rc != SIND_OK) { const std::string e = sind_last_error(); for (int s = s0; s < s0 + ns; s++) if (sbp->tail_rc[s] == SIND_OK) { sbp->tail_rc[s] = rc; sbp->tail_err[s] = "batched k-means: " + e; } return; }
                 if (fm.rc != SIND_OK) { for (int s = s0; s < s0 + ns; s++) if (sbp->tail_rc[s] == SIND_OK) { sbp->tail_rc[s] = fm.rc; sbp->tail_err[s] = "batched flow masks: " + fm.err; } return; }
+                // batched RAG stage of this round (non-split rounds only, like the flow masks'): the round's frames are counted before the first of them is queued
+                const bool ragb = p->rag_batch && !split;
+                if (ragb) {
+                    sind_pipe::RagRound& rr = p->ragr[g]; int n = 0;
+                    for (int s = s0; s < s0 + ns; s++) n += sbp->tail_rc[s] == SIND_OK && (sbp->first.empty() || t >= sbp->first[s]) && (sbp->active.empty() || t < sbp->active[s]);
+                    p->ragb[g].set_limits(p->rag_chunk, p->rag_planes);
+                    const int r = p->ragb[g].begin_round();
+                    if (r != SIND_OK) { const std::string e = sind_last_error(); for (int s = s0; s < s0 + ns; s++) if (sbp->tail_rc[s] == SIND_OK) { sbp->tail_rc[s] = r; sbp->tail_err[s] = "batched RAG statistics: " + e; } return; }
+                    std::lock_guard<std::mutex> lk(rr.m); rr.expected = n; rr.arrived = 0; rr.joined.assign(ns + 1, 0); rr.stream_of_slot.assign(ns, -1);
+                }
                 for (int s = s0; s < s0 + ns; s++) {
                     if (!(sbp->tail_rc[s] == SIND_OK && (sbp->first.empty() || t >= sbp->first[s]) && (sbp->active.empty() || t < sbp->active[s]))) continue;
+                    if (ragb) { const bool have = fm.n > 0; const FlowMasksReady fr = have ? fm.ready[s - s0] : FlowMasksReady{nullptr, nullptr, nullptr};
+                                p->workers.push(sbp->km_tails[g], [p, sbp, o, s, t, g, s0, fr, have](int w) { tail_rag_begin(p, sbp, o, s, t, g, w, &p->kmb[g].result(s - s0), have ? &fr : nullptr); }); continue; }
                     if (!split) { const bool have = fm.n > 0; const FlowMasksReady fr = have ? fm.ready[s - s0] : FlowMasksReady{nullptr, nullptr, nullptr};      // (by value: this thread may be gone when the task runs; the masks themselves stay until the group's next enqueue)
                                   p->workers.push(sbp->km_tails[g], [p, sbp, o, s, t, g, s0, fr, have](int w) { tail_task(p, sbp, o, s, t, w, &p->kmb[g].result(s - s0), false, have ? &fr : nullptr); }); continue; }
                     p->workers.push(sbp->km_tails[g], [p, sbp, o, s, t, g, s0, np](int w) {

@@ -108,6 +108,19 @@ class Pipeline:
         on = C.c_int(); n = C.c_longlong()
         check(lib().sind_pipe_get_flow_mask_batch(self._h, C.byref(on), C.byref(n)), "sind_pipe_get_flow_mask_batch"); return bool(on.value), int(n.value)
 
+    def set_rag_batch(self, on: bool):
+        """region-adjacency stage of SegAndMerge batched per chunk of a k-means round's frames (non-split rounds; default on; same results); resets the counters"""
+        check(lib().sind_pipe_set_rag_batch(self._h, int(bool(on))), "sind_pipe_set_rag_batch")
+
+    def rag_batch(self):
+        """(switch, frames of batched rounds that did not take the per-frame stage, frames the slab had no room for) since the switch was last set"""
+        on = C.c_int(); n = C.c_longlong(); f = C.c_longlong()
+        check(lib().sind_pipe_get_rag_batch(self._h, C.byref(on), C.byref(n), C.byref(f)), "sind_pipe_get_rag_batch"); return bool(on.value), int(n.value), int(f.value)
+
+    def set_rag_batch_chunk(self, chunk_frames: int, slab_planes_per_frame: int = -1):
+        """frames per set of launches of the batched RAG stage (< 1: a whole group; default 32) and the slab's input planes per frame (two per piece; default 64, < 0: keep)"""
+        check(lib().sind_pipe_set_rag_batch_chunk(self._h, int(chunk_frames), int(slab_planes_per_frame)), "sind_pipe_set_rag_batch_chunk")
+
     def host_info(self) -> dict:
         a = np.zeros(6, np.int32); check(lib().sind_pipe_host_info(self._h, ptr(a)), "sind_pipe_host_info")
         return dict(cpu_share=int(a[0]), workers=int(a[1]), cpu_tokens_max=int(a[2]), cores_usable=int(a[3]), cgroup_quota_cores=(int(a[4]) if a[4] >= 0 else None), local_world=int(a[5]))
@@ -261,6 +274,9 @@ class PipelineGroup:
     def kmeans_groups(self): return self.pipes[0].kmeans_groups()
     def set_flow_mask_batch(self, on): [p.set_flow_mask_batch(on) for p in self.pipes]
     def flow_mask_batch(self): r = [p.flow_mask_batch() for p in self.pipes]; return r[0][0], sum(x[1] for x in r)
+    def set_rag_batch(self, on): [p.set_rag_batch(on) for p in self.pipes]
+    def rag_batch(self): r = [p.rag_batch() for p in self.pipes]; return r[0][0], sum(x[1] for x in r), sum(x[2] for x in r)
+    def set_rag_batch_chunk(self, chunk_frames, slab_planes_per_frame=-1): [p.set_rag_batch_chunk(chunk_frames, slab_planes_per_frame) for p in self.pipes]
     def host_info(self): h = self.pipes[0].host_info(); h["pipelines"] = len(self.pipes); return h
 
     def set_active_frames(self, a):
