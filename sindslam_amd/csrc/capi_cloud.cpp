@@ -27,6 +27,8 @@ struct sind_cloud {
     }
 };
 
+sind::CloudResident sind::cloud_resident(const sind_cloud* c) { return sind::CloudResident{c->out.p, c->np, c->lastB, c->device, c->h_total.data()}; }
+
 extern "C" {
 
 int sind_cloud_create(double fx, double fy, double cx, double cy, double depth_scale, int width, int height, int max_batch, int device, sind_cloud** out) {

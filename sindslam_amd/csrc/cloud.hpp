@@ -2,6 +2,8 @@
 #pragma once
 #include "common.hpp"
 
+struct sind_cloud;
+
 namespace sind {
 
 constexpr int CLOUD_LABELS = 12, CLOUD_CHUNK = 1024;
@@ -50,5 +52,10 @@ struct CfArrays {                            // device pointers; per cloud b the
     CloudPoint* out;                         // [B][np]
 };
 int launch_cloud_filter(const CfArrays& a, int B, int nmax, int mean_k, double stddev_mul, hipStream_t s);
+
+// The clouds that the last sind_cloud_generate left on the device, for the other handles that read them in place (capi_occmap.cpp): rows of `stride` points,
+// lastB of them (0 before any generate), their sizes in host memory.
+struct CloudResident { const CloudPoint* pts; int stride, lastB, device; const int* n; };
+CloudResident cloud_resident(const sind_cloud* c);
 
 }  // namespace sind

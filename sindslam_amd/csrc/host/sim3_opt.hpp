@@ -29,6 +29,7 @@
 // returns -1 without touching anything, nBad = 0, 0 < 10: return 0.  A NaN chi2 compares false with th2: the pair stays.
 #pragma once
 #include "pose_opt.hpp"
+#include "fd_exp.hpp"
 
 struct sind_sim3opt_item;
 
@@ -40,20 +41,7 @@ struct Sim3OptOut { double q[4], t[3], s; int nIn, nBad, stages, iters[2]; doubl
 #define SIM3OPT_ENTRIES 36                                           // per edge: 28 of the upper triangle of J^T W J (row-major), 7 of J^T omega_r, rho[0]
 #define SIM3OPT_TRANSFORMS 15                                        // the estimate, then +delta and -delta of dimension 0, of dimension 1, ...
 
-// ---------------------------------------------------------------- exp, defined (see 5. above)
-SIND_HD inline double s3_exp(double x) {
-    if (!(x == x)) return x;
-    if (x > 709.782712893384) return DBL_MAX * 2.0;
-    if (x < -745.2) return 0.0;
-    const double ln2HI = 6.93147180369123816490e-01, ln2LO = 1.90821492927058770002e-10, invln2 = 1.44269504088896338700e+00;
-    const double P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03, P3 = 6.61375632143793436117e-05, P4 = -1.65339022054652515390e-06, P5 = 4.13813679705723846039e-08;
-    const double fn = __builtin_rint(x * invln2);
-    const double hi = x - fn * ln2HI, lo = fn * ln2LO;
-    const double r = hi - lo, t = r * r;
-    const double c = r - t * (P1 + t * (P2 + t * (P3 + t * (P4 + t * P5))));
-    const double y = 1.0 - ((lo - (r * c) / (2.0 - c)) - hi);
-    return ldexp(y, (int)fn);
-}
+// ---------------------------------------------------------------- exp, defined (see 5. above): s3_exp, in fd_exp.hpp since the occupancy map uses it too
 
 // ---------------------------------------------------------------- g2o::Sim3 (sim3.h)
 // Sim3(const Matrix3d& R, const Vector3d& t, double s) of LoopClosing.cc:296 over Converter::toMatrix3d / toVector3d: the FP32 read as FP64, Quaterniond(R) not normalised
