@@ -180,6 +180,10 @@ int sind_debug_div_scan(int device, unsigned long long counts[3], int* max_exp, 
  * kernel, 1 = one-wave kernel, 2 = one-wave kernel in its production form, which clears the working histogram: the first 257 words of every result
  * block then hold the cleared words.  mu1 (optional, variants 1 / 2): n x 256 values of Otsu's running class mean, the one rounding chain with a division. */
 int sind_debug_flow_thresholds(const int* hist, int n, int width, int height, int variant, int device, int* res, double* mu1);
+/* parity-test access to the large-motion test (DynaDetect.cc:1081-1114) without DeepFlow and without the sign flip: B flow fields (host f32 [B][fh][fw] each, fw x fh
+ * the 0.6-scaled grid of a W x H frame) go through the production launch of the magnitude maximum and histogram with batch B and the host decision the dense flow calls.
+ * flags: B values (0 / 1); hist (optional): B x 256 counts; maxflow (optional): B maxima of |flow|; end (optional): B x 2 = endFlow, endFlow2. */
+int sind_debug_large_motion(const float* u, const float* v, int B, int fw, int fh, int W, int H, int device, int* flags, int* hist, float* maxflow, int* end);
 /* parity-test access to the batched flow-mask stage (csrc/flow_mask.hip: k_residual_mag_frames, k_mag_hist_frames, k_flow_thresholds_frames,
  * k_flow_mask_bits_frames): n frames of dense flow (host f32 [n][height][width] each) and n homographies (row-major 3 x 3 doubles) go through the four
  * batched launches and, in the same call, frame by frame through the per-frame kernels.  Both sets come back: masks as u8 [n][height * width] (low: 0 / 128,
@@ -274,6 +278,9 @@ int sind_pipe_set_state(sind_pipe* p, int stream, const uint8_t* buf, size_t n);
  *     step's last frame: prime the stream again before it processes anything else.  NULL = all frames.  Not available with depth-ahead. */
 int sind_pipe_set_state_hashing(sind_pipe* p, int on);
 int sind_pipe_get_state_hashes(sind_pipe* p, uint64_t* out, size_t count);
+/* Which pairs of the step whose results were returned last took the reference's second DeepFlow pass (flow(n, n-1) instead of flow(n, n-2), DynaDetect.cc:1121-1131):
+ * streams x frames_per_step flags (0 / 1), pair k = stream * frames_per_step + frame.  Read-only; the flag depends on the frames alone, so a ragged step has all of them. */
+int sind_pipe_large_motion(sind_pipe* p, int* flags, int cap);
 int sind_pipe_set_active_frames(sind_pipe* p, const int* frames_per_stream);
 /* Retained steps: the repair runs of the chunked mode re-run only the stateful 1 % of a frame.  sind_pipe_reserve_retained(n) sets buffers for n steps aside
  * (device: flow, depth, plane-edge mask, normalised depth; page-locked host: depth, sample-grid flow); sind_pipe_retain_next(tag) keeps the phase-A outputs

@@ -124,6 +124,9 @@ void orc_dyna_debug(void* p, float* flow_full, double* H, float* thr /*maxError,
     if (info) { info[0] = g.largeMotion; info[1] = g.nPairs; info[2] = g.nClusters; }
 }
 
+// the large-motion test of the last call (DD:1093-1114): endFlow, endFlow2, largeMotion
+void orc_dyna_motion(void* p, int* out3) { const DynaIntermediates& g = ((DynaDetect*)p)->dbg; out3[0] = g.endFlow; out3[1] = g.endFlow2; out3[2] = g.largeMotion; }
+
 void orc_dyna_debug2(void* p, uint8_t* grad_edge, uint8_t* plane_contours, uint8_t* label_for_seg_edge) {
     DynaDetect* d = (DynaDetect*)p; put(d->dbg.gradEdge, grad_edge); put(d->dbg.planeContours, plane_contours); put(d->dbg.labelForSegEdge, label_for_seg_edge);
 }

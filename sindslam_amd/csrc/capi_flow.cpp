@@ -149,6 +149,25 @@ int sind_debug_flow_thresholds(const int* hist, int n, int width, int height, in
     }
     return SIND_OK;
 }
+int sind_debug_large_motion(const float* u, const float* v, int B, int fw, int fh, int W, int H, int device, int* flags, int* hist, float* maxflow, int* end) {
+    if (!u || !v || !flags || B < 1 || B > 4096 || fw < 1 || fh < 1 || fw > W || fh > H || W > 16384 || H > 16384) { sind_set_error("sind_debug_large_motion: bad arguments"); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(device));
+    const int nf = fw * fh; const size_t n = (size_t)nf * B;
+    DevBuf<float> du, dv, dmag; DevBuf<unsigned> dmax; DevBuf<int> dh;
+    SIND_TRY(du.alloc(n)); SIND_TRY(dv.alloc(n)); SIND_TRY(dmag.alloc(n)); SIND_TRY(dmax.alloc(B)); SIND_TRY(dh.alloc((size_t)B * 256));
+    HIP_TRY(hipMemcpy(du.p, u, n * sizeof(float), hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dv.p, v, n * sizeof(float), hipMemcpyHostToDevice));
+    SIND_TRY(sind::launch_mag_stats(nullptr, du.p, dv.p, dmag.p, dmax.p, dh.p, nullptr, nf, B));
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<unsigned> h_max(B); std::vector<int> h_hist((size_t)B * 256);
+    HIP_TRY(hipMemcpy(h_max.data(), dmax.p, B * sizeof(unsigned), hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(h_hist.data(), dh.p, h_hist.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; b++) {
+        float m; std::memcpy(&m, &h_max[b], 4);
+        flags[b] = sind::large_motion_decision(m, h_hist.data() + (size_t)b * 256, W, H, end ? end + 2 * b : nullptr) ? 1 : 0;
+        if (maxflow) maxflow[b] = m;
+    }
+    if (hist) std::copy(h_hist.begin(), h_hist.end(), hist);
+    return SIND_OK;
+}
 int sind_debug_flow_masks_batch(const float* u, const float* v, const double* hm, int n, int width, int height, int device,
                                 uint8_t* low_batch, uint8_t* high_batch, int* res_batch, uint8_t* low_frame, uint8_t* high_frame, int* res_frame) {
     if (!u || !v || !hm || !low_batch || !high_batch || !res_batch || !low_frame || !high_frame || !res_frame || n < 1 || n > 64 || width < 64 || width % 64 != 0 || height < 1 || height > 4096 || width > 4096) {

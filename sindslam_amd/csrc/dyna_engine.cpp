@@ -45,6 +45,17 @@ int DynaFront::gather(const uint8_t* pool, const int* idx, int B, uint8_t* out) 
     return SIND_OK;
 }
 
+bool large_motion_decision(float maxFlowf, const int* hist256, int W, int H, int* end2) {
+    const float scale_element = 0.6f;
+    const double maxFlow = maxFlowf;
+    const int endFlow = (int)(10.0f * scale_element * 255.0f / maxFlow);
+    int endFlow2 = 0; float ratio = 0.0f;
+    const float totalpixel = W * H * scale_element * scale_element;
+    for (int i = 0; i < 255; ++i) { ratio += (float)hist256[i]; if (ratio > 0.3f * totalpixel) { endFlow2 = i; break; } }
+    if (end2) { end2[0] = endFlow; end2[1] = endFlow2; }
+    return endFlow2 > endFlow;
+}
+
 int DynaFront::dense_flow(const uint8_t* pool, const int* cur, const int* prev1, const int* prev2, int B, float* U, float* V, int* large_motion,
                           float* dbg_du, float* dbg_dv, float* dbg_ru, float* dbg_rv) {
     if (B < 1 || B > maxB) { sind_set_error("dense_flow: batch %d outside [1,%d]", B, maxB); return SIND_E_ARG; }
@@ -70,12 +81,7 @@ int DynaFront::dense_flow(const uint8_t* pool, const int* cur, const int* prev1,
     const float scale_element = 0.6f;
     for (int b = 0; b < B; b++) {
         float maxFlowf; std::memcpy(&maxFlowf, &h_max[b], 4);
-        const double maxFlow = maxFlowf;
-        const int endFlow = (int)(10.0f * scale_element * 255.0f / maxFlow);
-        int endFlow2 = 0; float ratio = 0.0f;
-        const float totalpixel = cfg.W * cfg.H * scale_element * scale_element;
-        for (int i = 0; i < 255; ++i) { ratio += (float)h_hist[(size_t)b * 256 + i]; if (ratio > 0.3f * totalpixel) { endFlow2 = i; break; } }
-        if (endFlow2 > endFlow) { lm[b] = 1; flagged.push_back(b); }
+        if (large_motion_decision(maxFlowf, h_hist.data() + (size_t)b * 256, cfg.W, cfg.H)) { lm[b] = 1; flagged.push_back(b); }
     }
     if (large_motion) std::copy(lm.begin(), lm.end(), large_motion);
     // pass 2: flow(n, n-1) for the flagged pairs only (DD:1121-1131)

@@ -143,6 +143,11 @@ int sind_pipe_get_state_hashes(sind_pipe* p, uint64_t* out, size_t count) {
     if (!p->hashing || p->last_hash.size() != (size_t)2 * p->S * p->T) { sind_set_error("sind_pipe_get_state_hashes: state hashing is off or no step has finished yet"); return SIND_E_STATE; }
     std::memcpy(out, p->last_hash.data(), p->last_hash.size() * sizeof(uint64_t)); return SIND_OK;
 }
+int sind_pipe_large_motion(sind_pipe* p, int* flags, int cap) {
+    if (!p || !flags || cap < p->S * p->T) { sind_set_error("sind_pipe_large_motion: need room for streams x frames_per_step flags"); return SIND_E_ARG; }
+    if (p->last_large_motion.size() != (size_t)p->S * p->T) { sind_set_error("sind_pipe_large_motion: no step has finished yet"); return SIND_E_STATE; }
+    std::copy(p->last_large_motion.begin(), p->last_large_motion.end(), flags); return SIND_OK;
+}
 int sind_pipe_set_active_frames(sind_pipe* p, const int* frames_per_stream) {
     if (!p) { sind_set_error("sind_pipe_set_active_frames: null handle"); return SIND_E_ARG; }
     if (!frames_per_stream) { p->active_next.clear(); return SIND_OK; }

@@ -113,12 +113,13 @@ struct sind_pipe {
         bool few_chain = false;                                        // this step runs a handful of streams as per-stream chains (see phase_b_start)
         bool two_chain = false; std::unique_ptr<std::atomic<int>[]> fgate; int fgate_n = 0;      // ... each as a depth chain running ahead of a flow chain; per frame: depth stage done + previous flow stage done
         int retain_tag = -1;                                           // >= 0: the phase-A outputs of this step are kept under this tag when its tails are done
+        std::vector<int> large_motion;                                 // per pair k = s * T + t: took the second DeepFlow pass (every flow slice writes its own range)
     } sb[2];
     // Phase-A outputs of a step kept beyond the step (sind_pipe_retain_next): everything the tails read -- dense flow, depth copies, ORB front results,
     // CalOccluded results, sample-grid flow -- so that sind_pipe_replay can run the stateful tails of those frames again from another state without
     // computing the state-free 99 % of the frame again (the repair runs of the chunked sequence mode).  Buffers come from a reserve made up front.
     struct Retained { DevBuf<float> U, V, grid_dev; DevBuf<uint16_t> depth_dev; PinnedBuf<uint16_t> depth_h; PinnedBuf<float> grid_h; DevBuf<uint8_t> occ2_dev, depthN_dev;
-                      std::vector<OrbFrameResult> orb; std::vector<OccResult> occ; int tag = -1; };
+                      std::vector<OrbFrameResult> orb; std::vector<OccResult> occ; std::vector<int> large_motion; int tag = -1; };
     std::vector<std::unique_ptr<Retained>> spare, kept; int retain_tag_next = -1;
     int cur = 0; int occ_workers = 24;
     // CPU tokens (common.hpp) for the software-pipelined steps, where CalOccluded runners and tails compete for the quota (measured: throttled periods 7 -> 2
@@ -131,6 +132,7 @@ struct sind_pipe {
     std::vector<char> primed;
     // Chunked sequences (sindslam_amd/sequence.py): hashing = every tail leaves the fingerprint of its rolled state per frame (last_hash: the step whose results
     // were returned last, [S][T][2]); active_next = per-stream number of frames whose TAILS run in the next step (one step only; empty = all T)
+    std::vector<int> last_large_motion;      // large-motion flags of the step whose results were returned last, [S][T] (sind_pipe_large_motion)
     bool hashing = false; std::vector<uint64_t> last_hash; std::vector<int> active_next; int chain_max_streams = 12; bool split_rounds = true;      /* rounds: the next k-means waits for the depth halves of the tails only (pipeline_tails.cpp) */
     double stage_ms[6] = {0}; double tail_wait_ms = 0; double sor_ms = 0, sor_union_ms = 0, sor_bytes = 0; long long sor_launches = 0; int sor_slices = 1;      // launch groups of the large levels' solver in the last step (SorTimer kind 0: k_sor_wave by default, k_sor_stream with wave = 0)
     double sor_other_ms = 0, sor_other_bytes = 0; long long sor_other_launches = 0;                             // every other solver kernel outside k_coarse_chain (tiles, one-workgroup levels)

@@ -259,7 +259,7 @@ void phase_b_start(sind_pipe* p, sind_pipe::StepBuf& sb, const PipeOut& o) {
 }
 void swap_phase_a_outputs(sind_pipe::StepBuf& sb, sind_pipe::Retained& r) {
     sb.U.swap(r.U); sb.V.swap(r.V); sb.grid_dev.swap(r.grid_dev); sb.depth_dev.swap(r.depth_dev); sb.depth_h.swap(r.depth_h); sb.grid_h.swap(r.grid_h);
-    sb.occ2_dev.swap(r.occ2_dev); sb.depthN_dev.swap(r.depthN_dev); sb.orb.swap(r.orb); sb.occ.swap(r.occ);
+    sb.occ2_dev.swap(r.occ2_dev); sb.depthN_dev.swap(r.depthN_dev); sb.orb.swap(r.orb); sb.occ.swap(r.occ); sb.large_motion.swap(r.large_motion);
 }
 int phase_b_finish(sind_pipe* p, sind_pipe::StepBuf& sb) {
     for (std::thread& t : p->round_threads) if (t.joinable()) t.join();
@@ -267,7 +267,7 @@ int phase_b_finish(sind_pipe* p, sind_pipe::StepBuf& sb) {
     for (TaskGroup& g : sb.km_tails) WorkerPool::wait(g);      // (first: with split rounds a depth half queues its frame's flow half into tail_group when it is done)
     WorkerPool::wait(sb.tail_group);
     sb.pending = false;
-    p->last_hash = sb.state_hash;
+    p->last_hash = sb.state_hash; p->last_large_motion = sb.large_motion;
     if (sb.retain_tag >= 0) {                       // keep this step's phase-A outputs: they change places with a reserve set of the same sizes
         if (p->spare.empty()) { sind_set_error("sind_pipe: no reserve left to retain step %d (sind_pipe_reserve_retained)", sb.retain_tag); sb.retain_tag = -1; return SIND_E_STATE; }
         std::unique_ptr<sind_pipe::Retained> r = std::move(p->spare.back()); p->spare.pop_back();

@@ -153,6 +153,12 @@ class Pipeline:
         check(lib().sind_pipe_get_state_hashes(self._h, ptr(out), C.c_size_t(out.size)), "sind_pipe_get_state_hashes")
         return out
 
+    def large_motion(self) -> np.ndarray:
+        """which pairs of the step whose results were returned last took the second DeepFlow pass (flow(n, n-1) instead of flow(n, n-2)): i32 [S, T]"""
+        out = np.zeros((self.S, self.T), np.int32)
+        check(lib().sind_pipe_large_motion(self._h, ptr(out), out.size), "sind_pipe_large_motion")
+        return out
+
     def set_active_frames(self, frames_per_stream):
         """next step only: the stateful tail of stream s runs for its first frames_per_stream[s] frames (None = all)"""
         if frames_per_stream is None:
@@ -263,6 +269,7 @@ class PipelineGroup:
     def set_depth_ahead(self, on): [p.set_depth_ahead(on) for p in self.pipes]
     def set_chain_max_streams(self, n): [p.set_chain_max_streams(n) for p in self.pipes]
     def state_hashes(self): return np.concatenate([p.state_hashes() for p in self.pipes])
+    def large_motion(self): return np.concatenate([p.large_motion() for p in self.pipes])
     def get_state_bytes(self): return self.pipes[0].get_state_bytes()
     def get_state(self, s=0): p, k = self._of(s); return p.get_state(k)
     def set_state(self, s, blob): p, k = self._of(s); p.set_state(k, blob)

@@ -180,6 +180,10 @@ class DynaDetect:
         lib().orc_dyna_flow_only(self.p, _p(np.ascontiguousarray(bgr)), _p(full), _p(deep), _p(ref), C.byref(lm))
         return full, deep, ref, bool(lm.value)
 
+    def motion(self):
+        """the large-motion test of the last call (DD:1093-1114): (endFlow, endFlow2, largeMotion)"""
+        m = np.zeros(3, np.int32); lib().orc_dyna_motion(self.p, _p(m)); return int(m[0]), int(m[1]), bool(m[2])
+
     def detect_with_flow(self, bgr, depth, flow_full):
         dyna = np.empty((self.h, self.w), np.uint8); label = np.empty((self.h, self.w), np.uint8)
         lib().orc_dyna_detect_with_flow(self.p, _p(np.ascontiguousarray(bgr)), _p(np.ascontiguousarray(depth)),
@@ -197,6 +201,8 @@ class DynaDetect:
         for k in ("grad_edge", "plane_contours", "label_for_seg_edge"):
             d[k] = np.empty((h, w), np.uint8)
         lib().orc_dyna_debug2(self.p, _p(d["grad_edge"]), _p(d["plane_contours"]), _p(d["label_for_seg_edge"]))
+        d["motion"] = np.zeros(3, np.int32)                 # endFlow, endFlow2, largeMotion
+        lib().orc_dyna_motion(self.p, _p(d["motion"]))
         return d
 
 

@@ -96,6 +96,20 @@ def test_region_grow_size_gate_and_chunk_calls_without_a_gpu():
     assert L.sind_pipe_replay(None, 0, None, None, None, None, None, None, 0, None, None) == -1
 
 
+def test_large_motion_entry_points_without_a_gpu():
+    """the flag getter and the parity-test entry of the large-motion test: exported, declared, and argument errors before any device call"""
+    from sindslam_amd._lib import lib
+    from sindslam_amd.pipeline import Pipeline, PipelineGroup
+    L = lib()
+    assert {"sind_pipe_large_motion", "sind_debug_large_motion"} <= set(declared_symbols())
+    assert L.sind_pipe_large_motion(None, None, 0) == -1 and b"sind_pipe_large_motion" in L.sind_last_error()
+    z = np.zeros((1, 4, 4), np.float32); f = np.zeros(1, np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert L.sind_debug_large_motion(None, p(z), 1, 4, 4, 8, 8, 0, p(f), None, None, None) == -1
+    assert L.sind_debug_large_motion(p(z), p(z), 1, 9, 4, 8, 8, 0, p(f), None, None, None) == -1 and b"sind_debug_large_motion" in L.sind_last_error()
+    assert callable(Pipeline.large_motion) and callable(PipelineGroup.large_motion)
+
+
 def test_wave_solver_layout_covers_every_level_size():
     """k_sor_wave's strips and bands (sind_flow_wave_layout, host arithmetic): for every width up to 2000 the strips cover the level, a strip's kept columns plus its halos fit the
     128 columns a wave works on, the kept width is even (a lane's two pixels never straddle a cut); for heights and batch sizes the bands cover the rows and are never empty"""
