@@ -191,6 +191,13 @@ int sind_debug_large_motion(const float* u, const float* v, int B, int fw, int f
  * lo, hi, otsu, triangle as floats).  width must be a multiple of 64. */
 int sind_debug_flow_masks_batch(const float* u, const float* v, const double* homographies, int n, int width, int height, int device,
                                 uint8_t* low_batch, uint8_t* high_batch, int* res_batch, uint8_t* low_frame, uint8_t* high_frame, int* res_frame);
+/* the same, with the intermediate images of both paths and a way into the per-frame mask kernel's narrow path: byte_offset (0..15) moves the per-frame u8 residual and both
+ * per-frame mask planes that many bytes off their 16-byte alignment (0: the production layout, 16 pixels per thread; otherwise k_threshold_masks_dev takes one pixel per
+ * thread).  mag_batch / mag_frame (optional): the FP32 residual [n][height * width] of the batched and the per-frame kernels; magu8_batch / magu8_frame (optional): its
+ * u8 normalisation. */
+int sind_debug_flow_masks_stage(const float* u, const float* v, const double* homographies, int n, int width, int height, int device,
+                                uint8_t* low_batch, uint8_t* high_batch, int* res_batch, uint8_t* low_frame, uint8_t* high_frame, int* res_frame,
+                                int byte_offset, float* mag_batch, uint8_t* magu8_batch, float* mag_frame, uint8_t* magu8_frame);
 
 /* parity-test access to the GPU region grow of the PEAC plane refinement (AHCPlaneFitter.hpp:546-601 floodFill; csrc/peac_kernels.hip): n depth frames
  * (host u16 [n][height][width]) -> membership map per pixel (plane index or -1) from ONE kernel launch over all frames (member_gpu) and from the host

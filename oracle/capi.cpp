@@ -24,6 +24,14 @@ void orc_gaussian_blur_u8(const uint8_t* src, int w, int h, int ksize, double si
 void orc_gaussian_blur3_f32(const float* src, int w, int h, double sigma, float* out) { ImgF s(w, h); s.d.assign(src, src + (size_t)w * h); ImgF d; gaussian_blur3_f32(s, d, sigma); put(d, out); }
 double orc_otsu(const int* hist, int total) { return otsu_from_hist(hist, total); }
 double orc_triangle(const int* hist) { return triangle_from_hist(hist); }
+// the mask half of FlowToMasks (flow_residual_masks) on a caller-supplied flow (w*h*2 interleaved) and homography; thr = maxError, otsu, triangle, low, high
+void orc_flow_masks(const float* flow, const double* H, int w, int h, float* thr, int* hist, uint8_t* mag_u8, uint8_t* mask_low, uint8_t* mask_high) {
+    ImgF f(w, h, 2); std::memcpy(f.d.data(), flow, f.d.size() * sizeof(float));
+    FlowMaskOut o; flow_residual_masks(f, H, w, h, o);
+    if (thr) { thr[0] = o.maxError; thr[1] = o.otsu; thr[2] = o.triangle; thr[3] = o.thr_low; thr[4] = o.thr_high; }
+    if (hist) std::copy(o.hist, o.hist + 256, hist);
+    put(o.magU8, mag_u8); put(o.maskLow, mask_low); put(o.maskHigh, mask_high);
+}
 void orc_rng_gaussian(uint64_t seed, double sigma, int n, float* out) { RNG r(seed); for (int i = 0; i < n; i++) out[i] = (float)r.gaussian(sigma); }
 float orc_fast_atan2(float y, float x) { return fastAtan2(y, x); }
 int orc_deepflow_levels(int w, int h, int* ws, int* hs, int cap) { auto s = deepflow_level_sizes(w, h); for (int i = 0; i < (int)s.size() && i < cap; i++) { ws[i] = s[i].first; hs[i] = s[i].second; } return (int)s.size(); }

@@ -35,6 +35,55 @@ struct DynaIntermediates {   // everything a stage-by-stage parity test wants to
     Img8 label, dyna;                  // outputs
 };
 
+// The mask half of DD:1252-1367 as a function of the dense flow and the homography alone: residual, u8 normalisation, histogram, Otsu / Triangle, clamps, masks.
+struct FlowMaskOut {
+    float maxError = 0, otsu = 0, triangle = 0, thr_low = 0, thr_high = 0;
+    int hist[256] = {0};
+    Img8 magU8, maskLow, maskHigh;     // maskLow: 0/128, maskHigh: 0/255 (stImgMasks)
+};
+inline void flow_residual_masks(const ImgF& flow, const double H[9], int width, int height, FlowMaskOut& o) {
+    ImgF mag(width, height); float maxErr = 0;
+    for (int row = 0; row < height; ++row) for (int col = 0; col < width; ++col) {   // DD:1252-1271
+        double den = H[6] * col + H[7] * row + H[8];
+        double flowX2 = (col - (H[0] * col + H[1] * row + H[2]) / den);
+        double flowY2 = (row - (H[3] * col + H[4] * row + H[5]) / den);
+        float dx = flow.at(row, col, 0) - (float)flowX2, dy = flow.at(row, col, 1) - (float)flowY2;
+        float m = std::sqrt(dx * dx + dy * dy);
+        mag.at(row, col) = m; maxErr = std::max(maxErr, m);
+    }
+    const float maxErrorf = maxErr;
+    const float a = (float)(255.0 / (double)maxErr);
+    Img8 magN(width, height);
+    for (size_t i = 0; i < mag.d.size(); i++) magN.d[i] = sat_u8f(mag.d[i] * a);
+    hist256(magN, o.hist);
+    float thred1 = (float)otsu_from_hist(o.hist, width * height);
+    float thred2 = (float)triangle_from_hist(o.hist);
+    o.maxError = maxErrorf; o.otsu = thred1; o.triangle = thred2; o.magU8 = magN;
+    auto gt = [&](float t, Img8& out) { out.create(width, height); int n = 0; for (size_t i = 0; i < magN.d.size(); i++) { bool b = (double)magN.d[i] > (double)t; out.d[i] = b ? 255 : 0; n += b; } return n; };
+    Img8 th1, th2;
+    if (thred1 < thred2) {                      // DD:1309-1336
+        if (thred1 < 1.7f * 255.0f / maxErrorf) thred1 = 1.7f * 255.0f / maxErrorf;
+        else if (thred1 > 3.0f * 255.0f / maxErrorf) thred1 = 3.0f * 255.0f / maxErrorf;
+        int n = gt(thred1, th1);
+        if (n > 0.5 * width * height) { thred1 = thred1 + 0.2f * 255.0f / maxErrorf; gt(thred1, th1); }
+        if (thred2 < std::max(3.0f * 255.0f / maxErrorf, thred1 * 1.2f)) thred2 = std::max(3.0f * 255.0f / maxErrorf, thred1 * 1.2f);
+        else if (thred2 > 10.0f * 255.0f / maxErrorf) thred2 = 10.0f * 255.0f / maxErrorf;
+        gt(thred2, th2);
+        o.thr_low = thred1; o.thr_high = thred2;
+        o.maskLow = th1; o.maskHigh = th2;
+    } else {                                    // DD:1337-1367 (countNonZero(thred2) quirk: never relaxes, App. C-3)
+        if (thred2 < 1.7f * 255.0f / maxErrorf) thred2 = 1.7f * 255.0f / maxErrorf;
+        else if (thred2 > 3.0f * 255.0f / maxErrorf) thred2 = 3.0f * 255.0f / maxErrorf;
+        gt(thred2, th2);
+        if (thred1 < std::max(3.0f * 255.0f / maxErrorf, thred2 * 1.2f)) thred1 = std::max(3.0f * 255.0f / maxErrorf, thred2 * 1.2f);
+        else if (thred1 > 10.0f * 255.0f / maxErrorf) thred1 = 10.0f * 255.0f / maxErrorf;
+        gt(thred1, th1);
+        o.thr_low = thred2; o.thr_high = thred1;
+        o.maskLow = th2; o.maskHigh = th1;
+    }
+    for (auto& v : o.maskLow.d) v = v ? 128 : 0;  // "* 0.5": saturate_cast<uchar>(127.5) = 128
+}
+
 class DynaDetect {
 public:
     static const int numCluster = 12, nRowCluster = 3, nColCluster = 4;
@@ -144,46 +193,10 @@ public:
         if (h_estimator == 2) { if (h_seed) find_homography_prosac(in, inLast, H, 3.0, 0.995, 2000, h_seed); else find_homography_prosac(in, inLast, H); }
         else find_homography_rho_scheme(in, inLast, H, 3.0f, 0.995, 2000, h_seed ? h_seed : ~0ull);
         std::copy(H, H + 9, dbg.H);
-        ImgF mag(width, height); float maxErr = 0;
-        for (int row = 0; row < height; ++row) for (int col = 0; col < width; ++col) {   // DD:1252-1271
-            double den = H[6] * col + H[7] * row + H[8];
-            double flowX2 = (col - (H[0] * col + H[1] * row + H[2]) / den);
-            double flowY2 = (row - (H[3] * col + H[4] * row + H[5]) / den);
-            float dx = flow.at(row, col, 0) - (float)flowX2, dy = flow.at(row, col, 1) - (float)flowY2;
-            float m = std::sqrt(dx * dx + dy * dy);
-            mag.at(row, col) = m; maxErr = std::max(maxErr, m);
-        }
-        const float maxErrorf = maxErr;
-        const float a = (float)(255.0 / (double)maxErr);
-        Img8 magN(width, height);
-        for (size_t i = 0; i < mag.d.size(); i++) magN.d[i] = sat_u8f(mag.d[i] * a);
-        hist256(magN, dbg.hist);
-        float thred1 = (float)otsu_from_hist(dbg.hist, width * height);
-        float thred2 = (float)triangle_from_hist(dbg.hist);
-        dbg.maxError = maxErrorf; dbg.otsu = thred1; dbg.triangle = thred2; dbg.magU8 = magN;
-        auto gt = [&](float t, Img8& out) { out.create(width, height); int n = 0; for (size_t i = 0; i < magN.d.size(); i++) { bool b = (double)magN.d[i] > (double)t; out.d[i] = b ? 255 : 0; n += b; } return n; };
-        Img8 th1, th2;
-        if (thred1 < thred2) {                      // DD:1309-1336
-            if (thred1 < 1.7f * 255.0f / maxErrorf) thred1 = 1.7f * 255.0f / maxErrorf;
-            else if (thred1 > 3.0f * 255.0f / maxErrorf) thred1 = 3.0f * 255.0f / maxErrorf;
-            int n = gt(thred1, th1);
-            if (n > 0.5 * width * height) { thred1 = thred1 + 0.2f * 255.0f / maxErrorf; gt(thred1, th1); }
-            if (thred2 < std::max(3.0f * 255.0f / maxErrorf, thred1 * 1.2f)) thred2 = std::max(3.0f * 255.0f / maxErrorf, thred1 * 1.2f);
-            else if (thred2 > 10.0f * 255.0f / maxErrorf) thred2 = 10.0f * 255.0f / maxErrorf;
-            gt(thred2, th2);
-            dbg.thr_low = thred1; dbg.thr_high = thred2;
-            maskLow = th1; maskHigh = th2;
-        } else {                                    // DD:1337-1367 (countNonZero(thred2) quirk: never relaxes, App. C-3)
-            if (thred2 < 1.7f * 255.0f / maxErrorf) thred2 = 1.7f * 255.0f / maxErrorf;
-            else if (thred2 > 3.0f * 255.0f / maxErrorf) thred2 = 3.0f * 255.0f / maxErrorf;
-            gt(thred2, th2);
-            if (thred1 < std::max(3.0f * 255.0f / maxErrorf, thred2 * 1.2f)) thred1 = std::max(3.0f * 255.0f / maxErrorf, thred2 * 1.2f);
-            else if (thred1 > 10.0f * 255.0f / maxErrorf) thred1 = 10.0f * 255.0f / maxErrorf;
-            gt(thred1, th1);
-            dbg.thr_low = thred2; dbg.thr_high = thred1;
-            maskLow = th2; maskHigh = th1;
-        }
-        for (auto& v : maskLow.d) v = v ? 128 : 0;  // "* 0.5": saturate_cast<uchar>(127.5) = 128
+        FlowMaskOut fm; flow_residual_masks(flow, H, width, height, fm);
+        std::copy(fm.hist, fm.hist + 256, dbg.hist);
+        dbg.maxError = fm.maxError; dbg.otsu = fm.otsu; dbg.triangle = fm.triangle; dbg.magU8 = fm.magU8; dbg.thr_low = fm.thr_low; dbg.thr_high = fm.thr_high;
+        maskLow = fm.maskLow; maskHigh = fm.maskHigh;
         dbg.maskLow = maskLow; dbg.maskHigh = maskHigh;
     }
 

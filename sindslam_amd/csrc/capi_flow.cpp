@@ -170,12 +170,19 @@ int sind_debug_large_motion(const float* u, const float* v, int B, int fw, int f
 }
 int sind_debug_flow_masks_batch(const float* u, const float* v, const double* hm, int n, int width, int height, int device,
                                 uint8_t* low_batch, uint8_t* high_batch, int* res_batch, uint8_t* low_frame, uint8_t* high_frame, int* res_frame) {
-    if (!u || !v || !hm || !low_batch || !high_batch || !res_batch || !low_frame || !high_frame || !res_frame || n < 1 || n > 64 || width < 64 || width % 64 != 0 || height < 1 || height > 4096 || width > 4096) {
-        sind_set_error("sind_debug_flow_masks_batch: bad arguments (1..64 frames, width a multiple of 64)"); return SIND_E_ARG;
+    return sind_debug_flow_masks_stage(u, v, hm, n, width, height, device, low_batch, high_batch, res_batch, low_frame, high_frame, res_frame, 0, nullptr, nullptr, nullptr, nullptr);
+}
+int sind_debug_flow_masks_stage(const float* u, const float* v, const double* hm, int n, int width, int height, int device,
+                                uint8_t* low_batch, uint8_t* high_batch, int* res_batch, uint8_t* low_frame, uint8_t* high_frame, int* res_frame,
+                                int byte_offset, float* mag_batch, uint8_t* magu8_batch, float* mag_frame, uint8_t* magu8_frame) {
+    if (!u || !v || !hm || !low_batch || !high_batch || !res_batch || !low_frame || !high_frame || !res_frame || n < 1 || n > 64 || width < 64 || width % 64 != 0 || height < 1 || height > 4096 || width > 4096 ||
+        byte_offset < 0 || byte_offset > 15) {
+        sind_set_error("sind_debug_flow_masks_batch: bad arguments (1..64 frames, width a multiple of 64, byte offset 0..15)"); return SIND_E_ARG;
     }
     HIP_TRY(hipSetDevice(device));
-    const size_t np = (size_t)width * height, words = np / 64, slot = sind::flow_mask_slot_words(width, height), res_off = (2 * np + 15) / 16 * 16;
-    DevBuf<float> du, dv, dmag; DevBuf<uint8_t> dq, dmask; DevBuf<int> dh; DevBuf<unsigned long long> dout; DevBuf<sind::FlowMaskRec> drec;
+    const size_t np = (size_t)width * height, words = np / 64, slot = sind::flow_mask_slot_words(width, height), res_off = (2 * np + byte_offset + 15) / 16 * 16;
+    DevBuf<float> du, dv, dmag; DevBuf<uint8_t> dq, dqf, dmask; DevBuf<int> dh; DevBuf<unsigned long long> dout; DevBuf<sind::FlowMaskRec> drec;
+    SIND_TRY(dqf.alloc(np + 16));
     SIND_TRY(du.alloc(np * n)); SIND_TRY(dv.alloc(np * n)); SIND_TRY(dmag.alloc(np * n)); SIND_TRY(dq.alloc(np * n)); SIND_TRY(dh.alloc((size_t)264 * n)); SIND_TRY(dout.alloc(slot * n)); SIND_TRY(drec.alloc(n));
     SIND_TRY(dmask.alloc(res_off + 1088));
     HIP_TRY(hipMemcpy(du.p, u, np * n * sizeof(float), hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dv.p, v, np * n * sizeof(float), hipMemcpyHostToDevice));
@@ -194,14 +201,20 @@ int sind_debug_flow_masks_batch(const float* u, const float* v, const double* hm
         for (size_t k = 0; k < np; k++) { low_batch[np * i + k] = ((o[k >> 6] >> (k & 63)) & 1) ? 128 : 0; high_batch[np * i + k] = ((o[words + (k >> 6)] >> (k & 63)) & 1) ? 255 : 0; }
         std::memcpy(res_batch + (size_t)261 * i, o + 2 * words, 261 * sizeof(int));
     }
-    // ---- frame by frame: the kernels of DynaTail::flow_masks_gpu (the batched run left every working histogram zeroed; frame 0's serves all)
+    if (mag_batch) HIP_TRY(hipMemcpy(mag_batch, dmag.p, np * n * sizeof(float), hipMemcpyDeviceToHost));
+    if (magu8_batch) HIP_TRY(hipMemcpy(magu8_batch, dq.p, np * n, hipMemcpyDeviceToHost));
+    // ---- frame by frame: the kernels of DynaTail::flow_masks_gpu (the batched run left every working histogram zeroed; frame 0's serves all).  byte_offset moves the
+    // u8 residual and both mask planes off their 16-byte alignment, so that the masks take the one-pixel-per-thread path of k_threshold_masks_dev
+    uint8_t* q = dqf.p + byte_offset; uint8_t* low = dmask.p + byte_offset; uint8_t* high = low + np;
     for (int i = 0; i < n; i++) {
         int* res = reinterpret_cast<int*>(dmask.p + res_off);
-        SIND_TRY(sind::launch_residual(nullptr, du.p + np * i, dv.p + np * i, hm + 9 * i, dmag.p, reinterpret_cast<unsigned*>(dh.p + 256), dh.p, dq.p, width, height, false));
-        SIND_TRY(sind::launch_flow_thresholds_and_masks(nullptr, dh.p, width, height, res, dq.p, dmask.p, dmask.p + np));
+        SIND_TRY(sind::launch_residual(nullptr, du.p + np * i, dv.p + np * i, hm + 9 * i, dmag.p, reinterpret_cast<unsigned*>(dh.p + 256), dh.p, q, width, height, false));
+        SIND_TRY(sind::launch_flow_thresholds_and_masks(nullptr, dh.p, width, height, res, q, low, high));
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(low_frame + np * i, dmask.p, np, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(high_frame + np * i, dmask.p + np, np, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(low_frame + np * i, low, np, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(high_frame + np * i, high, np, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(res_frame + (size_t)261 * i, res, 261 * sizeof(int), hipMemcpyDeviceToHost));
+        if (mag_frame) HIP_TRY(hipMemcpy(mag_frame + np * i, dmag.p, np * sizeof(float), hipMemcpyDeviceToHost));
+        if (magu8_frame) HIP_TRY(hipMemcpy(magu8_frame + np * i, q, np, hipMemcpyDeviceToHost));
     }
     return SIND_OK;
 }

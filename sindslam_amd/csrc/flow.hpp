@@ -108,7 +108,6 @@ int launch_flow_thresholds_and_masks(hipStream_t s, int* hist, int W, int H, int
 static inline size_t flow_mask_slot_words(int W, int H) { return (2 * ((size_t)W * H / 64) + (261 * sizeof(int) + 7) / 8 + 1) / 2 * 2; }
 int launch_flow_masks_frames(hipStream_t s, const FlowMaskRec* recs_dev, const FlowMaskRec* recs_host, int n, int capacity, int W, int H);
 int debug_flow_thresholds(hipStream_t s, int* hist, int n, int W, int H, int variant, int* res, double* mu1);
-int launch_threshold_masks(hipStream_t s, const uint8_t* magu8, float lo, float hi, uint8_t* low, uint8_t* high, int n);
 int launch_gather_grid(hipStream_t s, const float* u, const float* v, float* out, int w, int h, int step, int B = 1);
 int launch_scale2(hipStream_t s, float* a, float* b, float sc, size_t n);
 

@@ -82,15 +82,6 @@ __global__ void k_residual_mag_frames(const FlowMaskRec* __restrict__ recs, int 
     const FlowMaskRec& R = recs[blockIdx.z];
     residual_mag_rows(R.U, R.V, R.H, R.mag, reinterpret_cast<unsigned*>(R.hist + 256), w, h, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y * RM_ROWS);
 }
-// masks from the u8 residual: low -> 128, high -> 255 (stImgMasks), thresholds decided on the host from the histogram
-__global__ void k_threshold_masks(const uint8_t* __restrict__ magu8, float thr_low, float thr_high, uint8_t* __restrict__ low,
-                                  uint8_t* __restrict__ high, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double q = (double)magu8[i];
-    low[i] = q > (double)thr_low ? 128 : 0;
-    high[i] = q > (double)thr_high ? 255 : 0;
-}
 // The two thresholds of stImgMasks from the residual's 256-bin histogram, on the device so that the flow-mask stage needs ONE host round trip (masks,
 // histogram and thresholds come back together): cv::threshold's THRESH_OTSU / THRESH_TRIANGLE return values (imgproc/thresh.cpp) and the clamping of
 // DD:1309-1367, with the host code's FP64 / FP32 operations in the same order (no contraction: the library is built with -ffp-contract=off).
@@ -328,7 +319,10 @@ __global__ void __launch_bounds__(256) k_flow_mask_bits_frames(const FlowMaskRec
         if (lane == 0) { R.out[word] = lo; R.out[(size_t)mask_words + word] = hi; }
     }
 }
-// (16 pixels per thread where the planes allow 16-byte accesses: one pixel per thread was 1 200 workgroups of turnover per 640 x 480 frame)
+// masks from the u8 residual: low -> 128, high -> 255 (stImgMasks), thresholds read from the result block of k_flow_thresholds
+// (16 pixels per thread where the planes allow 16-byte accesses: one pixel per thread was 1 200 workgroups of turnover per 640 x 480 frame).  The one-pixel-per-thread
+// path is not reached from production: DynaTail, the only caller outside the debug entry, takes widths that are a multiple of 64 and heights that are a multiple of 8 and
+// passes the start of allocations and a plane W * H bytes behind one, so its three planes are always 16-byte aligned.  sind_debug_flow_masks_stage runs it with a byte offset.
 __global__ void k_threshold_masks_dev(const uint8_t* __restrict__ magu8, const float* __restrict__ thr, uint8_t* __restrict__ low, uint8_t* __restrict__ high, int n, int wide) {
     const double tl = (double)thr[0], th = (double)thr[1];
     if (wide) {
@@ -372,10 +366,6 @@ int launch_residual(hipStream_t s, const float* u, const float* v, const double 
     hipLaunchKernelGGL(k_residual_mag, dim3(divup(w, 128), divup(h, RM_ROWS)), dim3(128), 0, s, u, v, Hm, mag, maxbits, w, h);
     const int n = w * h, gx = std::min(divup(n, 256), 64);
     hipLaunchKernelGGL(k_mag_hist, dim3(gx, 1), dim3(256), 0, s, mag, maxbits, hist, magu8, n);
-    return SIND_OK;
-}
-int launch_threshold_masks(hipStream_t s, const uint8_t* magu8, float lo, float hi, uint8_t* low, uint8_t* high, int n) {
-    hipLaunchKernelGGL(k_threshold_masks, dim3(divup(n, 256)), dim3(256), 0, s, magu8, lo, hi, low, high, n);
     return SIND_OK;
 }
 int launch_flow_thresholds_and_masks(hipStream_t s, int* hist, int W, int H, int* res, const uint8_t* magu8, uint8_t* low, uint8_t* high) {

@@ -84,6 +84,17 @@ def triangle(hist):
     hist = np.ascontiguousarray(hist, np.int32); return lib().orc_triangle(_p(hist))
 
 
+def flow_masks(u, v, H):
+    """the mask half of DynaDetect::FlowToMasks (oracle/dynadetect.hpp flow_residual_masks: residual, u8 normalisation, histogram, Otsu / Triangle, clamps,
+    masks) on a caller-supplied flow field (u, v: [h][w] float32) and homography (9 doubles)"""
+    u = np.ascontiguousarray(u, np.float32); v = np.ascontiguousarray(v, np.float32); h, w = u.shape
+    flow = np.ascontiguousarray(np.stack([u, v], axis=-1)); hm = np.ascontiguousarray(np.asarray(H, np.float64).reshape(9))
+    thr = np.zeros(5, np.float32); hist = np.zeros(256, np.int32)
+    q = np.empty((h, w), np.uint8); lo = np.empty((h, w), np.uint8); hi = np.empty((h, w), np.uint8)
+    lib().orc_flow_masks(_p(flow), _p(hm), w, h, _p(thr), _p(hist), _p(q), _p(lo), _p(hi))
+    return dict(hist=hist, maxError=thr[0], otsu=thr[1], triangle=thr[2], lo=thr[3], hi=thr[4], mag_u8=q, mask_low=lo, mask_high=hi)
+
+
 def rng_gaussian(seed, sigma, n):
     out = np.empty(n, np.float32); lib().orc_rng_gaussian(C.c_uint64(seed), C.c_double(sigma), n, _p(out)); return out
 
