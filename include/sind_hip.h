@@ -153,7 +153,7 @@ int sind_dyna_debug(sind_dyna* d, float* flow_deep, float* flow_refined, float* 
                     uint8_t* total_area, uint8_t* grad_edge, uint8_t* plane_contours, int* info3);
 
 /* parity-test access to the k-means centre sums: out = the FP32 value of  acc = 0; for (i) acc += x[i]  (round to nearest even, exactly cv::kmeans'
- * centre accumulation, kmeans.cpp) computed by the wave-parallel window arithmetic of k_km_seqsum (csrc/depth_kernels.hip) */
+ * centre accumulation, kmeans.cpp) computed by the wave-parallel window arithmetic of k_km_seqsum (csrc/depth_kmeans.hip) */
 int sind_debug_seqsum(const float* x, int n, int device, float* out);
 /* k-means pyramid levels of at most n points (default 81920 = the three coarse levels at 640 x 480) of a batch of at least b frames (default 32: the batched rounds of a
  * many-stream step) run every pass in ONE launch, one workgroup per frame (k_km_level_fused); n = 0: the per-pass kernels everywhere.  Same labels and centres bit for bit
@@ -207,7 +207,7 @@ int sind_debug_peac_grow(const uint16_t* depth, int n, int width, int height, fl
                          int8_t* member_gpu, int8_t* member_host, uint8_t* pair_gpu, uint8_t* pair_host, int* status);
 
 /* parity-test access to the GPU front of CalOccluded (DynaDetect.cc:429-482) and the depth normalisation of the region-adjacency stage (DynaDetect.cc:765-768) through the
- * production launchers (csrc/depth_kernels.hip: k_median5_u16, k_max_u16, k_grad_edge, k_morph_e4, k_depth_norm): n depth frames (host u16 [n][height][width], 1 <= n <= 64,
+ * production launchers (csrc/depth_edges.hip: k_median5_u16, k_max_u16, k_grad_edge, k_morph_e4, k_depth_norm): n depth frames (host u16 [n][height][width], 1 <= n <= 64,
  * 7 <= width, height <= 4096).  n == 1 takes the single-frame forms of the drop-in path, n >= 2 the batched forms of the pipeline.  Per frame: filt = medianBlur(5) (u16),
  * maxima [n][2] = {maximum of filt, maximum of the raw frame}, edge_pre / edge = the gradient edge before / after MORPH_OPEN with the 4 x 4 ellipse, total_area, depth_n = the
  * 8-bit normalised depth; images are [n][height][width]. */

@@ -245,8 +245,8 @@ int sind_debug_rag_batch(const unsigned long long* planes, const int* pieces, co
 }
 
 // parity-test access to the GPU front of CalOccluded and the depth normalisation of the RAG statistics: n depth frames (host, [n][height][width] u16) through the production
-// launchers with the arguments dyna_engine.cpp gives them -- n == 1: the single-frame forms of DynaTail::cal_occluded_p1 / seg_and_merge (maxima in slots 0 and 1 of one
-// two-word buffer), n >= 2: the batched forms of OccBatch::run (per-frame maxima slots, stride 1; the raw maxima n words behind the filtered ones).  The maxima are cleared
+// chain itself, OccFront (dyna_occluded.cpp) at capacity n -- what a tail runs at capacity 1 (maxima in slots 0 and 1 of one two-word buffer) and OccBatch at its chunk size
+// (per-frame maxima slots, stride 1; the raw maxima n words behind the filtered ones), less the PEAC block statistics, which need intrinsics.  The maxima are cleared
 // by launch_max_u16 itself, as in production.  maxima [n][2] = {of the filtered frame, of the raw frame}; edge_pre = the gradient edge before the 4 x 4 opening.
 int sind_debug_depth_front(const uint16_t* depth, int n, int width, int height, float depth_scale, int device,
                            uint16_t* filt_out, unsigned* maxima, uint8_t* edge_pre, uint8_t* edge_out, uint8_t* total_area, uint8_t* depth_n) {
@@ -254,34 +254,21 @@ int sind_debug_depth_front(const uint16_t* depth, int n, int width, int height, 
         sind_set_error("sind_debug_depth_front: bad arguments (1..64 frames of 7 x 7 to 4096 x 4096)"); return SIND_E_ARG; }
     HIP_TRY(hipSetDevice(device));
     const int W = width, H = height, N = W * H, B = n; const size_t NB = (size_t)N * B;
-    DevBuf<uint16_t> dd, filt; DevBuf<uint8_t> edge, edgeTmp, total, depthN; DevBuf<unsigned> umax;
-    SIND_TRY(dd.alloc(NB)); SIND_TRY(filt.alloc(NB)); SIND_TRY(edge.alloc(NB)); SIND_TRY(edgeTmp.alloc(NB)); SIND_TRY(total.alloc(NB)); SIND_TRY(depthN.alloc(NB)); SIND_TRY(umax.alloc((size_t)2 * B));
+    sind::DynaConfig cfg; cfg.W = W; cfg.H = H; cfg.depthScale = depth_scale; cfg.device = device;
+    sind::OccFront front; DevBuf<uint16_t> dd; DevBuf<uint8_t> depthN;
+    SIND_TRY(front.init(cfg, B, false)); SIND_TRY(dd.alloc(NB)); SIND_TRY(depthN.alloc(NB));
     HIP_TRY(hipMemcpy(dd.p, depth, NB * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(umax.p, 0xff, (size_t)2 * B * sizeof(unsigned)));      // a slot a launch forgets to clear shows
+    HIP_TRY(hipMemset(front.umax.p, 0xff, (size_t)2 * B * sizeof(unsigned)));      // a slot a launch forgets to clear shows
     hipStream_t s = nullptr;
-    if (B == 1) {
-        SIND_TRY(sind::launch_median5(s, dd.p, filt.p, W, H));
-        SIND_TRY(sind::launch_max_u16(s, filt.p, N, umax.p));
-        SIND_TRY(sind::launch_grad_edge(s, filt.p, umax.p, edge.p, total.p, W, H, depth_scale));
-        HIP_TRY(hipMemcpy(edge_pre, edge.p, NB, hipMemcpyDeviceToHost));
-        SIND_TRY(sind::launch_morph(s, edge.p, edgeTmp.p, W, H, 4, false));
-        SIND_TRY(sind::launch_morph(s, edgeTmp.p, edge.p, W, H, 4, true));
-        SIND_TRY(sind::launch_max_u16(s, dd.p, N, umax.p + 1)); SIND_TRY(sind::launch_depth_norm(s, dd.p, umax.p + 1, depthN.p, N));
-    } else {
-        SIND_TRY(sind::launch_max_u16(s, dd.p, N, umax.p + B, B, 1)); SIND_TRY(sind::launch_depth_norm(s, dd.p, umax.p + B, depthN.p, N, B, 1));
-        SIND_TRY(sind::launch_median5(s, dd.p, filt.p, W, H, B));
-        SIND_TRY(sind::launch_max_u16(s, filt.p, N, umax.p, B, 1));
-        SIND_TRY(sind::launch_grad_edge(s, filt.p, umax.p, edge.p, total.p, W, H, depth_scale, B, 1));
-        HIP_TRY(hipMemcpy(edge_pre, edge.p, NB, hipMemcpyDeviceToHost));
-        SIND_TRY(sind::launch_morph(s, edge.p, edgeTmp.p, W, H, 4, false, B));
-        SIND_TRY(sind::launch_morph(s, edgeTmp.p, edge.p, W, H, 4, true, B));
-    }
+    SIND_TRY(front.enqueue_edge(s, dd.p, B, depthN.p));
+    HIP_TRY(hipMemcpy(edge_pre, front.edge.p, NB, hipMemcpyDeviceToHost));
+    SIND_TRY(front.enqueue_open(s, dd.p, B));
     HIP_TRY(hipDeviceSynchronize());
     std::vector<unsigned> mh((size_t)2 * B);
-    HIP_TRY(hipMemcpy(mh.data(), umax.p, mh.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; b++) { maxima[2 * b] = mh[B == 1 ? 0 : b]; maxima[2 * b + 1] = mh[B == 1 ? 1 : B + b]; }
-    HIP_TRY(hipMemcpy(filt_out, filt.p, NB * 2, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(edge_out, edge.p, NB, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(total_area, total.p, NB, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(depth_n, depthN.p, NB, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mh.data(), front.umax.p, mh.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; b++) { maxima[2 * b] = mh[b]; maxima[2 * b + 1] = mh[B + b]; }
+    HIP_TRY(hipMemcpy(filt_out, front.filt.p, NB * 2, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(edge_out, front.edge.p, NB, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(total_area, front.total.p, NB, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(depth_n, depthN.p, NB, hipMemcpyDeviceToHost));
     return SIND_OK;
 }
 

@@ -1,4 +1,4 @@
-// Depth-side device stage interface (host side of depth_kernels.hip).
+// Depth-side device stage interface (host side of depth_kmeans.hip / depth_edges.hip / depth_rag.hip).
 #pragma once
 #include <cmath>
 #include "common.hpp"

@@ -1,14 +1,8 @@
-// Depth-side device stages of DynaDetect for gfx950 (reference ORB_SLAM2/src/DynaDetect.cc):
-//   SegByKmeans (:315-420): depth pyramid, back-projection, label up-sampling, cv::kmeans assignment + centre sums
-//   CalOccluded (:429-482): medianBlur(5), 5x5 max-difference depth edge, valid-area mask
-//   morphologyEx with elliptical elements (:51-59 and every MORPH_* call)
-//   PEAC initial 16x16 block statistics (PEAC/AHCPlaneSeg.hpp:180-262)
-//   SegAndMergeV2 region-adjacency statistics (:784-893, cal_hist :1685-1739) from per-pixel membership words
+// SegByKmeans on the device for gfx950 (reference ORB_SLAM2/src/DynaDetect.cc :315-420): depth pyramid, back-projection, label up-sampling,
+// cv::kmeans assignment + centre sums, and the launchers of the chain (depth.hpp).
 // Integer stages are bit-exact; FP32 expressions are written in the reference's operation order (-ffp-contract=off).
-#include <mutex>
 #include "common.hpp"
 #include "depth.hpp"
-#include "host/peac_fit.hpp"
 
 namespace sind {
 
@@ -629,370 +623,6 @@ __global__ void k_labels_to_u8(const int* __restrict__ labels, uint8_t* __restri
     if (i < n) { const int v = labels[i]; out[i] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 }
 
-// ---------------------------------------------------------------- medianBlur(5) on the depth image (values are integers, so the float median == u16 median)
-// (the CalOccluded kernels take the frame from blockIdx.z: the pipeline runs them once for all frames of a step)
-// A thread makes MED_ROWS outputs of one column: the 5 x (MED_ROWS + 4) window is loaded once (10 loads per pixel instead of 25) and a launch has a quarter of the waves.
-#define MED_ROWS 4
-__global__ void k_median5_u16(const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, int w, int h) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y0 = blockIdx.y * MED_ROWS;
-    if (x >= w) return;
-    src += (size_t)blockIdx.z * w * h; dst += (size_t)blockIdx.z * w * h;
-    int xs[5];
-    #pragma unroll
-    for (int dx = -2; dx <= 2; dx++) xs[dx + 2] = min(max(x + dx, 0), w - 1);
-    int win[MED_ROWS + 4][5];
-    #pragma unroll
-    for (int j = 0; j < MED_ROWS + 4; j++) {
-        const uint16_t* r = src + (size_t)min(max(y0 - 2 + j, 0), h - 1) * w;
-        #pragma unroll
-        for (int k = 0; k < 5; k++) win[j][k] = r[xs[k]];
-    }
-    #pragma unroll
-    for (int q = 0; q < MED_ROWS; q++) {
-        const int y = y0 + q;
-        if (y >= h) break;
-        int p[25];
-        #pragma unroll
-        for (int j = 0; j < 5; j++) {
-            #pragma unroll
-            for (int k = 0; k < 5; k++) p[j * 5 + k] = win[q + j][k];
-        }
-        // 99 compare-exchanges instead of the 625 comparisons of a rank count (median25_net.inc)
-        #define S(a, b) { const int lo_ = min(p[a], p[b]), hi_ = max(p[a], p[b]); p[a] = lo_; p[b] = hi_; }
-        #include "median25_net.inc"
-        #undef S
-        dst[y * w + x] = (uint16_t)p[12];
-    }
-}
-// (16-byte loads, eight samples each: with one 2-byte load per lane and turn the kernel took 0.5 ms for the 39 MB of a 64-frame round and 3 % of a step's wave cycles)
-__global__ void k_max_u16(const uint16_t* __restrict__ src, int n, unsigned* __restrict__ out, int out_stride, int wide) {
-    src += (size_t)blockIdx.y * n; out += (size_t)blockIdx.y * out_stride;
-    unsigned m = 0;
-    const int n8 = wide ? n >> 3 : 0; const uint4* s8 = reinterpret_cast<const uint4*>(src);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += gridDim.x * blockDim.x) {
-        const uint4 v = s8[i];
-        m = max(m, max(max(max(v.x & 0xffffu, v.x >> 16), max(v.y & 0xffffu, v.y >> 16)), max(max(v.z & 0xffffu, v.z >> 16), max(v.w & 0xffffu, v.w >> 16))));
-    }
-    for (int i = (n8 << 3) + blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) m = max(m, (unsigned)src[i]);      // n % 8 samples at the end
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
-// 5x5 max-difference depth edge + valid-area mask (DD:443-482); the 3-px frame is left 0 in both outputs
-#define GE_ROWS 4
-__global__ void k_grad_edge(const uint16_t* __restrict__ filt, const unsigned* __restrict__ dmax, uint8_t* __restrict__ edge,
-                            uint8_t* __restrict__ total_area, int w, int h, float depthScale, int dmax_stride) {
-    const int col = blockIdx.x * blockDim.x + threadIdx.x, row0 = blockIdx.y * GE_ROWS;
-    if (col >= w) return;
-    { const size_t fo = (size_t)blockIdx.z * w * h; filt += fo; edge += fo; total_area += fo; dmax += (size_t)blockIdx.z * dmax_stride; }
-    const bool col_in = col >= 3 && col < w - 3;
-    // the 5 x (GE_ROWS + 4) window of this column's rows, loaded once (rows / columns outside the image are never used: the 3-pixel frame has no window)
-    float win[GE_ROWS + 4][5];
-    #pragma unroll
-    for (int j = 0; j < GE_ROWS + 4; j++) {
-        const int r = row0 - 2 + j; const bool in = col_in && r >= 0 && r < h;
-        #pragma unroll
-        for (int k = 0; k < 5; k++) win[j][k] = in ? (float)filt[r * w + col + k - 2] : 0.f;
-    }
-    const float depth_max = (float)(*dmax);
-    #pragma unroll
-    for (int q = 0; q < GE_ROWS; q++) {
-        const int row = row0 + q;
-        if (row >= h) break;
-        uint8_t e = 0, t = 0;
-        if (row >= 3 && row < h - 3 && col_in) {
-            const float depth1 = win[q + 2][2];
-            if (depth1 > 0.0f && depth1 / depthScale < 6.0f) t = 255;
-            float val_max = 0.0f;
-            #pragma unroll
-            for (int i = -2; i <= 2; i++)
-                #pragma unroll
-                for (int j = -2; j <= 2; j++) {
-                    const float nb = win[q + 2 + i][j + 2];
-                    if ((depth1 - nb) > depth_max * 0.5f) continue;
-                    const float a = fabsf(depth1 - nb);
-                    val_max = fabsf(val_max) > a ? fabsf(val_max) : a;
-                }
-            if (val_max > depth1 * 0.03f && val_max > 400.0f) e = 255;
-        }
-        edge[row * w + col] = e; total_area[row * w + col] = t;
-    }
-}
-
-// ---------------------------------------------------------------- morphology with an elliptical element (max / min over in-image pixels)
-__global__ void k_morph(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int w, int h, MorphElem E, int is_dilate) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= w) return;
-    src += (size_t)blockIdx.z * w * h; dst += (size_t)blockIdx.z * w * h;
-    int m = is_dilate ? 0 : 255;
-    for (int i = 0; i < E.n; i++) {
-        const int yy = y + i - E.ay;
-        if (yy < 0 || yy >= h || E.j2[i] <= E.j1[i]) continue;
-        const uint8_t* r = src + (size_t)yy * w;
-        const int xa = max(x + E.j1[i] - E.ax, 0), xb = min(x + E.j2[i] - E.ax, w);
-        for (int xx = xa; xx < xb; xx++) m = is_dilate ? max(m, (int)r[xx]) : min(m, (int)r[xx]);
-    }
-    dst[y * w + x] = (uint8_t)m;
-}
-
-// The 4 x 4 ellipse of CalOccluded's MORPH_OPEN ({(0, 0)} in the row two above, columns -2 .. +1 in the rows -1, 0, +1), a thread walking MO_ROWS rows of one column: four
-// byte loads per source row serve every output row that sees it (5.5 loads per pixel instead of 13) and a launch has an eighth of the waves.  Same values as k_morph.
-#define MO_ROWS 8
-__global__ void k_morph_e4(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int w, int h, int is_dilate) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y0 = blockIdx.y * MO_ROWS;
-    if (x >= w) return;
-    src += (size_t)blockIdx.z * w * h; dst += (size_t)blockIdx.z * w * h;
-    const int none = is_dilate ? 0 : 255;
-    auto op = [&](int a, int b) { return is_dilate ? max(a, b) : min(a, b); };
-    int own[MO_ROWS + 3], four[MO_ROWS + 3];                 // source row y0 - 2 + j: the pixel itself, the extreme of its columns x - 2 .. x + 1 (inside the image)
-    #pragma unroll
-    for (int j = 0; j < MO_ROWS + 3; j++) {
-        const int yy = y0 - 2 + j;
-        own[j] = none; four[j] = none;
-        if (yy >= 0 && yy < h) {
-            const uint8_t* r = src + (size_t)yy * w;
-            const int c = r[x]; own[j] = c; int m = c;
-            if (x >= 2) m = op(m, (int)r[x - 2]);
-            if (x >= 1) m = op(m, (int)r[x - 1]);
-            if (x + 1 < w) m = op(m, (int)r[x + 1]);
-            four[j] = m;
-        }
-    }
-    #pragma unroll
-    for (int q = 0; q < MO_ROWS; q++) {
-        const int y = y0 + q;
-        if (y >= h) break;
-        dst[y * w + x] = (uint8_t)op(op(own[q], four[q + 1]), op(four[q + 2], four[q + 3]));
-    }
-}
-// ---------------------------------------------------------------- PEAC initial block statistics (16 x 16 blocks): one wave per SEVEN blocks.
-// Phase 1, all lanes: the points of the wave's blocks (x, y, z as the FLOATS the reference forms before it widens them) and each block's validity (a block with a missing
-// point or a depth jump to the right / lower neighbour is dropped as a whole, so the order of that test is free) go to LDS.  Phase 2: the nine FP64 moments of a block are
-// accumulated by nine lanes, each adding its 256 terms in the reference's row-major order (bit-exact with a sequential CPU loop) -- 63 lanes = 7 blocks x 9 moments, and a term
-// is two LDS reads, two conversions and one product.  (One block per wave with every term's point re-derived inside the sequential loop -- two float divisions per term on 9 of
-// 64 lanes -- was 6.9 % of ALL VALU cycles of a step and 2.8 % of its CU-busy cycles: profiles/r04/pmc_by_kernel.txt.)
-#define PEAC_BW 16
-#define PEAC_BPW 7                                                  // blocks per wave
-__global__ void __launch_bounds__(64) k_peac_block_stats(const uint16_t* __restrict__ depth, int w, int h, int Nw, int nblk, float fx, float fy, float cx, float cy,
-                                                         float depthScale, double depthAlpha, double depthChangeTol, PeacBlockStats* __restrict__ out) {
-    __shared__ float pt[PEAC_BPW][3][PEAC_BW * PEAC_BW];            // x, y, z per point of the wave's blocks
-    const int lane = threadIdx.x, blk0 = blockIdx.x * PEAC_BPW;
-    depth += (size_t)blockIdx.y * w * h; out += (size_t)blockIdx.y * nblk;
-    const float inv = 1.0f / depthScale;
-    auto zat = [&](int i, int j, float& zf) -> bool { const float d = (float)depth[i * w + j]; if (d < 1e-3f) return false; zf = d * inv; return true; };
-    unsigned validbits = 0;                                         // wave-uniform
-    for (int b = 0; b < PEAC_BPW; b++) {
-        const int blk = blk0 + b;
-        if (blk >= nblk) break;
-        const int by = blk / Nw, bx = blk - by * Nw;
-        bool ok = true;
-        #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int p = k * 64 + lane, i = by * PEAC_BW + (p >> 4), j = bx * PEAC_BW + (p & 15);
-            float zf = 0.f, zn;
-            if (!zat(i, j, zf)) ok = false;
-            else {
-                const double z = (double)zf, tol = depthAlpha * fabs(z) + depthChangeTol;
-                if (j + 1 < w && zat(i, j + 1, zn) && fabs(z - (double)zn) > tol) ok = false;
-                if (i + 1 < h && zat(i + 1, j, zn) && fabs(z - (double)zn) > tol) ok = false;
-            }
-            pt[b][0][p] = (j - cx) * zf / fx; pt[b][1][p] = (i - cy) * zf / fy; pt[b][2][p] = zf;
-        }
-        if (__all(ok)) validbits |= 1u << b;
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);                             // lgkmcnt(0): the wave's own LDS stores (wave-synchronous, no barrier needed)
-    __builtin_amdgcn_wave_barrier();
-    const int b = lane / 9, m = lane - 9 * b, blk = blk0 + b;
-    if (b >= PEAC_BPW || blk >= nblk) return;
-    const bool valid = (validbits >> b) & 1u;
-    // lane (b, m) accumulates moment m of block b: sx sy sz sxx syy szz sxy syz sxz = the sums of A, or of A x B
-    const int ia = (m == 1 || m == 4 || m == 7) ? 1 : (m == 2 || m == 5) ? 2 : 0, ib = (m == 3) ? 0 : (m == 4 || m == 6) ? 1 : 2;      // (x, y, z) = (0, 1, 2): xx yy zz xy yz xz
-    const bool single = m < 3;
-    double acc = 0;
-    if (valid) {
-        const float* A = pt[b][ia]; const float* B = pt[b][ib];
-        #pragma unroll 4
-        for (int p = 0; p < PEAC_BW * PEAC_BW; p++) {
-            const double av = (double)A[p], bv = (double)B[p];
-            acc += single ? av : av * bv;
-        }
-    }
-    double* o = &out[blk].sx; o[m] = acc;
-    if (m == 0) { out[blk].N = valid ? PEAC_BW * PEAC_BW : 0; out[blk].valid = valid ? 1 : 0; }
-}
-// Plane fit of every valid block (host/peac_fit.hpp, the host's own function): the 1200 (640 x 480) to 3600 (1280 x 720) initial nodes are a third of all the
-// fits of a frame's graph clustering (~1 us each on a host core: a 3 x 3 Jacobi iteration).  One thread per block.
-__global__ void k_peac_block_fit(PeacBlockStats* __restrict__ blocks, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    PeacBlockStats& S = blocks[i];
-    int fitted = 0;
-    if (S.valid && S.N >= 4) { double c[3], nrm[3], mse; peac_fit(&S.sx, S.N, c, nrm, mse); S.mse = mse; for (int k = 0; k < 3; k++) { S.center[k] = c[k]; S.normal[k] = nrm[k]; } fitted = 1; }
-    S.fitted = fitted; S.pad = 0;
-}
-
-// ---------------------------------------------------------------- imgDepth/depth_max*255 -> 8U (DD:765-768): u16 * (float)((1/max)*255), cvRound, saturate
-__global__ void k_depth_norm(const uint16_t* __restrict__ depth, const unsigned* __restrict__ dmax, uint8_t* __restrict__ out, int n, int dmax_stride) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    depth += (size_t)blockIdx.y * n; out += (size_t)blockIdx.y * n; dmax += (size_t)blockIdx.y * dmax_stride;
-    const float a = (float)((1.0 / (double)(*dmax)) * 255);
-    int v = d_cvRound((float)depth[i] * a);
-    v = min(max(v, 0), 65535);
-    out[i] = (uint8_t)min(v, 255);
-}
-
-// ---------------------------------------------------------------- region-adjacency statistics (SegAndMergeV2 RAG build + cal_hist inputs)
-// Input: bit planes [3][C][h*wpr] (img = piece mask, dil = 7-dilated piece, lj = "lianjie" fake-edge mask), 64 px per word.
-// Each lane takes one pixel; the 64 lanes of a wavefront share the plane words (broadcast loads) and assemble the pixel's
-// membership words.  One pass produces overlap[i][j] = |dil_i & dil_j|, overlapPlane[i][j] = |dil_i & dil_j & occ2|,
-// ljOverlap[i][j], ljArea[i] and hist[i][v] = 256-bin histogram of the normalised depth over img_i (value 255 dropped:
-// calcHist ranges {0,255}).  Counters are privatised in LDS when they fit (C <= 64) and flushed once per workgroup.
-// (body shared by the per-frame kernel and the frame-indexed one: the three plane sets as pointers of their own, the workgroup's index and count among
-// those of its frame, and the LDS block)
-template <bool USE_LDS>
-__device__ __forceinline__ void rag_stats_body(const unsigned long long* __restrict__ p_img, const unsigned long long* __restrict__ p_dil, const unsigned long long* __restrict__ p_lj,
-                                               int C, int w, int h, int wpr, const uint8_t* __restrict__ occ2, const uint8_t* __restrict__ depthN,
-                                               int* __restrict__ overlap, int* __restrict__ overlapPlane, int* __restrict__ ljOverlap,
-                                               int* __restrict__ ljArea, int* __restrict__ hist, int* sm, int block, int nblocks) {
-    int *lh = hist, *lo = overlap, *lp = overlapPlane, *ll = ljOverlap, *la = ljArea;
-    if (USE_LDS) {
-        lh = sm; lo = lh + C * 256; lp = lo + C * C; ll = lp + C * C; la = ll + C * C;
-        const int total = C * 256 + 3 * C * C + C;
-        for (int i = threadIdx.x; i < total; i += 256) sm[i] = 0;
-        __syncthreads();
-    }
-    const int NW = (C + 63) >> 6;
-    const size_t pw = (size_t)h * wpr;           // words per plane
-    const int n = w * h;
-    for (int i = block * 256 + threadIdx.x; i < n; i += nblocks * 256) {
-        const int y = i / w, x = i - y * w; const size_t widx = (size_t)y * wpr + (x >> 6); const int bit = x & 63;
-        // The 64 lanes of a wave sit on the 64 pixels of ONE plane word (w % 64 == 0 and every stride is a multiple of 64): lane c fetches
-        // the three words of piece c once, and each lane then picks its own bit out of the words broadcast with readlane -- 3 loads per
-        // 64 pieces instead of 3*C dependent loads per pixel, which is what this kernel's time used to be.
-        unsigned long long mi[4] = {0, 0, 0, 0}, md[4] = {0, 0, 0, 0}, ml[4] = {0, 0, 0, 0};
-        const int lane = threadIdx.x & 63;
-        #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            if (q >= NW) break;
-            const int c = (q << 6) + lane;
-            unsigned long long wi = 0, wd = 0, wl = 0;
-            if (c < C) { wi = p_img[(size_t)c * pw + widx]; wd = p_dil[(size_t)c * pw + widx]; wl = p_lj[(size_t)c * pw + widx]; }
-            const int cnt = min(64, C - (q << 6));
-            // lane `bit` wants bit `bit` of piece cc's words as bit cc of its own: the half of the word the lane's pixel lies in is fixed per lane, the half of the result per cc --
-            // 32-bit operations throughout (three instead of six per plane and piece: the 64-bit shifts by a lane-varying and by a uniform count were two passes each)
-            const bool upper = bit >= 32; const unsigned sh = (unsigned)bit & 31u;
-            unsigned ri[2] = {0u, 0u}, rd[2] = {0u, 0u}, rl[2] = {0u, 0u};
-            #pragma unroll
-            for (int hh = 0; hh < 2; hh++) {
-                const int c0 = hh * 32, c1 = min(cnt, c0 + 32);
-                for (int cc = c0; cc < c1; cc++) {
-                    const unsigned alo = (unsigned)__builtin_amdgcn_readlane((int)wi, cc), ahi = (unsigned)__builtin_amdgcn_readlane((int)(wi >> 32), cc);
-                    const unsigned dlo = (unsigned)__builtin_amdgcn_readlane((int)wd, cc), dhi = (unsigned)__builtin_amdgcn_readlane((int)(wd >> 32), cc);
-                    const unsigned llo = (unsigned)__builtin_amdgcn_readlane((int)wl, cc), lhi = (unsigned)__builtin_amdgcn_readlane((int)(wl >> 32), cc);
-                    const unsigned k = (unsigned)(cc - c0);
-                    ri[hh] |= (((upper ? ahi : alo) >> sh) & 1u) << k; rd[hh] |= (((upper ? dhi : dlo) >> sh) & 1u) << k; rl[hh] |= (((upper ? lhi : llo) >> sh) & 1u) << k;
-                }
-            }
-            mi[q] = ((unsigned long long)ri[1] << 32) | ri[0]; md[q] = ((unsigned long long)rd[1] << 32) | rd[0]; ml[q] = ((unsigned long long)rl[1] << 32) | rl[0];
-        }
-        const int dv = depthN[i];
-        if (dv < 255) {
-            #pragma unroll
-            for (int q = 0; q < 4; q++) { if (q >= NW) break; unsigned long long m = mi[q]; while (m) { const int c = (q << 6) + __ffsll((long long)m) - 1; m &= m - 1; atomicAdd(&lh[c * 256 + dv], 1); } }
-        }
-        int nd = 0, nl = 0;
-        #pragma unroll
-        for (int q = 0; q < 4; q++) { nd += __popcll(md[q]); nl += __popcll(ml[q]); }
-        if (nd >= 2) {
-            const bool pl = occ2[i] != 0;
-            for (int ci = 0; ci < C; ci++) { if (!((md[ci >> 6] >> (ci & 63)) & 1ull)) continue;
-                for (int cj = ci + 1; cj < C; cj++) { if (!((md[cj >> 6] >> (cj & 63)) & 1ull)) continue; atomicAdd(&lo[ci * C + cj], 1); if (pl) atomicAdd(&lp[ci * C + cj], 1); } }
-        }
-        if (nl >= 1) {
-            for (int ci = 0; ci < C; ci++) { if (!((ml[ci >> 6] >> (ci & 63)) & 1ull)) continue; atomicAdd(&la[ci], 1);
-                for (int cj = ci + 1; cj < C; cj++) { if (!((ml[cj >> 6] >> (cj & 63)) & 1ull)) continue; atomicAdd(&ll[ci * C + cj], 1); } }
-        }
-    }
-    if (USE_LDS) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < C * 256; i += 256) if (lh[i]) atomicAdd(&hist[i], lh[i]);
-        for (int i = threadIdx.x; i < C * C; i += 256) { if (lo[i]) atomicAdd(&overlap[i], lo[i]); if (lp[i]) atomicAdd(&overlapPlane[i], lp[i]); if (ll[i]) atomicAdd(&ljOverlap[i], ll[i]); }
-        for (int i = threadIdx.x; i < C; i += 256) if (la[i]) atomicAdd(&ljArea[i], la[i]);
-    }
-}
-template <bool USE_LDS>
-__global__ void __launch_bounds__(256) k_rag_stats(const unsigned long long* __restrict__ planes, int C, int w, int h, int wpr,
-                                                   const uint8_t* __restrict__ occ2, const uint8_t* __restrict__ depthN,
-                                                   int* __restrict__ overlap, int* __restrict__ overlapPlane, int* __restrict__ ljOverlap,
-                                                   int* __restrict__ ljArea, int* __restrict__ hist) {
-    extern __shared__ int sm[];
-    const size_t pw = (size_t)h * wpr;
-    rag_stats_body<USE_LDS>(planes, planes + (size_t)C * pw, planes + (size_t)2 * C * pw, C, w, h, wpr, occ2, depthN, overlap, overlapPlane, ljOverlap, ljArea, hist, sm, blockIdx.x, gridDim.x);
-}
-// One frame of every stream of a k-means group: blockIdx.y = the frame's record (depth.hpp), blockIdx.x = one of the few workgroups of that frame -- the
-// parallelism comes from the frames, so a frame's counters are zeroed and flushed by 8 - 32 workgroups instead of 128.  The launch's dynamic LDS holds the counters
-// of the chunk's largest C <= 64; a frame with more pieces counts in global memory (uniform per workgroup).  Counts are integers: any partition gives the same numbers.
-__global__ void __launch_bounds__(256) k_rag_stats_frames(const RagRec* __restrict__ recs, const unsigned long long* __restrict__ in, const unsigned long long* __restrict__ dil,
-                                                          int* __restrict__ res, int w, int h, int wpr) {
-    extern __shared__ int sm[];
-    const RagRec R = recs[blockIdx.y];
-    const int C = R.C; const size_t pw = (size_t)h * wpr;
-    const unsigned long long* p_img = in + R.plane_off; const unsigned long long* p_lj = p_img + (size_t)C * pw; const unsigned long long* p_dil = dil + R.plane_off / 2;
-    int* ov = res + R.res_off; int* ovp = ov + C * C; int* lj = ovp + C * C; int* la = lj + C * C; int* hs = la + C;
-    if (C <= 64) rag_stats_body<true>(p_img, p_dil, p_lj, C, w, h, wpr, R.occ2, R.depthN, ov, ovp, lj, la, hs, sm, blockIdx.x, gridDim.x);
-    else rag_stats_body<false>(p_img, p_dil, p_lj, C, w, h, wpr, R.occ2, R.depthN, ov, ovp, lj, la, hs, sm, blockIdx.x, gridDim.x);
-}
-
-// Elliptical dilation of bit planes (64 pixels per word), dst(x, y) = OR over the element of src(x + j - ax, y + i - ay) with positions
-// outside the image ignored: the 7x7 dilation of every piece of SegAndMergeV2 (DD:760-ish "imgEachClusterDilate") for the region-adjacency
-// statistics.  One thread per output word; a row of the element is a run of <= 15 shifts over a three-word window.
-// zero / nzero (optional): a block of ints cleared on the way -- the accumulators of k_rag_stats, which follows on the same stream (one fill launch less per frame).
-__device__ __forceinline__ unsigned long long dilate_plane_word(const unsigned long long* __restrict__ sp, int y, int k, int wpr, int H, const MorphElem& e, unsigned long long tail_mask) {
-    unsigned long long acc = 0ull;
-    for (int i = 0; i < e.n; i++) {
-        const int ys = y + i - e.ay;
-        if (ys < 0 || ys >= H || e.j2[i] <= e.j1[i]) continue;
-        const unsigned long long* r = sp + (size_t)ys * wpr;
-        const unsigned long long cur = r[k], prev = k > 0 ? r[k - 1] : 0ull, next = k + 1 < wpr ? r[k + 1] : 0ull;
-        for (int j = e.j1[i]; j < e.j2[i]; j++) {
-            const int t = j - e.ax;                      // dst bit x takes src bit x + t
-            if (t == 0) acc |= cur;
-            else if (t > 0) acc |= (cur >> t) | (next << (64 - t));
-            else acc |= (cur << (-t)) | (prev >> (64 + t));
-        }
-    }
-    if (k == wpr - 1) acc &= tail_mask;
-    return acc;
-}
-__global__ void k_dilate_planes(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst, int nplanes, int wpr, int H, MorphElem e,
-                                unsigned long long tail_mask, int* __restrict__ zero, int nzero) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, pw = (size_t)wpr * H;
-    for (size_t z = idx; z < (size_t)nzero; z += (size_t)gridDim.x * blockDim.x) zero[z] = 0;
-    if (idx >= pw * nplanes) return;
-    const int c = (int)(idx / pw), rem = (int)(idx - (size_t)c * pw), y = rem / wpr, k = rem - y * wpr;
-    dst[idx] = dilate_plane_word(src + (size_t)c * pw, y, k, wpr, H, e, tail_mask);
-}
-// the same for one frame of every stream of a group: blockIdx.y = the frame's record, the grid's x extent covers the chunk's largest C; every frame's
-// result block is cleared on the way
-__global__ void k_dilate_planes_frames(const RagRec* __restrict__ recs, const unsigned long long* __restrict__ in, unsigned long long* __restrict__ dil, int* __restrict__ res,
-                                       int wpr, int H, MorphElem e, unsigned long long tail_mask) {
-    const RagRec R = recs[blockIdx.y];
-    const int C = R.C;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, pw = (size_t)wpr * H;
-    const size_t nzero = (size_t)3 * C * C + C + (size_t)C * 256;
-    int* zero = res + R.res_off;
-    for (size_t z = idx; z < nzero; z += (size_t)gridDim.x * blockDim.x) zero[z] = 0;
-    if (idx >= pw * C) return;
-    const int c = (int)(idx / pw), rem = (int)(idx - (size_t)c * pw), y = rem / wpr, k = rem - y * wpr;
-    dil[R.plane_off / 2 + idx] = dilate_plane_word(in + R.plane_off + (size_t)c * pw, y, k, wpr, H, e, tail_mask);
-}
-int launch_dilate_planes(hipStream_t s, const unsigned long long* src, unsigned long long* dst, int nplanes, int w, int h, int n, int* zero, int nzero) {
-    const int wpr = (w + 63) / 64; const size_t total = (size_t)wpr * h * nplanes;
-    const unsigned long long tm = (w & 63) ? ((1ull << (w & 63)) - 1) : ~0ull;
-    hipLaunchKernelGGL(k_dilate_planes, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, dst, nplanes, wpr, h, make_ellipse(n), tm, zero, zero ? nzero : 0);
-    return SIND_OK;
-}
-
 // ---------------------------------------------------------------- launchers
 int launch_depth_half(hipStream_t s, const uint16_t* src, uint16_t* dst, int dw, int dh, int B, size_t src_stride, size_t dst_stride) {
     hipLaunchKernelGGL(k_depth_half, dim3(divup(dw, 128), dh, B), dim3(128), 0, s, src, dst, dw, dh, src_stride, dst_stride); return SIND_OK; }
@@ -1044,78 +674,5 @@ int debug_seqsum(hipStream_t s, const float* x_dev, int n, int* scratch_dev /* 2
 }
 int launch_labels_to_u8(hipStream_t s, const int* labels, uint8_t* out, int n, int B, size_t lab_stride, size_t out_stride) {
     hipLaunchKernelGGL(k_labels_to_u8, dim3(divup(n, 256), B), dim3(256), 0, s, labels, out, n, lab_stride, out_stride); return SIND_OK; }
-// B frames per launch (frame b at offset b * w * h of every image argument; maxima at out + b * out_stride)
-int launch_median5(hipStream_t s, const uint16_t* src, uint16_t* dst, int w, int h, int B) { hipLaunchKernelGGL(k_median5_u16, dim3(divup(w, 64), divup(h, MED_ROWS), B), dim3(64), 0, s, src, dst, w, h); return SIND_OK; }
-int launch_max_u16(hipStream_t s, const uint16_t* src, int n, unsigned* out, int B, int out_stride) {
-    if (B == 1 || out_stride == 1) HIP_TRY(hipMemsetAsync(out, 0, (size_t)B * sizeof(unsigned), s));
-    else for (int b = 0; b < B; b++) HIP_TRY(hipMemsetAsync(out + (size_t)b * out_stride, 0, sizeof(unsigned), s));
-    // 16-byte loads need every image of the launch to start on a 16-byte boundary: the base pointer aligned (a per-frame pointer into a batch buffer is only when the frame
-    // size is a multiple of 8 samples) and, for a batch, a multiple of 8 samples per image; anything else takes the 2-byte loop
-    const int wide = ((uintptr_t)src % 16 == 0 && (B == 1 || n % 8 == 0)) ? 1 : 0;
-    hipLaunchKernelGGL(k_max_u16, dim3(std::max(1, std::min(divup(n, 8 * 256), 64)), B), dim3(256), 0, s, src, n, out, out_stride, wide); return SIND_OK; }
-int launch_grad_edge(hipStream_t s, const uint16_t* filt, const unsigned* dmax, uint8_t* edge, uint8_t* total_area, int w, int h, float depthScale, int B, int dmax_stride) {
-    hipLaunchKernelGGL(k_grad_edge, dim3(divup(w, 128), divup(h, GE_ROWS), B), dim3(128), 0, s, filt, dmax, edge, total_area, w, h, depthScale, dmax_stride); return SIND_OK; }
-MorphElem make_ellipse(int n) {
-    MorphElem e; e.n = n; e.ax = n / 2; e.ay = n / 2;
-    for (int i = 0; i < MORPH_MAX; i++) { e.j1[i] = 0; e.j2[i] = 0; }
-    if (n == 1) { e.j2[0] = 1; return e; }
-    const int r = n / 2, c = n / 2; const double inv_r2 = r ? 1. / ((double)r * r) : 0;
-    for (int i = 0; i < n; i++) {
-        const int dy = i - r;
-        if (std::abs(dy) <= r) { const int dx = (int)std::lrint(c * std::sqrt((r * r - dy * dy) * inv_r2)); e.j1[i] = std::max(c - dx, 0); e.j2[i] = std::min(c + dx + 1, n); }
-    }
-    return e;
-}
-int launch_morph(hipStream_t s, const uint8_t* src, uint8_t* dst, int w, int h, int n, bool dilate, int B) {
-    if (n == 4) { hipLaunchKernelGGL(k_morph_e4, dim3(divup(w, 128), divup(h, MO_ROWS), B), dim3(128), 0, s, src, dst, w, h, dilate ? 1 : 0); return SIND_OK; }
-    hipLaunchKernelGGL(k_morph, dim3(divup(w, 128), h, B), dim3(128), 0, s, src, dst, w, h, make_ellipse(n), dilate ? 1 : 0); return SIND_OK; }
-int launch_peac_block_stats(hipStream_t s, const uint16_t* depth, int w, int h, int bw, int bh, float fx, float fy, float cx, float cy, float depthScale, PeacBlockStats* out, int B) {
-    if (bw != PEAC_BW || bh != PEAC_BW) { sind_set_error("peac_block_stats: %d x %d blocks (only %d x %d)", bw, bh, PEAC_BW, PEAC_BW); return SIND_E_ARG; }
-    const int nb = (w / bw) * (h / bh);
-    hipLaunchKernelGGL(k_peac_block_stats, dim3(divup(nb, PEAC_BPW), B), dim3(64), 0, s, depth, w, h, w / bw, nb, fx, fy, cx, cy, depthScale, 0.04, 0.02 * 1000, out);
-    hipLaunchKernelGGL(k_peac_block_fit, dim3(divup(nb * B, 64)), dim3(64), 0, s, out, nb * B); return SIND_OK; }
-int launch_depth_norm(hipStream_t s, const uint16_t* depth, const unsigned* dmax, uint8_t* out, int n, int B, int dmax_stride) {
-    hipLaunchKernelGGL(k_depth_norm, dim3(divup(n, 256), B), dim3(256), 0, s, depth, dmax, out, n, dmax_stride); return SIND_OK; }
-int launch_rag_stats(hipStream_t s, const unsigned long long* planes, int C, int w, int h, int wpr, const uint8_t* occ2, const uint8_t* depthN,
-                     int* overlap, int* overlapPlane, int* ljOverlap, int* ljArea, int* hist, bool already_zero) {
-    if (C < 1 || C > 254) { sind_set_error("rag_stats: %d pieces unsupported (1..254)", C); return SIND_E_ARG; }
-    if (already_zero) {}                                  // cleared by the dilation kernel ahead of this one on the stream
-    else if (overlapPlane == overlap + C * C && ljOverlap == overlapPlane + C * C && ljArea == ljOverlap + C * C && hist == ljArea + C)
-        HIP_TRY(hipMemsetAsync(overlap, 0, ((size_t)3 * C * C + C + (size_t)C * 256) * sizeof(int), s));        // the caller's five outputs are one block: one fill
-    else {
-        HIP_TRY(hipMemsetAsync(overlap, 0, (size_t)C * C * sizeof(int), s)); HIP_TRY(hipMemsetAsync(overlapPlane, 0, (size_t)C * C * sizeof(int), s));
-        HIP_TRY(hipMemsetAsync(ljOverlap, 0, (size_t)C * C * sizeof(int), s)); HIP_TRY(hipMemsetAsync(ljArea, 0, (size_t)C * sizeof(int), s));
-        HIP_TRY(hipMemsetAsync(hist, 0, (size_t)C * 256 * sizeof(int), s));
-    }
-    if (C <= 64) {
-        const size_t shm = ((size_t)C * 256 + 3 * (size_t)C * C + C) * sizeof(int);      // <= 64 KB + 48 KB + 256 B of the 160 KB LDS
-        static SindPerDeviceInit attr_init;       // the pool's workers call this concurrently; once per device
-        HIP_TRY(attr_init.run([] { return hipFuncSetAttribute((const void*)k_rag_stats<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024); }));
-        hipLaunchKernelGGL(k_rag_stats<true>, dim3(128), dim3(256), shm, s, planes, C, w, h, wpr, occ2, depthN, overlap, overlapPlane, ljOverlap, ljArea, hist);
-    } else {
-        hipLaunchKernelGGL(k_rag_stats<false>, dim3(256), dim3(256), 0, s, planes, C, w, h, wpr, occ2, depthN, overlap, overlapPlane, ljOverlap, ljArea, hist);
-    }
-    return SIND_OK;
-}
-int launch_rag_frames(hipStream_t s, const RagRec* recs_dev, const RagRec* host, int n, const unsigned long long* in, size_t in_words, unsigned long long* dil, int* res, size_t res_ints, int w, int h) {
-    if (n < 1 || n > 65535 || !recs_dev || !host || !in || !dil || !res || w < 64 || w % 64 != 0 || h < 1) { sind_set_error("launch_rag_frames: %d records, %d x %d", n, w, h); return SIND_E_ARG; }
-    const int wpr = w / 64; const size_t pw = (size_t)h * wpr;
-    int maxC = 0, maxLds = 0;
-    for (int i = 0; i < n; i++) {
-        const RagRec& R = host[i];
-        if (R.C < 1 || R.C > 254 || !R.occ2 || !R.depthN || (R.plane_off & 1) || R.plane_off + (size_t)2 * R.C * pw > in_words || R.res_off + rag_result_ints(R.C) > res_ints) {
-            sind_set_error("launch_rag_frames: record %d (%d pieces) has a null pointer or leaves its slab", i, R.C); return SIND_E_ARG; }
-        maxC = std::max(maxC, R.C); if (R.C <= 64) maxLds = std::max(maxLds, R.C);
-    }
-    hipLaunchKernelGGL(k_dilate_planes_frames, dim3((unsigned)((pw * maxC + 255) / 256), n), dim3(256), 0, s, recs_dev, in, dil, res, wpr, h, make_ellipse(7), ~0ull);
-    // workgroups per frame: the frame's counters (C = 20: 6 340) are zeroed and flushed once per workgroup, each of which should have many more pixels than that --
-    // 8 at 64 frames (150 pixels per thread at 640 x 480), up to 32 for a small chunk, no more than the frame has 256-pixel groups
-    const int per_frame = std::max(1, std::min(std::max(8, std::min(32, 512 / n)), (int)((size_t)w * h / 256)));
-    const size_t shm = rag_result_ints(maxLds) * sizeof(int);
-    static SindPerDeviceInit attr_init;
-    HIP_TRY(attr_init.run([] { return hipFuncSetAttribute((const void*)k_rag_stats_frames, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024); }));
-    hipLaunchKernelGGL(k_rag_stats_frames, dim3(per_frame, n), dim3(256), shm, s, recs_dev, in, dil, res, w, h, wpr);
-    return SIND_OK;
-}
 
 }  // namespace sind

@@ -2,6 +2,7 @@
 // per-stream tail (k-means, depth edges, PEAC, split/merge re-clustering, residual thresholds, mask fusion).
 #pragma once
 #include <algorithm>
+#include <chrono>
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -14,6 +15,8 @@
 namespace sind {
 
 struct DynaConfig { int W = 640, H = 480; float fx = 0, fy = 0, cx = 0, cy = 0, depthScale = 5000.f; int device = 0; };
+
+static inline double tick_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- state-free front for B frames at once (reference DynaDetect.cc:1386-1392 gray, :1033-1147 flow) ------------------
 class DynaFront {
@@ -53,10 +56,21 @@ struct OccCtx { BitImg occ, totalArea; std::vector<PtI> endPoints; std::unique_p
 // ---- GPU half of CalOccluded for a chunk of frames at once (state free: depth only).  Host-side results of one frame: OccGpuOut.
 struct OccGpuOut { const uint8_t* edge; const uint8_t* total; const PeacBlockStats* blocks;
                    uint8_t* occ2_stage = nullptr; hipEvent_t occ2_event = nullptr; };      // optional: page-locked N bytes for the occ2 upload and the event recorded behind it
-struct OccBatch {
+// The one statement of that half: the device workspaces for up to `cap` frames and the launches.  Frames at depth_dev + b * W * H; maxima of the filtered frames in
+// umax[0, cap), of the raw frames (taken for the normalisation only) in umax[cap, 2 * cap).  Launches only (and the maxima's fills): no copy back, no wait, no allocation.
+struct OccFront {
     DynaConfig cfg; int cap = 0;
     DevBuf<uint16_t> filt; DevBuf<uint8_t> edge, edgeTmp, total; DevBuf<unsigned> umax; DevBuf<PeacBlockStats> blocks;
-    int init(const DynaConfig& c, int chunk);
+    int init(const DynaConfig& c, int cap, bool block_stats = true);      // block_stats = false: no PEAC block statistics wanted (the parity entry, which has no intrinsics)
+    // in two parts for whoever wants the edge before its opening: depthN_dev != nullptr: raw maximum + 8-bit normalised depth; then median 5, maximum, gradient edge + valid area ...
+    int enqueue_edge(hipStream_t s, const uint16_t* depth_dev, int B, uint8_t* depthN_dev) const;
+    // ... MORPH_OPEN with element4 (erode, dilate) and the PEAC block statistics
+    int enqueue_open(hipStream_t s, const uint16_t* depth_dev, int B) const;
+    int enqueue(hipStream_t s, const uint16_t* depth_dev, int B, uint8_t* depthN_dev) const { SIND_TRY(enqueue_edge(s, depth_dev, B, depthN_dev)); return enqueue_open(s, depth_dev, B); }
+};
+struct OccBatch {
+    OccFront front;
+    int init(const DynaConfig& c, int chunk) { return front.init(c, chunk); }
     // frames at depth_dev + b * W * H; outputs (host, page-locked): edge / valid-area masks and block statistics per frame; depthN_dev (device, optional)
     int run(hipStream_t s, const uint16_t* depth_dev, int B, uint8_t* depthN_dev, uint8_t* edge_h, uint8_t* total_h, PeacBlockStats* blocks_h);
 };
@@ -70,6 +84,16 @@ struct DepthStageOut { std::vector<uint8_t> label3; int maxNum = 0; BitImg total
 // small kernels are not worth a launch each (measured: 55 k launches per 512-pair step, the tails phase bound by their summed durations at a
 // concurrency of ~2) -- one batched chain with blockIdx = (work, frame) does the same arithmetic with 1 / B of the launches.
 struct KmFrameResult { const uint8_t* label8; float centers[KM_K][3]; int counts[KM_K]; };
+// The one statement of the chain: the device workspaces for up to `cap` frames and the launches (depth pyramid; per level, coarsest first: points, labels -- the 3 x 4 grid or
+// the resized previous labels at level 3, the resized coarser level below --, cv::kmeans; the u8 labels).  The caller puts the previous labels into labPrev8 and reads lab8 / kstate.
+struct KmChain {
+    int W = 0, H = 0, N = 0, cap = 0;
+    DevBuf<uint16_t> dpyr[4]; DevBuf<float> px, py, pz, comp; DevBuf<int> lab[4], seg; DevBuf<uint8_t> labPrev8, lab8; DevBuf<KmState> kstate;
+    int init(int W, int H, int cap);
+    // frame b: device depth at depth_base + b * depth_stride.  use_prev_dev (device, one int per frame): both level-3 label kernels run and pick their frames by the flags;
+    // nullptr: the one that use_prev_host names.  Launches only -- no copy, no wait, no allocation: the tail records the call into a HIP graph.
+    int enqueue(hipStream_t s, const DynaConfig& cfg, const KmFuse& fuse, const uint16_t* depth_base, size_t depth_stride, int B, const int* use_prev_dev, bool use_prev_host) const;
+};
 class KMeansBatch {
 public:
     int init(const DynaConfig& c, int maxB, hipStream_t s);
@@ -80,8 +104,8 @@ public:
     hipStream_t stream = nullptr;
     KmFuse km_fuse = g_km_fuse_default;      // copied when the object is made; never changes afterwards
 private:
-    DynaConfig cfg; int W = 0, H = 0, N = 0, maxB = 0;
-    DevBuf<uint16_t> dpyr[4]; DevBuf<float> px, py, pz, comp; DevBuf<int> lab[4], seg, use_prev_d; DevBuf<uint8_t> labPrev8, lab8; DevBuf<KmState> kstate;
+    DynaConfig cfg; int N = 0, maxB = 0;
+    KmChain km; DevBuf<int> use_prev_d;
     PinnedBuf<uint8_t> h_prev, h_lab8; PinnedBuf<KmState> h_state; PinnedBuf<int> h_use_prev;
     std::vector<KmFrameResult> res;
 };
@@ -207,9 +231,8 @@ private:
     int lastCnt[256] = {0}, lastDyn[256] = {0};
     std::vector<uint8_t> kmLabelLast; bool kmLabelLastAny = false;   // imgLabelLast as seen by the depth half (k-means warm labels, DD:374-395)
     // device workspaces
-    DevBuf<uint16_t> dpyr[4], filt; DevBuf<float> px, py, pz; DevBuf<int> lab[4]; DevBuf<uint8_t> lab8, labPrev8, edge, edgeTmp, total, depthN, occ2_d, magu8, low_d;
-    DevBuf<int> kpart; DevBuf<float> kcomp; DevBuf<unsigned long long> planes_d; DevBuf<unsigned> umax_d; DevBuf<int> hist_d, rag_d; DevBuf<float> mag, grid_d;
-    DevBuf<PeacBlockStats> blocks_d;
+    KmChain km; OccFront occ;       // the k-means chain and the GPU front of CalOccluded, one frame each
+    DevBuf<uint8_t> depthN, occ2_d, magu8, low_d; DevBuf<unsigned long long> planes_d; DevBuf<int> hist_d, rag_d; DevBuf<float> mag, grid_d;
     // page-locked staging of everything that crosses PCIe in a tail
     PinnedBuf<float> h_grid; PinnedBuf<int> h_hist, h_rag; PinnedBuf<uint8_t> h_ab, h_lab8; PinnedBuf<KmState> h_kstate; PinnedBuf<PeacBlockStats> h_blocks;
     PinnedBuf<unsigned long long> h_planes;
@@ -220,10 +243,10 @@ private:
     int fuse(const BitImg& maskLow, const BitImg& maskHigh, const DepthStageOut& d, uint8_t* dyna_out, uint8_t* label_out);
     int kmeans(const uint16_t* depth_dev, std::vector<uint8_t>& label8, float centers[KM_K][3], int counts[KM_K]);
     bool hist_clean = false;      // hist_d's working block is known to be zero (left so by k_flow_thresholds)
-    DevBuf<KmState> kstate; DevBuf<uint16_t> depth_fix; hipGraphExec_t kmGraph[2] = {nullptr, nullptr}; bool kmGraphBroken = false;
-    int kmeans_enqueue(const uint16_t* depth0, bool prevLabels);
-    int cal_occluded(const uint16_t* depth_host, const uint16_t* depth_dev, BitImg& totalArea, BitImg& occ1, BitImg& occ2, const OccGpuOut* pre = nullptr);
-    int cal_occluded_p1(const uint16_t* depth_host, const uint16_t* depth_dev, OccCtx& c, const OccGpuOut* pre, uint8_t* grow_block, int depth_index);
+    DevBuf<uint16_t> depth_fix; hipGraphExec_t kmGraph[2] = {nullptr, nullptr}; bool kmGraphBroken = false;
+    // depthN_dev (optional, only without `pre`): the 8-bit normalised depth rides ahead of the edge chain (OccFront)
+    int cal_occluded(const uint16_t* depth_host, const uint16_t* depth_dev, BitImg& totalArea, BitImg& occ1, BitImg& occ2, const OccGpuOut* pre = nullptr, uint8_t* depthN_dev = nullptr);
+    int cal_occluded_p1(const uint16_t* depth_host, const uint16_t* depth_dev, OccCtx& c, const OccGpuOut* pre, uint8_t* grow_block, int depth_index, uint8_t* depthN_dev = nullptr);
     int cal_occluded_p2(OccCtx& c, const int8_t* member8, const uint8_t* pair_seen, const int* grow_status, BitImg& occ1, BitImg& occ2);
     int finish_occluded(OccResult& out, const OccGpuOut* pre);
     struct OwnGrow { PeacGrowBatch batch; PinnedBuf<uint8_t> in_h, pair_h; PinnedBuf<int8_t> member_h; PinnedBuf<int> status_h; };

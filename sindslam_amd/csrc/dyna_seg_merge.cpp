@@ -1,0 +1,261 @@
+// DynaDetect engine, SegAndMergeV2 (DD:653-1018, cal_hist :1685-1739): pieces on the host, region-adjacency statistics on the GPU (per frame, or RagBatch for one frame
+// of every stream of a k-means group), greedy merge on the host.
+#include <algorithm>
+#include <atomic>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <thread>
+#include "dyna.hpp"
+
+namespace sind {
+
+// ---- DD:653-1018: split every depth cluster on edges into pieces, region-adjacency statistics on the GPU, greedy merge on the host
+// host part up to the pieces in score order and pieceOf; they stay in segAll / segPieceOf (no pieces: segAll is empty and the frame's labels are all 0)
+int DynaTail::seg_pieces(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& labelForSegEdge, const uint16_t* depth_host) {
+    typedef SegPiece Piece;
+    std::vector<Piece>& all = segAll; all.clear();
+    double tf = tick_ms();
+    #define FLAP(i) { const double t_ = tick_ms(); t_fine[i] += t_ - tf; tf = t_; }
+    const EllipseElem e4(4), e9(9), e10(10);
+    const BitImg occDil = occ1.dilated(e10);
+    const float depth_weight = 1.5f;
+    // pieces of one depth cluster (DD:668-760); the clusters are independent, the result keeps the cluster order
+    auto pieces_of = [&](int i, std::vector<Piece>& out, bool timed) {
+        const BitImg& orig = allLabels[i];
+        double tq = tick_ms();
+        #define QLAP(i) { if (timed) { const double t_ = tick_ms(); t_fine[i] += t_ - tq; tq = t_; } }
+        BitImg each = orig; each.andnot(occ1);
+        { const Rect eb = each.bbox(); if (eb.empty()) return; each = each.opened_rows(e4, eb.y0, eb.y1); }
+        QLAP(12)
+        std::vector<Contour> contours; find_contours(each, contours, true);
+        QLAP(13)
+        for (const Contour& c : contours) {
+            if (!(c.size() > 50 && contour_area(c) > 80)) continue;
+            tq = tick_ms();
+            const Rect bb = contour_bbox(c);
+            Piece p; p.img.create(W, H); draw_filled(p.img, c);
+            p.img = p.img.dilated(e9, bb.y0, bb.y1); p.img.and_rows(orig, bb.y0 - 4, bb.y1 + 4);       // the 9x9 element reaches 4 rows up and down
+            p.area = (float)p.img.count_rows(bb.y0 - 4, bb.y1 + 4);
+            QLAP(14)
+            BitImg t1(W, H); draw_thick2(t1, c); t1.andnot_rows(occDil, bb.y0 - 1, bb.y1 + 1); t1.and_rows(labelForSegEdge, bb.y0 - 1, bb.y1 + 1);
+            if (t1.count_rows(bb.y0 - 1, bb.y1 + 1) > 20) {
+                std::vector<Contour> c2; const Rect r2{std::max(bb.x0 - 2, 0), std::max(bb.y0 - 2, 0), std::min(bb.x1 + 2, W - 1), std::min(bb.y1 + 2, H - 1)};
+                find_contours(t1, c2, true, &r2);
+                std::vector<const Contour*> kept; for (const Contour& q : c2) if (q.size() >= 30) kept.push_back(&q);
+                if (!kept.empty()) { p.lianjie.create(W, H); draw_filled(p.lianjie, kept); p.hasLianjie = true; }
+            }
+            QLAP(15)
+            // myCluster::calCenterPoint (DD:256-293): float sums in row-major order; only z is used afterwards
+            { float f3 = 0.f; const Rect ib = p.img.bbox();
+              for (int y = ib.y0; y <= ib.y1; y++) { const uint64_t* r = p.img.row(y);
+                for (int k = 0; k < p.img.wpr; k++) { uint64_t m = r[k]; while (m) { const int x = (k << 6) + __builtin_ctzll(m); m &= m - 1;
+                    const uint16_t d = depth_host[(size_t)y * W + x];
+                    // (float)d / depthScale >= 6 is monotonic in d: compared against the first raw value that satisfies it (zInvalidFrom, init())
+                    float pzv = 0.f; if (!((int)d >= zInvalidFrom || d == 0)) { const float depth2 = (float)d * invDepthScale; pzv = (float)(depth2 * depth_weight); }
+                    f3 += pzv; } } }
+              p.cz = f3 / p.area; }
+            QLAP(16)
+            out.push_back(std::move(p));
+        }
+        #undef QLAP
+    };
+    const int nCl = std::max(0, (int)allLabels.size() - 1);
+    if (piece_threads > 1 && nCl > 1) {        // a stream alone on the GPU (in-order sequence mode) leaves host cores idle: the clusters go to a few helper threads
+        std::vector<std::vector<Piece>> per(nCl); std::atomic<int> next{0}; std::vector<std::thread> team;
+        auto work = [&] { for (int i; (i = next.fetch_add(1)) < nCl;) pieces_of(i, per[i], false); };
+        for (int t = 1; t < std::min(piece_threads, nCl); t++) team.emplace_back(work);
+        work();
+        for (auto& t : team) t.join();
+        for (auto& v : per) for (Piece& q : v) all.push_back(std::move(q));
+    } else for (int i = 0; i < nCl; i++) pieces_of(i, all, true);
+    FLAP(6)
+    const int C = (int)all.size();
+    dbg.nClusters = C;
+    if (C == 0) return SIND_OK;
+    if (C > 254) { all.clear(); sind_set_error("seg_and_merge: %d pieces exceed the 8-bit label range of the reference", C); return SIND_E_CAPACITY; }
+    for (Piece& p : all) p.score = (float)(p.area * 0.0003f - p.cz);
+    std::sort(all.begin(), all.end(), [](const Piece& a, const Piece& b) { return a.score > b.score; });
+    segPieceOf.assign(N, (uint8_t)(C + 1));       // index of the piece that owns a pixel (the reference paints the pieces in score order)
+    for (int i = 0; i < C; i++) all[i].img.paint_u8(segPieceOf.data(), W, (uint8_t)i);
+    FLAP(10)
+    #undef FLAP
+    return SIND_OK;
+}
+// the pieces' planes and their connection areas' (zeros for a piece without one), C planes of H * W / 64 words each
+void DynaTail::rag_pack(unsigned long long* pieces, unsigned long long* conn) const {
+    const int C = (int)segAll.size(); const size_t pw = (size_t)H * (W / 64);
+    for (int i = 0; i < C; i++) {
+        std::memcpy(pieces + (size_t)i * pw, segAll[i].img.d.data(), pw * 8);
+        if (segAll[i].hasLianjie) std::memcpy(conn + (size_t)i * pw, segAll[i].lianjie.d.data(), pw * 8); else std::memset(conn + (size_t)i * pw, 0, pw * 8);
+    }
+}
+int DynaTail::rag_own(const int** rag) { HIP_TRY(hipSetDevice(cfg.device)); const double t0 = tick_ms(); const int r = seg_rag_gpu(rag); t_stage[4] += tick_ms() - t0; return r; }
+// ---- the GPU stage for this frame alone (every path that is not batched): upload the 2*C bit planes, dilation, one pass over the frame, the counters back, one wait
+int DynaTail::seg_rag_gpu(const int** rag_out) {
+    const int C = (int)segAll.size(); const BitImg& occ2 = segOcc2; const OccResult* pre = segPre; const uint16_t* depth_dev = segDepthDev;
+    double tf = tick_ms();
+    #define FLAP(i) { const double t_ = tick_ms(); t_fine[i] += t_ - tf; tf = t_; }
+    const int wpr = W / 64; const size_t pw = (size_t)H * wpr;
+    SIND_TRY(h_planes.alloc((size_t)3 * C * pw)); SIND_TRY(h_rag.alloc((size_t)3 * C * C + C + (size_t)C * 256));
+    unsigned long long* planes = h_planes.p; const size_t planes_n = (size_t)3 * C * pw;
+    // plane sets: [0, C) pieces, [C, 2C) their 7x7 dilations (formed on the GPU from the first set), [2C, 3C) connection areas
+    rag_pack(planes, planes + (size_t)2 * C * pw);
+    FLAP(10)
+    SIND_TRY(planes_d.alloc(planes_n)); SIND_TRY(rag_d.alloc((size_t)3 * C * C + C + (size_t)C * 256));
+    FLAP(11)
+    HIP_TRY(hipMemcpyAsync(planes_d.p, planes, (size_t)C * pw * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(planes_d.p + (size_t)2 * C * pw, planes + (size_t)2 * C * pw, (size_t)C * pw * 8, hipMemcpyHostToDevice, stream));
+    SIND_TRY(launch_dilate_planes(stream, planes_d.p, planes_d.p + (size_t)C * pw, C, W, H, 7, rag_d.p, (int)((size_t)3 * C * C + C + (size_t)C * 256)));      // also clears the RAG accumulators
+    const uint8_t* occ2_use = pre && pre->occ2_dev ? pre->occ2_dev : occ2_d.p;
+    if (pre && pre->occ2_dev && pre->occ2_event) HIP_TRY(hipStreamWaitEvent(stream, pre->occ2_event, 0));       // uploaded on the CalOccluded runner's stream without a host wait
+    if (!(pre && pre->occ2_dev)) { occ2.to_u8((h_ab.p + N), W, 255); HIP_TRY(hipMemcpyAsync(occ2_d.p, (h_ab.p + N), N, hipMemcpyHostToDevice, stream)); }
+    FLAP(7)
+    const uint8_t* depthN_use = pre && pre->depthN_dev ? pre->depthN_dev : depthN.p;
+    if (!(pre && pre->depthN_dev)) { SIND_TRY(launch_max_u16(stream, depth_dev, N, occ.umax.p + 1)); SIND_TRY(launch_depth_norm(stream, depth_dev, occ.umax.p + 1, depthN.p, N)); }      // (the raw-maximum slot of the one-frame OccFront)
+    int* ov_d = rag_d.p; int* ovp_d = ov_d + C * C; int* lj_d = ovp_d + C * C; int* la_d = lj_d + C * C; int* hist_dd = la_d + C;
+    SIND_TRY(launch_rag_stats(stream, planes_d.p, C, W, H, wpr, occ2_use, depthN_use, ov_d, ovp_d, lj_d, la_d, hist_dd, true));
+    PinnedBuf<int>& rag = h_rag;
+    HIP_TRY(hipMemcpyAsync(rag.data(), rag_d.p, ((size_t)3 * C * C + C + (size_t)C * 256) * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(sind_stream_wait(stream));
+    FLAP(8)
+    #undef FLAP
+    *rag_out = rag.data();
+    return SIND_OK;
+}
+// host part from the counters on: cal_hist, merge matrix, folds, labelNew
+void DynaTail::seg_finish(const int* rag, std::vector<uint8_t>& labelNew) {
+    const std::vector<SegPiece>& all = segAll; const std::vector<uint8_t>& pieceOf = segPieceOf; const int C = (int)all.size();
+    double tf = tick_ms();
+    #define FLAP(i) { const double t_ = tick_ms(); t_fine[i] += t_ - tf; tf = t_; }
+    const int* ov = rag; const int* ovp = ov + C * C; const int* ljo = ovp + C * C; const int* lja = ljo + C * C; const int* hst = lja + C;
+    // cal_hist (DD:1685-1739) from the two masked histograms
+    auto cal_hist = [&](int a, int b, double out[3]) {
+        float h1[256], h2[256]; double m1 = 0, m2 = 0, mn1 = DBL_MAX, mn2 = DBL_MAX;
+        for (int i = 0; i < 256; i++) { h1[i] = (float)hst[a * 256 + i]; h2[i] = (float)hst[b * 256 + i]; m1 = std::max<double>(m1, h1[i]); m2 = std::max<double>(m2, h2[i]); mn1 = std::min<double>(mn1, h1[i]); mn2 = std::min<double>(mn2, h2[i]); }
+        const int hist_h = 400;
+        auto norm_minmax = [&](float* h, double mn, double mx) { const double scale = (mx - mn) > DBL_EPSILON ? (double)hist_h / (mx - mn) : 0, shift = 0 - mn * scale; for (int i = 0; i < 256; i++) h[i] = h[i] * (float)scale + (float)shift; };
+        if (m1 > m2) { norm_minmax(h1, mn1, m1); const float s = (float)(1.0 / (m1 / hist_h)); for (int i = 0; i < 256; i++) h2[i] = h2[i] * s; }
+        else         { norm_minmax(h2, mn2, m2); const float s = (float)(1.0 / (m2 / hist_h)); for (int i = 0; i < 256; i++) h1[i] = h1[i] * s; }
+        double s1 = 0, s2 = 0, s11 = 0, s12 = 0, s22 = 0, bh = 0, inter = 0;
+        for (int j = 0; j < 256; j++) { const double x = h1[j], y = h2[j]; s12 += x * y; s1 += x; s11 += x * x; s2 += y; s22 += y * y; bh += std::sqrt(x * y); inter += std::min(h1[j], h2[j]); }
+        const double scale = 1. / 256, num = s12 - s1 * s2 * scale, denom2 = (s11 - s1 * s1 * scale) * (s22 - s2 * s2 * scale);
+        out[0] = std::fabs(denom2) > DBL_EPSILON ? num / std::sqrt(denom2) : 1.;
+        double ss = s1 * s2; ss = std::fabs(ss) > FLT_EPSILON ? 1. / std::sqrt(ss) : 1.;
+        out[1] = 1 - std::sqrt(std::max(1. - bh * ss, 0.));
+        out[2] = inter;
+    };
+    const int M = C + 1, numCluster = KM_K;
+    std::vector<float> mTotal((size_t)M * M, 0.f), m2((size_t)M * M, 0.f), m3((size_t)M * M, 0.f), wgt((size_t)M * M, 1.f), rej((size_t)M * M, 1.f);
+    const float thredshold = 0.9f; const int smallLabel = (int)std::min(0.7f * C, 15.0f);
+    for (int i = 0; i < C; i++) for (int j = i + 1; j < C; j++) {
+        float v2 = 0, v3 = 0, lessArea; int lessLabel;
+        if (all[i].area < all[j].area) { lessArea = all[i].area; lessLabel = i; } else { lessArea = all[j].area; lessLabel = j; }
+        if (lessLabel < 10) wgt[i * M + j] = wgt[j * M + i] = 0.7f;
+        else if (lessLabel > smallLabel) wgt[i * M + j] = wgt[j * M + i] = 2.0f;
+        const int overlap = ov[i * C + j], overlapPlane = ovp[i * C + j];
+        if (overlap > std::min(200.0f, lessArea * 0.4f)) {
+            double isMerge[3]; cal_hist(i, j, isMerge);
+            v3 = (float)(isMerge[0] + isMerge[1] + isMerge[2] * 0.0005);
+            if (overlapPlane > 100 && lessLabel < smallLabel) { rej[i * M + j] = rej[j * M + i] = 0.f; continue; }
+            else if (v3 < 0.19f && lessLabel < smallLabel) { rej[i * M + j] = rej[j * M + i] = 0.f; continue; }
+            if (all[i].hasLianjie && all[j].hasLianjie) {
+                const int o = ljo[i * C + j];
+                if (o > 0) { const int a1 = lja[i], a2 = lja[j];
+                    if (o > std::min(50, (int)(0.5 * std::min(a1, a2)))) { v2 = (float)o; if ((o > 0.62 * a1) || (o > 0.62 * a2)) v2 = (float)std::max(250, o); } }
+            }
+            m2[i * M + j] = m2[j * M + i] = v2; m3[i * M + j] = m3[j * M + i] = v3;
+        }
+    }
+    for (size_t k = 0; k < mTotal.size(); k++) mTotal[k] = ((m2[k] * 0.01f + m3[k]) * rej[k]) * wgt[k];
+    int countMerged = 0;
+    std::vector<std::vector<int>> merge(M); std::vector<int> mergeSit(M, 0);
+    auto fold = [&](int dst, int j) {
+        std::vector<float> col(M); for (int r = 0; r < M; r++) col[r] = mTotal[r * M + j];
+        for (int r = 0; r < M; r++) mTotal[r * M + dst] += col[r];
+        for (int c = 0; c < M; c++) mTotal[dst * M + c] += col[c];
+        for (int r = 0; r < M; r++) mTotal[r * M + j] = 0.f;
+        for (int c = 0; c < M; c++) mTotal[j * M + c] = 0.f;
+    };
+    for (int i = 0; i < std::min(numCluster - 1 + countMerged, C); i++)
+        for (int j = i + 1; j < std::min(numCluster - 1 + countMerged, C); j++) {
+            const float sorce = mTotal[j * M + i];
+            if (sorce > thredshold) {
+                int toMerge = i; const float toMergeValue = mTotal[j * M + i];
+                for (int k = 0; k < j; k++) if (mTotal[k * M + j] > toMergeValue) toMerge = k;
+                mergeSit[j] = 1; merge[toMerge].push_back(j); fold(toMerge, j); countMerged++;
+            }
+        }
+    for (int i = std::min(numCluster - 1 + countMerged, C); i < C; i++) {
+        int mergeCluster = C; float maxScore = 0.2f;
+        for (int j = 0; j < i; j++) { const float score = mTotal[j * M + i]; if (score > maxScore) { maxScore = score; mergeCluster = j; } }
+        mergeSit[i] = 1; merge[mergeCluster].push_back(i); fold(mergeCluster, i);
+    }
+    int labelindex = 1; std::vector<uint8_t> lut(256, 0);
+    for (int i = 0; i < C; i++) {
+        if (mergeSit[i]) continue;
+        std::vector<char> sel(M + 1, 0); sel[i] = 1;
+        for (int mj : merge[i]) { sel[mj] = 1; for (int mk : merge[mj]) sel[mk] = 1; }
+        // the reference paints labels in increasing order, a later group overwrites an earlier one on shared pieces
+        for (int q = 0; q <= M; q++) if (sel[q]) lut[q] = (uint8_t)labelindex;
+        labelindex++;
+    }
+    for (int k = 0; k < N; k++) labelNew[k] = lut[pieceOf[k]];
+    FLAP(9)
+    #undef FLAP
+}
+
+// ---- the GPU stage of SegAndMerge for one frame of every stream of a k-means group, in chunks (see dyna.hpp)
+int RagBatch::init(const DynaConfig& c, int max_frames, hipStream_t s) {
+    cfg = c; W = c.W; H = c.H; cap = max_frames; stream = s; pw = (size_t)H * (W / 64);
+    if (W % 64 != 0 || max_frames < 1) { sind_set_error("RagBatch: width must be a multiple of 64 (got %d), %d frames", W, max_frames); return SIND_E_ARG; }
+    SIND_TRY(recs_h.alloc(cap)); SIND_TRY(recs_d.alloc(cap));
+    occ2_ev.assign(cap, nullptr); done.resize(cap, nullptr);
+    for (hipEvent_t& e : done) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return SIND_OK;
+}
+RagBatch::~RagBatch() { for (hipEvent_t e : done) if (e) (void)hipEventDestroy(e); }
+int RagBatch::begin_round() {
+    HIP_TRY(hipSetDevice(cfg.device));
+    // result blocks: 16 K ints per frame hold 40 pieces (3 C^2 + 257 C); a frame that does not fit takes the per-frame stage
+    in_cap = (size_t)cap * planes_frame * pw; res_cap = (size_t)cap * 16384;
+    SIND_TRY(in_h.alloc(std::max<size_t>(in_cap, 2))); SIND_TRY(in_d.alloc(std::max<size_t>(in_cap, 2))); SIND_TRY(dil_d.alloc(std::max<size_t>(in_cap / 2, 1)));
+    SIND_TRY(res_d.alloc(res_cap)); SIND_TRY(res_h.alloc(res_cap));
+    std::lock_guard<std::mutex> lk(m);
+    n_slots = 0; in_used = 0; res_used = 0;
+    return SIND_OK;
+}
+bool RagBatch::reserve(int C, int* slot, unsigned long long** pieces, unsigned long long** conn) {
+    if (C < 1 || C > 254) return false;
+    const size_t words = (size_t)2 * C * pw, ints = rag_result_ints(C);
+    std::lock_guard<std::mutex> lk(m);
+    if (n_slots >= cap || in_used + words > in_cap || res_used + ints > res_cap) return false;
+    RagRec& R = recs_h.p[n_slots];
+    R.plane_off = in_used; R.res_off = res_used; R.C = C; R.pad = 0; R.occ2 = nullptr; R.depthN = nullptr;
+    *pieces = in_h.p + in_used; *conn = *pieces + (size_t)C * pw; *slot = n_slots++;
+    in_used += words; res_used += ints;
+    return true;
+}
+void RagBatch::set_inputs(int slot, const uint8_t* occ2, const uint8_t* depthN, hipEvent_t ev) { recs_h.p[slot].occ2 = occ2; recs_h.p[slot].depthN = depthN; occ2_ev[slot] = ev; }
+int RagBatch::enqueue(int chunk) {
+    HIP_TRY(hipSetDevice(cfg.device));
+    int first, n; { std::lock_guard<std::mutex> lk(m); first = chunk_first(chunk); n = chunk_count(chunk); }
+    if (chunk < 0 || n < 1) { sind_set_error("RagBatch::enqueue: chunk %d holds no frame", chunk); return SIND_E_ARG; }
+    const RagRec& A = recs_h.p[first]; const RagRec& Z = recs_h.p[first + n - 1];
+    const size_t w0 = A.plane_off, w1 = Z.plane_off + (size_t)2 * Z.C * pw, r0 = A.res_off, r1 = Z.res_off + rag_result_ints(Z.C);
+    std::lock_guard<std::mutex> lk(enq);      // (two chunks of a round may be enqueued by two pool threads: one chunk's calls stay together on the stream)
+    for (int b = first; b < first + n; b++) if (occ2_ev[b]) HIP_TRY(hipStreamWaitEvent(stream, occ2_ev[b], 0));       // occ2 uploaded on the CalOccluded runner's stream without a host wait
+    HIP_TRY(hipMemcpyAsync(in_d.p + w0, in_h.p + w0, (w1 - w0) * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(recs_d.p + first, recs_h.p + first, (size_t)n * sizeof(RagRec), hipMemcpyHostToDevice, stream));
+    SIND_TRY(launch_rag_frames(stream, recs_d.p + first, recs_h.p + first, n, in_d.p, in_cap, dil_d.p, res_d.p, res_cap, W, H));
+    HIP_TRY(hipMemcpyAsync(res_h.p + r0, res_d.p + r0, (r1 - r0) * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(done[chunk], stream));
+    return SIND_OK;
+}
+int RagBatch::wait(int chunk) {
+    if (chunk < 0 || chunk >= cap) { sind_set_error("RagBatch::wait: chunk %d", chunk); return SIND_E_ARG; }
+    HIP_TRY(sind_event_wait(done[chunk]));
+    return SIND_OK;
+}
+
+}  // namespace sind

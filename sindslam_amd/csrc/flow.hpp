@@ -98,7 +98,7 @@ bool sor_stream_fits(int h, int total);
 int launch_coarse_chain(hipStream_t s, FlowPlanes& Pl, const float* pyr0, const float* pyr1, const std::vector<std::pair<int, int>>& levels, const std::vector<size_t>& level_off,
                         int first, int last, int B, const VarParams& V, bool init_zero, bool upsample_last, float post, float* out_u, float* out_v);
 int launch_mag_stats(hipStream_t s, const float* u, const float* v, float* mag, unsigned* maxbits, int* hist, uint8_t* out_u8, int n, int B);
-// Host half of the large-motion test (DD:1093-1114) for one image (dyna_engine.cpp): the maximum of |flow| and the 256-bin histogram of its 8-bit normalisation
+// Host half of the large-motion test (DD:1093-1114) for one image (dyna_front.cpp): the maximum of |flow| and the 256-bin histogram of its 8-bit normalisation
 // (launch_mag_stats) -> does the pair take the second DeepFlow pass.  W x H is the FULL frame (totalpixel is 0.36 W H, not fw * fh).  end2 (optional): endFlow, endFlow2.
 bool large_motion_decision(float maxFlow, const int* hist256, int W, int H, int* end2 = nullptr);
 int launch_residual(hipStream_t s, const float* u, const float* v, const double H[9], float* mag, unsigned* maxbits, int* hist, uint8_t* magu8, int w, int h, bool already_zero = false);

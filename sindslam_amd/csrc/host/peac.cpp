@@ -2,7 +2,7 @@
 // (reference include/PEAC/AHCPlaneFitter.hpp:186-236 run, :881-1039 initGraph, :1050-1256 ahCluster,
 //  :274-400 refineDetails, :603-705 findBlockMembership, :546-594 floodFill; AHCPlaneSeg.hpp:103-134 PCA;
 //  AHCParamSet.hpp:48-148 thresholds; DisjointSet.hpp).
-// Split of work: the 1200 per-window second-order statistics come from the GPU (depth_kernels.hip k_peac_block_stats); the graph
+// Split of work: the 1200 per-window second-order statistics come from the GPU (depth_edges.hip k_peac_block_stats); the graph
 // (<= 1200 nodes, priority queue, disjoint sets) is serial and stays here (part1 / part2); the pixel-level region grow along the plane
 // borders (floodFill, :546-601) runs on the GPU as a level-synchronous ordered BFS (peac_kernels.hip k_peac_grow, same visiting order as
 // the FIFO), with grow_host as the statement of that FIFO for inputs beyond the kernel's fixed capacities and for the CPU tests.

@@ -1,4 +1,4 @@
-"""GPU: the wave-parallel EXACT sequential FP32 sum behind the k-means centres (k_km_seqsum, csrc/depth_kernels.hip) against the plain
+"""GPU: the wave-parallel EXACT sequential FP32 sum behind the k-means centres (k_km_seqsum, csrc/depth_kmeans.hip) against the plain
 left-to-right float32 accumulation of cv::kmeans (kmeans.cpp "compute centers"; numpy's add.accumulate is that loop) -- bit for bit, on data
 chosen to hit every premise of the window arithmetic: binade crossings in both directions, exact ties, exact powers of two, zeros, huge
 dynamic range, runs longer than the LDS ring, lengths that are not a multiple of anything."""
