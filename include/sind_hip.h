@@ -288,6 +288,9 @@ int sind_pipe_get_state_hashes(sind_pipe* p, uint64_t* out, size_t count);
 /* Which pairs of the step whose results were returned last took the reference's second DeepFlow pass (flow(n, n-1) instead of flow(n, n-2), DynaDetect.cc:1121-1131):
  * streams x frames_per_step flags (0 / 1), pair k = stream * frames_per_step + frame.  Read-only; the flag depends on the frames alone, so a ragged step has all of them. */
 int sind_pipe_large_motion(sind_pipe* p, int* flags, int cap);
+/* Which schedule the stateful tails of that step took: 0 = one chain per stream over whole tails, 1 = chains over flow halves (depth-ahead), 2 = two chains per stream
+ * (ragged / replayed steps with few live streams), 3 = rounds, 4 = split rounds.  Read-only; SIND_E_STATE before the first step.  The results do not depend on it. */
+int sind_pipe_last_schedule(sind_pipe* p, int* kind);
 int sind_pipe_set_active_frames(sind_pipe* p, const int* frames_per_stream);
 /* Retained steps: the repair runs of the chunked mode re-run only the stateful 1 % of a frame.  sind_pipe_reserve_retained(n) sets buffers for n steps aside
  * (device: flow, depth, plane-edge mask, normalised depth; page-locked host: depth, sample-grid flow); sind_pipe_retain_next(tag) keeps the phase-A outputs

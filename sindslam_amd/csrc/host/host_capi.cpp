@@ -6,6 +6,7 @@
 #include <cstring>
 #include "host.hpp"
 #include "peac_fit4.hpp"
+#include "pipe_schedule.hpp"
 #include "../orb.hpp"
 
 using namespace sind;
@@ -95,6 +96,12 @@ int sindh_octree(const float* xyr, int n, int minX, int maxX, int minY, int maxY
     distribute_octree(in, minX, maxX, minY, maxY, N, out);
     for (int i = 0; i < (int)out.size() && i < cap; i++) { out_xyr[3 * i] = out[i].x; out_xyr[3 * i + 1] = out[i].y; out_xyr[3 * i + 2] = out[i].response; }
     return (int)out.size();
+}
+// the tail schedule of a sind_pipe step (pipe_schedule.hpp): returns the TailSchedule, *inline_poll = its chains run the next frame in place and poll before sleeping
+int sindh_pipe_schedule(int S, int workers, int batch_km, int depth_ahead, int split_rounds, int chain_max_streams, int ragged, int nact, int* inline_poll) {
+    const TailPlan pl = tail_schedule(S, workers, batch_km != 0, depth_ahead != 0, split_rounds != 0, chain_max_streams, ragged != 0, nact);
+    if (inline_poll) *inline_poll = pl.inline_poll ? 1 : 0;
+    return (int)pl.kind;
 }
 
 }  // extern "C"

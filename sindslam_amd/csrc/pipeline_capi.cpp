@@ -3,6 +3,15 @@
 
 extern "C" {
 
+// both step buffers at rest (flush: the message also says how to get there)
+static int no_step_pending(sind_pipe* p, const char* name, bool flush = false) {
+    if (!p->sb[0].pending && !p->sb[1].pending) return SIND_OK;
+    sind_set_error("%s: a submitted step is still pending%s", name, flush ? ", call sind_pipe_flush first" : ""); return SIND_E_STATE;
+}
+// from phase A's time stamps: front, dense flow, ORB + CalOccluded left over, (upload), tails, total
+static void fill_stage_ms(sind_pipe* p, const double t[4], double tails_ms, double total_ms) {
+    p->stage_ms[0] = t[1] - t[0]; p->stage_ms[1] = t[2] - t[1]; p->stage_ms[2] = t[3] - t[2]; p->stage_ms[3] = 0; p->stage_ms[4] = tails_ms; p->stage_ms[5] = total_ms;
+}
 static int check_inputs(sind_pipe* p, const void* a, const void* b) {
     if (!p || !a || !b) { sind_set_error("sind_pipe: null input"); return SIND_E_ARG; }
     for (int s = 0; s < p->S; s++) if (!p->primed[s]) { sind_set_error("sind_pipe: stream %d was not primed", s); return SIND_E_STATE; }
@@ -14,14 +23,14 @@ static int check_inputs(sind_pipe* p, const void* a, const void* b) {
 int sind_pipe_process_dev(sind_pipe* p, const uint8_t* bgr_dev, const uint16_t* depth_dev, uint8_t* dyna, uint8_t* label, uint8_t* mask_dil,
                           sind_keypoint* kps, int cap, int* nkp, uint8_t* desc) {
     SIND_TRY(check_inputs(p, bgr_dev, depth_dev));
-    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_process: a submitted step is still pending, call sind_pipe_flush first"); return SIND_E_STATE; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_process", true));
     p->gate.set_capacity(1 << 20);                 // no pool task is running between two calls: safe to re-base the token count
     double t[4]; const double t0 = now_ms();
     SIND_TRY(phase_a(p, p->sb[0], bgr_dev, depth_dev, t, p->depth_ahead));
     const PipeOut o{dyna, label, mask_dil, kps, cap, nkp, desc};
     SIND_TRY(phase_b(p, p->sb[0], o));
     const double t4 = now_ms();
-    p->stage_ms[0] = t[1] - t[0]; p->stage_ms[1] = t[2] - t[1]; p->stage_ms[2] = t[3] - t[2]; p->stage_ms[3] = 0; p->stage_ms[4] = t4 - t[3]; p->stage_ms[5] = t4 - t0;
+    fill_stage_ms(p, t, t4 - t[3], t4 - t0);
     grow_adapt(p, t[3] - t[2], t[3] - t0);             // synchronous step: phase A waits for CalOccluded only; its tails have the host to themselves afterwards
     return SIND_OK;
 }
@@ -50,7 +59,7 @@ int sind_pipe_submit_dev(sind_pipe* p, const uint8_t* bgr_dev, const uint16_t* d
         return rb != SIND_OK ? rb : ra;
     }
     // tail_wait_ms: how long this call still waited for the previous step's tails after its own phase A was done (0 = the tails are hidden)
-    p->stage_ms[0] = t[1] - t[0]; p->stage_ms[1] = t[2] - t[1]; p->stage_ms[2] = t[3] - t[2]; p->stage_ms[3] = 0; p->tail_wait_ms = has_prev ? t4 - ta1 : 0; p->stage_ms[4] = tb1 - tb0; p->stage_ms[5] = t4 - t0;
+    fill_stage_ms(p, t, tb1 - tb0, t4 - t0); p->tail_wait_ms = has_prev ? t4 - ta1 : 0;
     p->cur ^= 1;
     grow_adapt(p, (t[3] - t[2]) + p->tail_wait_ms, t4 - t0);
     return SIND_OK;
@@ -73,9 +82,9 @@ int sind_pipe_process(sind_pipe* p, const uint8_t* bgr, const uint16_t* depth, u
                       int cap, int* nkp, uint8_t* desc) {
     if (!p || !bgr || !depth) { sind_set_error("sind_pipe_process: null input"); return SIND_E_ARG; }
     HIP_TRY(hipSetDevice(p->c.device));
-    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_process: a submitted step is still pending, call sind_pipe_flush first"); return SIND_E_STATE; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_process", true));
     const double t_in = now_ms();
-    const size_t np = (size_t)p->c.width * p->c.height, B = (size_t)p->S * p->T;
+    const size_t np = p->np(), B = (size_t)p->S * p->T;
     SIND_TRY(p->bgr_d.alloc(np * 3 * B)); SIND_TRY(p->depth_d.alloc(np * B));
     // Upload from the caller's (pageable) buffers: the pool's workers copy 4 MB pieces into page-locked staging (two buffers each) and
     // queue the DMA on their own streams; 393 MB of a 256-pair step arrive in ~8 ms (stage_ms[3], "host_upload").
@@ -105,7 +114,7 @@ int sind_pipe_process(sind_pipe* p, const uint8_t* bgr, const uint16_t* depth, u
 
 int sind_pipe_set_depth_ahead(sind_pipe* p, int on) {
     if (!p) return SIND_E_ARG;
-    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_set_depth_ahead: a submitted step is still pending"); return SIND_E_STATE; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_set_depth_ahead"));
     HIP_TRY(hipSetDevice(p->c.device));
     if (on && !p->active_next.empty()) { sind_set_error("sind_pipe_set_depth_ahead: a ragged step is pending (sind_pipe_set_active_frames)"); return SIND_E_STATE; }
     if (on) SIND_TRY(ensure_dtails(p));
@@ -116,7 +125,7 @@ int sind_pipe_set_depth_ahead(sind_pipe* p, int on) {
 size_t sind_pipe_state_bytes(sind_pipe* p) { return p && !p->tails.empty() ? p->tails[0]->state_bytes() : 0; }
 int sind_pipe_get_state(sind_pipe* p, int s, uint8_t* buf, size_t n) {
     if (!p || s < 0 || s >= p->S || !buf || n < sind_pipe_state_bytes(p)) { sind_set_error("sind_pipe_get_state: bad arguments"); return SIND_E_ARG; }
-    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_get_state: a submitted step is still pending, call sind_pipe_flush first"); return SIND_E_STATE; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_get_state", true));
     p->tails[s]->save_state(buf, true, false); depth_half(p, s)->save_state(buf, false, true);
     return SIND_OK;
 }
@@ -133,7 +142,7 @@ int sind_pipe_set_state(sind_pipe* p, int s, const uint8_t* buf, size_t n) {
 // ---- chunked sequences: per-frame state fingerprints and ragged steps
 int sind_pipe_set_state_hashing(sind_pipe* p, int on) {
     if (!p) { sind_set_error("sind_pipe_set_state_hashing: null handle"); return SIND_E_ARG; }
-    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_set_state_hashing: a submitted step is still pending"); return SIND_E_STATE; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_set_state_hashing"));
     p->hashing = on != 0;
     for (auto& t : p->tails) t->hash_state = p->hashing;
     return SIND_OK;
@@ -148,6 +157,11 @@ int sind_pipe_large_motion(sind_pipe* p, int* flags, int cap) {
     if (p->last_large_motion.size() != (size_t)p->S * p->T) { sind_set_error("sind_pipe_large_motion: no step has finished yet"); return SIND_E_STATE; }
     std::copy(p->last_large_motion.begin(), p->last_large_motion.end(), flags); return SIND_OK;
 }
+int sind_pipe_last_schedule(sind_pipe* p, int* kind) {
+    if (!p || !kind) { sind_set_error("sind_pipe_last_schedule: null argument"); return SIND_E_ARG; }
+    if (p->last_schedule < 0) { sind_set_error("sind_pipe_last_schedule: no step has finished yet"); return SIND_E_STATE; }
+    *kind = p->last_schedule; return SIND_OK;
+}
 int sind_pipe_set_active_frames(sind_pipe* p, const int* frames_per_stream) {
     if (!p) { sind_set_error("sind_pipe_set_active_frames: null handle"); return SIND_E_ARG; }
     if (!frames_per_stream) { p->active_next.clear(); return SIND_OK; }
@@ -161,14 +175,13 @@ int sind_pipe_set_active_frames(sind_pipe* p, const int* frames_per_stream) {
 int sind_pipe_reserve_retained(sind_pipe* p, int steps) {
     if (!p || steps < 0 || steps > 64) { sind_set_error("sind_pipe_reserve_retained: 0..64 steps"); return SIND_E_ARG; }
     HIP_TRY(hipSetDevice(p->c.device));
-    const size_t np = (size_t)p->c.width * p->c.height, B = (size_t)p->S * p->T, gsz = (size_t)2 * ((p->c.width - 1) / 10) * ((p->c.height - 1) / 10);
+    const size_t np = p->np(), gsz = p->gsz();
     // the reserve is `steps` sets, not "at least": spare sets beyond it are freed (their HBM and page-locked host memory go back), so that a caller whose larger request
     // failed half-way can retry with a smaller one and really get the difference back (kept sets hold results and are never freed here: release them first)
     while (!p->spare.empty() && (int)(p->spare.size() + p->kept.size()) > steps) p->spare.pop_back();
     while ((int)(p->spare.size() + p->kept.size()) < steps) {
         std::unique_ptr<sind_pipe::Retained> r(new sind_pipe::Retained());
-        SIND_TRY(r->U.alloc(np * B)); SIND_TRY(r->V.alloc(np * B)); SIND_TRY(r->grid_dev.alloc(gsz * B)); SIND_TRY(r->depth_dev.alloc(np * B)); SIND_TRY(r->depth_h.alloc(np * B));
-        SIND_TRY(r->grid_h.alloc(gsz * B)); SIND_TRY(r->occ2_dev.alloc(np * B)); SIND_TRY(r->depthN_dev.alloc(np * B));
+        SIND_TRY(r->a.alloc(np, (size_t)p->S * p->T, gsz));
         p->spare.push_back(std::move(r));
     }
     return SIND_OK;
@@ -189,7 +202,7 @@ int sind_pipe_release_retained(sind_pipe* p, int tag) {
 // Outputs as in sind_pipe_process ([S][T] layout, only the frames that ran are written); fingerprints through sind_pipe_get_state_hashes.
 int sind_pipe_replay(sind_pipe* p, int tag, const int* first, const int* last, uint8_t* dyna, uint8_t* label, uint8_t* mask_dil, sind_keypoint* kps, int cap, int* nkp, uint8_t* desc) {
     if (!p || !first || !last) { sind_set_error("sind_pipe_replay: null argument"); return SIND_E_ARG; }
-    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_replay: a submitted step is still pending, call sind_pipe_flush first"); return SIND_E_STATE; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_replay", true));
     if (p->depth_ahead) { sind_set_error("sind_pipe_replay: not available with depth-ahead"); return SIND_E_STATE; }
     sind_pipe::Retained* r = nullptr; for (auto& k : p->kept) if (k->tag == tag) r = k.get();
     if (!r) { sind_set_error("sind_pipe_replay: no retained step with tag %d", tag); return SIND_E_ARG; }
@@ -197,7 +210,7 @@ int sind_pipe_replay(sind_pipe* p, int tag, const int* first, const int* last, u
     HIP_TRY(hipSetDevice(p->c.device));
     p->gate.set_capacity(1 << 20);
     sind_pipe::StepBuf& sb = p->sb[0];
-    swap_phase_a_outputs(sb, *r);
+    sb.a.swap(r->a);
     sb.first.assign(first, first + p->S); sb.active.assign(last, last + p->S); sb.depth_ahead = false; sb.retain_tag = -1;
     sb.state_hash.assign((size_t)2 * p->S * p->T, 0);
     const PipeOut o{dyna, label, mask_dil, kps, cap, nkp, desc};
@@ -205,7 +218,7 @@ int sind_pipe_replay(sind_pipe* p, int tag, const int* first, const int* last, u
     const int rc = phase_b(p, sb, o);
     p->stage_ms[4] = now_ms() - t0;
     sb.first.clear(); sb.active.clear();
-    swap_phase_a_outputs(sb, *r);
+    sb.a.swap(r->a);
     return rc;
 }
 
@@ -222,12 +235,12 @@ int sind_pipe_set_kmeans_groups(sind_pipe* p, int groups) {
 int sind_pipe_get_kmeans_groups(sind_pipe* p, int* groups) { if (!p || !groups) { sind_set_error("sind_pipe_get_kmeans_groups: null argument"); return SIND_E_ARG; } *groups = p->batch_km ? p->km_groups : 0; return SIND_OK; }
 int sind_pipe_set_flow_mask_batch(sind_pipe* p, int on) {
     if (!p) { sind_set_error("sind_pipe_set_flow_mask_batch: null handle"); return SIND_E_ARG; }
-    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_set_flow_mask_batch: a submitted step is still pending"); return SIND_E_STATE; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_set_flow_mask_batch"));
     p->fm_batch = on != 0; p->fm_frames = 0; return SIND_OK;
 }
 int sind_pipe_set_rag_batch(sind_pipe* p, int on) {
     if (!p) { sind_set_error("sind_pipe_set_rag_batch: null handle"); return SIND_E_ARG; }
-    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_set_rag_batch: a submitted step is still pending"); return SIND_E_STATE; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_set_rag_batch"));
     p->rag_batch = on != 0; p->rag_frames = 0; p->rag_fallback = 0; return SIND_OK;
 }
 int sind_pipe_get_rag_batch(sind_pipe* p, int* on, long long* frames_batched, long long* frames_fallback) {
@@ -236,7 +249,7 @@ int sind_pipe_get_rag_batch(sind_pipe* p, int* on, long long* frames_batched, lo
 }
 int sind_pipe_set_rag_batch_chunk(sind_pipe* p, int chunk_frames, int slab_planes_per_frame) {
     if (!p) { sind_set_error("sind_pipe_set_rag_batch_chunk: null handle"); return SIND_E_ARG; }
-    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_set_rag_batch_chunk: a submitted step is still pending"); return SIND_E_STATE; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_set_rag_batch_chunk"));
     if (slab_planes_per_frame > 1024) { sind_set_error("sind_pipe_set_rag_batch_chunk: %d planes per frame (at most 1024)", slab_planes_per_frame); return SIND_E_ARG; }
     p->rag_chunk = chunk_frames < 1 ? 0 : chunk_frames; if (slab_planes_per_frame >= 0) p->rag_planes = slab_planes_per_frame; return SIND_OK;
 }
@@ -248,7 +261,7 @@ int sind_pipe_get_flow_mask_batch(sind_pipe* p, int* on, long long* frames_batch
 // each takes its part of the process's CPU share -- the tokens of its pool tasks and its CalOccluded runners follow
 int sind_pipe_set_cpu_share(sind_pipe* p, int cores) {
     if (!p || cores < 1) { sind_set_error("sind_pipe_set_cpu_share: at least one core"); return SIND_E_ARG; }
-    if (p->sb[0].pending || p->sb[1].pending) { sind_set_error("sind_pipe_set_cpu_share: a submitted step is still pending"); return SIND_E_STATE; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_set_cpu_share"));
     cores = std::min(cores, 16); p->cpu_share = cores; p->host_info[0] = cores;
     p->cpu_tokens_max = std::max(2, cores + 2); p->cpu_tokens_min = std::max(2, cores - 3); p->cpu_tokens = p->cpu_tokens_min;
     p->host_info[2] = p->cpu_tokens_max;

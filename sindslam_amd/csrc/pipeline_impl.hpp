@@ -7,62 +7,60 @@
 //            DynaDetect tail, dilation, dynamic-mask erasure of the ORB keypoints.
 #include <algorithm>
 #include <chrono>
-#include <condition_variable>
 #include <cstring>
-#include <deque>
-#include <functional>
-#include <mutex>
 #include <string>
-#include <thread>
-#include <pthread.h>
 #include <sched.h>
 #include <ctime>
 #include <cstdio>
 #include "../../include/sind_hip.h"
 #include "dyna.hpp"
 #include "orb.hpp"
+#include "pipeline_pool.hpp"
+#include "host/pipe_schedule.hpp"
 
 using namespace sind;
 
-// Fixed pool of host workers shared by the CalOccluded tasks of the step in phase A and the stateful tails of the step in phase B.
-// The GPU boxes give a process a bounded CPU share (16 cores per GPU on this pool): one bounded pool instead of a thread set per
-// phase keeps the runnable threads under that share, which matters most in the pipelined mode where both kinds of task coexist.
 // CPU time (user + system) of the calling thread in ms, for the SIND_TAIL_TIMING report of the short-lived phase-A threads
 static inline double thread_cpu_ms() { timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 inline std::atomic<long long> g_cpu_us_flow{0}, g_cpu_us_orb{0}, g_cpu_steps{0};
 
-struct TaskGroup { std::mutex m; std::condition_variable cv; int left = 0; };
-class WorkerPool {
-public:
-    void start(int n, int device, SindHostGate* gate, int spin_us = 0) {
-        for (int i = 0; i < n; i++) th.emplace_back([this, i, device, gate, spin_us] {
-            (void)pthread_setname_np(pthread_self(), "sind-worker");      // names show up in /proc/<pid>/task/*/comm (bench.py --thread-cpu)
-            (void)hipSetDevice(device);
-            t_sind_spin_us = spin_us;
-            for (;;) {
-                std::pair<std::function<void(int)>, TaskGroup*> job;
-                { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [this] { return stop || !q.empty(); }); if (q.empty()) return; job = std::move(q.front()); q.pop_front(); }
-                gate->acquire(); t_sind_gate = gate;          // a CPU token while the task computes (handed back inside every wait for the GPU)
-                job.first(i);
-                t_sind_gate = nullptr; gate->release();
-                { std::lock_guard<std::mutex> lk(job.second->m); if (--job.second->left == 0) job.second->cv.notify_all(); }
-            } });
+// First failure per slot (a stream, a frame, a flow slice).  A slot is written by the task that owns it, without a lock.
+struct Failures {
+    std::vector<int> rc; std::vector<std::string> err;
+    void reset(int n) { rc.assign(n, SIND_OK); err.assign(n, std::string()); }
+    bool ok(int i) const { return rc[i] == SIND_OK; }
+    void fail(int i, int r, const std::string& e) { rc[i] = r; err[i] = e; }
+    void fail(int i, int r) { fail(i, r, sind_last_error()); }
+    void fail_all(int i0, int i1, int r, const char* prefix, const std::string& msg = sind_last_error()) {      /* slots that have not failed yet */ for (int i = i0; i < i1; i++) if (ok(i)) fail(i, r, prefix + msg); }
+    // the first failed slot becomes the last error: fmt takes slot / per and the message
+    int first_error(const char* fmt, int per = 1) const { for (int i = 0; i < (int)rc.size(); i++) if (!ok(i)) { sind_set_error(fmt, i / per, err[i].c_str()); return rc[i]; } return SIND_OK; }
+};
+
+// Phase-A outputs of a step, everything the tails read; a member of both step buffers and of every retained step, which change places by swap()
+struct PhaseAOut {
+    DevBuf<float> U, V; DevBuf<uint16_t> depth_dev; PinnedBuf<uint16_t> depth_h;       // (page-locked: the 157 MB device-to-host copy of a step must not block the enqueueing thread)
+    DevBuf<uint8_t> occ2_dev, depthN_dev;                  // per frame: plane-edge mask and normalised depth for the tails' RAG statistics (filled by the CalOccluded tasks)
+    DevBuf<float> grid_dev; PinnedBuf<float> grid_h;       // flow at the 10-px sample grid of every frame (DD:1182-1204), gathered right after the dense flow
+    std::vector<OrbFrameResult> orb; std::vector<OccResult> occ;
+    std::vector<int> large_motion;                         // per pair k = s * T + t: took the second DeepFlow pass (every flow slice writes its own range)
+    // gsz = 0 (construction): flow and depth copies only -- the rest comes with the first step that fills this set
+    int alloc(size_t np, size_t B, size_t gsz) {
+        SIND_TRY(U.alloc(np * B)); SIND_TRY(V.alloc(np * B)); SIND_TRY(depth_dev.alloc(np * B)); SIND_TRY(depth_h.alloc(np * B));
+        if (gsz == 0) return SIND_OK;
+        SIND_TRY(occ2_dev.alloc(np * B)); SIND_TRY(depthN_dev.alloc(np * B)); SIND_TRY(grid_dev.alloc(gsz * B)); SIND_TRY(grid_h.alloc(gsz * B));
+        return SIND_OK;
     }
-    void push(TaskGroup& g, std::function<void(int)> fn) {
-        { std::lock_guard<std::mutex> lk(g.m); g.left++; }
-        { std::lock_guard<std::mutex> lk(m); q.emplace_back(std::move(fn), &g); }
-        cv.notify_one();
+    void swap(PhaseAOut& o) {
+        U.swap(o.U); V.swap(o.V); depth_dev.swap(o.depth_dev); depth_h.swap(o.depth_h); occ2_dev.swap(o.occ2_dev); depthN_dev.swap(o.depthN_dev); grid_dev.swap(o.grid_dev); grid_h.swap(o.grid_h);
+        orb.swap(o.orb); occ.swap(o.occ); large_motion.swap(o.large_motion);
     }
-    static void wait(TaskGroup& g) { std::unique_lock<std::mutex> lk(g.m); g.cv.wait(lk, [&g] { return g.left == 0; }); }
-    int size() const { return (int)th.size(); }
-    ~WorkerPool() { { std::lock_guard<std::mutex> lk(m); stop = true; } cv.notify_all(); for (auto& t : th) if (t.joinable()) t.join(); }
-private:
-    std::vector<std::thread> th; std::mutex m; std::condition_variable cv; std::deque<std::pair<std::function<void(int)>, TaskGroup*>> q; bool stop = false;
 };
 
 struct sind_pipe {
     sind_pipe_config c{}; DynaConfig dc; int S = 0, T = 0, fw = 0, fh = 0;
-    hipStream_t stream = nullptr, orb_stream = nullptr; hipEvent_t ev_gray = nullptr, ev_depth = nullptr; std::vector<hipStream_t> worker_streams, worker_streams_lo;      // one HIP stream per pool worker, shared by the tasks it runs
+    size_t np() const { return (size_t)c.width * c.height; }      // pixels of a frame
+    size_t gsz() const { return (size_t)2 * ((c.width - 1) / 10) * ((c.height - 1) / 10); }      // values of a frame's sample-grid flow
+    hipStream_t stream = nullptr, orb_stream = nullptr; hipEvent_t ev_gray = nullptr, ev_depth = nullptr; std::vector<hipStream_t> worker_streams;      // one HIP stream per pool worker, shared by the tasks it runs
     DynaFront front; std::vector<std::unique_ptr<DynaFront>> extra_fronts; std::vector<hipStream_t> extra_streams; hipEvent_t ev_pool = nullptr;      // batch slices 1.. of the dense flow (slice 0 = front)
     OrbEngine orb; std::vector<std::unique_ptr<DynaTail>> tails;
     // Depth halves (k-means warm labels + their workspaces) as objects of their own, present once depth-ahead has been switched on: the
@@ -71,12 +69,12 @@ struct sind_pipe {
     // k-means of one frame of every stream as ONE batched kernel chain (phase B then runs frame t of all streams as a round: batched k-means,
     // then the S tails of that frame on the pool); used when there are several streams and the depth half is not run ahead
     static constexpr int KM_GROUPS = 4;
-    KMeansBatch kmb[KM_GROUPS]; int km_groups = 1, km_groups_max = 1, km_groups_fixed = -1; hipStream_t km_stream = nullptr, km_streams[KM_GROUPS] = {nullptr}; bool batch_km = false;
+    KMeansBatch kmb[KM_GROUPS]; int km_groups = 1, km_groups_max = 1, km_groups_fixed = -1; hipStream_t km_streams[KM_GROUPS] = {nullptr}; bool batch_km = false;
     // flow-mask stage of a round, batched the same way (FlowMaskBatch, dyna.hpp): in the non-split rounds every stream of a group holds the state its homography needs
     // once the round thread has waited for the previous round's tails, so the homographies are computed on the pool WHILE the batched k-means runs and the stage's
     // kernels run once for the group.  One set per handle: phase B of two steps is never in flight together (a submit finishes the previous step's tails before it returns).
     FlowMaskBatch fmb[KM_GROUPS]; bool fm_batch = true; std::atomic<long long> fm_frames{0};
-    // RAG stage of SegAndMerge in the same rounds, batched per chunk of the group's frames (RagBatch, dyna.hpp; pipeline_tails.cpp: tail_rag_begin) on the group's k-means
+    // RAG stage of SegAndMerge in the same rounds, batched per chunk of the group's frames (RagBatch, dyna.hpp; pipeline_frame.cpp: tail_rag_begin) on the group's k-means
     // stream, which is idle while the round's tails run.  rag_chunk: frames per set of launches (< 1: the whole group); rag_planes: input planes of slab per frame
     struct RagRound { std::mutex m; int expected = 0, arrived = 0; std::vector<int> joined, stream_of_slot; };      // frames of the round / through their first task, packed slots per chunk, whose slot
     RagBatch ragb[KM_GROUPS]; RagRound ragr[KM_GROUPS]; bool rag_batch = true; int rag_chunk = 32, rag_planes = 64; std::atomic<long long> rag_frames{0}, rag_fallback{0};
@@ -96,9 +94,7 @@ struct sind_pipe {
     DevBuf<uint8_t> bgr_d, gray, gray_orb, pool; DevBuf<uint16_t> depth_d;
     // two sets of phase-A outputs: step i's phase A (GPU) overlaps with step i-1's phase B (host threads + small kernels)
     struct StepBuf {
-        DevBuf<float> U, V; DevBuf<uint16_t> depth_dev; PinnedBuf<uint16_t> depth_h;       /* page-locked: the 157 MB device-to-host copy of a step must not block the enqueueing thread */ std::vector<OrbFrameResult> orb; std::vector<OccResult> occ; bool pending = false;
-        DevBuf<uint8_t> occ2_dev, depthN_dev;                  // per frame: plane-edge mask and normalised depth for the tails' RAG statistics (filled by the CalOccluded tasks)
-        DevBuf<float> grid_dev; PinnedBuf<float> grid_h;       // flow at the 10-px sample grid of every frame (DD:1182-1204), gathered right after the dense flow
+        PhaseAOut a; bool pending = false;
         std::atomic<int> occ_next{0};                          // next frame for the CalOccluded runner tasks
         std::vector<OccCtx> occ_ctx; PinnedBuf<uint8_t> grow_in_h, grow_pair_h; PinnedBuf<int8_t> grow_member_h; PinnedBuf<int> grow_status_h;      // per frame: state between the halves, the grow's input block and results
         std::vector<hipEvent_t> grow_ev; std::unique_ptr<std::atomic<int>[]> grow_left, grow_state; std::atomic<int> occ_next2{0}; int grow_q = 4;      // per chunk: first halves still out, 0 = not launched / 1 = launched / < 0 = failed
@@ -106,20 +102,21 @@ struct sind_pipe {
         // depth half of the tails (k-means, SegAndMerge) run ahead, underneath the dense flow (synchronous steps only): per-frame results,
         // and a gate per frame that opens when both its CalOccluded result and the stream's previous depth stage are there
         bool depth_ahead = false; std::vector<DepthStageOut> dout; std::unique_ptr<std::atomic<int>[]> gate; TaskGroup depth_group;
-        std::vector<int> depth_rc; std::vector<std::string> depth_err;
-        TaskGroup fm_group[4];                                         // per k-means group: the homography tasks of a round's batched flow-mask stage
-        TaskGroup occ_group, tail_group, km_tails[4]; int km_groups = 1, km_first[5] = {0, 0, 0, 0, 0};       /* (4 = sind_pipe::KM_GROUPS) the step's own partition of the streams */ std::vector<int> occ_rc, tail_rc, dchain_rc; std::vector<std::string> occ_err, tail_err, dchain_err;      /* dchain_*: the depth chain of a stream in two-chain mode (its flow chain writes tail_*: two workers, two slots) */
+        TaskGroup fm_group[KM_GROUPS];      // per k-means group: the homography tasks of a round's batched flow-mask stage
+        TaskGroup occ_group, tail_group, km_tails[KM_GROUPS]; int km_groups = 1, km_first[KM_GROUPS + 1] = {0};       // the step's own partition of the streams
+        Failures occ_fail, depth_fail, tail_fail, dchain_fail;      // per frame: CalOccluded, depth stage run ahead; per stream: tail, depth chain (two chains / split rounds: its flow chain writes tail_fail -- two workers, two slots)
         std::vector<int> active, first; std::vector<uint64_t> state_hash;      // tails of stream s run for first[s] <= t < active[s] (empty: 0 / all T); per-frame state fingerprints [S][T][2]
-        bool few_chain = false;                                        // this step runs a handful of streams as per-stream chains (see phase_b_start)
-        bool two_chain = false; std::unique_ptr<std::atomic<int>[]> fgate; int fgate_n = 0;      // ... each as a depth chain running ahead of a flow chain; per frame: depth stage done + previous flow stage done
+        // the frames [t0, t1) of stream s whose tails run in this step (set_active_frames and replay admit 0 <= first[s] and active[s] <= T only: no clamp)
+        struct Frames { int t0, t1; };
+        bool ragged() const { return !first.empty() || !active.empty(); } Frames range(int s, int T) const { return {first.empty() ? 0 : first[s], active.empty() ? T : active[s]}; }
+        bool runs(int s, int t) const { const Frames r = range(s, t + 1); return r.t0 <= t && t < r.t1; }      // (t + 1: any bound above t stands for "all T")
+        TailPlan plan{TailSchedule::Chains, false};      // what phase_b_start decided for this step (host/pipe_schedule.hpp)
+        std::unique_ptr<std::atomic<int>[]> fgate; int fgate_n = 0;      // two chains / split rounds, per frame: depth stage done + previous flow stage done
         int retain_tag = -1;                                           // >= 0: the phase-A outputs of this step are kept under this tag when its tails are done
-        std::vector<int> large_motion;                                 // per pair k = s * T + t: took the second DeepFlow pass (every flow slice writes its own range)
     } sb[2];
-    // Phase-A outputs of a step kept beyond the step (sind_pipe_retain_next): everything the tails read -- dense flow, depth copies, ORB front results,
-    // CalOccluded results, sample-grid flow -- so that sind_pipe_replay can run the stateful tails of those frames again from another state without
+    // Phase-A outputs of a step kept beyond the step (sind_pipe_retain_next), so that sind_pipe_replay can run the stateful tails of those frames again from another state without
     // computing the state-free 99 % of the frame again (the repair runs of the chunked sequence mode).  Buffers come from a reserve made up front.
-    struct Retained { DevBuf<float> U, V, grid_dev; DevBuf<uint16_t> depth_dev; PinnedBuf<uint16_t> depth_h; PinnedBuf<float> grid_h; DevBuf<uint8_t> occ2_dev, depthN_dev;
-                      std::vector<OrbFrameResult> orb; std::vector<OccResult> occ; std::vector<int> large_motion; int tag = -1; };
+    struct Retained { PhaseAOut a; int tag = -1; };
     std::vector<std::unique_ptr<Retained>> spare, kept; int retain_tag_next = -1;
     int cur = 0; int occ_workers = 24;
     // CPU tokens (common.hpp) for the software-pipelined steps, where CalOccluded runners and tails compete for the quota (measured: throttled periods 7 -> 2
@@ -133,7 +130,8 @@ struct sind_pipe {
     // Chunked sequences (sindslam_amd/sequence.py): hashing = every tail leaves the fingerprint of its rolled state per frame (last_hash: the step whose results
     // were returned last, [S][T][2]); active_next = per-stream number of frames whose TAILS run in the next step (one step only; empty = all T)
     std::vector<int> last_large_motion;      // large-motion flags of the step whose results were returned last, [S][T] (sind_pipe_large_motion)
-    bool hashing = false; std::vector<uint64_t> last_hash; std::vector<int> active_next; int chain_max_streams = 12; bool split_rounds = true;      /* rounds: the next k-means waits for the depth halves of the tails only (pipeline_tails.cpp) */
+    int last_schedule = -1;      // TailSchedule of that step (sind_pipe_last_schedule); -1: none yet
+    bool hashing = false; std::vector<uint64_t> last_hash; std::vector<int> active_next; int chain_max_streams = 12; bool split_rounds = true;      /* rounds: the next k-means waits for the depth halves of the tails only (pipeline_rounds.cpp) */
     double stage_ms[6] = {0}; double tail_wait_ms = 0; double sor_ms = 0, sor_union_ms = 0, sor_bytes = 0; long long sor_launches = 0; int sor_slices = 1;      // launch groups of the large levels' solver in the last step (SorTimer kind 0: k_sor_wave by default, k_sor_stream with wave = 0)
     double sor_other_ms = 0, sor_other_bytes = 0; long long sor_other_launches = 0;                             // every other solver kernel outside k_coarse_chain (tiles, one-workgroup levels)
     SindHostGate gate;           // CPU tokens of this handle's pool tasks (common.hpp)
@@ -177,16 +175,23 @@ static inline int make_stream(hipStream_t* out, bool high_priority) {
     return SIND_OK;
 }
 
-// ---- the parts of the pipeline (pipeline_build.cpp: handle, streams, pool; pipeline_phase_a.cpp: the state-free batch of a step; pipeline_tails.cpp: the stateful tails
-// on the worker pool; pipeline_capi.cpp: the step entry points, state blobs, retained steps / replay, settings and statistics of the C ABI)
+// ---- the parts of the pipeline: pipeline_build.cpp (handle, streams, pool), pipeline_phase_a.cpp (the state-free batch of a step), phase B = pipeline_frame.cpp (what a frame's tail
+// does), pipeline_chains.cpp, pipeline_rounds.cpp, pipeline_phase_b.cpp (schedule decision, start, finish), pipeline_capi.cpp (the C ABI: steps, state blobs, replay, settings, statistics)
 struct PipeOut { uint8_t *dyna, *label, *mask; sind_keypoint* kps; int cap; int* nkp; uint8_t* desc; };
+typedef sind_pipe::StepBuf StepBuf;
 int pipe_build(sind_pipe* p, const sind_pipe_config* cfg);
 int ensure_dtails(sind_pipe* p);
 DynaTail* depth_half(sind_pipe* p, int s);
-int phase_a(sind_pipe* p, sind_pipe::StepBuf& sb, const uint8_t* bgr_dev, const uint16_t* depth_dev, double t[4], bool depth_ahead = false);
-void depth_task(sind_pipe* p, sind_pipe::StepBuf* sb, int k, int worker);
-void phase_b_start(sind_pipe* p, sind_pipe::StepBuf& sb, const PipeOut& o);
-int phase_b_finish(sind_pipe* p, sind_pipe::StepBuf& sb);
-int phase_b(sind_pipe* p, sind_pipe::StepBuf& sb, const PipeOut& o);
-void swap_phase_a_outputs(sind_pipe::StepBuf& sb, sind_pipe::Retained& r);
-
+int phase_a(sind_pipe* p, StepBuf& sb, const uint8_t* bgr_dev, const uint16_t* depth_dev, double t[4], bool depth_ahead = false);
+// (km / fm: the frame's share of a round's batched k-means and flow-mask stage, or null)
+bool tail_one(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t, int worker, const KmFrameResult* km, const FlowMasksReady* fm = nullptr);
+void tail_rag_begin(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t, int g, int worker, const KmFrameResult* km, const FlowMasksReady* fm);
+void depth_task(sind_pipe* p, StepBuf* sb, int k, int worker);
+void tail_task(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t, int worker);
+void depth_chain(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t0, int t1, int worker);
+void flow_chain(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t, int t1, int worker);
+void arm_flow_gates(sind_pipe* p, StepBuf& sb);
+void start_rounds(sind_pipe* p, StepBuf* sb, const PipeOut& o);
+void phase_b_start(sind_pipe* p, StepBuf& sb, const PipeOut& o);
+int phase_b_finish(sind_pipe* p, StepBuf& sb);
+int phase_b(sind_pipe* p, StepBuf& sb, const PipeOut& o);

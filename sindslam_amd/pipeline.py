@@ -159,6 +159,12 @@ class Pipeline:
         check(lib().sind_pipe_large_motion(self._h, ptr(out), out.size), "sind_pipe_large_motion")
         return out
 
+    SCHEDULES = ("chains", "flow_chains", "two_chains", "rounds", "split_rounds")
+
+    def last_schedule(self) -> str:
+        """which schedule the stateful tails of the step whose results were returned last took (csrc/host/pipe_schedule.hpp); the results do not depend on it"""
+        k = C.c_int(); check(lib().sind_pipe_last_schedule(self._h, C.byref(k)), "sind_pipe_last_schedule"); return self.SCHEDULES[k.value]
+
     def set_active_frames(self, frames_per_stream):
         """next step only: the stateful tail of stream s runs for its first frames_per_stream[s] frames (None = all)"""
         if frames_per_stream is None:
@@ -270,6 +276,7 @@ class PipelineGroup:
     def set_chain_max_streams(self, n): [p.set_chain_max_streams(n) for p in self.pipes]
     def state_hashes(self): return np.concatenate([p.state_hashes() for p in self.pipes])
     def large_motion(self): return np.concatenate([p.large_motion() for p in self.pipes])
+    def last_schedule(self): return [p.last_schedule() for p in self.pipes]
     def get_state_bytes(self): return self.pipes[0].get_state_bytes()
     def get_state(self, s=0): p, k = self._of(s); return p.get_state(k)
     def set_state(self, s, blob): p, k = self._of(s); p.set_state(k, blob)
