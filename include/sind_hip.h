@@ -1195,7 +1195,7 @@ int sindh_cloud_filter_outliers(int B, const sind_cloud_point* points, int strid
  * is restated from octomap 1.9 AS RECALLED (ColorOcTree, OccupancyOcTreeBase::insertRay / updateNodeLogOdds, OcTreeBaseImpl::computeRayKeys).  PARITY WITH A REAL
  * OCTOMAP BUILD IS UNPINNED; the contract is what is built and tested.  csrc/host/occmap.hpp is the one source of the arithmetic for host and device.
  *
- * The map is FLAT: every voxel lives at octomap's finest depth (16).  A voxel has a 3 x 16-bit key, known (0 / 1), logodds (FP32; 0 when it becomes known) and a
+ * The map is FLAT: every voxel lives at octomap's finest depth (16); inner nodes and pruned leaves exist in the SNAPSHOT TREE taken from it (further down).  A voxel has a 3 x 16-bit key, known (0 / 1), logodds (FP32; 0 when it becomes known) and a
  * colour r, g, b (255, 255, 255 when it becomes known).
  * Create: resolution (the reference: 0.020; accepted range [1e-6, 1e6]), prob_hit 0.7, prob_miss 0.4, clamp_min 0.1192, clamp_max 0.971, occ_thres (octomap's
  *   default 0.5; the reference sets 0.7 at :119) -- each probability, inside (0, 1), becomes (float) log(p / (1 - p)), once, on the host, with the C library.
@@ -1222,7 +1222,7 @@ int sindh_cloud_filter_outliers(int B, const sind_cloud_point* points, int strid
  * Queries: occupied = every known voxel with logodds >= occ_thres_log as a sind_cloud_point (x, y, z = (float) coord(key), its colour, a = 0), in octomap's
  *   leaf_iterator order: ascending Morton code of the key from bit 15 down, z the most significant bit of each triple, then y, then x (the sort runs on the host).  out
  *   may be NULL to get the count; more than cap: SIND_E_CAPACITY with *n_out filled.  read: for n keys [n][3] the known flag, the log-odds bits and r, g, b [n][3]
- *   (zeros for an unknown voxel).  size: the number of known voxels (NOT octomap's size(), which counts inner nodes).  clear.
+ *   (zeros for an unknown voxel).  size: the number of known voxels (NOT octomap's size(), which counts inner nodes: that is n_nodes of the snapshot tree).  clear.
  * Capacity: a key frame that would take the map beyond max_voxels known voxels returns SIND_E_CAPACITY and leaves every value, colour and known flag as they were; in
  *   a batch the key frames before it are in the map (as B calls would leave it), it and the later ones are not, and their stats are zero.  The table has 2 max_voxels
  *   slots or more and refuses claims beyond three quarters of them; slots claimed by a refused key frame stay claimed (and unknown) until clear, so after refused
@@ -1230,15 +1230,54 @@ int sindh_cloud_filter_outliers(int B, const sind_cloud_point* points, int strid
  * DELIBERATE DIVERGENCES from the reference's octomap:
  *   1. Non-finite points.  The reference feeds them to (int) floor(..), which is undefined; here they are skipped (no ray, no colour, not counted).  A non-finite origin
  *      is SIND_E_ARG.  Likewise a ray whose FP32 length underflows to 0 never ends in octomap's loop; here a key that would leave [0, 65536) ends it.
- *   2. No pruning and no .ot / fullMapToMsg serialisation.  octomap merges eight sibling leaves of equal value and colour into their parent.  Log-odds are unaffected (a
+ *   2. The map itself is never pruned.  octomap merges eight sibling leaves of equal value and colour into their parent WHILE IT INSERTS.  Log-odds are unaffected (a
  *      pruned leaf equals its children and is expanded by copying before any update).  Two things differ: occupied reports the 8^k finest voxels where the reference
- *      reports one coarser leaf centre, and an integrateNodeColor that meets a pruned leaf colours all of that leaf's voxels at once (tests/occmap_ref.py carries a
- *      pruning tree that counts these; profiles/occmap.txt has the count on real data).
+ *      reports one coarser leaf centre (the snapshot tree below reports the coarser leaf), and an integrateNodeColor that meets a pruned leaf colours all of that
+ *      leaf's voxels at once (tests/occmap_ref.py carries a pruning tree that counts these; profiles/occmap.txt has the count on real data).  Inner nodes, prune(),
+ *      the .ot file and fullMapToMsg's data come from the SNAPSHOT TREE, which is the fully pruned form of the flat map: it differs from the reference's online tree
+ *      exactly where the flat map already differs (voxels coloured while they sat in a pruned leaf), and beyond that in inner-node colours that octomap keeps from a
+ *      prune / expand history, which are white here.  (On the CPU, with the pruning tree of tests/occmap_ref.py as the online tree: where no colour met a pruned
+ *      leaf the online tree's leaves equal the snapshot's, even without a final prune(); where one did, they do not: tests/test_occmap_tree_cpu.py.)
  * sind_occmap_insert: points [B][stride] with n_points[b] used (a host array; points is a device pointer if inputs_on_device), origins [B][3] floats (host);
  *   stats [B] (may be NULL).  sind_occmap_insert_generated reads the clouds that the last sind_cloud_generate on `cloud` left on the device (the reference inserts the
  *   UNFILTERED tempCloudOneFrame, so it does not chain on the filter); SIND_E_STATE if B exceeds that call's B.  Eleven launches per key frame whatever the cloud, on
  *   the handle's stream, ONE host wait per call, no allocation per call (the workspace lives on the handle; stats grows once if B > 8).
  * sindh_occmap_* are the host twin (libsind_host.so too): the literal sequential loops over a flat hash map, the same arithmetic, host arrays only.
+ *
+ * SNAPSHOT TREE (sind_occmap_tree, sind_occmap_write_ot): octomap's tree over the flat map as it is at the call -- what octotree->write(".ot") (:184) saves,
+ * what octomap_msgs::fullMapToMsg (:327-340) publishes and what the leaf loop (:349-365) walks.  Read-only on the map; insert, occupied, read, size and clear are as
+ * before.  Restated from octomap 1.9 AS RECALLED (OcTreeBaseImpl::prune / pruneNode / isNodeCollapsible, OccupancyOcTreeBase::updateInnerOccupancy,
+ * ColorOcTree::getAverageChildColor, OcTreeBaseImpl::writeData, AbstractOcTree::write); PARITY WITH A REAL OCTOMAP BUILD, and with its file format, IS UNPINNED.
+ * csrc/host/occmap_tree.hpp is the one source of the arithmetic for host and device.
+ * Tree: depth 16.  The child index at depth d (0 .. 15) of a key is ((kz >> (15-d)) & 1) << 2 | ((ky >> (15-d)) & 1) << 1 | ((kx >> (15-d)) & 1), the Morton order of
+ *   occupied.  Every known voxel is a depth-16 leaf, every proper prefix of a known key an inner node.  An empty map is an empty tree: 0 nodes, no root.
+ * Inner value: the maximum log-odds of the existing children (updateOccupancyChildren), compared as floats.
+ * Inner colour: inner_colour = 0: (255, 255, 255), which is what the reference's tree holds (its updateInnerOccupancy() call is commented out, :321).
+ *   inner_colour = 1: getAverageChildColor, bottom-up: per channel the integer sum over the existing children whose colour is not (255, 255, 255), integer-divided by
+ *   their number; white if there is none; an inner child contributes its own average.
+ * Pruning (prune = 1, OcTreeBaseImpl::prune()): for depth 15 down to 1 (the root is never pruned) every node of that depth that is collapsible -- all eight children
+ *   exist, none has children, all eight are equal in value (float ==) and colour -- becomes a leaf with child 0's value and colour; a depth that prunes nothing ends
+ *   the walk.  On a tree that starts flat ONE BOTTOM-UP SWEEP OVER THE LEVELS GIVES THE SAME RESULT (a node can only become collapsible through children that
+ *   collapsed one level below, and below a level that pruned nothing no level can prune): the device does the sweep, the host twin the literal loop.  prune = 0 keeps
+ *   every depth-16 leaf.  Pruning and inner_colour commute (eight equal children average and maximise to themselves).
+ * Stream (writeData): the nodes in pre-order, 8 bytes each: the FP32 value, r, g, b, then one byte with bit i set iff child i exists (0 for a leaf); the children
+ *   follow in ascending i.  8 n_nodes bytes.
+ * .ot file (sind_occmap_write_ot): the lines "# Octomap OcTree file", "# (feel free to add / change comments, but leave the first line as it is!)", "#",
+ *   "id ColorOcTree", "size <n_nodes>", "res <resolution, as a default-precision C++ ostream prints it>", "data", each ended by '\n'; then the stream.  fullMapToMsg is
+ *   {id: "ColorOcTree", resolution, binary: false, data: the stream}.
+ * Leaves: in pre-order, which is leaf_iterator order: a sind_cloud_point (the centre, the colour, a = 0) and the depth.  The centre per axis of a leaf of depth d that
+ *   holds the key k is (float) (((double) ((int) (k >> (16-d) << (16-d)) - 32768) + 0.5 * (double) (1 << (16-d))) * resolution).  occupied_only = 1 keeps the leaves
+ *   with value >= occ_thres_log: with prune = 1 the list the reference's loop walks, with prune = 0 the list of sind_occmap_occupied, byte for byte.
+ * Stats: n_nodes (octomap's size()), n_inner, n_leaves, n_pruned (nodes collapsed), n_occupied_leaves, leaves_at_depth[17]; they do not depend on occupied_only.
+ * Call: data (cap_bytes), leaves / leaf_depth (cap_leaves) and n_leaves_out may each be NULL (leaf_depth only together with leaves); with no outputs the call returns
+ *   the counts: stats, and in *n_leaves_out the leaves the list would hold.  8 n_nodes > cap_bytes or more leaves than cap_leaves: SIND_E_CAPACITY with the counts
+ *   filled and no output written, as sind_occmap_occupied does.  The call never changes the map and keeps nothing between calls.
+ * Workspace and limit: the table of inner nodes is allocated at the first tree call and kept on the handle: as many slots as the flat table has (the power of two >=
+ *   max(1024, 2 max_voxels)), 64 bytes each, and A TREE MAY HAVE HALF AS MANY INNER NODES AS THERE ARE SLOTS (so at least max_voxels, and at least 512); a map whose
+ *   tree needs more (N scattered voxels can need 16 N) returns SIND_E_CAPACITY, without counts.  The output staging grows to the largest tree asked for.
+ * Device schedule: 18 launches bottom-up (a sweep that resets the table, the voxels, one kernel per depth 15 .. 0) and, if any output is asked for, 16 top-down (one per
+ *   depth), on the handle's stream, whatever the map; TWO host waits per call (the counts, then the copies sized by them), one if no output is asked for.
+ *   sind_occmap_write_ot does the same and then writes the file on the host.
  */
 #define SIND_OCCMAP_MIN_RESOLUTION 1e-6
 #define SIND_OCCMAP_MAX_RESOLUTION 1e6
@@ -1248,7 +1287,7 @@ int sind_occmap_create(double resolution, double prob_hit, double prob_miss, dou
                        int device, sind_occmap** out);
 int sind_occmap_destroy(sind_occmap* h);
 int sind_occmap_clear(sind_occmap* h);
-int sind_occmap_size(sind_occmap* h);                        /* >= 0: the known voxels */
+int sind_occmap_size(sind_occmap* h);                        /* >= 0: the known voxels; octomap's size() is sind_occmap_tree's n_nodes */
 int sind_occmap_insert(sind_occmap* h, int B, const sind_cloud_point* points, int stride, const int* n_points, const float* origins, int inputs_on_device,
                        sind_occmap_stats* stats);
 int sind_occmap_insert_generated(sind_occmap* h, sind_cloud* cloud, int B, const float* origins, sind_occmap_stats* stats);
@@ -1263,6 +1302,17 @@ int sindh_occmap_size(sindh_occmap* h);
 int sindh_occmap_insert(sindh_occmap* h, int B, const sind_cloud_point* points, int stride, const int* n_points, const float* origins, sind_occmap_stats* stats);
 int sindh_occmap_occupied(sindh_occmap* h, sind_cloud_point* out, int cap, int* n_out);
 int sindh_occmap_read(sindh_occmap* h, const uint16_t* keys, int n, uint8_t* known, uint32_t* logodds, uint8_t* rgb);
+
+/* The snapshot tree (contract above, "SNAPSHOT TREE"). */
+typedef struct sind_occmap_tree_stats { int n_nodes, n_inner, n_leaves, n_pruned, n_occupied_leaves; int leaves_at_depth[17]; } sind_occmap_tree_stats;
+int sind_occmap_tree(sind_occmap* h, int prune, int inner_colour, int occupied_only,
+                     uint8_t* data, size_t cap_bytes,                                                      /* the writeData stream; may be NULL */
+                     sind_cloud_point* leaves, uint8_t* leaf_depth, int cap_leaves, int* n_leaves_out,     /* each may be NULL (leaf_depth only with leaves) */
+                     sind_occmap_tree_stats* stats);
+int sind_occmap_write_ot(sind_occmap* h, int prune, int inner_colour, const char* path);                   /* the .ot file: header + stream */
+int sindh_occmap_tree(sindh_occmap* h, int prune, int inner_colour, int occupied_only, uint8_t* data, size_t cap_bytes, sind_cloud_point* leaves, uint8_t* leaf_depth,
+                      int cap_leaves, int* n_leaves_out, sind_occmap_tree_stats* stats);
+int sindh_occmap_write_ot(sindh_occmap* h, int prune, int inner_colour, const char* path);
 
 /* helper of the rgbd_tum_noros-shaped harness (sindslam_amd/harness.py): PNG scanline reconstruction, raw = h x (1 + stride) bytes */
 int sind_png_unfilter(const uint8_t* raw, int h, int stride, int bytes_per_pixel, uint8_t* out);

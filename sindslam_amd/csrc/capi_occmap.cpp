@@ -6,6 +6,7 @@
 #include "occmap_dev.hpp"
 
 static_assert(sizeof(sind_occmap_stats) == sizeof(sind::OccStats), "the ABI struct is the kernels' struct");
+static_assert(sizeof(sind_occmap_tree_stats) == sizeof(sind::OccTreeStats), "the ABI struct is the shared struct");
 
 struct sind_occmap {
     int device = 0, maxVoxels = 0, maxPoints = 0, S = 0, gen = 0; sind::OccParams P{}; hipStream_t stream = nullptr;
@@ -13,6 +14,10 @@ struct sind_occmap {
     DevBuf<sind::OccStats> stats; DevBuf<sind::CloudPoint> staging;
     // queries: allocated at first use, then reused
     DevBuf<unsigned long long> occKey; DevBuf<uint32_t> occCol; DevBuf<int> occCount; DevBuf<uint8_t> readBuf;
+    // the snapshot tree: the node workspace is allocated at the first tree call (sized from max_voxels) and kept; the outputs grow with the largest tree asked for
+    int treeT = 0, treeMaxInner = 0; DevBuf<sind::OccTreeNode> treeNode; DevBuf<int> treeList, treeCtl;
+    DevBuf<unsigned long long> treeData; DevBuf<sind::CloudPoint> treeLeaves; DevBuf<uint8_t> treeDepth;
+    sind::OccTreeArrays tree() { sind::OccTreeArrays t{}; t.T = treeT; t.maxInner = treeMaxInner; t.node = treeNode.p; t.list = treeList.p; t.ctl = treeCtl.p; return t; }
     std::vector<sind::OccStats> h_stats; std::vector<unsigned long long> h_occKey; std::vector<uint32_t> h_occCol;
     sind::OccArrays arrays() {
         sind::OccArrays a{}; a.S = S; a.limit = S - S / 4; a.maxVoxels = maxVoxels;
@@ -54,6 +59,44 @@ int check_frames(sind_occmap* h, int B, const int* n, int stride, const float* o
         if (!sind::occ_finite(origins[3 * b], origins[3 * b + 1], origins[3 * b + 2])) { sind_set_error("%s: origin %d is not finite", who, b); return SIND_E_ARG; }
         if (n[b] > h->maxPoints) { sind_set_error("%s: cloud %d has %d points, the handle holds %d", who, b, n[b], h->maxPoints); return SIND_E_CAPACITY; }
     }
+    return SIND_OK;
+}
+
+// The bottom-up half and the call's first wait: the counts.  nListed = the leaves the list will hold.
+int tree_counts(sind_occmap* h, int prune, int innerColour, int occupiedOnly, sind_occmap_tree_stats* stats, int* nListed, const char* who) {
+    hipStream_t s = h->stream;
+    if (!h->treeT) {
+        const int T = h->S, maxInner = h->S / 2;                       // the header's rule: the flat table's slots, half of them inner nodes at most
+        SIND_TRY(h->treeNode.alloc(T)); SIND_TRY(h->treeList.alloc(maxInner)); SIND_TRY(h->treeCtl.alloc(sind::OCCT_NCTL));
+        h->treeT = T; h->treeMaxInner = maxInner;
+    }
+    SIND_TRY(sind::launch_occmap_tree_up(h->arrays(), h->tree(), h->P, prune != 0, innerColour != 0, s));
+    int ctl[sind::OCCT_NCTL];
+    HIP_TRY(hipMemcpyAsync(ctl, h->treeCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));                                 // wait 1: the counts
+    if (ctl[sind::OCCT_OVERFLOW]) {
+        sind_set_error("%s: the tree has more than %d inner nodes (half the %d slots that max_voxels = %d gives)", who, h->treeMaxInner, h->treeT, h->maxVoxels);
+        return SIND_E_CAPACITY;
+    }
+    sind_occmap_tree_stats st{}; const int* coll = ctl + sind::OCCT_COLLAPSED;
+    st.n_nodes = ctl[sind::OCCT_NNODES]; st.n_leaves = ctl[sind::OCCT_NLEAVES]; st.n_inner = st.n_nodes - st.n_leaves; st.n_occupied_leaves = ctl[sind::OCCT_NOCC];
+    for (int d = 1; d < 16; d++) { st.n_pruned += coll[d]; st.leaves_at_depth[d] = coll[d] - 8 * coll[d - 1]; }      // a collapsed node is a leaf unless its parent collapsed too
+    st.leaves_at_depth[16] = st.n_leaves + 7 * st.n_pruned - 8 * coll[15];                                             // every collapse turns eight leaves into one
+    *stats = st; *nListed = occupiedOnly ? st.n_occupied_leaves : st.n_leaves;
+    return SIND_OK;
+}
+
+// The top-down half into host arrays of exactly n_nodes records / nListed leaves, and the call's second wait.  data, leaves and depth may each be NULL.
+int tree_outputs(sind_occmap* h, int occupiedOnly, const sind_occmap_tree_stats& st, int nListed, uint8_t* data, sind_cloud_point* leaves, uint8_t* depth) {
+    if ((!data && !leaves) || !st.n_nodes) return SIND_OK;
+    hipStream_t s = h->stream; sind::OccTreeOut o{};
+    if (data) { SIND_TRY(h->treeData.alloc(st.n_nodes)); o.data = h->treeData.p; o.capNodes = st.n_nodes; }
+    if (leaves) { SIND_TRY(h->treeLeaves.alloc(std::max(nListed, 1))); SIND_TRY(h->treeDepth.alloc(std::max(nListed, 1))); o.leaves = h->treeLeaves.p; o.depth = h->treeDepth.p; o.capLeaves = nListed; }
+    SIND_TRY(sind::launch_occmap_tree_down(h->arrays(), h->tree(), h->P, occupiedOnly != 0, o, s));
+    if (data) HIP_TRY(hipMemcpyAsync(data, o.data, (size_t)st.n_nodes * 8, hipMemcpyDeviceToHost, s));
+    if (leaves && nListed) HIP_TRY(hipMemcpyAsync(leaves, o.leaves, (size_t)nListed * sizeof(sind::CloudPoint), hipMemcpyDeviceToHost, s));
+    if (leaves && depth && nListed) HIP_TRY(hipMemcpyAsync(depth, o.depth, (size_t)nListed, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));                                 // wait 2: the copies sized by the counts
     return SIND_OK;
 }
 
@@ -171,6 +214,29 @@ int sind_occmap_read(sind_occmap* h, const uint16_t* keys, int n, uint8_t* known
     HIP_TRY(hipMemcpyAsync(rgb, dRgb, 3 * N, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(known, dKnown, N, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return SIND_OK;
+}
+
+int sind_occmap_tree(sind_occmap* h, int prune, int inner_colour, int occupied_only, uint8_t* data, size_t cap_bytes, sind_cloud_point* leaves, uint8_t* leaf_depth,
+                     int cap_leaves, int* n_leaves_out, sind_occmap_tree_stats* stats) {
+    if (!h || !stats || (leaves && cap_leaves < 0) || (leaf_depth && !leaves)) { sind_set_error("sind_occmap_tree: bad arguments"); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(h->device));
+    int nListed = 0;
+    SIND_TRY(tree_counts(h, prune, inner_colour, occupied_only, stats, &nListed, "sind_occmap_tree"));
+    if (n_leaves_out) *n_leaves_out = nListed;
+    if (data && (size_t)stats->n_nodes * 8 > cap_bytes) { sind_set_error("sind_occmap_tree: the stream has %zu bytes, capacity %zu", (size_t)stats->n_nodes * 8, cap_bytes); return SIND_E_CAPACITY; }
+    if (leaves && nListed > cap_leaves) { sind_set_error("sind_occmap_tree: %d leaves, capacity %d", nListed, cap_leaves); return SIND_E_CAPACITY; }
+    return tree_outputs(h, occupied_only, *stats, nListed, data, leaves, leaf_depth);
+}
+
+int sind_occmap_write_ot(sind_occmap* h, int prune, int inner_colour, const char* path) {
+    if (!h || !path) { sind_set_error("sind_occmap_write_ot: bad arguments"); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(h->device));
+    sind_occmap_tree_stats st; int nListed = 0;
+    SIND_TRY(tree_counts(h, prune, inner_colour, 0, &st, &nListed, "sind_occmap_write_ot"));
+    std::vector<uint8_t> data((size_t)st.n_nodes * 8);
+    SIND_TRY(tree_outputs(h, 0, st, nListed, data.data(), nullptr, nullptr));
+    if (!sind::occ_tree_write_file(path, sind::occ_tree_ot_header(st.n_nodes, h->P.res), data.data(), data.size())) { sind_set_error("sind_occmap_write_ot: cannot write %s", path); return SIND_E_ARG; }
     return SIND_OK;
 }
 

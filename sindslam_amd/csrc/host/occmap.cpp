@@ -6,12 +6,10 @@
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
-#include "occmap.hpp"
+#include "occmap_twin.hpp"
 #include "sind_hip.h"
 
 using namespace sind;
-
-struct sindh_occmap { OccParams P; int maxVoxels, maxPoints; std::unordered_map<uint64_t, OccVoxel> map; };
 
 namespace {
 

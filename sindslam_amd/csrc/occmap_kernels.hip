@@ -29,10 +29,6 @@ namespace {
 
 constexpr int OCC_TOUCH_BLOCKS = 1024;
 
-__device__ __forceinline__ unsigned occ_hash(unsigned long long k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned)k;
-}
 __device__ __forceinline__ void occ_fail(const OccArrays& a, int b) { atomicMin(&a.ctl[OCC_FAILED], b); a.ctl[OCC_OVERFLOW] = 1; }
 __device__ __forceinline__ bool occ_failed(const OccArrays& a) { return __atomic_load_n(&a.ctl[OCC_OVERFLOW], __ATOMIC_RELAXED) != 0; }
 
@@ -52,15 +48,6 @@ __device__ int occ_claim(const OccArrays& a, unsigned long long k, int b) {
         if (cur == k) return (int)h;
     }
     occ_fail(a, b); return -1;
-}
-__device__ int occ_lookup(const OccArrays& a, unsigned long long k) {
-    unsigned h = occ_hash(k) & (unsigned)(a.S - 1);
-    for (int probe = 0; probe < a.S; probe++, h = (h + 1) & (unsigned)(a.S - 1)) {
-        const unsigned long long cur = a.slot[h].key;
-        if (cur == k) return (int)h;
-        if (cur == OCC_EMPTY) return -1;
-    }
-    return -1;
 }
 // the first toucher of a slot in key frame `gen` appends it to the touched list
 __device__ __forceinline__ void occ_touch(const OccArrays& a, int slot, int gen) {
