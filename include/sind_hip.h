@@ -76,6 +76,13 @@ int sind_flow_set_wave_solver(sind_flow* f, int on, int target_items, int bands)
 /* how k_sor_wave cuts a w x h level of B pairs (host arithmetic only, no GPU needed): out = {column strips, kept columns per strip, row bands, kept rows per band}.  A strip works on
  * 128 columns -- its kept ones plus 10 on every side that is not an image border --, a band on its kept rows plus 10 on every cut side. */
 int sind_flow_wave_layout(int w, int h, int B, int target_items, int bands, int out[4]);
+/* k_sor_wave cuts its column strips over groups of `group` consecutive images laid side by side (image i of a group at the columns [i * period, i * period + w) of a virtual
+ * row; the period is even and > w, the columns between two images stay zero): 0 = the group size of 1 .. 32 that needs the fewest waves per launch (default), 1 = every image
+ * on its own (sind_flow_wave_layout's launch), n = exactly min(n, images of the launch) (tests).  Same bits either way. */
+int sind_flow_set_wave_pack(sind_flow* f, int group);
+/* the layout under that setting (host arithmetic only): out = {images per group, period, column strips per GROUP, kept columns per strip, row bands, kept rows per band}.  The
+ * strips are sind_flow_wave_layout's uniform ones over the (group - 1) * period + w columns of the virtual row; the bands are sind_flow_wave_layout's. */
+int sind_flow_wave_pack_layout(int w, int h, int B, int target_items, int bands, int group, int out[6]);
 /* which kernel solves a w x h level of B pairs with `total` SOR iterations under the given settings (host arithmetic only, no GPU needed; for tests of the policy).  The settings are
  * the setters' arguments: mode / fuse / tile_w / tile_h as in sind_flow_set_sor_tiled, wave as `on` of sind_flow_set_wave_solver, stream_min_b = images per launch from which the
  * large levels get their own solver (80 in every handle), latency_tiles and coarse_chain as in their setters.  out[0] = kernel: 0 k_coarse_chain (the whole level in one launch),

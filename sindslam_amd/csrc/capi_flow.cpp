@@ -248,6 +248,12 @@ int sind_flow_wave_layout(int w, int h, int B, int target_items, int bands, int 
     if (w < 1 || h < 1 || B < 1 || target_items < 0 || bands < 0 || !out) return SIND_E_ARG;
     sind::sor_wave_layout(w, h, B, target_items > 0 ? target_items : sind::SolverCfg().wave_items, bands, &out[0], &out[1], &out[2], &out[3]); return SIND_OK;
 }
+int sind_flow_set_wave_pack(sind_flow* f, int group) { if (!f || group < 0) return SIND_E_ARG; f->eng.solver.wave_group = group; return SIND_OK; }
+int sind_flow_wave_pack_layout(int w, int h, int B, int target_items, int bands, int group, int out[6]) {
+    if (w < 1 || h < 1 || B < 1 || target_items < 0 || bands < 0 || group < 0 || !out) return SIND_E_ARG;
+    const sind::SorWavePack L = sind::sor_wave_pack_layout(w, h, B, target_items > 0 ? target_items : sind::SolverCfg().wave_items, bands, group);
+    out[0] = L.G; out[1] = L.Pw; out[2] = L.strips; out[3] = L.IW; out[4] = L.bands; out[5] = L.BH; return SIND_OK;
+}
 int sind_flow_set_coef_kernel(sind_flow* f, int variant) { if (!f || variant < 0 || variant > 3) return SIND_E_ARG; f->eng.solver.coef_kernel = variant == 3 ? 1 : variant; f->eng.solver.coef_xcd = variant == 3 ? 0 : 1; return SIND_OK; }
 int sind_flow_set_sor(sind_flow* f, int mode, int fuse, int tile_w) {
     if (tile_w != 64 && tile_w != 128) { sind_set_error("sind_flow_set_sor: bad arguments"); return SIND_E_ARG; }

@@ -67,6 +67,8 @@ struct SolverCfg {
                                // headline step 1571-1607 pairs/s at 1024, 1522-1578 at 680, 1534-1542 at 2048, profiles/r05/ab_wave_bench.txt)
     int wave_bands = 0;        // > 0: exactly this many row bands (tests)
     int wave_prefetch = 2;     // k_sor_wave: steps between a row's request and its take-over (1 .. 3; 16 registers per row in flight)
+    int wave_group = 0;        // k_sor_wave: images laid side by side in one virtual row that the column strips are cut over (sor_wave_pack_layout): 0 = the group size of 1 .. 32 that
+                               // needs the fewest waves, 1 = every image on its own, n = exactly min(n, images of the launch) (tests)
     int coef_kernel = 1;       // 1: k_coef_lanes (neighbours from lanes; short forms of sqrt and c / sqrt), 2: k_coef_lanes with the IEEE forms, 0: k_coef (neighbours from memory)
     int coef_xcd = 1;          // k_coef_lanes: the tiles of a pair go to one XCD (1) or round-robin over the eight in grid order (0: A/B timing)
     bool coarse_chain = true;  // levels that are one workgroup's work (<= 4096 pixels): the whole level (all of them, in a pyramid) in ONE launch (k_coarse_chain, flow_coarse.hip);
@@ -88,9 +90,12 @@ int launch_level_up(hipStream_t s, FlowPlanes& P, int sw, int sh, const float* I
 // flow_coarse.hip: the one-workgroup levels of a pyramid (or one such level) in one launch
 int coarse_level_P(int w, int h);
 int launch_sor_tile(hipStream_t s, FlowPlanes& P, int w, int h, int B, int iters, float omega);
-// flow_wave.hip: 5 iterations of a level as one-wave row pipelines (column strips x row bands x images); the result is in P.dWu / P.dWv (swapped with their partners)
-int launch_sor_wave(hipStream_t s, FlowPlanes& P, int w, int h, int B, float omega, int target_items, int force_bands, int prefetch);
+// flow_wave.hip: 5 iterations of a level as one-wave row pipelines (column strips x row bands x groups of images); the result is in P.dWu / P.dWv (swapped with their partners)
+int launch_sor_wave(hipStream_t s, FlowPlanes& P, int w, int h, int B, float omega, int target_items, int force_bands, int prefetch, int force_group);
 void sor_wave_layout(int w, int h, int B, int target_items, int force_bands, int* strips, int* IW, int* bands, int* BH);
+// the same level with G consecutive images side by side at a period of Pw columns: strips per GROUP and their kept width; the row bands are sor_wave_layout's
+struct SorWavePack { int G, Pw, strips, IW, bands, BH; };
+SorWavePack sor_wave_pack_layout(int w, int h, int B, int target_items, int force_bands, int force_group);
 int sor_tile_count(int w, int h, int iters);
 // flow_stream.hip: 5 iterations of a level of h >= 4 rows as one workgroup per (column strip, image); the result is in P.dWu / P.dWv (swapped with their partners)
 int launch_sor_stream(hipStream_t s, FlowPlanes& P, int w, int h, int B, float omega, int wg_cap);

@@ -313,7 +313,7 @@ int sor_iterations(hipStream_t s, FlowPlanes& P, int w, int h, int B, float omeg
             case SOR_COLOR:         SIND_TRY(launch_sor_color(s, P, w, h, B, omega)); *nlaunch += 1; break;
             case SOR_LATENCY_TILES: SIND_TRY(launch_sor_tile(s, P, w, h, B, k, omega)); break;
             case SOR_ONE_WORKGROUP: SIND_TRY(launch_sor_fused_level(s, P, w, h, B, k, omega)); break;
-            case SOR_WAVE:          SIND_TRY(launch_sor_wave(s, P, w, h, B, omega, C.wave_items, C.wave_bands, C.wave_prefetch)); break;
+            case SOR_WAVE:          SIND_TRY(launch_sor_wave(s, P, w, h, B, omega, C.wave_items, C.wave_bands, C.wave_prefetch, C.wave_group)); break;
             case SOR_STREAM:        SIND_TRY(launch_sor_stream(s, P, w, h, B, omega, C.stream_wg_cap)); break;
             case SOR_FUSED_TILES:   SIND_TRY(launch_sor_fused_tiles(s, P, w, h, B, k, omega, C)); break;
             default: sind_set_error("sor_iterations: the coarse chain solves its levels itself"); return SIND_E_ARG;

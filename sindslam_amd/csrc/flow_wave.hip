@@ -17,7 +17,13 @@
 //     computes 10 columns / rows beyond what it keeps on every cut side;
 //   * a row is requested PF = 2 steps before it enters the window, into a separate set of registers (16 per row in flight; a step is 1 - 2 us); reciprocals RN(1 / a) are
 //     formed at the take-over (sor_rcp), 0 for pixels outside the image: their update returns exactly 0;
-//   * consecutive workgroups go to the same XCD, so the strips of an image share their halo columns and seam cache lines in that XCD's L2.
+//   * consecutive workgroups go to the same XCD, so the strips of an image share their halo columns and seam cache lines in that XCD's L2;
+//   * the strips are cut over GROUPS of images (sor_wave_pack_layout): the G images of a group lie side by side in a virtual row, image i at the columns [i Pw, i Pw + w), and
+//     the same uniform strips are cut over its (G - 1) Pw + w columns, so a group pays for one partly empty last strip instead of every image for its own.  Only the
+//     prologue knows: a lane decodes its virtual column once into (image of the group, true column), its constant offset is (image x w x h + column) x 4 under descriptors
+//     that span the group's images, and in0 / in1 are true only for columns inside an image that exists.  Pw is even and > w: a lane's two pixels lie in one image, true
+//     and virtual column have the same parity (the t & 1 rule above holds), and between two images lie one or two columns that load nothing and keep du = dv = 0 with
+//     reciprocal 0 -- the lanes right of an image of the one-image layout, and the value an image border reads there.  G = 1 is that layout.
 // Same float operations on the same operands in the same order as SS_UPDATE / sor_pixel: bit-identical results (tests/test_flow_gpu.py, against the oracle).
 // Where it stands: 227 us per launch of 512 pairs against 192 us with a tenth of the arithmetic (memory alone) and 171 us with every load from the cache
 // (instructions alone); -DSWV_SKIP=n / -DSWV_ROWFIX build those two experiments (profiles/tools/wave_skip.sh).
@@ -50,7 +56,7 @@ __device__ __forceinline__ void swv_update(SwvRow& R, const SwvRow& U, const Swv
 
 extern __shared__ float swv_lds[];
 struct SwvFlight { swv_u2 a11, a12, a22, b1, b2, w, u, v; };          // the row in flight (requested a step before it is taken over)
-// buffer descriptors of this wave's image (scalar registers; an access is descriptor + scalar row offset + the lane's constant column offset), lane constants
+// buffer descriptors of this wave's group of images (scalar registers; an access is descriptor + scalar row offset + the lane's constant column offset), lane constants
 struct SwvCtx {
     __amdgpu_buffer_rsrc_t pA11, pA12, pA22, pB1, pB2, pW, pU, pV, oU, oV;
     float* lbase; float omega; unsigned xoff, row_bytes; int ys; unsigned nrows; int by0, by1; bool in0, in1, keep0, keep1;
@@ -136,29 +142,42 @@ __device__ __forceinline__ void swv_steps(SwvRow (&win)[SWV_NW], SwvFlight (&FL)
 }
 
 // PF: rows in flight (a row is requested PF steps before it is taken over; 16 registers each)
+// An item is (strip, band, group): the G images of a group lie side by side in a virtual row, image i at the columns [i Pw, i Pw + w), and the strips are cut over that row.
 template <int PF>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-k_sor_wave(int strips, int bands, int items, int w, int h, int IW, int BH, float omega, const float* __restrict__ gA11, const float* __restrict__ gA12, const float* __restrict__ gA22,
-           const float* __restrict__ gB1, const float* __restrict__ gB2, const float* __restrict__ gW, const float* __restrict__ gU, const float* __restrict__ gV,
+k_sor_wave(int strips, int bands, int items, int w, int h, int IW, int BH, int G, int Pw, int B, float omega, const float* __restrict__ gA11, const float* __restrict__ gA12,
+           const float* __restrict__ gA22, const float* __restrict__ gB1, const float* __restrict__ gB2, const float* __restrict__ gW, const float* __restrict__ gU, const float* __restrict__ gV,
            float* __restrict__ gUo, float* __restrict__ gVo) {
     const int lane = threadIdx.x;
-    // consecutive items -- the column strips of one band of one image, which share their halo columns and the cache lines at their seams -- go to the SAME XCD (workgroups are
+    // consecutive items -- the column strips of one band of one group, which share their halo columns and the cache lines at their seams -- go to the SAME XCD (workgroups are
     // handed to the eight XCDs round-robin): the second reader of a line finds it in that XCD's L2
     const int per_xcd = (int)gridDim.x >> 3, item = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
     if (item >= items) return;
-    const int strip = item % strips, rest = item / strips, band = rest % bands, image = rest / bands;
-    // columns: keeps [ix0, ix1), works on [ex0, ex0 + 128); rows: keeps [by0, by1), works on [ys, ye)
-    const int ix0 = strip * IW, ix1 = min(ix0 + IW, w), ex0 = max(ix0 - SWV_HALO, 0);
+    const int strip = item % strips, rest = item / strips, band = rest % bands, group = rest / bands;
+    const int image0 = group * G, present = min(G, B - image0);               // the group's images (the last group may be short)
+    const int vw = (present - 1) * Pw + w;                                   // its virtual row
+    // columns of the virtual row: keeps [ix0, ix1), works on [ex0, ex0 + 128); rows: keeps [by0, by1), works on [ys, ye)
+    const int ix0 = strip * IW, ix1 = min(ix0 + IW, vw), ex0 = max(ix0 - SWV_HALO, 0);
+    if (ix0 >= vw) return;                                                   // (a strip beyond a short last group keeps nothing)
     const int by0 = band * BH, by1 = min(by0 + BH, h), ys = max(by0 - SWV_HALO, 0), ye = min(by1 + SWV_HALO, h);
     const unsigned nrows = (unsigned)(ye - ys);
-    const int x0 = ex0 + 2 * lane;
-    const bool in0 = x0 < w, in1 = x0 + 1 < w;
-    const bool keep0 = x0 >= ix0 && x0 < ix1, keep1 = x0 + 1 >= ix0 && x0 + 1 < ix1;
-    const size_t base = (size_t)image * w * h;
-    const unsigned plane_bytes = (unsigned)w * (unsigned)h * 4u;
-    auto rs = [&](const float* plane) { return __builtin_amdgcn_make_buffer_rsrc((void*)(plane + base), 0, plane_bytes, 0x00020000); };
+    // the lane's virtual column -> (image within the group, true column).  Pw and xv are even: x0 is even and x0 + 1 < Pw, so both pixels lie in the same period, and a
+    // pixel's true column has the parity of its virtual one
+    const int xv = ex0 + 2 * lane, li = xv / Pw, x0 = xv - li * Pw;
+    // (the four flags as comparisons of two lane constants with scalars, as in the one-image layout -- xa: the true column, w for a lane in no image; xk: the virtual column
+    // of a lane in an image, else -2 --, and opaque to the compiler: it forms the flags again where it needs them instead of holding four lane masks in scalar registers
+    // through the loop, which spilled 290 scalar registers more)
+    int xa = li < present ? x0 : w, xk = (li < present && x0 < w) ? xv : -2;
+    asm volatile("" : "+v"(xa), "+v"(xk));
+    const bool in0 = xa < w, in1 = xa + 1 < w;
+    const bool keep0 = xk >= ix0 && xk < ix1, keep1 = in1 && xk + 1 >= ix0 && xk + 1 < ix1;
+    // descriptors over the group's images: no lane can address memory outside them (the host keeps G planes below 2^31 bytes)
+    const size_t base = (size_t)image0 * w * h;
+    const unsigned plane = (unsigned)w * (unsigned)h, group_bytes = (unsigned)present * plane * 4u;
+    auto rs = [&](const float* p) { return __builtin_amdgcn_make_buffer_rsrc((void*)(p + base), 0, group_bytes, 0x00020000); };
+    const unsigned xoff = in0 ? ((unsigned)li * plane + (unsigned)x0) * 4u : 0u;
     const SwvCtx C{rs(gA11), rs(gA12), rs(gA22), rs(gB1), rs(gB2), rs(gW), rs(gU), rs(gV), rs(gUo), rs(gVo),
-                   swv_lds + lane, omega, (unsigned)x0 * 4u, (unsigned)w * 4u, ys, nrows, by0, by1, in0, in1, keep0, keep1};
+                   swv_lds + lane, omega, xoff, (unsigned)w * 4u, ys, nrows, by0, by1, in0, in1, keep0, keep1};
     const int Tb = (ys - 1 - PF) & ~1, Tend = ye + SWV_NS - 1;    // steps Tb .. Tend - 1 (Tb even: step K of the loop body updates pixel K & 1; row ys is requested in step ys - 1 - PF)
     int lo = 0;
     {
@@ -175,26 +194,51 @@ k_sor_wave(int strips, int bands, int items, int w, int h, int IW, int BH, float
     }
 }
 
-// Column strips and row bands of a w x h level.  One strip: w <= 128; two: the kept width + 10 <= 128; more: + 20.  The bands are the launch's parallelism knob: every cut
+// Uniform column strips over W columns.  One strip: W <= 128; two: the kept width + 10 <= 128; more: + 20.  The kept width is even.
+static void swv_strips(int W, int* strips, int* IW) {
+    int n = 1, iw = (W + 1) & ~1;
+    if (W > 128) { for (n = 2;; n++) { iw = (divup(W, n) + 1) & ~1; if (iw + (n == 2 ? SWV_HALO : 2 * SWV_HALO) <= 128) break; } }
+    *strips = n; *IW = iw;
+}
+// Column strips and row bands of a w x h level, every image on its own.  The bands are the launch's parallelism knob: every cut
 // costs 20 rows of recomputation, so there are only as many as it takes to give the chip `target_items` waves (8 per compute unit = 2048 fill it).
 void sor_wave_layout(int w, int h, int B, int target_items, int force_bands, int* strips, int* IW, int* bands, int* BH) {
-    int n = 1, iw = (w + 1) & ~1;
-    if (w > 128) { for (n = 2;; n++) { iw = (divup(w, n) + 1) & ~1; if (iw + (n == 2 ? SWV_HALO : 2 * SWV_HALO) <= 128) break; } }
+    int n, iw;
+    swv_strips(w, &n, &iw);
     int nb = force_bands > 0 ? force_bands : (int)std::min<long long>(std::max(1, h / 40), std::max<long long>(1, divup(target_items, n * std::max(B, 1))));
     nb = std::max(1, std::min(nb, h));
     const int bh = divup(h, nb);
     nb = divup(h, bh);
     *strips = n; *IW = iw; *bands = nb; *BH = bh;
 }
+// The same level with the images of a launch in groups of G, a group's images side by side in one virtual row: image i at the columns [i Pw, i Pw + w), Pw even and > w, so
+// that neighbours are separated by one (odd w) or two (even w) columns that stay zero -- what an image border reads today.  The strips are the uniform ones over the
+// (G - 1) Pw + w columns of that row; an interior strip pays its 20 halo columns once per 108 kept ones wherever the images' seams fall, and only a group's last strip is
+// partly empty.  G: the size in 1 .. 32 with the fewest strips per launch (the smaller at a tie: G = 1 is sor_wave_layout's launch); force_group > 0: min(force_group, B).
+// The row bands are sor_wave_layout's.  G planes stay below 2^31 bytes: a lane's offset within its group is 32 bits.
+SorWavePack sor_wave_pack_layout(int w, int h, int B, int target_items, int force_bands, int force_group) {
+    SorWavePack L{1, (w + 2) & ~1, 0, 0, 0, 0};
+    sor_wave_layout(w, h, B, target_items, force_bands, &L.strips, &L.IW, &L.bands, &L.BH);
+    const int gmax = (int)std::min<long long>(std::min(32, std::max(B, 1)), std::max<long long>(1, (1ll << 29) / ((long long)w * h)));
+    const int lo = force_group > 0 ? std::min(force_group, gmax) : 2, hi = force_group > 0 ? lo : gmax;
+    long long best = (long long)B * L.strips;
+    for (int G = std::max(lo, 2); G <= hi; G++) {
+        int n, iw;
+        swv_strips((G - 1) * L.Pw + w, &n, &iw);
+        const long long total = (long long)divup(B, G) * n;
+        if (force_group > 0 || total < best) { best = total; L.G = G; L.strips = n; L.IW = iw; }
+    }
+    return L;
+}
 
-int launch_sor_wave(hipStream_t s, FlowPlanes& P, int w, int h, int B, float omega, int target_items, int force_bands, int prefetch) {
-    int strips, IW, bands, BH;
-    sor_wave_layout(w, h, B, target_items, force_bands, &strips, &IW, &bands, &BH);
+int launch_sor_wave(hipStream_t s, FlowPlanes& P, int w, int h, int B, float omega, int target_items, int force_bands, int prefetch, int force_group) {
     if ((long long)w * h > (1ll << 28)) { sind_set_error("launch_sor_wave: %d x %d level", w, h); return SIND_E_ARG; }
+    const SorWavePack L = sor_wave_pack_layout(w, h, B, target_items, force_bands, force_group);
     const size_t shm = (size_t)SWV_NW * SWV_ROWF * sizeof(float);
-    const int items = strips * bands * B;
+    const int items = L.strips * L.bands * divup(B, L.G);
     auto kern = prefetch <= 1 ? k_sor_wave<1> : prefetch == 2 ? k_sor_wave<2> : k_sor_wave<3>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(divup(items, 8) * 8)), dim3(64), shm, s, strips, bands, items, w, h, IW, BH, omega, P.A11, P.A12, P.A22, P.b1, P.b2, P.wgt, P.dWu, P.dWv, P.dWu2, P.dWv2);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(divup(items, 8) * 8)), dim3(64), shm, s, L.strips, L.bands, items, w, h, L.IW, L.BH, L.G, L.Pw, B, omega, P.A11, P.A12, P.A22, P.b1, P.b2, P.wgt,
+                       P.dWu, P.dWv, P.dWu2, P.dWv2);
     std::swap(P.dWu, P.dWu2); std::swap(P.dWv, P.dWv2);       // strips and bands read each other's halo: not in place
     return SIND_OK;
 }

@@ -33,6 +33,11 @@ class FlowStage:
         bands > 0: exactly that many row bands (tests); same bits"""
         check(lib().sind_flow_set_wave_solver(self._h, 1 if on else 0, int(target_items), int(bands)), "sind_flow_set_wave_solver")
 
+    def set_wave_pack(self, group: int = 0):
+        """k_sor_wave's column strips over groups of images laid side by side: 0 = the group size that needs the fewest waves (default), 1 = every image on its own,
+        n = exactly min(n, images of the launch) (tests); same bits"""
+        check(lib().sind_flow_set_wave_pack(self._h, int(group)), "sind_flow_set_wave_pack")
+
     def set_coef_kernel(self, variant: int):
         check(lib().sind_flow_set_coef_kernel(self._h, int(variant)), "sind_flow_set_coef_kernel")
 
