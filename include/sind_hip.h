@@ -1376,6 +1376,32 @@ int sind_seq_stats(sind_seq* q, double out16[16]);
 sind_pipe* sind_seq_pipeline(sind_seq* q);        /* the main pipeline of this rank (sind_pipe_stats, sind_pipe_gather_masks, ...) */
 int sind_seq_step_outputs(sind_seq* q, const uint8_t** dyna, const uint8_t** label, const uint8_t** mask_dilated);   /* the page-locked [S][T][H][W] arrays of the last delivered step */
 
+/* ---- SegAndMerge piece extraction on the device: parity-test access to its border following (k_piece_contours) -------------------------------------------------------
+ * n bit planes (host, [n][height][ceil(width / 64)] words, bit x & 63 of word x / 64) -> their external borders from the device (one launch, one wave per plane) and from
+ * the host function (find_contours, external only).  Per plane: counts [3] = contours, points, status (0; 1 = more than cap_contours contours; 2 = more than cap_points
+ * chain points: the device then stops and reports what it had, the host reports the totals and fills what fits); hdr [cap_contours][10] = start x, start y, length,
+ * offset of the first point, box x0 y0 x1 y1, twice the contour area (low word, high word); pts [cap_points][2] = x, y of every point, contour after contour. */
+int sind_debug_contours(const unsigned long long* planes, int n, int width, int height, int device, int cap_contours, int cap_points,
+                        int* counts_gpu, int* hdr_gpu, int* pts_gpu, int* counts_host, int* hdr_host, int* pts_host);
+/* The whole stage (reference DynaDetect.cc:664-729 and the ranking :733-752): n frames of k cluster planes [n][k][words] (all k are cut), occ1 and labelForSegEdge (already
+ * dilated) [n][words], depth [n][height][width] u16 -> the pieces from the device stage (one batched object of capacity n: 13 launches whatever the frames hold) and from the
+ * host function; ONE frame (n = 1; width a multiple of 64, height of 8) instead runs through a tail of its own with the switch on: its capacity-1 stage on its own stream,
+ * the fallback to the host function, the ranking and k_piece_commit (planes and piece_of then come from the device).  Per frame and side: info [4] = number of pieces C,
+ * status (0; else a plane exceeded a capacity: batched, the device results are not to be used; one frame, the tail fell back and the results are the host function's), and for one
+ * frame the tail's counters frames_on_device, frames_fallen_back (0 otherwise);
+ * the first min(C, cap) pieces in discovery order: recs [cap][12] = cluster, start x, start y, contour length, twice the contour area (low, high word), hasLianjie, box
+ * x0 y0 x1 y1, rank after the host's sort (-1 when C is 0 or above 254); vals [cap][2] = area, cz; piece and connection planes [cap][words]; piece_of [height * width] =
+ * rank of the piece that owns the pixel, C + 1 elsewhere (untouched when nothing is ranked).  The sort and piece_of are the host's on both sides. */
+int sind_debug_seg_pieces(const unsigned long long* planes, int k, const unsigned long long* occ1, const unsigned long long* label_edge, const uint16_t* depth, int n, int width, int height,
+                          float depth_scale, int device, int cap, int* info_gpu, int* recs_gpu, float* vals_gpu, unsigned long long* pieces_gpu, unsigned long long* conn_gpu, uint8_t* piece_of_gpu,
+                          int* info_host, int* recs_host, float* vals_host, unsigned long long* pieces_host, unsigned long long* conn_host, uint8_t* piece_of_host);
+/* The switch: SegAndMerge's piece extraction of a handle on the GPU instead of the host.  Off by default; the results do not depend on it.  A frame in which a plane
+ * exceeds a capacity of the device stage runs the host function and is counted as fallen back.  The second call of each pair only reads. */
+int sind_dyna_set_device_pieces(sind_dyna* d, int on);
+int sind_dyna_device_pieces(sind_dyna* d, int* on, long long* frames_on_device, long long* frames_fallen_back);
+int sind_pipe_set_device_pieces(sind_pipe* p, int on);      /* every stream's tail; not while a step is pending */
+int sind_pipe_device_pieces(sind_pipe* p, int* on, long long* frames_on_device, long long* frames_fallen_back);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,15 @@ int sind_debug_set_kmeans_fused_min_batch(int b) { if (b < 1) return SIND_E_ARG;
 // debug != 0: keep what sind_dyna_debug reports (intermediate images of every stage, the raw and refined flow copied back every frame); off by default
 int sind_dyna_set_debug(sind_dyna* d, int on) { if (!d) return SIND_E_ARG; d->debug = on != 0; d->tail.keep_debug = d->debug; return SIND_OK; }
 // overlap != 0 (default): the depth half of a frame runs beside its dense flow (own stream, own host thread); 0 = one after the other.  Same results.
+// on != 0: SegAndMerge's piece extraction of this handle runs on the GPU (DynaTail::device_pieces); off by default.  Same results
+int sind_dyna_set_device_pieces(sind_dyna* d, int on) { if (!d) { sind_set_error("sind_dyna_set_device_pieces: null handle"); return SIND_E_ARG; } d->tail.device_pieces = on != 0; return SIND_OK; }
+int sind_dyna_device_pieces(sind_dyna* d, int* on, long long* frames_on_device, long long* frames_fallen_back) {
+    if (!d) { sind_set_error("sind_dyna_device_pieces: null handle"); return SIND_E_ARG; }
+    if (on) *on = d->tail.device_pieces ? 1 : 0;
+    if (frames_on_device) *frames_on_device = d->tail.n_pieces_device;
+    if (frames_fallen_back) *frames_fallen_back = d->tail.n_pieces_fallback;
+    return SIND_OK;
+}
 int sind_dyna_set_overlap(sind_dyna* d, int on) { if (!d) return SIND_E_ARG; d->overlap = on != 0; return SIND_OK; }
 // mean milliseconds per sind_dyna_detect call since the last reset: [0..5] upload, dense flow (calling thread), wait for the depth half after the flow, flow masks + fusion,
 // depth half (its own thread when overlapped), whole call; [6..11] the tail's stages: flow masks, k-means, label preparation, CalOccluded, SegAndMerge, fusion.

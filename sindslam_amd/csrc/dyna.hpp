@@ -11,6 +11,8 @@
 #include "flow.hpp"
 #include "peac_grow.hpp"
 #include "host/host.hpp"
+#include "host/pieces.hpp"
+#include "pieces_dev.hpp"
 
 namespace sind {
 
@@ -167,12 +169,14 @@ private:
     std::vector<hipEvent_t> occ2_ev, done;
 };
 
-struct SegPiece { BitImg img, lianjie; bool hasLianjie = false; float area = 0, score = -10, cz = 0; };      // a piece of SegAndMerge (DD:668-760)
-
 class DynaTail {
 public:
     DynaConfig cfg; hipStream_t stream = nullptr; DynaDebug dbg; bool keep_debug = false;
     KmFuse km_fuse = g_km_fuse_default;      // copied when the object is made; never changes afterwards
+    // SegAndMerge's piece extraction on the GPU (PieceStage of pieces_dev.hpp at capacity 1, on this tail's stream) instead of the host function; off by default.  Same pieces
+    // in the same order, bit for bit; a frame in which a plane exceeds a capacity of the device stage runs the host function and counts as fallen back.  The workspaces
+    // are made by the first frame that takes the path.
+    bool device_pieces = false; long long n_pieces_device = 0, n_pieces_fallback = 0;
     int piece_threads = 1;        // host threads for the per-cluster piece extraction of SegAndMerge (> 1 only when host cores idle: a single stream in the in-order mode)
     int init(const DynaConfig& c, hipStream_t s);
     ~DynaTail() { for (auto& g : kmGraph) if (g) (void)hipGraphExecDestroy(g); }
@@ -194,7 +198,7 @@ public:
     int process_end(const int* rag, uint8_t* dyna_out, uint8_t* label_out);
     DynaTail* rag_half() { return pendHalf ? pendHalf : this; }
     int rag_pieces() const { return (int)segAll.size(); }
-    bool rag_batchable() const { return segPre && segPre->occ2_dev && segPre->depthN_dev; }
+    bool rag_batchable() const { return !segOnDevice && segPre && segPre->occ2_dev && segPre->depthN_dev; }      // (pieces cut on the device stay there: RagBatch takes host planes, such a frame runs rag_own)
     const OccResult* rag_pre() const { return segPre; }
     void rag_pack(unsigned long long* pieces, unsigned long long* conn) const;
     int rag_own(const int** rag);
@@ -260,6 +264,17 @@ private:
     int depth_stage_end(DepthStageOut& out, const int* rag);
     int seg_pieces(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& labelForSegEdge, const uint16_t* depth_host);
     int seg_rag_gpu(const int** rag);
+    std::unique_ptr<PieceStage> pieceStage; PinnedBuf<unsigned long long> h_pieceIn, h_pieceOut; PinnedBuf<PieceRecDev> h_pieceRecs; PinnedBuf<PieceFrameHdr> h_pieceHdr; PinnedBuf<int> h_pieceNp;
+    int seg_pieces_device(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& labelForSegEdge, std::vector<SegPiece>& all, bool* done);      // dyna_pieces.cpp
+    bool segOnDevice = false;      // this frame's pieces were cut on the device: segAll holds their records only, the planes lie in planes_d (rank order), pieceOf in pieceOf_d
+    DevBuf<uint8_t> pieceOf_d; DevBuf<int> pieceOrder_d; PinnedBuf<int> h_pieceOrder; PinnedBuf<uint8_t> h_pieceOf;
+    int seg_pieces_commit();       // dyna_pieces.cpp: the rank order up, k_piece_commit
+public:
+    // parity-test access (sind_debug_seg_pieces, n = 1): this tail's own piece path -- switch, capacity-1 stage on its stream, fallback, ranking, commit -- on given planes.
+    // k cluster planes (all are cut), depth_dev on the device.  Afterwards `out` holds the pieces in RANK order with their planes and pieceOf, wherever they were made
+    int debug_seg_pieces(const unsigned long long* planes, int k, const unsigned long long* occ1, const unsigned long long* label_edge, const uint16_t* depth_host, const uint16_t* depth_dev,
+                         std::vector<SegPiece>& out, std::vector<uint8_t>& piece_of);
+private:
     void seg_finish(const int* rag, std::vector<uint8_t>& labelNew);
 };
 

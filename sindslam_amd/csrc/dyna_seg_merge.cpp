@@ -1,4 +1,4 @@
-// DynaDetect engine, SegAndMergeV2 (DD:653-1018, cal_hist :1685-1739): pieces on the host, region-adjacency statistics on the GPU (per frame, or RagBatch for one frame
+// DynaDetect engine, SegAndMergeV2 (DD:653-1018, cal_hist :1685-1739): pieces on the host (host/pieces.hpp; opt-in on the GPU: dyna_pieces.cpp), region-adjacency statistics on the GPU (per frame, or RagBatch for one frame
 // of every stream of a k-means group), greedy merge on the host.
 #include <algorithm>
 #include <atomic>
@@ -17,67 +17,21 @@ int DynaTail::seg_pieces(const std::vector<BitImg>& allLabels, const BitImg& occ
     std::vector<Piece>& all = segAll; all.clear();
     double tf = tick_ms();
     #define FLAP(i) { const double t_ = tick_ms(); t_fine[i] += t_ - tf; tf = t_; }
-    const EllipseElem e4(4), e9(9), e10(10);
-    const BitImg occDil = occ1.dilated(e10);
-    const float depth_weight = 1.5f;
-    // pieces of one depth cluster (DD:668-760); the clusters are independent, the result keeps the cluster order
-    auto pieces_of = [&](int i, std::vector<Piece>& out, bool timed) {
-        const BitImg& orig = allLabels[i];
-        double tq = tick_ms();
-        #define QLAP(i) { if (timed) { const double t_ = tick_ms(); t_fine[i] += t_ - tq; tq = t_; } }
-        BitImg each = orig; each.andnot(occ1);
-        { const Rect eb = each.bbox(); if (eb.empty()) return; each = each.opened_rows(e4, eb.y0, eb.y1); }
-        QLAP(12)
-        std::vector<Contour> contours; find_contours(each, contours, true);
-        QLAP(13)
-        for (const Contour& c : contours) {
-            if (!(c.size() > 50 && contour_area(c) > 80)) continue;
-            tq = tick_ms();
-            const Rect bb = contour_bbox(c);
-            Piece p; p.img.create(W, H); draw_filled(p.img, c);
-            p.img = p.img.dilated(e9, bb.y0, bb.y1); p.img.and_rows(orig, bb.y0 - 4, bb.y1 + 4);       // the 9x9 element reaches 4 rows up and down
-            p.area = (float)p.img.count_rows(bb.y0 - 4, bb.y1 + 4);
-            QLAP(14)
-            BitImg t1(W, H); draw_thick2(t1, c); t1.andnot_rows(occDil, bb.y0 - 1, bb.y1 + 1); t1.and_rows(labelForSegEdge, bb.y0 - 1, bb.y1 + 1);
-            if (t1.count_rows(bb.y0 - 1, bb.y1 + 1) > 20) {
-                std::vector<Contour> c2; const Rect r2{std::max(bb.x0 - 2, 0), std::max(bb.y0 - 2, 0), std::min(bb.x1 + 2, W - 1), std::min(bb.y1 + 2, H - 1)};
-                find_contours(t1, c2, true, &r2);
-                std::vector<const Contour*> kept; for (const Contour& q : c2) if (q.size() >= 30) kept.push_back(&q);
-                if (!kept.empty()) { p.lianjie.create(W, H); draw_filled(p.lianjie, kept); p.hasLianjie = true; }
-            }
-            QLAP(15)
-            // myCluster::calCenterPoint (DD:256-293): float sums in row-major order; only z is used afterwards
-            { float f3 = 0.f; const Rect ib = p.img.bbox();
-              for (int y = ib.y0; y <= ib.y1; y++) { const uint64_t* r = p.img.row(y);
-                for (int k = 0; k < p.img.wpr; k++) { uint64_t m = r[k]; while (m) { const int x = (k << 6) + __builtin_ctzll(m); m &= m - 1;
-                    const uint16_t d = depth_host[(size_t)y * W + x];
-                    // (float)d / depthScale >= 6 is monotonic in d: compared against the first raw value that satisfies it (zInvalidFrom, init())
-                    float pzv = 0.f; if (!((int)d >= zInvalidFrom || d == 0)) { const float depth2 = (float)d * invDepthScale; pzv = (float)(depth2 * depth_weight); }
-                    f3 += pzv; } } }
-              p.cz = f3 / p.area; }
-            QLAP(16)
-            out.push_back(std::move(p));
-        }
-        #undef QLAP
-    };
-    const int nCl = std::max(0, (int)allLabels.size() - 1);
-    if (piece_threads > 1 && nCl > 1) {        // a stream alone on the GPU (in-order sequence mode) leaves host cores idle: the clusters go to a few helper threads
-        std::vector<std::vector<Piece>> per(nCl); std::atomic<int> next{0}; std::vector<std::thread> team;
-        auto work = [&] { for (int i; (i = next.fetch_add(1)) < nCl;) pieces_of(i, per[i], false); };
-        for (int t = 1; t < std::min(piece_threads, nCl); t++) team.emplace_back(work);
-        work();
-        for (auto& t : team) t.join();
-        for (auto& v : per) for (Piece& q : v) all.push_back(std::move(q));
-    } else for (int i = 0; i < nCl; i++) pieces_of(i, all, true);
+    bool on_device = false;
+    if (device_pieces) SIND_TRY(seg_pieces_device(allLabels, occ1, labelForSegEdge, all, &on_device));      // (counts the frame as on the device or as fallen back)
+    segOnDevice = on_device;
+    if (!on_device) seg_pieces_host(allLabels.data(), std::max(0, (int)allLabels.size() - 1), occ1, labelForSegEdge, depth_host, zInvalidFrom, invDepthScale, piece_threads, t_fine, all);      // (host/pieces.hpp)
     FLAP(6)
     const int C = (int)all.size();
     dbg.nClusters = C;
-    if (C == 0) return SIND_OK;
-    if (C > 254) { all.clear(); sind_set_error("seg_and_merge: %d pieces exceed the 8-bit label range of the reference", C); return SIND_E_CAPACITY; }
-    for (Piece& p : all) p.score = (float)(p.area * 0.0003f - p.cz);
-    std::sort(all.begin(), all.end(), [](const Piece& a, const Piece& b) { return a.score > b.score; });
-    segPieceOf.assign(N, (uint8_t)(C + 1));       // index of the piece that owns a pixel (the reference paints the pieces in score order)
-    for (int i = 0; i < C; i++) all[i].img.paint_u8(segPieceOf.data(), W, (uint8_t)i);
+    if (C == 0) { segOnDevice = false; return SIND_OK; }
+    if (C > 254) { all.clear(); segOnDevice = false; sind_set_error("seg_and_merge: %d pieces exceed the 8-bit label range of the reference", C); return SIND_E_CAPACITY; }
+    seg_pieces_rank(all);
+    if (on_device) SIND_TRY(seg_pieces_commit());      // the planes stay on the device, in rank order in the RAG stage's layout; pieceOf is painted there and comes back with the RAG counters
+    else {
+        segPieceOf.assign(N, (uint8_t)(C + 1));       // index of the piece that owns a pixel (the reference paints the pieces in score order)
+        for (int i = 0; i < C; i++) all[i].img.paint_u8(segPieceOf.data(), W, (uint8_t)i);
+    }
     FLAP(10)
     #undef FLAP
     return SIND_OK;
@@ -97,15 +51,22 @@ int DynaTail::seg_rag_gpu(const int** rag_out) {
     double tf = tick_ms();
     #define FLAP(i) { const double t_ = tick_ms(); t_fine[i] += t_ - tf; tf = t_; }
     const int wpr = W / 64; const size_t pw = (size_t)H * wpr;
-    SIND_TRY(h_planes.alloc((size_t)3 * C * pw)); SIND_TRY(h_rag.alloc((size_t)3 * C * C + C + (size_t)C * 256));
-    unsigned long long* planes = h_planes.p; const size_t planes_n = (size_t)3 * C * pw;
+    SIND_TRY(h_rag.alloc((size_t)3 * C * C + C + (size_t)C * 256));
+    const size_t planes_n = (size_t)3 * C * pw;
     // plane sets: [0, C) pieces, [C, 2C) their 7x7 dilations (formed on the GPU from the first set), [2C, 3C) connection areas
-    rag_pack(planes, planes + (size_t)2 * C * pw);
-    FLAP(10)
-    SIND_TRY(planes_d.alloc(planes_n)); SIND_TRY(rag_d.alloc((size_t)3 * C * C + C + (size_t)C * 256));
-    FLAP(11)
-    HIP_TRY(hipMemcpyAsync(planes_d.p, planes, (size_t)C * pw * 8, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(planes_d.p + (size_t)2 * C * pw, planes + (size_t)2 * C * pw, (size_t)C * pw * 8, hipMemcpyHostToDevice, stream));
+    if (segOnDevice) {         // k_piece_commit wrote the first and the third set already (seg_pieces_commit, which sized planes_d): no pack, no upload
+        SIND_TRY(rag_d.alloc((size_t)3 * C * C + C + (size_t)C * 256));
+        if (planes_d.n < planes_n) { sind_set_error("seg_rag_gpu: the committed planes are missing"); return SIND_E_STATE; }
+    } else {
+        SIND_TRY(h_planes.alloc((size_t)3 * C * pw));
+        unsigned long long* planes = h_planes.p;
+        rag_pack(planes, planes + (size_t)2 * C * pw);
+        FLAP(10)
+        SIND_TRY(planes_d.alloc(planes_n)); SIND_TRY(rag_d.alloc((size_t)3 * C * C + C + (size_t)C * 256));
+        FLAP(11)
+        HIP_TRY(hipMemcpyAsync(planes_d.p, planes, (size_t)C * pw * 8, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(planes_d.p + (size_t)2 * C * pw, planes + (size_t)2 * C * pw, (size_t)C * pw * 8, hipMemcpyHostToDevice, stream));
+    }
     SIND_TRY(launch_dilate_planes(stream, planes_d.p, planes_d.p + (size_t)C * pw, C, W, H, 7, rag_d.p, (int)((size_t)3 * C * C + C + (size_t)C * 256)));      // also clears the RAG accumulators
     const uint8_t* occ2_use = pre && pre->occ2_dev ? pre->occ2_dev : occ2_d.p;
     if (pre && pre->occ2_dev && pre->occ2_event) HIP_TRY(hipStreamWaitEvent(stream, pre->occ2_event, 0));       // uploaded on the CalOccluded runner's stream without a host wait
@@ -117,7 +78,9 @@ int DynaTail::seg_rag_gpu(const int** rag_out) {
     SIND_TRY(launch_rag_stats(stream, planes_d.p, C, W, H, wpr, occ2_use, depthN_use, ov_d, ovp_d, lj_d, la_d, hist_dd, true));
     PinnedBuf<int>& rag = h_rag;
     HIP_TRY(hipMemcpyAsync(rag.data(), rag_d.p, ((size_t)3 * C * C + C + (size_t)C * 256) * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (segOnDevice) HIP_TRY(hipMemcpyAsync(h_pieceOf.p, pieceOf_d.p, N, hipMemcpyDeviceToHost, stream));      // pieceOf rides under the same wait
     HIP_TRY(sind_stream_wait(stream));
+    if (segOnDevice) segPieceOf.assign(h_pieceOf.p, h_pieceOf.p + N);
     FLAP(8)
     #undef FLAP
     *rag_out = rag.data();

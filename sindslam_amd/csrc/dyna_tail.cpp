@@ -17,8 +17,7 @@ namespace sind {
 // ======================================================================================================= tail
 int DynaTail::init(const DynaConfig& c, hipStream_t s) {
     cfg = c; stream = s; W = c.W; H = c.H; N = W * H;
-    invDepthScale = 1.0f / cfg.depthScale; zInvalidFrom = 65536;
-    for (int d = 65535; d >= 0; d--) { if ((float)(uint16_t)d / cfg.depthScale >= (float)(uint16_t)6) zInvalidFrom = d; else break; }
+    invDepthScale = 1.0f / cfg.depthScale; zInvalidFrom = z_invalid_from(cfg.depthScale);
     if (W % 64 != 0 || W % 8 != 0 || H % 8 != 0) { sind_set_error("DynaTail: width must be a multiple of 64 and height of 8 (got %dx%d)", W, H); return SIND_E_ARG; }
     reset();
     SIND_TRY(km.init(W, H, 1)); SIND_TRY(occ.init(cfg, 1));       // the k-means chain's and the CalOccluded front's workspaces for one frame (dyna_kmeans.cpp, dyna_occluded.cpp)
@@ -121,7 +120,7 @@ int DynaTail::depth_stage_begin(const uint16_t* depth_host, const uint16_t* dept
     else SIND_TRY(cal_occluded(depth_host, depth_dev, out.totalArea, occ1, occ2));
     LAP(3)
     out.label3.assign(N, 0);
-    segAll.clear(); segDepthDev = depth_dev; segPre = pre && pre->ready ? pre : nullptr;
+    segAll.clear(); segOnDevice = false; segDepthDev = depth_dev; segPre = pre && pre->ready ? pre : nullptr;
     if (!allLabels.empty()) SIND_TRY(seg_pieces(allLabels, occ1, labelForSegEdge, depth_host));
     LAP(4)
     #undef LAP

@@ -6,11 +6,57 @@
 #pragma once
 #include <deque>
 #include "bitimg.hpp"
+#ifndef SIND_HD
+#if defined(__HIPCC__)
+#define SIND_HD __host__ __device__
+#else
+#define SIND_HD
+#endif
+#endif
 
 namespace sind {
 
 struct PtI { int x, y; };
 typedef std::vector<PtI> Contour;
+
+// The border-following state machine itself (icvFetchContour), ONE source for the host (find_contours below, on its byte copy) and the device (k_piece_contours of
+// depth_pieces.hip, on 2-bit cells): the walk around one border that starts at cell i0 = (x0, y0) of a 0-framed image with rows of w cells.  Px is the pixel accessor:
+// nz(i) = the cell is not background, one(i) = it still holds the unmarked value 1, set(i, end) = mark it (end: with the "border leaves to the right" flag).
+// emit(x, y) takes the points in order and returns false when it has no room.  At most max_steps points are walked: a data-independent bound for the device, INT_MAX on the
+// host.  Returns the number of points, or -1 when a bound was hit.  Directions: 0 = +x, then counter-clockwise on the screen (1 = +x -y, 2 = -y, ...).
+SIND_HD inline int dir_dx(int s) { return (int)((0x901Au >> (2 * (s & 7))) & 3u) - 1; }      // {1, 1, 0, -1, -1, -1, 0, 1}
+SIND_HD inline int dir_dy(int s) { return (int)((0xA901u >> (2 * (s & 7))) & 3u) - 1; }      // {0, -1, -1, -1, 0, 1, 1, 1}
+template <class Px, class Emit>
+SIND_HD inline int trace_border(Px& px, int w, int i0, int x0, int y0, bool is_hole, Emit& emit, int max_steps) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    auto delta = [w](int s) { return dir_dy(s) * w + dir_dx(s); };      // (no indexed local array on the device: it would live in scratch memory)
+#else
+    const int dtab[8] = {1, -w + 1, -w, -w - 1, -1, w - 1, w, w + 1};
+    auto delta = [&dtab](int s) { return dtab[s & 7]; };
+#endif
+    int cx = x0, cy = y0, n = 0;
+    int i1, i3, i4 = -1;
+    int s, s_end; s_end = s = is_hole ? 0 : 4;
+    do { s = (s - 1) & 7; i1 = i0 + delta(s); } while (!px.nz(i1) && s != s_end);
+    if (s == s_end) { px.set(i0, true); return emit(cx, cy) ? 1 : -1; }
+    i3 = i0;
+    for (;;) {
+        s_end = s; s = s < 15 ? s : 15;
+        while (s < 15) { i4 = i3 + delta(++s); if (px.nz(i4)) break; }
+        s &= 7;
+        if ((unsigned)(s - 1) < (unsigned)s_end) px.set(i3, true);
+        else if (px.one(i3)) px.set(i3, false);
+        if (n >= max_steps || !emit(cx, cy)) return -1;
+        n++;
+        cx += dir_dx(s); cy += dir_dy(s);
+        if (i4 == i0 && i3 == i1) break;
+        i3 = i4; s = (s + 4) & 7;
+    }
+    return n;
+}
+// the host's cells: signed chars 0 / 1 / mark / mark | -128
+struct BytePx { signed char* img; int mark;
+    bool nz(int i) const { return img[i] != 0; } bool one(int i) const { return img[i] == 1; } void set(int i, bool end) { img[i] = (signed char)(end ? (mark | -128) : mark); } };
 
 // Suzuki-Abe border following (OpenCV contours.cpp icvFetchContour semantics: 8-connectivity, start pixel order of the
 // raster scan, pixel marks so that every border is traced once).  external_only: outermost borders only.
@@ -33,9 +79,6 @@ inline void find_contours(const BitImg& src, std::vector<Contour>& out, bool ext
             for (int q = 0; q < 8; q++) { const uint64_t v = spread8((unsigned)(m >> (8 * q)) & 0xffu) & 0x0101010101010101ull; std::memcpy(o + ((k - kx0) << 6) + 8 * q, &v, 8); }
         }
     }
-    const int d8[8] = {1, -w + 1, -w, -w - 1, -1, w - 1, w, w + 1};
-    int deltas[16]; for (int i = 0; i < 16; i++) deltas[i] = d8[i & 7];
-    static const int cdx[8] = {1, 1, 0, -1, -1, -1, 0, 1}, cdy[8] = {0, -1, -1, -1, 0, 1, 1, 1};
     const int ox = xa - 1, oy = bb.y0 - 1;
     int nbd = 2;
     for (int y = 1; y < h - 1; y++) {
@@ -56,27 +99,11 @@ inline void find_contours(const BitImg& src, std::vector<Contour>& out, bool ext
             if (start && external_only && (is_hole || rowp[lnbd_x] > 0)) start = false;
             if (start) {
                 lnbd_x = x - (is_hole ? 1 : 0);
-                int px = x - (is_hole ? 1 : 0), py = y;
-                signed char* i0 = rowp + px; signed char *i1, *i3, *i4 = nullptr;
-                const int mark = external_only ? 2 : nbd;
+                const int px = x - (is_hole ? 1 : 0);
                 out.emplace_back(); Contour& c = out.back();
-                int s, s_end; s_end = s = is_hole ? 0 : 4;
-                do { s = (s - 1) & 7; i1 = i0 + deltas[s]; } while (*i1 == 0 && s != s_end);
-                if (s == s_end) { *i0 = (signed char)(mark | -128); c.push_back({px + ox, py + oy}); }
-                else {
-                    i3 = i0;
-                    for (;;) {
-                        s_end = s; s = std::min(s, 15);
-                        while (s < 15) { i4 = i3 + deltas[++s]; if (*i4 != 0) break; }
-                        s &= 7;
-                        if ((unsigned)(s - 1) < (unsigned)s_end) *i3 = (signed char)(mark | -128);
-                        else if (*i3 == 1) *i3 = (signed char)mark;
-                        c.push_back({px + ox, py + oy});
-                        px += cdx[s]; py += cdy[s];
-                        if (i4 == i0 && i3 == i1) break;
-                        i3 = i4; s = (s + 4) & 7;
-                    }
-                }
+                BytePx cells{img.data(), external_only ? 2 : nbd};
+                auto emit = [&c](int ex, int ey) { c.push_back({ex, ey}); return true; };
+                trace_border(cells, w, (int)((size_t)y * w + px), px + ox, y + oy, is_hole, emit, 0x7fffffff);
                 if (!external_only) { nbd++; if (nbd > 127) nbd = 2; }
                 p = is_hole ? 0 : rowp[x];
             }

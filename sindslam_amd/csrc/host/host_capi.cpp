@@ -5,6 +5,8 @@
 // sindh_essential_graph in essential_graph.cpp, sindh_global_ba in global_ba.cpp, sindh_triangulate and sindh_update_points in map_points.cpp.
 #include <cstring>
 #include "host.hpp"
+#include "pieces.hpp"
+#include "../pieces_dev.hpp"
 #include "peac_fit4.hpp"
 #include "pipe_schedule.hpp"
 #include "../orb.hpp"
@@ -42,6 +44,23 @@ int sindh_find_contours(const uint8_t* src, int w, int h, int external_only, int
     for (auto& c : cs) { if (nc >= cap_contours) break; lens[nc++] = (int)c.size(); for (auto& p : c) { if (np < cap_pts) { pts_xy[2 * np] = p.x; pts_xy[2 * np + 1] = p.y; } np++; } }
     return (int)cs.size();
 }
+// Piece extraction of SegAndMerge (pieces.hpp) and the ranking DynaTail::seg_pieces puts behind it.  Bit planes in BitImg's layout ([h][ceil(w / 64)] words): k cluster planes
+// (all of them are cut), occ1, labelForSegEdge (already dilated); depth [h][w] u16.  Returns the number of pieces C; the first min(C, cap) come back in DISCOVERY order:
+// recs [cap][12] ints = cluster, start x, start y, contour length, twice the contour area (low, high word), hasLianjie, box x0 y0 x1 y1, rank after the sort (-1 when
+// C is 0 or above 254: then nothing is ranked and piece_of is left alone); vals [cap][2] floats = area, cz; piece / connection planes [cap][h * wpr] (a piece without
+// a connection area: zeros); piece_of [h * w] = rank of the piece that owns the pixel (the highest rank wins), C + 1 elsewhere.
+int sindh_seg_pieces(const uint64_t* planes, int k, const uint64_t* occ1, const uint64_t* label_edge, const uint16_t* depth, int w, int h, float depth_scale, int cap,
+                     int* recs, float* vals, uint64_t* piece_planes, uint64_t* conn_planes, uint8_t* piece_of) {
+    if (!planes || !occ1 || !label_edge || !depth || k < 0 || w < 1 || h < 1 || cap < 0 || !(depth_scale > 0)) return -1;
+    const int wpr = (w + 63) >> 6; const size_t pw = (size_t)h * wpr;
+    auto img = [&](const uint64_t* p) { BitImg b(w, h); std::memcpy(b.d.data(), p, pw * 8); return b; };
+    std::vector<BitImg> cl(k); for (int i = 0; i < k; i++) cl[i] = img(planes + (size_t)i * pw);
+    std::vector<SegPiece> all;
+    seg_pieces_host(cl.data(), k, img(occ1), img(label_edge), depth, z_invalid_from(depth_scale), 1.0f / depth_scale, 1, nullptr, all);
+    return seg_pieces_export(all, w, h, cap, recs, vals, piece_planes, conn_planes, piece_of);
+}
+// the device stage's documented capacities (pieces_dev.hpp), so that the tests' scenes can be held against them
+void sindh_piece_capacities(int* out6) { piece_capacities(out6); }
 void sindh_draw(const uint8_t* src, int w, int h, int filled, uint8_t* out) {     // draw every external contour of src, filled or thickness 2
     const BitImg b = BitImg::from_u8(src, w, h, w); std::vector<Contour> cs; find_contours(b, cs, true);
     BitImg o(w, h);

@@ -179,6 +179,7 @@ int ensure_dtails(sind_pipe* p) {
         d[s].reset(new DynaTail()); SIND_TRY(d[s]->init(p->dc, p->worker_streams[s % p->worker_streams.size()]));
         st.resize(p->tails[s]->state_bytes()); p->tails[s]->save_state(st.data(), false, true); d[s]->load_state(st.data(), false, true);      // the warm labels move over
         d[s]->piece_threads = p->tails[s]->piece_threads;
+        d[s]->device_pieces = p->device_pieces;
     }
     p->dtails.swap(d); return SIND_OK;
 }

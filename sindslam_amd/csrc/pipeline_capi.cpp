@@ -139,6 +139,26 @@ int sind_pipe_set_state(sind_pipe* p, int s, const uint8_t* buf, size_t n) {
     return SIND_OK;
 }
 
+// ---- SegAndMerge's piece extraction on the GPU for every stream (DynaTail::device_pieces); off by default.  The schedule and the results do not depend on it
+int sind_pipe_set_device_pieces(sind_pipe* p, int on) {
+    if (!p) { sind_set_error("sind_pipe_set_device_pieces: null handle"); return SIND_E_ARG; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_set_device_pieces"));
+    p->device_pieces = on != 0;
+    for (auto& t : p->tails) t->device_pieces = p->device_pieces;
+    for (auto& t : p->dtails) if (t) t->device_pieces = p->device_pieces;
+    return SIND_OK;
+}
+int sind_pipe_device_pieces(sind_pipe* p, int* on, long long* frames_on_device, long long* frames_fallen_back) {
+    if (!p) { sind_set_error("sind_pipe_device_pieces: null handle"); return SIND_E_ARG; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_device_pieces", true));
+    long long a = 0, b = 0;
+    for (auto& t : p->tails) { a += t->n_pieces_device; b += t->n_pieces_fallback; }
+    for (auto& t : p->dtails) if (t) { a += t->n_pieces_device; b += t->n_pieces_fallback; }
+    if (on) *on = p->device_pieces ? 1 : 0;
+    if (frames_on_device) *frames_on_device = a;
+    if (frames_fallen_back) *frames_fallen_back = b;
+    return SIND_OK;
+}
 // ---- chunked sequences: per-frame state fingerprints and ragged steps
 int sind_pipe_set_state_hashing(sind_pipe* p, int on) {
     if (!p) { sind_set_error("sind_pipe_set_state_hashing: null handle"); return SIND_E_ARG; }

@@ -63,6 +63,7 @@ struct sind_pipe {
     hipStream_t stream = nullptr, orb_stream = nullptr; hipEvent_t ev_gray = nullptr, ev_depth = nullptr; std::vector<hipStream_t> worker_streams;      // one HIP stream per pool worker, shared by the tasks it runs
     DynaFront front; std::vector<std::unique_ptr<DynaFront>> extra_fronts; std::vector<hipStream_t> extra_streams; hipEvent_t ev_pool = nullptr;      // batch slices 1.. of the dense flow (slice 0 = front)
     OrbEngine orb; std::vector<std::unique_ptr<DynaTail>> tails;
+    bool device_pieces = false;      // every stream's tail (and depth half) cuts its pieces on the GPU (DynaTail::device_pieces)
     // Depth halves (k-means warm labels + their workspaces) as objects of their own, present once depth-ahead has been switched on: the
     // depth chain of step i+1 (phase A) may then run while the flow chain of step i (phase B) is still going on the same stream of frames.
     std::vector<std::unique_ptr<DynaTail>> dtails;

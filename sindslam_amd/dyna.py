@@ -23,6 +23,16 @@ class DynaDetect:
         check(lib().sind_dyna_set_overlap(self._h, 1 if overlap else 0), "sind_dyna_set_overlap")
         check(lib().sind_dyna_prime(self._h, ptr(np.ascontiguousarray(imgLast)), ptr(np.ascontiguousarray(imgLastLast)), self.w * 3), "sind_dyna_prime")
 
+    def set_device_pieces(self, on: bool = True):
+        """SegAndMerge's piece extraction on the GPU instead of the host (off by default; the results do not depend on it)"""
+        check(lib().sind_dyna_set_device_pieces(self._h, int(bool(on))), "sind_dyna_set_device_pieces")
+
+    def device_pieces(self):
+        """(on, frames whose pieces were cut on the GPU, frames that fell back to the host function)"""
+        on = C.c_int(0); a = C.c_longlong(0); b = C.c_longlong(0)
+        check(lib().sind_dyna_device_pieces(self._h, C.byref(on), C.byref(a), C.byref(b)), "sind_dyna_device_pieces")
+        return bool(on.value), int(a.value), int(b.value)
+
     def set_flow_max_levels(self, n: int):
         """build-side option of BASELINE.json config 5 ("3-level flow pyramid"): finest n levels of the DeepFlow pyramid only; 0 = all"""
         check(lib().sind_dyna_set_flow_max_levels(self._h, int(n)), "sind_dyna_set_flow_max_levels")

@@ -143,6 +143,16 @@ class Pipeline:
         blob = np.ascontiguousarray(blob, np.uint8)
         check(lib().sind_pipe_set_state(self._h, stream, ptr(blob), C.c_size_t(blob.size)), "sind_pipe_set_state")
 
+    def set_device_pieces(self, on: bool = True):
+        """SegAndMerge's piece extraction of every stream on the GPU instead of the host (off by default; schedule and results do not depend on it)"""
+        check(lib().sind_pipe_set_device_pieces(self._h, int(bool(on))), "sind_pipe_set_device_pieces")
+
+    def device_pieces(self):
+        """(on, frames whose pieces were cut on the GPU, frames that fell back to the host function), summed over the streams"""
+        on = C.c_int(0); a = C.c_longlong(0); b = C.c_longlong(0)
+        check(lib().sind_pipe_device_pieces(self._h, C.byref(on), C.byref(a), C.byref(b)), "sind_pipe_device_pieces")
+        return bool(on.value), int(a.value), int(b.value)
+
     def set_state_hashing(self, on: bool = True):
         """every tail leaves a 128-bit fingerprint of its rolled inter-frame state per frame (read with state_hashes())"""
         check(lib().sind_pipe_set_state_hashing(self._h, int(bool(on))), "sind_pipe_set_state_hashing")
@@ -272,6 +282,10 @@ class PipelineGroup:
     def submit_dev(self, b, d): return all(self._all(lambda i, p: p.submit_dev(*self._ptrs(i, b, d))))
     def flush(self): return all(self._all(lambda i, p: p.flush()))
     def set_state_hashing(self, on=True): [p.set_state_hashing(on) for p in self.pipes]
+    def set_device_pieces(self, on=True): [p.set_device_pieces(on) for p in self.pipes]
+    def device_pieces(self):
+        r = [p.device_pieces() for p in self.pipes]
+        return all(v[0] for v in r), sum(v[1] for v in r), sum(v[2] for v in r)
     def set_depth_ahead(self, on): [p.set_depth_ahead(on) for p in self.pipes]
     def set_chain_max_streams(self, n): [p.set_chain_max_streams(n) for p in self.pipes]
     def state_hashes(self): return np.concatenate([p.state_hashes() for p in self.pipes])
