@@ -867,7 +867,7 @@ int sind_match_sim3_optimize(sind_match* m, const sind_sim3opt_item* items, int 
  * from the optimizer's set-up on (src/Optimizer.cc:506-743; LocalMapping::Run, src/LocalMapping.cc:100): the g2o graph of the local key frames (free, the one with
  * mnId 0 fixed), the fixed cameras and the local map points (marginalised), one EdgeSE3ProjectXYZ or EdgeStereoSE3ProjectXYZ with a Huber kernel per observation,
  * BlockSolver_6_3's Schur complement under OptimizationAlgorithmLevenberg, optimize(5), the outliers moved to level 1 and the kernels removed, optimize(10), the final
- * classification.  ONE launch for all items (csrc/match_localba.hip, one workgroup per item; csrc/host/local_ba.hpp is one FP64 source for host and device and states
+ * classification.  ONE launch for all items (csrc/match_localba.hip, one workgroup per item; csrc/host/local_ba.hpp over csrc/host/ba_schur.hpp is one FP64 source for host and device and states
  * the order of every sum).  Calibration is the handle's fx fy cx cy bf, as for sind_match_pose_optimize.
  * What stays with the caller: the graph collection (:455-504: lLocalKeyFrames, lLocalMapPoints, lFixedCameras; sindslam_amd/optimizer.py mirrors it), and after the
  * call, under the map mutex, EraseMapPointMatch and EraseObservation for every erased observation (:748-757), SetPose (:762-768), SetWorldPos and
@@ -883,7 +883,7 @@ int sind_match_sim3_optimize(sind_match* m, const sind_sim3opt_item* items, int 
  * step, stage_lambda = _currentLambda at its end; a stage that did not run keeps zeros.
  * Valid: B = 0; n_obs = 0 (initializeOptimization refuses an empty graph and nothing is optimised: the outputs are the conversions alone).
  * Unpinned: parity with a real g2o / Eigen build, above all the reduced system (a dense LDL^T in natural order here, SimplicialLDLT under AMD ordering there); see the
- * head of local_ba.hpp.  Not offered: a stop flag that flips in the middle of an optimize.
+ * head of ba_schur.hpp.  Not offered: a stop flag that flips in the middle of an optimize.
  * Limits: 256 key frames of kind 0, 4096 key frames, 65536 points, 2^20 observations, 2^24 entries of the co-observation lists (sum over the points of k (k + 1) / 2,
  * k = its observations in key frames of kind 0), B <= max_batch: beyond them SIND_E_CAPACITY.  The workspace lives on the handle, grows between calls to the largest
  * call seen and is freed with the handle.
@@ -958,7 +958,7 @@ int sindh_essential_graph(const sind_essgraph_item* items, int B, int fix_scale)
  * OptimizationAlgorithmLevenberg, initializeOptimization(), ONE optimize(iterations); no levels and no classification.  A global BA is one large item, so the phases
  * of the algorithm are KERNELS OVER THE WHOLE GRID, one element per lane, on the handle's stream (csrc/match_globalba.hip), stream order the only synchronisation, and
  * the Levenberg-Marquardt control flow runs on the host with one wait per linearisation and one per trial; no cooperative launch, no grid-wide flags, no atomics.
- * csrc/host/global_ba.hpp is one FP64 source for host and device and states the order of every sum: it is local BA's contract, with the reduced camera system stored and
+ * csrc/host/global_ba.hpp over csrc/host/ba_schur.hpp is one FP64 source for host and device; ba_schur.hpp states the order of every sum, once for both bundle adjustments, with the reduced camera system stored and
  * factored as a natural-order envelope in 6 x 6 block rows.  The B items of a call run one after the other.  Calibration is the handle's fx fy cx cy bf.
  * What stays with the caller: the collection of the graph (:68-184; sindslam_amd/optimizer.py mirrors it) and what follows the optimize (:193-235: SetPose / SetWorldPos
  * or mTcwGBA / mPosGBA, and UpdateNormalAndDepth, which sind_match_update_points below does for all points in one call), and the tail of RunGlobalBundleAdjustment
@@ -974,7 +974,7 @@ int sindh_essential_graph(const sind_essgraph_item* items, int B, int fix_scale)
  * factor's envelope, env_dense_entries = those of the dense lower triangle in 6 x 6 blocks, 36 n (n + 1) / 2.
  * Valid: B = 0; no key frame but mnId 0 (only the points move); no observations (nothing is optimised); n_mp = 0; no key frame with mnId 0 (nothing is fixed).
  * Unpinned: parity with a real g2o / Eigen build, above all the reduced system (a natural-order envelope LDL^T here, SimplicialLDLT under AMD ordering there) and the
- * order of a point's observations (a std::map keyed by pointers there); see the heads of global_ba.hpp and local_ba.hpp.  Not offered: a stop flag that flips in the
+ * order of a point's observations (a std::map keyed by pointers there); see the heads of ba_schur.hpp and global_ba.hpp.  Not offered: a stop flag that flips in the
  * middle of the optimize.
  * Limits: 4096 key frames, 2^20 points, 2^22 observations, 2^26 entries of the co-observation lists (sum over the points of k (k + 1) / 2, k = its observations in key
  * frames with mnId != 0), 2^25 stored entries of the envelope (sum over the key frames with a Hessian index I of 36 (I - first(I) + 1), first(I) the smallest index among

@@ -113,7 +113,7 @@ int sind_match_local_ba(sind_match* m, const sind_localba_item* items, int B) {
     SIND_TRY(w.reserve(B, (size_t)m->maxB));
     const sind::MatchParams& c = m->prm;
     const sind::PoseOptCam K{(double)c.fx, (double)c.fy, (double)c.cx, (double)c.cy, (double)c.bf};
-    for (int b = 0; b < B; b++) { sind::lba_fill(items[b], w.host(b)); sind::lba_bind(w.plan[b], items[b].do_more, K, w.dev(b), w.views.h[b]); }
+    for (int b = 0; b < B; b++) { sind::ba_fill(sind::ba_item(items[b]), w.host(b)); sind::lba_bind(w.plan[b], items[b].do_more, K, w.dev(b), w.views.h[b]); }
     hipStream_t s = m->stream;
     SIND_TRY(w.upload(B, s));
     SIND_TRY(sind::launch_local_ba(w.views.d.p, B, s));
@@ -163,10 +163,10 @@ int sind_match_global_ba(sind_match* m, const sind_globalba_item* items, int B, 
         return SIND_E_CAPACITY;
     }
     HIP_TRY(hipSetDevice(m->device));
-    SIND_TRY(w.reserve(B, (size_t)m->maxB)); SIND_TRY(m->gbaSc.alloc(sind::GBA_SC_N));
+    SIND_TRY(w.reserve(B, (size_t)m->maxB)); SIND_TRY(m->gbaSc.alloc(sind::BA_SC_N));
     const sind::MatchParams& c = m->prm;
     const sind::PoseOptCam K{(double)c.fx, (double)c.fy, (double)c.cx, (double)c.cy, (double)c.bf};
-    for (int b = 0; b < B; b++) { sind::gba_fill(items[b], w.host(b)); sind::gba_bind(w.plan[b], K, w.dev(b), w.views.h[b]); }
+    for (int b = 0; b < B; b++) { sind::ba_fill(sind::ba_item(items[b]), w.host(b)); sind::gba_bind(w.plan[b], K, w.dev(b), w.views.h[b]); }
     hipStream_t s = m->stream;
     SIND_TRY(w.I.up(w.at[B].ints, s)); SIND_TRY(w.Fin.up(w.at[B].floatsIn, s));
     std::vector<sind::GbaDiag> dg((size_t)B);

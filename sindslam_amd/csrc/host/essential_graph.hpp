@@ -10,7 +10,7 @@
 // The Levenberg-Marquardt scalars are computed by every lane from the same workspace values, so the control flow is uniform over the workgroup.
 //
 // RECALLED (not defined again): Sim3Q, s3_exp, s3_exp7, s3_mul, s3_inverse, s3_map, s3_oplus, s3_perturbed, s3_from_input (sim3_opt.hpp); po_sincos, po_quat_to_matrix
-// (pose_opt.hpp); lba_chain (local_ba.hpp); levenberg_optimize (g2o_lm.hpp), here with the user's initial lambda.
+// (pose_opt.hpp); ba_chain (ba_schur.hpp); levenberg_optimize (g2o_lm.hpp), here with the user's initial lambda.
 // DEFINED here: s3_log_d and s3_acos_d (std::log and acos), s3_lu3_solve, s3_log (Sim3::log), the phases ess_*, the envelope LDL^T, EssLm, essential_graph, ess_point.
 //
 // THE LITERAL READINGS of g2o.
@@ -21,7 +21,7 @@
 // Edges.  In the item's order (g2o's internal edge id is the insertion order).  Vertex 0 is edge_i, vertex 1 is edge_j.  The measurement is Sjw * Swi: for kind 0 (a
 //   LoopConnections edge, :857-872) from vScw of both ends, for kind 1 (spanning tree, loop edges, covisibility, :889-979) from the NonCorrectedSim3 entry of an end
 //   where there is one, else vScw.  computeError: _error = (C * v1->estimate() * v2->estimate().inverse()).log(), the products left to right.  chi2 = e . (I e): the
-//   seven squares added in ascending order; activeChi2 is one chain over the edges in ascending order (lba_chain).
+//   seven squares added in ascending order; activeChi2 is one chain over the edges in ascending order (ba_chain<8>).
 // Sim3::log (sim3.h:148-230).  sigma = log(s); R = toRotationMatrix; d = 0.5 * (R00 + R11 + R22 - 1); the four branches on fabs(sigma) < eps and d > 1 - eps exactly
 //   as written, with cos and sin of theta from po_sincos; W = (A Omega + B Omega2) + C I entry by entry as s3_exp7 has it, Omega2 = Omega * Omega; upsilon =
 //   W.lu().solve(t), DEFINED as s3_lu3_solve: elimination with partial pivoting (the FIRST largest |entry| of the column from the diagonal down), the multipliers
@@ -70,7 +70,7 @@
 #pragma once
 #include <vector>
 #include "sim3_opt.hpp"
-#include "local_ba.hpp"                                              // lba_chain
+#include "ba_schur.hpp"                                              // ba_chain
 
 struct sind_essgraph_item;
 
@@ -331,7 +331,7 @@ template <class Ex> SIND_HD inline void ess_sums(Ex& ex, const EssView& w, bool 
             const int p = (idx - nV) / 49, r = ((idx - nV) % 49) / 7, c = (idx - nV) % 7;
             for (int q = w.pairStart[p]; q < w.pairStart[p + 1]; q++) { const int ce = w.pairE[q]; s = s + w.C[(size_t)(ce >> 1) * ESS_C + 70 + ((ce & 1) ? 7 * c + r : 7 * r + c)]; }
             w.Ho[idx - nV] = s;
-        } else w.sc[ESS_SC_CHI] = lba_chain(w.chiE, w.nE);
+        } else w.sc[ESS_SC_CHI] = ba_chain<8>(w.chiE, w.nE);
     });
 }
 SIND_HD inline int ess_tri(int r, int c) { return r * 7 - r * (r - 1) / 2 + (c - r); }     // entry (r, c), r <= c, of a 7 x 7 upper triangle stored row-major
@@ -407,7 +407,7 @@ template <class Ex> SIND_HD inline void ess_update(Ex& ex, const EssView& w) {
 // computeScale (optimization_algorithm_levenberg.cpp:182-189) -> sc[ESS_SC_SCALE]
 template <class Ex> SIND_HD inline void ess_scale(Ex& ex, const EssView& w, double lambda) {
     ex.par(w.n, [&](int i) { const double xj = w.x[i]; w.term[i] = xj * (lambda * xj + w.Hd[(i / 7) * ESS_V + 28 + i % 7]); });
-    ex.par(1, [&](int) { w.sc[ESS_SC_SCALE] = lba_chain(w.term, w.n); });
+    ex.par(1, [&](int) { w.sc[ESS_SC_SCALE] = ba_chain<8>(w.term, w.n); });
 }
 
 // optimize(20) as levenberg_optimize's problem

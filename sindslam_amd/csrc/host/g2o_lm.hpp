@@ -1,4 +1,4 @@
-// What PoseOptimization (pose_opt.hpp), OptimizeSim3 (sim3_opt.hpp) and LocalBundleAdjustment (local_ba.hpp) share of g2o and Eigen, restated ONCE: Eigen's quaternion
+// What PoseOptimization (pose_opt.hpp), OptimizeSim3 (sim3_opt.hpp) and the bundle adjustments (ba_schur.hpp) share of g2o and Eigen, restated ONCE: Eigen's quaternion
 // product, the upper triangle of J^T W J, Eigen's pivoted LDLT behind LinearSolverDense, the dense N x N system of a single free vertex, and the control flow of
 // SparseOptimizer::optimize over OptimizationAlgorithmLevenberg::solve.  Everything is SIND_HD inline: the host twins and the device kernels compile the same text,
 // IEEE FP64 on both sides and no contraction (-ffp-contract=off), so they give the same bits.  A correction to one of the literal readings below is made here, once.
@@ -34,7 +34,7 @@ SIND_HD inline void po_quat_mul(const double a[4], const double b[4], double r[4
 
 // The upper triangle (row-major) of J^T (W I) J, J of two rows or, if `third`, of three: Omega = invSigma2 * I (times rho[1]) applied as one multiplication per row, every
 // sum in ascending row order.  NOT SHARED, because the arithmetic differs between the callers: the Jacobians themselves (po_edge_contrib multiplies by invz and invz_2,
-// lba_edge divides by z and z_2, as the reference's two source files do), the right-hand sides (rho1 * (A^T (s e)) there, A^T (-(s e) rho1) in lba_edge and
+// ba_edge divides by z and z_2, as the reference's two source files do), the right-hand sides (rho1 * (A^T (s e)) there, A^T (-(s e) rho1) in ba_edge and
 // s3_edge_contrib) and local BA's B^T W A, which is not a triangle
 template <int R, int N> SIND_HD inline void jtwj_upper(const double (&J)[R][N], double W, bool third, double* c) {
     static_assert(R == 2 || R == 3, "two rows, or three of which the last may be unused");

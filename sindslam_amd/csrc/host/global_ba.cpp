@@ -1,7 +1,6 @@
 // Host twin of sind_match_global_ba (reference src/Optimizer.cc:49-237): global_ba.hpp with the plain runner, and what the two entry points share: the argument
-// check, the digest of an item into the lists the phases walk (GbaPlan: the limits first, then the per-pose edge lists, the per-point edges by pose rank, the
-// co-observation lists keyed by the two ranks, first(I) and the offsets of the envelope) and the copy of one item's results.  Compiled into libsind_hip.so
-// (capi_match_opt.cpp calls the shared part) and into libsind_host.so.
+// check, the digest of an item (GbaPlan: the limits first, then global BA's rule for the free poses and the active sets over ba_plan.cpp's lists, first(I) and the
+// offsets of the envelope) and the copy of one item's results.  Compiled into libsind_hip.so (capi_match_opt.cpp calls the shared part) and into libsind_host.so.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -17,25 +16,11 @@ const char* const gba_check_text[] = {"", "negative count", "null array", "point
                                       "kf_id is not strictly ascending"};
 
 int gba_check(const ::sind_globalba_item& q) {
-    if (q.n_kf < 0 || q.n_mp < 0) return 1;
-    if (q.n_kf && (!q.kf_id || !q.Tcw || !q.Tcw_out)) return 2;
-    if (q.n_mp && (!q.mp_id || !q.x3Dw || !q.obs_start || !q.x3Dw_out || !q.included)) return 2;
-    if (q.n_mp) { if (q.obs_start[0] != 0) return 6; for (int j = 0; j < q.n_mp; j++) if (q.obs_start[j + 1] < q.obs_start[j]) return 6; }
-    const int nObs = q.n_mp ? q.obs_start[q.n_mp] : 0;
-    if (nObs && (!q.obs_kf || !q.obs_xy || !q.u_right || !q.inv_sigma2)) return 2;
+    const BaItem it = ba_item(q);
+    if (const int r = ba_check_arrays(it, false, !q.included, false)) return r;
     for (int k = 1; k < q.n_kf; k++) if (q.kf_id[k] <= q.kf_id[k - 1]) return 9;
-    { std::vector<int64_t> v(q.mp_id, q.mp_id + q.n_mp); std::sort(v.begin(), v.end()); if (std::adjacent_find(v.begin(), v.end()) != v.end()) return 3; }
-    std::vector<int> seen((size_t)q.n_kf, -1);
-    for (int j = 0; j < q.n_mp; j++) for (int e = q.obs_start[j]; e < q.obs_start[j + 1]; e++) {
-        const int k = q.obs_kf[e];
-        if (k < 0 || k >= q.n_kf) return 4;
-        if (seen[k] == j) return 5;
-        seen[k] = j;
-    }
-    for (int e = 0; e < nObs; e++) if (!(q.inv_sigma2[e] >= 0 && std::isfinite(q.inv_sigma2[e]))) return 7;
-    for (size_t k = 0; k < (size_t)16 * q.n_kf; k++) if (!std::isfinite(q.Tcw[k])) return 8;
-    for (size_t k = 0; k < (size_t)3 * q.n_mp; k++) if (!std::isfinite(q.x3Dw[k])) return 8;
-    return 0;
+    if (ba_ids_repeat(q.mp_id, q.n_mp)) return 3;
+    return ba_check_obs(it);
 }
 
 // the block rows of every block column of the envelope: I >= J with first(I) <= J, ascending (J itself first); cs: how many
@@ -52,21 +37,18 @@ static void gba_columns(const std::vector<int>& first, std::vector<int>& colStar
 }
 
 int gba_plan(const ::sind_globalba_item& q, GbaPlan& pl) {
-    const int nKf = q.n_kf, nMp = q.n_mp, nObs = nMp ? q.obs_start[nMp] : 0;
+    const BaItem it = ba_item(q);
+    const int nKf = it.nKf, nMp = it.nMp, nObs = it.nObs;
     if (nKf > GBA_MAX_KF || nMp > GBA_MAX_MP || nObs > GBA_MAX_OBS) return SIND_E_CAPACITY;
     std::vector<int> free_, kfPose((size_t)nKf, -1);                 // kf_id ascends: the item's order is buildIndexMapping's pose order
     for (int k = 0; k < nKf; k++) if (q.kf_id[k] != 0) { kfPose[k] = (int)free_.size(); free_.push_back(k); }
     const int P = (int)free_.size();
     // the counts the limits speak of, before any list: the co-observation entries, then first(I) and the envelope
-    std::vector<int> ptNF((size_t)nMp, 0), ptAct((size_t)nMp, 0), nEdge((size_t)P, 0);
-    size_t total = 0; int nActPts = 0;
-    for (int j = 0; j < nMp; j++) {
-        size_t k = 0;
-        for (int e = q.obs_start[j]; e < q.obs_start[j + 1]; e++) { const int s = kfPose[q.obs_kf[e]]; if (s >= 0) { k++; nEdge[s]++; } }
-        ptNF[j] = (int)k; total += k * (k + 1) / 2;
-        ptAct[j] = q.obs_start[j + 1] > q.obs_start[j]; nActPts += ptAct[j];
-    }
+    std::vector<int> ptNF, nEdge, ptAct((size_t)nMp, 0);
+    const size_t total = ba_count(it, kfPose, P, ptNF, nEdge);
     if (total > (size_t)GBA_MAX_PAIRS) return SIND_E_CAPACITY;
+    int nActPts = 0;
+    for (int j = 0; j < nMp; j++) { ptAct[j] = q.obs_start[j + 1] > q.obs_start[j]; nActPts += ptAct[j]; }
     std::vector<int> poseIdx((size_t)P, -1);
     int nAct = 0;
     for (int s = 0; s < P; s++) if (nEdge[s]) poseIdx[s] = nAct++;
@@ -80,95 +62,31 @@ int gba_plan(const ::sind_globalba_item& q, GbaPlan& pl) {
     std::vector<int> rowOff((size_t)nAct + 1, 0);
     size_t env = 0;
     for (int I = 0; I < nAct; I++) { env += (size_t)36 * (I - first[I] + 1); if (env > (size_t)GBA_MAX_ENV) return SIND_E_CAPACITY; rowOff[I + 1] = (int)env; }
-    // the lists
-    std::vector<int> ptOrder((size_t)nMp); std::iota(ptOrder.begin(), ptOrder.end(), 0);
-    std::sort(ptOrder.begin(), ptOrder.end(), [&](int a, int b) { return q.mp_id[a] < q.mp_id[b]; });
-    std::vector<int> ePt((size_t)nObs), ptSorted((size_t)nObs, 0), poseEdgeStart((size_t)P + 1, 0);
-    auto rankOf = [&](int e) { return kfPose[q.obs_kf[e]]; };
-    for (int j = 0; j < nMp; j++) {
-        int* srt = ptSorted.data() + q.obs_start[j]; int c = 0;
-        for (int e = q.obs_start[j]; e < q.obs_start[j + 1]; e++) { ePt[e] = j; if (rankOf(e) >= 0) srt[c++] = e; }
-        std::sort(srt, srt + c, [&](int a, int b) { return rankOf(a) < rankOf(b); });
-    }
-    for (int s = 0; s < P; s++) poseEdgeStart[s + 1] = poseEdgeStart[s] + nEdge[s];
-    std::vector<int> poseEdge((size_t)poseEdgeStart[P]), fill(poseEdgeStart.begin(), poseEdgeStart.end() - 1);
-    for (int e = 0; e < nObs; e++) { const int s = rankOf(e); if (s >= 0) poseEdge[fill[s]++] = e; }
-    // the co-observation lists: per pair of free poses s1 <= s2 in ascending (s1, s2), the points both see in ascending mp_id.  Generated in point order and sorted
-    // stably by the pair, so the order inside a pair stays the point order
-    struct Ent { int64_t key; int e1, e2; };
-    std::vector<Ent> ent; ent.reserve(total);
-    for (int o = 0; o < nMp; o++) {
-        const int j = ptOrder[o]; const int* srt = ptSorted.data() + q.obs_start[j];
-        for (int a = 0; a < ptNF[j]; a++) for (int b = a; b < ptNF[j]; b++) ent.push_back({(int64_t)rankOf(srt[a]) * P + rankOf(srt[b]), srt[a], srt[b]});
-    }
-    std::stable_sort(ent.begin(), ent.end(), [](const Ent& a, const Ent& b) { return a.key < b.key; });
-    std::vector<int> pairStart, pairS1, pairS2, pairE(2 * total), diagPair((size_t)P, -1);
-    for (size_t t = 0; t < total; t++) {
-        if (t == 0 || ent[t].key != ent[t - 1].key) {
-            const int s1 = (int)(ent[t].key / P), s2 = (int)(ent[t].key % P);
-            if (s1 == s2) diagPair[s1] = (int)pairS1.size();
-            pairStart.push_back((int)t); pairS1.push_back(s1); pairS2.push_back(s2);
-        }
-        pairE[2 * t] = ent[t].e1; pairE[2 * t + 1] = ent[t].e2;
-    }
-    pairStart.push_back((int)total);
-    const int nPair = (int)pairS1.size();
-    std::vector<Ent>().swap(ent);
+    ba_lists(it, kfPose, free_, ptNF, nEdge, total, pl);
     std::vector<int> colStart, colRow, colLast;
     gba_columns(first, colStart, colRow, colLast, pl.cs);
 
-    pl.nKf = nKf; pl.nMp = nMp; pl.nObs = nObs; pl.P = P; pl.nAct = nAct; pl.nActPts = nActPts; pl.nPair = nPair; pl.nEnv = (int)env;
+    pl.nAct = nAct; pl.nActPts = nActPts; pl.nEnv = (int)env;
     pl.envDense = (long long)36 * nAct * (nAct + 1) / 2;
-    pl.I.clear();
-    auto add = [&](const std::vector<int>& v) { const size_t o = pl.I.size(); pl.I.insert(pl.I.end(), v.begin(), v.end()); return o; };
-    pl.oKfPose = add(kfPose); pl.oPoseKf = add(free_); pl.oPtOrder = add(ptOrder);
-    { const size_t o = pl.I.size(); if (nMp) pl.I.insert(pl.I.end(), q.obs_start, q.obs_start + nMp + 1); else pl.I.push_back(0); pl.oObsStart = o; }
-    pl.oEPt = add(ePt);
-    { const size_t o = pl.I.size(); if (nObs) pl.I.insert(pl.I.end(), q.obs_kf, q.obs_kf + nObs); pl.oEKf = o; }
-    pl.oPoseEdgeStart = add(poseEdgeStart); pl.oPoseEdge = add(poseEdge); pl.oPtNF = add(ptNF); pl.oPtSorted = add(ptSorted);
-    pl.oPairStart = add(pairStart); pl.oPairS1 = add(pairS1); pl.oPairS2 = add(pairS2); pl.oPairE = add(pairE); pl.oDiagPair = add(diagPair);
-    pl.oPoseIdx = add(poseIdx); pl.oPtAct = add(ptAct);
-    pl.oFirst = add(first); pl.oRowOff = add(rowOff); pl.oColStart = add(colStart); pl.oColRow = add(colRow); pl.oColLast = add(colLast);
-    const size_t n = 6 * (size_t)nAct, nx = 6 * (size_t)P + 3 * (size_t)nMp;
-    pl.z = ItemSizes{};
-    pl.z.ints = pl.I.size();
-    pl.z.floatsIn = 16 * (size_t)nKf + 3 * (size_t)nMp + 4 * (size_t)nObs; pl.z.floatsOut = 16 * (size_t)nKf + 3 * (size_t)nMp;
-    pl.z.work = GBA_SC_N + 14 * (size_t)nKf + 6 * (size_t)nMp + (size_t)(LBA_C + 18) * nObs + 27 * (size_t)P + 21 * (size_t)nMp + env + 2 * n + 2 * nx + nObs;
+    pl.oPoseIdx = pl.add(poseIdx); pl.oPtAct = pl.add(ptAct);
+    pl.oFirst = pl.add(first); pl.oRowOff = pl.add(rowOff); pl.oColStart = pl.add(colStart); pl.oColRow = pl.add(colRow); pl.oColLast = pl.add(colLast);
+    ba_sizes(pl);
+    pl.z.work += env + 12 * (size_t)nAct;                            // the envelope, Dg, y
     return SIND_OK;
 }
 
-void gba_fill(const ::sind_globalba_item& q, const ItemPtrs& p) {
-    const int nObs = q.n_mp ? q.obs_start[q.n_mp] : 0; float* F = p.Fin;
-    if (q.n_kf) std::memcpy(F, q.Tcw, sizeof(float) * 16 * q.n_kf);
-    F += 16 * (size_t)q.n_kf;
-    if (q.n_mp) std::memcpy(F, q.x3Dw, sizeof(float) * 3 * q.n_mp);
-    F += 3 * (size_t)q.n_mp;
-    for (int e = 0; e < nObs; e++) { F[4 * (size_t)e] = q.obs_xy[2 * (size_t)e]; F[4 * (size_t)e + 1] = q.obs_xy[2 * (size_t)e + 1]; F[4 * (size_t)e + 2] = q.u_right[e]; F[4 * (size_t)e + 3] = q.inv_sigma2[e]; }
-}
-
 void gba_bind(const GbaPlan& pl, const PoseOptCam& K, const ItemPtrs& p, GbaView& v) {
-    int* I = p.I; const float* Fin = p.Fin; float* Fout = p.Fout;
-    const size_t nKf = pl.nKf, nMp = pl.nMp, nObs = pl.nObs, P = pl.P, n = 6 * (size_t)pl.nAct, nx = 6 * P + 3 * nMp;
-    v.nKf = pl.nKf; v.nMp = pl.nMp; v.nObs = pl.nObs; v.P = pl.P; v.nAct = pl.nAct; v.nActPts = pl.nActPts; v.nPair = pl.nPair; v.nEnv = pl.nEnv; v.K = K;
+    int* I = p.I; const size_t n = 6 * (size_t)pl.nAct, nx = 6 * (size_t)pl.P + 3 * (size_t)pl.nMp;
+    double* d = ba_bind(pl, K, p, p.D, v);
+    v.nAct = pl.nAct; v.nActPts = pl.nActPts; v.nEnv = pl.nEnv;
     v.delta[0] = (double)(float)sqrt(5.99); v.delta[1] = (double)(float)sqrt(7.815);        // const float thHuber2D = sqrt(5.99), thHuber3D = sqrt(7.815) (:85-86); setDelta takes a double
-    v.Tcw = Fin; v.x3Dw = Fin + 16 * nKf; v.eObs = v.x3Dw + 3 * nMp;
-    v.kfPose = I + pl.oKfPose; v.poseKf = I + pl.oPoseKf; v.ptOrder = I + pl.oPtOrder; v.obsStart = I + pl.oObsStart; v.ePt = I + pl.oEPt; v.eKf = I + pl.oEKf;
-    v.poseEdgeStart = I + pl.oPoseEdgeStart; v.poseEdge = I + pl.oPoseEdge; v.ptNF = I + pl.oPtNF; v.ptSorted = I + pl.oPtSorted;
-    v.pairStart = I + pl.oPairStart; v.pairS1 = I + pl.oPairS1; v.pairS2 = I + pl.oPairS2; v.pairE = I + pl.oPairE; v.diagPair = I + pl.oDiagPair;
-    v.poseIdx = I + pl.oPoseIdx; v.ptAct = I + pl.oPtAct;
     v.first = I + pl.oFirst; v.rowOff = I + pl.oRowOff; v.colStart = I + pl.oColStart; v.colRow = I + pl.oColRow; v.colLast = I + pl.oColLast;
-    static_assert(sizeof(PoseQ) == 7 * sizeof(double), "the layout of the working state");
-    double* d = p.D;
-    v.sc = d; d += GBA_SC_N; v.est = (PoseQ*)d; d += 7 * nKf; v.bak = (PoseQ*)d; d += 7 * nKf; v.X = d; d += 3 * nMp; v.Xbak = d; d += 3 * nMp;
-    v.C = d; d += LBA_C * nObs; v.BD = d; d += 18 * nObs; v.Hpp = d; d += 27 * P; v.Hll = d; d += 9 * nMp; v.Dinv = d; d += 9 * nMp; v.db = d; d += 3 * nMp;
-    v.E = d; d += (size_t)pl.nEnv; v.Dg = d; d += n; v.y = d; d += n; v.x = d; d += nx; v.term = d; d += nx; v.rho = d; d += nObs;
-    v.TcwOut = Fout; v.XOut = Fout + 16 * nKf;
+    v.Hs = d; d += (size_t)pl.nEnv; v.Dg = d; d += n; v.y = d; d += n; v.x = d; d += nx; v.term = d; d += nx; v.rho = d; d += pl.nObs;
 }
 
 void gba_store(const ::sind_globalba_item& q, const GbaPlan& pl, const ItemPtrs& p, const GbaDiag& dg) {
-    const float* Fout = p.Fout; const int* ptAct = pl.I.data() + pl.oPtAct;
-    if (pl.nKf) std::memcpy(q.Tcw_out, Fout, sizeof(float) * 16 * pl.nKf);
-    if (pl.nMp) std::memcpy(q.x3Dw_out, Fout + 16 * (size_t)pl.nKf, sizeof(float) * 3 * pl.nMp);
+    const int* ptAct = pl.I.data() + pl.oPtAct;
+    ba_store(ba_item(q), pl, p);
     for (int j = 0; j < pl.nMp; j++) q.included[j] = (uint8_t)ptAct[j];
     if (q.n_iters) *q.n_iters = dg.iters;
     if (q.chi2) *q.chi2 = dg.chi2;
@@ -182,7 +100,7 @@ void gba_store(const ::sind_globalba_item& q, const GbaPlan& pl, const ItemPtrs&
 using GbaHost = HostItem<GbaPlan, GbaView>;
 static void gba_host_bind(GbaHost& h, const ::sind_globalba_item& q, const float* K5) {
     h.store();
-    gba_fill(q, h.p);
+    ba_fill(ba_item(q), h.p);
     gba_bind(h.pl, {(double)K5[0], (double)K5[1], (double)K5[2], (double)K5[3], (double)K5[4]}, h.p, h.v);
 }
 
@@ -243,16 +161,16 @@ int sindh_globalba_factor(int nAct, const int* first, const double* H, const dou
     std::vector<int> f(first, first + nAct), rowOff((size_t)nAct + 1, 0), colStart, colRow, colLast, cs, idx((size_t)nAct);
     for (int I = 0; I < nAct; I++) { rowOff[I + 1] = rowOff[I] + 36 * (I - f[I] + 1); idx[I] = I; }
     sind::gba_columns(f, colStart, colRow, colLast, cs);
-    std::vector<double> E((size_t)rowOff[nAct] + 1, 0.0), Dg((size_t)n + 1, 0.0), y(b, b + n), sc(sind::GBA_SC_N, 0.0);
+    std::vector<double> E((size_t)rowOff[nAct] + 1, 0.0), Dg((size_t)n + 1, 0.0), y(b, b + n), sc(sind::BA_SC_N, 0.0);
     sind::GbaView w{};
     w.P = nAct; w.nAct = nAct; w.nEnv = rowOff[nAct]; w.first = f.data(); w.rowOff = rowOff.data(); w.colStart = colStart.data(); w.colRow = colRow.data(); w.colLast = colLast.data();
-    w.poseIdx = idx.data(); w.E = E.data(); w.Dg = Dg.data(); w.y = y.data(); w.x = x; w.sc = sc.data();
+    w.poseIdx = idx.data(); w.Hs = E.data(); w.Dg = Dg.data(); w.y = y.data(); w.x = x; w.sc = sc.data();
     for (int i = 0; i < n; i++) for (int j = sind::gba_fcol(w, i); j <= i; j++) E[sind::gba_at(w, i, j)] = H[(size_t)j * n + i];
     sind::GbaSeqRun run;
     for (int J = 0; J < nAct; J++) { run.go(36 * cs[J], sind::GbaFactorPre{w, J}); run.go(1, sind::GbaFactorDiag{w, J}); run.go(6 * (cs[J] - 1), sind::GbaFactorPost{w, J}); }
     run.tri(w);
     for (int i = 0; i < n; i++) D[i] = Dg[i];
-    return sc[sind::GBA_SC_FAIL] != 0.0 ? 1 : 0;
+    return sc[sind::BA_SC_FAIL] != 0.0 ? 1 : 0;
 }
 
 }  // extern "C"

@@ -134,7 +134,7 @@ int launch_local_ba(const LbaView* views, int B, hipStream_t s);
 int launch_essential_graph(const EssView* views, int B, int maxMp, hipStream_t s);
 
 // Optimizer::BundleAdjustment, the optimize of a global BA: kernels per phase over the whole grid on stream s, the Levenberg-Marquardt driver on the host
-// (match_globalba.hip, host/global_ba.hpp).  w: device pointers throughout; cs: GbaPlan::cs; pinned: [GBA_SC_N] page-locked.  Returns after the last phase is enqueued
+// (match_globalba.hip, host/global_ba.hpp).  w: device pointers throughout; cs: GbaPlan::cs; pinned: [BA_SC_N] page-locked.  Returns after the last phase is enqueued
 #define GBA_THREADS 256                                              // profiles/match_global_ba.txt: the compiler's resource report of the edge kernel and the choice
 struct GbaCounters { long long launches = 0, waits = 0; };
 int launch_global_ba(const GbaView& w, const int* cs, int iterations, bool robust, double* pinned, hipStream_t s, GbaDiag& dg, GbaCounters& cnt);

@@ -8,7 +8,7 @@
 //
 // Shape.  k_ess_graph: one workgroup per item, B items per grid.  The error lanes carry the weight of a linearisation: 29 evaluations of log(C * Si * Sj^-1) per edge,
 // each with its own branches of Sim3::log, so neighbouring lanes diverge inside s3_log; the values they write (7 doubles each) lie densely in the item's workspace.
-// The ordered sums are one lane per entry of a block, walking the vertex's or the pair's edges in ascending order; one more lane carries the chi2 chain (lba_chain).
+// The ordered sums are one lane per entry of a block, walking the vertex's or the pair's edges in ascending order; one more lane carries the chi2 chain (ba_chain<8>).
 // LDL^T: column by column over the envelope, the entries of a column spread over the lanes, each lane forming the pivot for itself (which saves the second barrier of
 // a column); a column's k loop is as long as the envelope's row, not as the matrix.  The finished L(j, .) * D strip of a column is NOT staged in LDS: each lane reads
 // row j and D from global memory (L2-resident: a row is at most a few KB and every lane of the column reads the same addresses, which the memory system broadcasts);

@@ -1,5 +1,6 @@
-// Optimizer::BundleAdjustment (reference src/Optimizer.cc:49-237), the optimize of a global bundle adjustment, as PHASES OVER THE WHOLE GRID.  host/global_ba.hpp is
-// the one source of the arithmetic, of the order of every sum and of the control flow for this file and for the host twin (host/global_ba.cpp): every phase there is
+// Optimizer::BundleAdjustment (reference src/Optimizer.cc:49-237), the optimize of a global bundle adjustment, as PHASES OVER THE WHOLE GRID.  host/ba_schur.hpp (the
+// phases local BA has too) and host/global_ba.hpp (the envelope, the control flow) are the one source of the arithmetic and of the order of every sum for this file and
+// for the host twin (host/global_ba.cpp): every phase there is
 // a named function of ONE output element (an edge, one entry of one vertex's Hessian block, one entry of an upper block of Hschur, one entry of the factor, a point, a
 // vertex) wrapped in a functor.  This file names the runner: run.go(n, phase) is one launch of k_gba_phase<Phase>, ceil(n / GBA_THREADS) workgroups of GBA_THREADS
 // lanes, one element per lane, `if (idx < n)`; the grids are not capped.  The device result is compared with the host's bit for bit (tests/test_globalba_gpu.py).
@@ -8,7 +9,7 @@
 // (profiles/match_local_ba.txt).  A global BA is always one item, of hundreds of key frames and about 10^5 observations, so its parallel phases are as wide as their
 // element counts here: edge evaluation one lane per observation; the ordered sums one lane per entry of a vertex's block; Dinv and db per point, BDinv per edge; the
 // Schur complement one lane per entry of an upper block and one per entry of coefficients; back-substitution per point, update per vertex, computeScale's terms per
-// entry of x.  THE SERIAL CHAINS KEEP THEIR ORDER and are the known floor: one lane carries the chi2 chain over rho[0] laid out densely (gba_chain: lba_chain's order, 32 loads in flight), in the same launch
+// entry of x.  THE SERIAL CHAINS KEEP THEIR ORDER and are the known floor: one lane carries the chi2 chain over rho[0] laid out densely (ba_chain<32>: 32 loads in flight), in the same launch
 // as the vertex sums; one lane carries computeScale's chain; one lane the max diagonal, once per call.
 // The factorisation of the reduced camera system (a natural-order envelope in 6 x 6 block rows) costs at most three launches per block column, never one per scalar
 // column: every stored entry of the block column takes its terms left of the column, one lane finishes the diagonal block, every row below finishes inside the column.
@@ -48,12 +49,12 @@ struct GbaDevRun {
         err = hipGetLastError(); cnt->launches++;
     }
     void fetch(const GbaView& w, double* sc) {
-        for (int k = 0; k < GBA_SC_N; k++) sc[k] = 0.0;
-        if (err == hipSuccess) err = hipMemcpyAsync(pinned, w.sc, GBA_SC_N * sizeof(double), hipMemcpyDeviceToHost, s);
+        for (int k = 0; k < BA_SC_N; k++) sc[k] = 0.0;
+        if (err == hipSuccess) err = hipMemcpyAsync(pinned, w.sc, BA_SC_N * sizeof(double), hipMemcpyDeviceToHost, s);
         if (err == hipSuccess) err = hipStreamSynchronize(s);
         cnt->waits++;
-        if (err == hipSuccess) for (int k = 0; k < GBA_SC_N; k++) sc[k] = pinned[k];
-        else sc[GBA_SC_CHI] = NAN;                                   // ends the driver's loops: every compare that continues them fails
+        if (err == hipSuccess) for (int k = 0; k < BA_SC_N; k++) sc[k] = pinned[k];
+        else sc[BA_SC_CHI] = NAN;                                   // ends the driver's loops: every compare that continues them fails
     }
 };
 

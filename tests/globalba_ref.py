@@ -1,5 +1,5 @@
 """Optimizer::BundleAdjustment (reference src/Optimizer.cc:49-237) restated in Python with NumPy FP64 scalars, in the orders that the head of
-sindslam_amd/csrc/host/global_ba.hpp states.  The graph, the ordered sums, the Schur loop nest, the DENSE LDL^T and the Levenberg-Marquardt loop are localba_ref.Graph's
+sindslam_amd/csrc/host/ba_schur.hpp states.  The graph, the ordered sums, the Schur loop nest, the DENSE LDL^T and the Levenberg-Marquardt loop are localba_ref.Graph's
 (the contract is local BA's); what is restated here is what differs: which key frames are free (all but the one with id 0), the Huber deltas (the floats sqrt(5.99) and
 sqrt(7.815)), kernels only if robust, one optimize(iterations), no levels.  Because the reduced system is solved by the dense definition here and through the envelope
 in the library, bit equality of the two checks the envelope.  Plain sequential loops, for small scenes only."""

@@ -1,5 +1,5 @@
 """Optimizer::LocalBundleAdjustment (reference src/Optimizer.cc:506-778) restated in Python with NumPy FP64 scalars, operation for operation in the order that the head
-of sindslam_amd/csrc/host/local_ba.hpp states (vertex order, edge order, the ordered sums, the Schur loop nest, the dense LDL^T, back-substitution); the pose algebra,
+of sindslam_amd/csrc/host/ba_schur.hpp states (vertex order, edge order, the ordered sums, the Schur loop nest, the dense LDL^T, back-substitution); the pose algebra,
 the edge errors and the Huber kernel are poseopt_ref's.  Plain sequential loops over plain lists, for small scenes only.  Bit equality with the host library is BY
 CONSTRUCTION of the two texts; tests/test_localba_cpu.py asserts it and checks the result against things that are neither."""
 from __future__ import annotations

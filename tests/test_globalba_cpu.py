@@ -71,6 +71,102 @@ def test_the_parent_as_yardstick():
     assert _host(G.from_local(scenes[3])[0], 5, True)["included"][7] == 0
 
 
+def _mixed_window():
+    """a local window of 3 free key frames (index 2 without an edge), the fixed key frame with id 0 (index 3) and a fixed camera (index 4) whose observations are all
+    monocular; 38 points seen by three key frames each, one point seen by the two fixed cameras alone and one seen by key frame 0 alone -> the scene"""
+    import globalba_scene as G
+    import localba_scene as SC
+    s = SC.scene(61, 3, 2, 38, kind="mixed", outliers=3, obs_per_point=3)
+    s["kf_kind"] = np.array([0, 0, 0, 1, 2], np.uint8); s["kf_id"] = s["kf_id"].copy(); s["kf_id"][3] = 0
+    s = G.without_kf_obs(s, 2)
+    s["u_right"] = np.where(s["obs_kf"] == 4, np.float32(-1.0), s["u_right"]).astype(np.float32)
+    X = np.array([0.3, -0.2, 6.0]); Y = np.array([-0.6, 0.4, 5.2])
+    s = SC.with_point(s, X + 0.02, [SC.seen(s, 3, X, mono=False), SC.seen(s, 4, X)])
+    return SC.with_point(s, Y - 0.02, [SC.seen(s, 3, Y, mono=False)])
+
+
+def _observations(s, keep):
+    """a copy of the scene with the observations of the mask alone"""
+    out = dict(s)
+    for key in ("obs_kf", "obs_xy", "u_right", "inv_sigma2", "planted"):
+        out[key] = s[key][keep]
+    out["obs_start"] = np.concatenate([[0], np.cumsum(keep)])[np.asarray(s["obs_start"])].astype(np.int32)
+    return out
+
+
+def _as_global(s):
+    """the scene as a global-BA item: the key frames in ascending kf_id (globalba_scene.from_local, which refuses fixed cameras) -> item, order"""
+    order = np.argsort(s["kf_id"], kind="stable"); inv = np.empty(len(order), np.int32); inv[order] = np.arange(len(order), dtype=np.int32)
+    it = {k: s[k] for k in ("mp_id", "x3Dw", "obs_start", "obs_xy", "u_right", "inv_sigma2")}
+    it.update(kf_id=np.asarray(s["kf_id"])[order], Tcw=np.asarray(s["Tcw"])[order], obs_kf=inv[np.asarray(s["obs_kf"], np.int64)])
+    return it, order
+
+
+def _global_linear(it, robust):
+    import globalba_scene as G
+    from sindslam_amd.matcher import globalba_items
+    arr, keep = globalba_items([it])
+    P = int((np.asarray(it["kf_id"]) != 0).sum())
+    Cc = np.zeros((len(it["obs_kf"]), LBA_C)); x = np.zeros(6 * P + 3 * len(it["mp_id"])); lam = np.zeros(1)
+    K = np.ascontiguousarray(G.K5)
+    assert G.host().sindh_globalba_linear(C.addressof(arr), robust, K.ctypes.data, Cc.ctypes.data, x.ctypes.data, lam.ctypes.data) == 0
+    return Cc, x, lam[0]
+
+
+def test_both_bundle_adjustments_linearise_and_solve_a_mixed_window_alike():
+    """The phases the two bundle adjustments share (csrc/host/ba_schur.hpp) through both views, beyond the all-stereo case: the first linearisation and the first
+    trial's solve of a mixed mono / stereo window with 3 free and 2 fixed key frames, 40 points, a point seen by fixed cameras alone and a free key frame without an
+    edge.  C, x and lambda bit for bit, (1) sindh_globalba_linear(robust = 1) against sindh_localba_linear on the stereo observations alone, where the Huber deltas of
+    the two agree, and (2) sindh_globalba_linear(robust = 0) against the numpy restatement on the whole window.
+    Global BA fixes the key frame with id 0 and no other.  The window's second fixed camera therefore carries monocular observations only: among the stereo
+    observations it has none, so global BA holds it as one more free key frame without an edge (no Hessian index, its six entries of x stay +0), and (1) compares
+    the same reduced system.  In (2) it is a free pose of global BA and of its restatement, and the point that only key frame 0 sees is the one seen by fixed cameras
+    alone."""
+    import globalba_ref as GR
+    import globalba_scene as G
+    import localba_scene as SC
+    from sindslam_amd.matcher import localba_items
+    s = _mixed_window()
+    assert list(s["kf_kind"]) == [0, 0, 0, 1, 2] and len(s["mp_id"]) == 40 and not (s["obs_kf"] == 2).any()
+    assert (s["u_right"] < 0).any() and (s["u_right"] >= 0).any() and (s["u_right"][s["obs_kf"] == 4] < 0).all()
+    assert set(s["obs_kf"][s["obs_start"][38]:s["obs_start"][39]]) == {3, 4} and list(s["obs_kf"][s["obs_start"][39]:]) == [3]
+    # (1) the stereo observations alone, through both views
+    st = _observations(s, s["u_right"] >= 0)
+    assert len(st["obs_kf"]) > 40 and not (st["obs_kf"] == 4).any()
+    arr, keep = localba_items([st])
+    n_obs, M = len(st["obs_kf"]), 40
+    Cl = np.zeros((n_obs, LBA_C)); xl = np.zeros(6 * 3 + 3 * M); ll = np.zeros(1)
+    K = np.ascontiguousarray(SC.K5)
+    SC.host().sindh_localba_linear.argtypes = [C.c_void_p] * 5
+    assert SC.host().sindh_localba_linear(C.addressof(arr), K.ctypes.data, Cl.ctypes.data, xl.ctypes.data, ll.ctypes.data) == 0
+    it, order = _as_global(st)
+    Cg, xg, lg = _global_linear(it, 1)
+    free_g = [k for k in order if int(st["kf_id"][k]) != 0]              # global BA's pose ranks as key frames of the scene
+    free_l = sorted([k for k in range(5) if st["kf_kind"][k] == 0], key=lambda k: int(st["kf_id"][k]))
+    assert len(free_g) == 4 and [k for k in free_g if k != 4] == free_l
+    poses = np.concatenate([xg[6 * free_g.index(k):6 * free_g.index(k) + 6] for k in free_l])
+    assert np.array_equal(SC.bits(Cg), SC.bits(Cl)) and SC.bits(np.float64(lg)) == SC.bits(np.float64(ll[0])) and lg > 0
+    assert np.array_equal(SC.bits(poses), SC.bits(xl[:18])) and np.array_equal(SC.bits(xg[24:]), SC.bits(xl[18:]))
+    assert not SC.bits(xg[6 * free_g.index(4):6 * free_g.index(4) + 6]).any() and not SC.bits(xl[6 * free_l.index(2):6 * free_l.index(2) + 6]).any() and np.abs(xl).max() > 1e-4
+    # (2) the whole window without kernels against the restatement
+    it, order = _as_global(s)
+    Cg, xg, lg = _global_linear(it, 0)
+    with np.errstate(all="ignore"):
+        g = GR.Graph(it, G.K5)
+        assert g.activate() > 0 and g.n_act == 3 and g.P == 4
+        g.x = [GR.ZERO] * (6 * g.P + 3 * g.n_mp)
+        g.evaluate(False, True); g.sums()
+        lam = GR.F(1e-5) * g.max_diagonal()
+        Cr = np.zeros_like(Cg)
+        for e, c in enumerate(g.C):
+            if "Hp" in c:
+                Cr[e, 0:21] = c["Hp"]; Cr[e, 21:27] = c["bp"]; Cr[e, 36:54] = np.array(c["Hpl"]).reshape(18)
+            Cr[e, 27:33] = c["Hl"]; Cr[e, 33:36] = c["bl"]; Cr[e, 54] = c["rho0"]; Cr[e, 55] = c["chi2"]
+        assert g.solve(lam)
+    assert np.array_equal(SC.bits(Cg), SC.bits(Cr)) and SC.bits(np.float64(lg)) == SC.bits(np.float64(lam)) and np.array_equal(SC.bits(xg), SC.bits(np.array(g.x, np.float64)))
+    assert sum("Hp" not in c for c in g.C) >= 3 and np.abs(xg[6 * g.P + 3 * 39:]).max() > 0
+
+
 def test_envelope_with_a_loop_equals_the_dense_restatement():
     """40 key frames, window 5, one loop (2, 37): block row 37 starts at block column 2, the rows between do not; the restatement factors the dense 234 x 234"""
     import globalba_scene as G

@@ -13,7 +13,7 @@ SIND_E_ARG, SIND_E_CAPACITY = -1, -5
 SCHUR_DEVIATION = 1.06e-13                                               # measured: |x - numpy's solve of the full (6P + 3M) system| / |x|, the largest over the scenes below
 JACOBIAN_DEVIATION = 6.43e-10                                            # measured: analytic against central differences, relative to the largest entry of the edge's Jacobian
 SCIPY_GAP = 1.23e-5                                                     # measured: (stage 2's chi2 - scipy's minimum of the same cost) / that minimum; the stop criterion ends a stage after three steps that gain under 1e-3
-LBA_C = 56                                                              # doubles per edge of csrc/host/local_ba.hpp
+LBA_C = 56                                                              # doubles per edge of csrc/host/ba_schur.hpp
 
 
 def _host(s):
