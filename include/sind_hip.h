@@ -1395,6 +1395,30 @@ int sind_debug_contours(const unsigned long long* planes, int n, int width, int 
 int sind_debug_seg_pieces(const unsigned long long* planes, int k, const unsigned long long* occ1, const unsigned long long* label_edge, const uint16_t* depth, int n, int width, int height,
                           float depth_scale, int device, int cap, int* info_gpu, int* recs_gpu, float* vals_gpu, unsigned long long* pieces_gpu, unsigned long long* conn_gpu, uint8_t* piece_of_gpu,
                           int* info_host, int* recs_host, float* vals_host, unsigned long long* pieces_host, unsigned long long* conn_host, uint8_t* piece_of_host);
+/* The piece stage batched per round (PieceBatch, csrc/dyna.hpp): n frames (1..64; width a multiple of 64, height of 8) of k cluster planes, occ1, labelForSegEdge, depth as
+ * above, plus occ2 and the 8-bit normalised depth [n][height][width] u8 for the region-adjacency statistics.  Device side (the *_gpu outputs): the real PieceBatch in chunks
+ * of `chunk` frames (n = 5, chunk 3: a full and a partial chunk) with the depth planes at non-uniform device offsets (the stage's depth table), the host step
+ * (seg_pieces_order), k_piece_commit_frames / k_piece_paint_frames into a RagBatch's device slab and launch_rag_frames on it; a frame whose status is not 0 runs the host
+ * function and is packed from the host into the same run.  Host side: the host function, the ranking, rag_pack and launch_rag_frames on a host-packed slab (the path of a
+ * round without the switch).  Per frame and side: info [4] = number of pieces C, error code (0, or SIND_E_CAPACITY for more than 254 pieces: nothing else is returned for
+ * the frame and sind_last_error holds the text), fell back (a capacity of the device stage was exceeded), committed on the device; recs / vals / piece and connection planes /
+ * piece_of in the layout of sind_debug_seg_pieces (on the device side the planes and piece_of are read back from where the kernels wrote them: the slab's [0, C) / [C, 2C)
+ * sets in rank order, zeros of a missing connection area included); rag [rag_cap] ints = the frame's result block (3 C^2 + C + 256 C ints: overlap, overlapPlane,
+ * connection overlap, connection areas, histograms). */
+int sind_debug_pieces_batch(const unsigned long long* planes, int k, const unsigned long long* occ1, const unsigned long long* label_edge, const uint16_t* depth, const uint8_t* occ2,
+                            const uint8_t* depth_n, int n, int width, int height, float depth_scale, int device, int chunk, int cap, int rag_cap,
+                            int* info_gpu, int* recs_gpu, float* vals_gpu, unsigned long long* pieces_gpu, unsigned long long* conn_gpu, uint8_t* piece_of_gpu, int* rag_gpu,
+                            int* info_host, int* recs_host, float* vals_host, unsigned long long* pieces_host, unsigned long long* conn_host, uint8_t* piece_of_host, int* rag_host);
+/* The round's switch (default off; with it off nothing is launched, allocated or changed): in the non-split `rounds` schedule with the batched RAG stage on, a round's
+ * frames cut their pieces through their k-means group's PieceBatch -- one chain of 13 launches per chunk of rag_chunk (at most 64) frames instead of the host function,
+ * the planes committed straight into the RAG batch's device slab: two waits per chunk, none per frame, no piece plane over PCIe in either direction.  Every other
+ * schedule (chains, flow_chains, two_chains, split_rounds, rounds without the batched RAG stage) is untouched: there sind_pipe_set_device_pieces alone decides, and
+ * sind_pipe_device_pieces keeps counting only that per-tail stage.  The workspaces (about 2 GB per k-means group at 640 x 480 and chunk 32, csrc/dyna.hpp) are made by the
+ * first round that uses them; an allocation failure fails the step with its text.  frames_batched: frames whose pieces were cut and committed on the device;
+ * frames_fallback: frames that exceeded a capacity of the stage and ran the host function.  A frame with no cluster to cut, no pieces, or more than 254 (SIND_E_CAPACITY, as
+ * on every path) counts as neither.  Same results, bit for bit.  Not while a step is pending. */
+int sind_pipe_set_pieces_batch(sind_pipe* p, int on);
+int sind_pipe_get_pieces_batch(sind_pipe* p, int* on, long long* frames_batched, long long* frames_fallback);
 /* The switch: SegAndMerge's piece extraction of a handle on the GPU instead of the host.  Off by default; the results do not depend on it.  A frame in which a plane
  * exceeds a capacity of the device stage runs the host function and is counted as fallen back.  The second call of each pair only reads. */
 int sind_dyna_set_device_pieces(sind_dyna* d, int on);

@@ -276,12 +276,13 @@ __global__ void __launch_bounds__(256) k_piece_draw2(PieceFrameHdr* __restrict__
 // myCluster::calCenterPoint's z (DD:256-293): the FP32 sum of (float)d * invDepthScale * 1.5f over the piece's pixels in row-major order, one add after the other, product
 // and add separate; a raw depth of 0 or >= z_invalid adds 0.  One wave per piece: 64 plane words are fetched at once, the lanes of a word's 64 pixels form their terms,
 // and the running sum takes them in bit order.
+// Frame b's depth plane: depth_tab[b] where a table is given (a chunk's frames come from arbitrary streams), else depth + b * depth_stride.
 __global__ void __launch_bounds__(64) k_piece_centre(const PieceFrameHdr* __restrict__ frames, PieceRecDev* __restrict__ recs, const u64* __restrict__ pb, const uint16_t* __restrict__ depth,
-                                                     size_t depth_stride, int z_invalid, float inv_scale, int wpr, int W, int H) {
+                                                     size_t depth_stride, const uint16_t* const* __restrict__ depth_tab, int z_invalid, float inv_scale, int wpr, int W, int H) {
     const int slot = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
     if (slot >= min(frames[b].pieces, PIECE_SLOTS)) return;
     const size_t ps = (size_t)b * PIECE_SLOTS + slot; const int pw = wpr * H;
-    const u64* img = pb + ps * (size_t)pw; const uint16_t* dp = depth + (size_t)b * depth_stride;
+    const u64* img = pb + ps * (size_t)pw; const uint16_t* dp = depth_tab ? depth_tab[b] : depth + (size_t)b * depth_stride;
     float f3 = 0.f;
     for (int base = 0; base < pw; base += 64) {
         const int wi = base + lane;
@@ -331,7 +332,61 @@ int launch_piece_commit(hipStream_t s, const PieceStage& st, int b, int C, const
     return SIND_OK;
 }
 
-int PieceStage::enqueue(hipStream_t s, int n, const uint16_t* depth_dev, size_t depth_stride, int z_invalid_from, float inv_depth_scale) {
+// ---- the same for the frames of a chunk, into the batched RAG stage's slab (PieceCommitRec, pieces_dev.hpp).  grid (words, the chunk's largest C, frames)
+__global__ void __launch_bounds__(256) k_piece_commit_frames(const PieceCommitRec* __restrict__ recs, const int* __restrict__ table, const u64* __restrict__ pb, const u64* __restrict__ pa,
+                                                             u64* __restrict__ slab, size_t pw) {
+    const PieceCommitRec R = recs[blockIdx.z];
+    const int r = blockIdx.y; const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= R.C || idx >= pw) return;
+    const int slot = table[R.tab_off + r];
+    if (slot < 0 || slot >= PIECE_SLOTS) return;
+    const size_t src = ((size_t)R.b * PIECE_SLOTS + slot) * pw + idx;
+    u64* out = slab + R.plane_off;
+    out[(size_t)r * pw + idx] = pb[src];
+    out[((size_t)R.C + r) * pw + idx] = table[R.tab_off + PIECE_SLOTS + r] ? pa[src] : 0ull;
+}
+// pieceOf of a chunk's frames.  k_piece_paint walks the ranks from the top with one dependent load per rank and pixel; the 64 pixels of a plane word read the SAME word
+// of every rank, so here a wave owns one word position: its lanes load that word from 64 ranks at once (lane l: rank top - l), a ballot names the ranks whose word is not
+// empty -- a few of the C, pieces overlap little -- and only those are looked at, highest rank first; a pixel keeps the first rank that has its bit.  Same result: the
+// owner is the highest rank whose plane has the pixel.  Four waves per workgroup; grid (words / 4, frames)
+__global__ void __launch_bounds__(256) k_piece_paint_frames(const PieceCommitRec* __restrict__ recs, const int* __restrict__ table, const u64* __restrict__ pb,
+                                                            uint8_t* __restrict__ piece_of, int W, int H, int wpr) {
+    const PieceCommitRec R = recs[blockIdx.y];
+    const int lane = threadIdx.x & 63; const size_t pw = (size_t)wpr * H; const size_t widx = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (widx >= pw) return;                         // (the whole wave)
+    const int y = (int)(widx / wpr), x = ((int)(widx - (size_t)y * wpr) << 6) + lane;
+    const u64* planes = pb + (size_t)R.b * PIECE_SLOTS * pw + widx;
+    int owner = -1;
+    for (int top = R.C - 1; top >= 0; top -= 64) {
+        const int r = top - lane; u64 mine = 0ull;
+        if (r >= 0) { const int slot = table[R.tab_off + r]; if (slot >= 0 && slot < PIECE_SLOTS) mine = planes[(size_t)slot * pw]; }
+        u64 nz = __ballot(mine != 0ull);
+        while (nz) {
+            const int l = __ffsll((long long)nz) - 1; nz &= nz - 1;
+            const u64 m = ((u64)(unsigned)__builtin_amdgcn_readlane((int)(mine >> 32), l) << 32) | (u64)(unsigned)__builtin_amdgcn_readlane((int)mine, l);
+            if (owner < 0 && ((m >> lane) & 1ull)) owner = top - l;
+        }
+        if (__ballot(owner < 0) == 0ull) break;
+    }
+    if (x < W) piece_of[R.piece_of_off + (size_t)y * W + x] = (uint8_t)(owner < 0 ? R.C + 1 : owner);
+}
+int launch_piece_commit_frames(hipStream_t s, const PieceStage& st, const PieceCommitRec* recs_dev, const PieceCommitRec* host, int n, const int* table_dev, size_t table_ints,
+                               unsigned long long* slab, size_t slab_words, uint8_t* piece_of, size_t piece_of_bytes) {
+    if (n < 1 || n > st.cap || !recs_dev || !host || !table_dev || !slab || !piece_of) { sind_set_error("launch_piece_commit_frames: %d frames (capacity %d) or a null pointer", n, st.cap); return SIND_E_ARG; }
+    int maxC = 0;
+    for (int i = 0; i < n; i++) {
+        const PieceCommitRec& R = host[i];
+        if (R.b < 0 || R.b >= st.cap || R.C < 1 || R.C > 254 || R.tab_off < 0 || (size_t)R.tab_off + 2 * PIECE_SLOTS > table_ints || R.plane_off + (size_t)2 * R.C * st.pw > slab_words ||
+            R.piece_of_off + st.N > piece_of_bytes) { sind_set_error("launch_piece_commit_frames: record %d (frame %d, %d pieces) leaves the stage, its table, the slab or pieceOf", i, R.b, R.C); return SIND_E_ARG; }
+        maxC = std::max(maxC, R.C);
+    }
+    hipLaunchKernelGGL(k_piece_commit_frames, dim3((unsigned)((st.pw + 255) / 256), maxC, n), dim3(256), 0, s, recs_dev, table_dev, st.pb.p, st.pa.p, slab, st.pw);
+    hipLaunchKernelGGL(k_piece_paint_frames, dim3((unsigned)((st.pw + 3) / 4), n), dim3(256), 0, s, recs_dev, table_dev, st.pb.p, piece_of, st.W, st.H, st.wpr);
+    HIP_TRY(hipGetLastError());
+    return SIND_OK;
+}
+
+int PieceStage::enqueue(hipStream_t s, int n, const uint16_t* depth_dev, size_t depth_stride, int z_invalid_from, float inv_depth_scale, const uint16_t* const* depth_tab) {
     if (n < 1 || n > cap) { sind_set_error("PieceStage::enqueue: %d frames, capacity %d", n, cap); return SIND_E_ARG; }
     const u64 tm = (W & 63) ? ((1ull << (W & 63)) - 1) : ~0ull;
     const unsigned gw = (unsigned)((pw + 255) / 256);
@@ -349,7 +404,7 @@ int PieceStage::enqueue(hipStream_t s, int n, const uint16_t* depth_dev, size_t 
     hipLaunchKernelGGL(k_piece_clear, dim3(gw, PIECE_SLOTS, n), dim3(256), 0, s, frames.p, pa.p, (u64*)nullptr, (u64*)nullptr, (u64*)nullptr, pw);
     hipLaunchKernelGGL(k_piece_draw2, dim3(PIECE_SLOTS, n), dim3(256), 0, s, frames.p, recs.p, l2.hdr.p, l2.chain.p, l2.count.p, l2.cap_contours, l2.cap_points, pa.p, pd.p, area.p, band.p, wpr, W, H);
     hipLaunchKernelGGL(k_piece_fill, dim3((H + 255) / 256, PIECE_SLOTS, n), dim3(256), 0, s, frames.p, pa.p, pd.p, wpr, H);
-    hipLaunchKernelGGL(k_piece_centre, dim3(PIECE_SLOTS, n), dim3(64), 0, s, frames.p, recs.p, pb.p, depth_dev, depth_stride, z_invalid_from, inv_depth_scale, wpr, W, H);
+    hipLaunchKernelGGL(k_piece_centre, dim3(PIECE_SLOTS, n), dim3(64), 0, s, frames.p, recs.p, pb.p, depth_dev, depth_stride, depth_tab, z_invalid_from, inv_depth_scale, wpr, W, H);
     HIP_TRY(hipGetLastError());
     return SIND_OK;
 }

@@ -5,6 +5,7 @@
 #include <chrono>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <vector>
 #include "common.hpp"
 #include "depth.hpp"
@@ -153,6 +154,15 @@ public:
     int begin_round();                                                 // forget the previous round's slots (whose results are no longer needed)
     // a slot and plane space for a frame of C pieces: *pieces and *conn take C planes each.  false: the slabs are full (the frame takes the per-frame stage)
     bool reserve(int C, int* slot, unsigned long long** pieces, unsigned long long** conn);
+    // The same for the frames of one piece chunk (PieceBatch) at once: n consecutive slots, so that the run is still one set of launches.  on_device[i]: the frame's planes
+    // are written into the DEVICE slab by the commit kernels (at plane_off(slot)) and no H2D covers them; else pieces[i] / conn[i] point into the page-locked slab as above.
+    // slots[i] = -1: the slabs had no room for frame i (the others still form a run).  Returns the first slot handed out (-1: none).
+    int reserve_run(int n, const int* C, const uint8_t* on_device, int* slots, unsigned long long** pieces, unsigned long long** conn);
+    size_t plane_off(int slot) const { return recs_h.p[slot].plane_off; }
+    unsigned long long* slab_dev() { return in_d.p; }
+    size_t slab_words() const { return in_cap; }
+    // slots [first, first + n) as one set of launches; its results are there after wait(ev) (ev < the capacity; enqueue(chunk) = the chunk's slots with ev = chunk)
+    int enqueue_run(int first, int n, int ev);
     void set_inputs(int slot, const uint8_t* occ2, const uint8_t* depthN, hipEvent_t occ2_event);      // occ2_event: recorded behind the frame's occ2 upload on another stream (or nullptr)
     int chunk_of(int slot) const { return slot / chunk_n; }
     int chunk_first(int chunk) const { return chunk * chunk_n; }
@@ -166,8 +176,69 @@ private:
     DynaConfig cfg; int W = 0, H = 0, cap = 0, chunk_n = 32, planes_frame = 64, n_slots = 0; size_t pw = 0, in_used = 0, res_used = 0, in_cap = 0, res_cap = 0;
     std::mutex m, enq;
     PinnedBuf<unsigned long long> in_h; DevBuf<unsigned long long> in_d, dil_d; PinnedBuf<RagRec> recs_h; DevBuf<RagRec> recs_d; DevBuf<int> res_d; PinnedBuf<int> res_h;
-    std::vector<hipEvent_t> occ2_ev, done;
+    std::vector<hipEvent_t> occ2_ev, done; std::vector<uint8_t> on_dev;      // on_dev: the slot's planes lie in the device slab already
+    bool reserve_locked(int C, bool dev, int* slot, unsigned long long** pieces, unsigned long long** conn);
 };
+
+// ---- SegAndMerge's piece extraction (DD:664-729) for one frame of EVERY stream of a k-means group, in chunks: one PieceStage (pieces_dev.hpp) of capacity `chunk` in
+// front of the RagBatch's join, its commit writing straight into the RagBatch's device slab.  Per tail the stage was a chain of 13 + 2 launches of mostly one-wave
+// kernels with two waits (profiles/seg_pieces.txt); here a chunk is ONE such chain.  A frame takes a slot (any pool thread) and packs its inputs into the page-locked
+// slab; slots are handed out in order and chunk c holds slots [c * chunk, (c + 1) * chunk).  enqueue(chunk): the chunk's inputs up (cluster planes, occ1,
+// labelForSegEdge, plane counts, depth table: five copies, each contiguous over the chunk), the 13 launches, frame headers and records down, one event.  After the host
+// step (seg_pieces_order per frame, host/pieces.hpp) commit(chunk) sends the order tables up and launches k_piece_commit_frames / k_piece_paint_frames for the frames
+// that stayed on the device, and brings their pieceOf back on the same stream: whoever waits for the RAG launches behind it has pieceOf too.
+// Capacity: the chunk is at most 64 frames (PieceStage::init), whatever the RAG chunk setting says.
+// Workspaces (made by the first round that uses them; an allocation failure is returned with its text, nothing else is tried).  With pw = H * W / 64 words per plane:
+//   4 plane sets of PIECE_SLOTS planes per frame           chunk * 4 * 255 * pw * 8 bytes      640 x 480, chunk 32: 1.25 GB
+//   3 sets of PIECE_KMAX planes + 3 planes per frame       chunk * 39 * pw * 8                 48 MB
+//   first-level tracer (12 planes per frame)               chunk * 12 * (1024 * 40 + 32768 * 4) 66 MB
+//   second-level tracer (255 planes per frame)             chunk * 255 * (256 * 40 + 16384 * 4) 0.62 GB
+//   the stage's own depth planes (unused here), records    chunk * (W * H * 2 + 255 * 72)      20 MB
+//   above 144 KB of mark cells per plane (1280 x 720)      chunk * 267 * (W + 2)(H + 2) / 4    (global scratch: 1.98 GB at 1280 x 720, none at 640 x 480)
+//   per frame of the GROUP: input slab 14 planes (page-locked), pieceOf W * H (device and page-locked), records 16 KB, tables 2 KB
+// i.e. about 2.0 GB at 640 x 480 and chunk 32 (1.25 GB of it the four plane sets, 0.62 GB the second-level tracer); at 1280 x 720 the plane sets are three times
+// as large (3.8 GB), the tracers stay, and the scratch cells come on top: about 6.6 GB.  One object per k-means group.
+class PieceBatch {
+public:
+    int init(const DynaConfig& c, int max_frames, hipStream_t s);      // (cheap: the workspaces are made by the first round that uses them)
+    ~PieceBatch();
+    void set_chunk(int chunk) { chunk_n = std::max(1, std::min(chunk < 1 ? cap : chunk, std::min(cap, 64))); }      // not while a round is running
+    int chunk_frames() const { return chunk_n; }
+    int begin_round();                                                 // workspaces on first use; forget the previous round's slots
+    int take_slot();                                                   // -1: every slot of the group is taken
+    // the frame's inputs into its slot: nCl (1 .. PIECE_KMAX) cluster planes, occ1, labelForSegEdge, where its depth plane lies on the device
+    void pack(int slot, const BitImg* labels, int nCl, const BitImg& occ1, const BitImg& label_edge, const uint16_t* depth_dev);
+    int chunk_of(int slot) const { return slot / chunk_n; }
+    int chunk_first(int chunk) const { return chunk * chunk_n; }
+    int chunk_count(int chunk) const { return std::max(0, std::min(chunk_n, n_slots - chunk * chunk_n)); }
+    int slots() const { return n_slots; }
+    int enqueue(int chunk, int z_invalid_from, float inv_depth_scale);
+    int wait(int chunk);
+    const PieceFrameHdr& header(int slot) const { return hdr_h.p[slot]; }
+    const PieceRecDev* records(int slot) const { return recs_h.p + (size_t)slot * PIECE_SLOTS; }
+    int* order_table(int slot) { return tab_h.p + (size_t)slot * 2 * PIECE_SLOTS; }      // [0, PIECE_SLOTS): slot per rank; [PIECE_SLOTS, 2 PIECE_SLOTS): has_conn per rank
+    // frames `slots[i]` of the chunk (C[i] ranked pieces, order tables filled) into `slab` at plane_off[i]: tables up, two launches, pieceOf down.  No wait
+    int commit(int chunk, int n, const int* slots, const int* C, const size_t* plane_off, unsigned long long* slab, size_t slab_words);
+    const uint8_t* piece_of(int slot) const { return pof_h.p + (size_t)slot * N; }
+    std::mutex& flush_mutex() { return flush_mu; }      // one chunk at a time from its piece launches to its commit launches: the stage's planes are the chunk's until then
+    const PieceStage& stage() const { return st; }
+    hipStream_t stream = nullptr;
+private:
+    DynaConfig cfg; int W = 0, H = 0, cap = 0, chunk_n = 32, n_slots = 0; size_t pw = 0, N = 0; bool ready = false;
+    std::mutex m, flush_mu;
+    PieceStage st; DevBuf<const uint16_t*> dtab_d; DevBuf<uint8_t> pof_d; DevBuf<PieceCommitRec> crec_d; DevBuf<int> tab_d;
+    PinnedBuf<unsigned long long> planes_h, occ1_h, edge_h; PinnedBuf<int> np_h; PinnedBuf<const uint16_t*> dtab_h;      // per slot: PIECE_KMAX planes, occ1, labelForSegEdge, plane count, depth pointer
+    PinnedBuf<PieceFrameHdr> hdr_h; PinnedBuf<PieceRecDev> recs_h; PinnedBuf<int> tab_h; PinnedBuf<PieceCommitRec> crec_h; PinnedBuf<uint8_t> pof_h;
+    std::vector<hipEvent_t> done;
+};
+// One frame of a chunk through the flush below: its depth-half tail (in), and what became of it (out): rc / err != OK: the frame failed (more than 254 pieces) and
+// nothing else holds; rag_slot >= 0: its counters are rb.result(rag_slot) after the flush; rag_slot < 0 with pieces: the slab had no room, it takes the per-frame stage
+// (own); on_device: its planes were committed on the device and its pieceOf is pb.piece_of(slot)
+struct PieceChunkFrame { DynaTail* half = nullptr; int rc = 0; std::string err; int rag_slot = -1; bool own = false, on_device = false, fell_back = false; };
+// The flush of one piece chunk, stated once for the pipeline and the parity entry: piece launches, wait, the host step of every frame (a frame whose status is not 0
+// runs the host function here and is packed from the host: the run may mix both kinds), reservation of the run, commit and paint launches, RAG launches, wait.
+// fr: chunk_count(chunk) frames in slot order.  A failure returned is the chunk's: every frame of it has failed.
+int piece_chunk_flush(PieceBatch& pb, RagBatch& rb, int chunk, PieceChunkFrame* fr);
 
 class DynaTail {
 public:
@@ -195,7 +266,28 @@ public:
     // normalised depth are on the device already; rag_pack() writes the piece and connection planes; rag_own() is the per-frame stage.  Same arithmetic in the same order.
     int process_begin(const uint16_t* depth_host, const uint16_t* depth_dev, const float* U, const float* V, const OccResult* precomputed, DynaTail* depth_half,
                       const KmFrameResult* km, const FlowMasksReady* fm);
-    int process_end(const int* rag, uint8_t* dyna_out, uint8_t* label_out);
+    // piece_of: the frame's pieceOf where a PieceBatch painted it (seg_pieces_batched from records), else nullptr
+    int process_end(const int* rag, uint8_t* dyna_out, uint8_t* label_out, const uint8_t* piece_of = nullptr);
+    // process_begin in two parts around a round's batched piece stage (PieceBatch): process_begin_inputs runs the frame up to the INPUTS of SegAndMerge's piece
+    // extraction (on rag_half(): piece_labels() -- the last one is the farthest cluster, which is not cut --, piece_occ1(), piece_edge(), piece_depth_dev());
+    // seg_pieces_batched() is the rest of process_begin from the frame's records (ranked: seg_pieces_order) or, with recs = nullptr, through the host function.
+    // piece_batchable(): the frame has 1 .. PIECE_KMAX clusters to cut and its depth, occ2 and normalised depth are on the device.  process_begin = both parts, the
+    // second through seg_pieces.  order / has_conn: PIECE_SLOTS ints each (the commit kernels' table).  SIND_E_CAPACITY: more than 254 pieces, as on every path.
+    int process_begin_inputs(const uint16_t* depth_host, const uint16_t* depth_dev, const float* U, const float* V, const OccResult* precomputed, DynaTail* depth_half,
+                             const KmFrameResult* km, const FlowMasksReady* fm);
+    bool piece_batchable() const { const int nCl = (int)segLabels.size() - 1; return nCl >= 1 && nCl <= PIECE_KMAX && segDepthDev && segPre && segPre->occ2_dev && segPre->depthN_dev; }
+    const std::vector<BitImg>& piece_labels() const { return segLabels; }
+    const BitImg& piece_occ1() const { return segOcc1; }
+    const BitImg& piece_edge() const { return segEdge; }
+    const uint16_t* piece_depth_dev() const { return segDepthDev; }
+    int seg_pieces_batched(const PieceRecDev* recs, int C, int* order, int* has_conn);
+    int piece_z_invalid_from() const { return zInvalidFrom; }
+    float piece_inv_depth_scale() const { return invDepthScale; }
+    // parity-test access (sind_debug_pieces_batch): a frame's piece inputs as process_begin_inputs leaves them, and its pieces afterwards
+    void debug_set_piece_inputs(const unsigned long long* planes, int k, const unsigned long long* occ1, const unsigned long long* label_edge, const uint16_t* depth_host,
+                                const uint16_t* depth_dev, const OccResult* pre);
+    const std::vector<SegPiece>& debug_pieces() const { return segAll; }
+    const std::vector<uint8_t>& debug_piece_of() const { return segPieceOf; }
     DynaTail* rag_half() { return pendHalf ? pendHalf : this; }
     int rag_pieces() const { return (int)segAll.size(); }
     bool rag_batchable() const { return !segOnDevice && segPre && segPre->occ2_dev && segPre->depthN_dev; }      // (pieces cut on the device stay there: RagBatch takes host planes, such a frame runs rag_own)
@@ -261,8 +353,13 @@ private:
     std::vector<SegPiece> segAll; std::vector<uint8_t> segPieceOf; BitImg segOcc1, segOcc2; const uint16_t* segDepthDev = nullptr; const OccResult* segPre = nullptr;
     BitImg pendLow, pendHigh; DepthStageOut pendD; DynaTail* pendHalf = nullptr;      // process_begin -> process_end
     int depth_stage_begin(const uint16_t* depth_host, const uint16_t* depth_dev, const OccResult* precomputed, DepthStageOut& out, const KmFrameResult* km);
+    // depth_stage_begin = depth_stage_inputs (up to the inputs of the piece extraction, kept in segLabels / segOcc1 / segEdge / segDepthHost) + depth_stage_pieces
+    std::vector<BitImg> segLabels; BitImg segEdge; const uint16_t* segDepthHost = nullptr;
+    int depth_stage_inputs(const uint16_t* depth_host, const uint16_t* depth_dev, const OccResult* precomputed, DepthStageOut& out, const KmFrameResult* km);
+    int depth_stage_pieces();
+    int seg_pieces_check_and_rank(bool on_device);      // the rest of seg_pieces once segAll holds the pieces in discovery order
     int depth_stage_end(DepthStageOut& out, const int* rag);
-    int seg_pieces(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& labelForSegEdge, const uint16_t* depth_host);
+    int seg_pieces(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& labelForSegEdge, const uint16_t* depth_host, bool allow_device = true);
     int seg_rag_gpu(const int** rag);
     std::unique_ptr<PieceStage> pieceStage; PinnedBuf<unsigned long long> h_pieceIn, h_pieceOut; PinnedBuf<PieceRecDev> h_pieceRecs; PinnedBuf<PieceFrameHdr> h_pieceHdr; PinnedBuf<int> h_pieceNp;
     int seg_pieces_device(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& labelForSegEdge, std::vector<SegPiece>& all, bool* done);      // dyna_pieces.cpp

@@ -56,12 +56,7 @@ int DynaTail::seg_pieces_device(const std::vector<BitImg>& allLabels, const BitI
     const int C = h_pieceHdr.p[0].pieces;
     if (h_pieceHdr.p[0].status != 0 || C < 0) { n_pieces_fallback++; return SIND_OK; }
     *done = true; n_pieces_device++;
-    all.resize(C);                 // (more than 254: the caller reports the capacity error from the count, as on the host path)
-    for (int i = 0; i < std::min(C, PIECE_SLOTS); i++) {
-        const PieceRecDev& r = h_pieceRecs.p[i]; SegPiece& p = all[i];
-        p.cluster = r.cluster; p.clen = r.clen; p.start = PtI{r.sx, r.sy}; p.sum2 = ((long long)r.sum2_hi << 32) | (long long)r.sum2_lo; p.box = Rect{r.x0, r.y0, r.x1, r.y1};
-        p.area = (float)r.area; p.cz = r.cz; p.hasLianjie = r.has_conn != 0;
-    }
+    seg_pieces_from_records(h_pieceRecs.p, C, all);                 // (more than 254: the caller reports the capacity error from the count, as on the host path)
     return SIND_OK;
 }
 // segAll is ranked (disc = the piece's slot in the stage): the order goes up and k_piece_commit writes the planes into planes_d and pieceOf into pieceOf_d.  No wait
@@ -89,6 +84,126 @@ int DynaTail::debug_seg_pieces(const unsigned long long* planes, int k, const un
             p.lianjie.create(W, H); std::memcpy(p.lianjie.d.data(), pl.data() + ((size_t)2 * C + r) * pw, pw * 8); }
     } else piece_of = segPieceOf;
     out = segAll; segAll.clear(); segOnDevice = false;
+    return SIND_OK;
+}
+void DynaTail::debug_set_piece_inputs(const unsigned long long* planes, int k, const unsigned long long* occ1w, const unsigned long long* edgew, const uint16_t* depth_host,
+                                      const uint16_t* depth_dev, const OccResult* pre) {
+    const size_t pw = (size_t)H * (W / 64);
+    auto img = [&](const unsigned long long* q) { BitImg b(W, H); std::memcpy(b.d.data(), q, pw * 8); return b; };
+    segLabels.assign(k + 1, BitImg(W, H)); for (int i = 0; i < k; i++) segLabels[i] = img(planes + (size_t)i * pw);      // (the last one: the farthest cluster, which is not cut)
+    segOcc1 = img(occ1w); segEdge = img(edgew); segDepthHost = depth_host; segDepthDev = depth_dev; segPre = pre; segAll.clear(); segOnDevice = false;
+}
+
+// ---- the piece stage of one frame of every stream of a k-means group, in chunks (see dyna.hpp)
+int PieceBatch::init(const DynaConfig& c, int max_frames, hipStream_t s) {
+    cfg = c; W = c.W; H = c.H; cap = max_frames; stream = s; pw = (size_t)H * (W / 64); N = (size_t)W * H;
+    if (W % 64 != 0 || max_frames < 1) { sind_set_error("PieceBatch: width must be a multiple of 64 (got %d), %d frames", W, max_frames); return SIND_E_ARG; }
+    set_chunk(chunk_n);
+    return SIND_OK;
+}
+PieceBatch::~PieceBatch() { for (hipEvent_t e : done) if (e) (void)hipEventDestroy(e); }
+int PieceBatch::begin_round() {
+    HIP_TRY(hipSetDevice(cfg.device));
+    if (!ready || st.cap < chunk_n) {
+        SIND_TRY(st.init(W, H, chunk_n));      // (an allocation that fails is the round's failure, with hipMalloc's text)
+        SIND_TRY(dtab_d.alloc(chunk_n)); SIND_TRY(crec_d.alloc(chunk_n)); SIND_TRY(crec_h.alloc((size_t)cap)); SIND_TRY(tab_d.alloc((size_t)chunk_n * 2 * PIECE_SLOTS));
+        SIND_TRY(pof_d.alloc((size_t)cap * N)); SIND_TRY(pof_h.alloc((size_t)cap * N));
+        SIND_TRY(planes_h.alloc((size_t)cap * PIECE_KMAX * pw)); SIND_TRY(occ1_h.alloc((size_t)cap * pw)); SIND_TRY(edge_h.alloc((size_t)cap * pw)); SIND_TRY(np_h.alloc(cap)); SIND_TRY(dtab_h.alloc(cap));
+        SIND_TRY(hdr_h.alloc(cap)); SIND_TRY(recs_h.alloc((size_t)cap * PIECE_SLOTS)); SIND_TRY(tab_h.alloc((size_t)cap * 2 * PIECE_SLOTS));
+        if (done.empty()) { done.assign(cap, nullptr); for (hipEvent_t& e : done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
+        ready = true;
+    }
+    std::lock_guard<std::mutex> lk(m);
+    n_slots = 0;
+    return SIND_OK;
+}
+int PieceBatch::take_slot() { std::lock_guard<std::mutex> lk(m); return ready && n_slots < cap ? n_slots++ : -1; }
+void PieceBatch::pack(int slot, const BitImg* labels, int nCl, const BitImg& occ1, const BitImg& label_edge, const uint16_t* depth_dev) {
+    nCl = std::max(0, std::min(nCl, PIECE_KMAX));
+    for (int i = 0; i < nCl; i++) std::memcpy(planes_h.p + ((size_t)slot * PIECE_KMAX + i) * pw, labels[i].d.data(), pw * 8);
+    std::memcpy(occ1_h.p + (size_t)slot * pw, occ1.d.data(), pw * 8); std::memcpy(edge_h.p + (size_t)slot * pw, label_edge.d.data(), pw * 8);
+    np_h.p[slot] = nCl; dtab_h.p[slot] = depth_dev;
+}
+int PieceBatch::enqueue(int chunk, int z_invalid_from, float inv_depth_scale) {
+    HIP_TRY(hipSetDevice(cfg.device));
+    int first, n; { std::lock_guard<std::mutex> lk(m); first = chunk_first(chunk); n = chunk_count(chunk); }
+    if (chunk < 0 || n < 1 || n > st.cap) { sind_set_error("PieceBatch::enqueue: chunk %d holds %d frames (capacity %d)", chunk, n, st.cap); return SIND_E_ARG; }
+    for (int b = first; b < first + n; b++) if (!dtab_h.p[b]) { sind_set_error("PieceBatch::enqueue: slot %d has no depth plane", b); return SIND_E_STATE; }
+    // (planes a frame does not have keep what an earlier frame left in the slab: the kernels stop at the frame's plane count)
+    HIP_TRY(hipMemcpyAsync(st.in_planes.p, planes_h.p + (size_t)first * PIECE_KMAX * pw, (size_t)n * PIECE_KMAX * pw * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(st.occ1.p, occ1_h.p + (size_t)first * pw, (size_t)n * pw * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(st.label_edge.p, edge_h.p + (size_t)first * pw, (size_t)n * pw * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(st.nplanes_d.p, np_h.p + first, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(dtab_d.p, dtab_h.p + first, (size_t)n * sizeof(const uint16_t*), hipMemcpyHostToDevice, stream));
+    SIND_TRY(st.enqueue(stream, n, nullptr, 0, z_invalid_from, inv_depth_scale, dtab_d.p));
+    HIP_TRY(hipMemcpyAsync(hdr_h.p + first, st.frames.p, (size_t)n * sizeof(PieceFrameHdr), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(recs_h.p + (size_t)first * PIECE_SLOTS, st.recs.p, (size_t)n * PIECE_SLOTS * sizeof(PieceRecDev), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(done[chunk], stream));
+    return SIND_OK;
+}
+int PieceBatch::wait(int chunk) {
+    if (chunk < 0 || chunk >= (int)done.size()) { sind_set_error("PieceBatch::wait: chunk %d", chunk); return SIND_E_ARG; }
+    HIP_TRY(sind_event_wait(done[chunk]));
+    return SIND_OK;
+}
+int PieceBatch::commit(int chunk, int n, const int* slots, const int* C, const size_t* plane_off, unsigned long long* slab, size_t slab_words) {
+    if (n < 1) return SIND_OK;
+    HIP_TRY(hipSetDevice(cfg.device));
+    const int first = chunk_first(chunk);
+    if (n > st.cap) { sind_set_error("PieceBatch::commit: %d frames, capacity %d", n, st.cap); return SIND_E_ARG; }
+    for (int i = 0; i < n; i++) {
+        const int b = slots[i] - first;
+        if (b < 0 || b >= chunk_n || (i > 0 && slots[i] <= slots[i - 1])) { sind_set_error("PieceBatch::commit: slot %d is not of chunk %d", slots[i], chunk); return SIND_E_ARG; }
+        crec_h.p[first + i] = PieceCommitRec{(unsigned long long)plane_off[i], (unsigned long long)((size_t)slots[i] * N), b, C[i], b * 2 * PIECE_SLOTS, 0};
+    }
+    const int lo = slots[0], hi = slots[n - 1];
+    HIP_TRY(hipMemcpyAsync(tab_d.p + (size_t)(lo - first) * 2 * PIECE_SLOTS, tab_h.p + (size_t)lo * 2 * PIECE_SLOTS, (size_t)(hi - lo + 1) * 2 * PIECE_SLOTS * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(crec_d.p, crec_h.p + first, (size_t)n * sizeof(PieceCommitRec), hipMemcpyHostToDevice, stream));
+    SIND_TRY(launch_piece_commit_frames(stream, st, crec_d.p, crec_h.p + first, n, tab_d.p, (size_t)chunk_n * 2 * PIECE_SLOTS, slab, slab_words, pof_d.p, (size_t)cap * N));
+    // pieceOf of the frames between the first and the last committed one in one copy (a fallen-back frame in between rides along unused)
+    HIP_TRY(hipMemcpyAsync(pof_h.p + (size_t)lo * N, pof_d.p + (size_t)lo * N, (size_t)(hi - lo + 1) * N, hipMemcpyDeviceToHost, stream));
+    return SIND_OK;
+}
+
+int piece_chunk_flush(PieceBatch& pb, RagBatch& rb, int chunk, PieceChunkFrame* fr) {
+    const int first = pb.chunk_first(chunk), n = pb.chunk_count(chunk);
+    if (n < 1 || n > 64) { sind_set_error("piece_chunk_flush: chunk %d holds %d frames", chunk, n); return SIND_E_ARG; }
+    if (pb.stream != rb.stream) { sind_set_error("piece_chunk_flush: the piece and the RAG batch must share a stream (the commit is ordered in front of the RAG launches by it)"); return SIND_E_STATE; }
+    int C[64], rag_slots[64], cslots[64], cC[64], m = 0, nc = 0, idx[64]; uint8_t dev[64]; unsigned long long *pieces[64], *conn[64]; size_t coff[64];
+    int run_first = -1, run_n = 0;
+    {
+        std::lock_guard<std::mutex> lk(pb.flush_mutex());
+        SIND_TRY(pb.enqueue(chunk, fr[0].half->piece_z_invalid_from(), fr[0].half->piece_inv_depth_scale()));
+        SIND_TRY(pb.wait(chunk));
+        // the host step: records -> ranked pieces and the order table; a frame beyond a capacity of the stage runs the host function here
+        for (int i = 0; i < n; i++) {
+            PieceChunkFrame& f = fr[i]; const PieceFrameHdr& h = pb.header(first + i);
+            f.rc = SIND_OK; f.err.clear(); f.rag_slot = -1; f.own = false; f.on_device = false; f.fell_back = h.status != 0 || h.pieces < 0;
+            int* tab = pb.order_table(first + i);
+            f.rc = f.fell_back ? f.half->seg_pieces_batched(nullptr, 0, nullptr, nullptr) : f.half->seg_pieces_batched(pb.records(first + i), h.pieces, tab, tab + PIECE_SLOTS);
+            if (f.rc != SIND_OK) { f.err = sind_last_error(); continue; }
+            if (f.half->rag_pieces() < 1) continue;
+            f.on_device = !f.fell_back;
+            idx[m] = i; C[m] = f.half->rag_pieces(); dev[m] = f.on_device ? 1 : 0; m++;
+        }
+        // the run: consecutive slots of the RAG batch, the planes of the frames that stayed on the device written there by the commit kernels
+        if (m > 0) run_first = rb.reserve_run(m, C, dev, rag_slots, pieces, conn);
+        for (int k = 0; k < m; k++) {
+            PieceChunkFrame& f = fr[idx[k]];
+            if (rag_slots[k] < 0) {      // no room in the slabs: the per-frame stage, from host planes
+                f.own = true;
+                if (f.on_device) { f.on_device = false; f.fell_back = true; f.rc = f.half->seg_pieces_batched(nullptr, 0, nullptr, nullptr); if (f.rc != SIND_OK) f.err = sind_last_error(); }
+                continue;
+            }
+            f.rag_slot = rag_slots[k]; run_n++;
+            const OccResult* pre = f.half->rag_pre(); rb.set_inputs(f.rag_slot, pre->occ2_dev, pre->depthN_dev, pre->occ2_event);
+            if (f.on_device) { cslots[nc] = first + idx[k]; cC[nc] = C[k]; coff[nc] = rb.plane_off(f.rag_slot); nc++; }
+            else f.half->rag_pack(pieces[k], conn[k]);
+        }
+        SIND_TRY(pb.commit(chunk, nc, cslots, cC, coff, rb.slab_dev(), rb.slab_words()));
+        if (run_n > 0) SIND_TRY(rb.enqueue_run(run_first, run_n, chunk));
+    }
+    if (run_n > 0) SIND_TRY(rb.wait(chunk));      // (the counters, and pieceOf in front of them on the stream)
     return SIND_OK;
 }
 
@@ -156,11 +271,9 @@ int sind_debug_seg_pieces(const unsigned long long* planes, int k, const unsigne
     for (int b = 0; b < n; b++) {
         // ---- the device's pieces as the host's type, then the same export (ranking, pieceOf) for both sides
         const int C = fh[b].pieces, nc = std::min(std::max(C, 0), PIECE_SLOTS);
-        std::vector<SegPiece> all(nc);
+        std::vector<SegPiece> all; seg_pieces_from_records(rh.data() + (size_t)b * PIECE_SLOTS, nc, all);
         for (int i = 0; i < nc; i++) {
-            const PieceRecDev& r = rh[(size_t)b * PIECE_SLOTS + i]; SegPiece& p = all[i];
-            p.cluster = r.cluster; p.clen = r.clen; p.start = PtI{r.sx, r.sy}; p.sum2 = ((long long)r.sum2_hi << 32) | (long long)r.sum2_lo; p.box = Rect{r.x0, r.y0, r.x1, r.y1};
-            p.area = (float)r.area; p.cz = r.cz; p.hasLianjie = r.has_conn != 0;
+            SegPiece& p = all[i];
             p.img.create(width, height); HIP_TRY(hipMemcpy(p.img.d.data(), st.pb.p + ((size_t)b * PIECE_SLOTS + i) * pw, pw * 8, hipMemcpyDeviceToHost));
             if (p.hasLianjie) { p.lianjie.create(width, height); HIP_TRY(hipMemcpy(p.lianjie.d.data(), st.pa.p + ((size_t)b * PIECE_SLOTS + i) * pw, pw * 8, hipMemcpyDeviceToHost)); }
         }
@@ -176,6 +289,92 @@ int sind_debug_seg_pieces(const unsigned long long* planes, int k, const unsigne
         info_host[4 * b + 1] = info_host[4 * b + 2] = info_host[4 * b + 3] = 0;
     }
     return SIND_OK;
+}
+
+// parity-test access to the round's batched piece stage (PieceBatch, piece_chunk_flush, the commit kernels, the RAG launches on the device slab) against the host
+// function packed from the host: see include/sind_hip.h
+int sind_debug_pieces_batch(const unsigned long long* planes, int k, const unsigned long long* occ1, const unsigned long long* label_edge, const uint16_t* depth, const uint8_t* occ2,
+                            const uint8_t* depth_n, int n, int width, int height, float depth_scale, int device, int chunk, int cap, int rag_cap,
+                            int* info_gpu, int* recs_gpu, float* vals_gpu, unsigned long long* pieces_gpu, unsigned long long* conn_gpu, uint8_t* piece_of_gpu, int* rag_gpu,
+                            int* info_host, int* recs_host, float* vals_host, unsigned long long* pieces_host, unsigned long long* conn_host, uint8_t* piece_of_host, int* rag_host) {
+    if (!planes || !occ1 || !label_edge || !depth || !occ2 || !depth_n || !info_gpu || !recs_gpu || !vals_gpu || !pieces_gpu || !conn_gpu || !piece_of_gpu || !rag_gpu || !info_host || !recs_host ||
+        !vals_host || !pieces_host || !conn_host || !piece_of_host || !rag_host || k < 1 || k > PIECE_KMAX || n < 1 || n > 64 || chunk < 1 || chunk > 64 || width < 64 || width % 64 != 0 || height < 8 ||
+        height % 8 != 0 || width > 8192 || height > 8192 || cap < 1 || cap > PIECE_SLOTS || rag_cap < 1 || !(depth_scale > 0)) {
+        sind_set_error("sind_debug_pieces_batch: bad arguments (1..64 frames of 1..%d planes, chunks of 1..64, width a multiple of 64, height of 8, 1..%d records)", PIECE_KMAX, PIECE_SLOTS); return SIND_E_ARG; }
+    HIP_TRY(hipSetDevice(device));
+    using namespace sind;
+    const size_t pw = (size_t)height * (width / 64), N = (size_t)width * height;
+    DynaConfig cfg; cfg.W = width; cfg.H = height; cfg.depthScale = depth_scale; cfg.device = device;
+    hipStream_t ts = nullptr; HIP_TRY(hipStreamCreateWithFlags(&ts, hipStreamNonBlocking));
+    auto run = [&]() -> int {
+        // the frames' depth planes at growing distances: no one stride reaches them, the stage reads them through its table
+        std::vector<size_t> doff(n); size_t dtotal = 0; for (int b = 0; b < n; b++) { dtotal += (size_t)1024 * b; doff[b] = dtotal; dtotal += N; }
+        DevBuf<uint16_t> dd; DevBuf<uint8_t> o2, dn; SIND_TRY(dd.alloc(dtotal)); SIND_TRY(o2.alloc((size_t)n * N)); SIND_TRY(dn.alloc((size_t)n * N));
+        for (int b = 0; b < n; b++) HIP_TRY(hipMemcpyAsync(dd.p + doff[b], depth + (size_t)b * N, N * 2, hipMemcpyHostToDevice, ts));
+        HIP_TRY(hipMemcpyAsync(o2.p, occ2, (size_t)n * N, hipMemcpyHostToDevice, ts)); HIP_TRY(hipMemcpyAsync(dn.p, depth_n, (size_t)n * N, hipMemcpyHostToDevice, ts));
+        HIP_TRY(sind_stream_wait(ts));
+        std::vector<std::unique_ptr<DynaTail>> tails(n); std::vector<OccResult> pre(n);
+        for (int b = 0; b < n; b++) { tails[b].reset(new DynaTail()); SIND_TRY(tails[b]->init(cfg, ts)); pre[b].ready = true; pre[b].occ2_dev = o2.p + (size_t)b * N; pre[b].depthN_dev = dn.p + (size_t)b * N; }
+        for (int side = 0; side < 2; side++) {       // 0: the host function, packed from the host (today's path); 1: the batched device stage
+            int* info = side ? info_gpu : info_host; int* recs = side ? recs_gpu : recs_host; float* vals = side ? vals_gpu : vals_host; int* rag_out = side ? rag_gpu : rag_host;
+            uint64_t* pl_out = reinterpret_cast<uint64_t*>(side ? pieces_gpu : pieces_host); uint64_t* cn_out = reinterpret_cast<uint64_t*>(side ? conn_gpu : conn_host); uint8_t* po_out = side ? piece_of_gpu : piece_of_host;
+            RagBatch rb; PieceBatch pb; std::vector<PieceChunkFrame> fr(n);
+            SIND_TRY(rb.init(cfg, n, ts)); rb.set_limits(chunk, 128); SIND_TRY(rb.begin_round());
+            for (int b = 0; b < n; b++) { tails[b]->debug_set_piece_inputs(planes + (size_t)b * k * pw, k, occ1 + (size_t)b * pw, label_edge + (size_t)b * pw, depth + (size_t)b * N, dd.p + doff[b], &pre[b]); fr[b] = PieceChunkFrame(); fr[b].half = tails[b].get(); }
+            if (side) {
+                SIND_TRY(pb.init(cfg, n, ts)); pb.set_chunk(chunk); SIND_TRY(pb.begin_round());
+                for (int b = 0; b < n; b++) {
+                    DynaTail& t = *tails[b];
+                    if (!t.piece_batchable() || pb.take_slot() != b) { sind_set_error("sind_debug_pieces_batch: frame %d did not get its slot", b); return SIND_E_STATE; }
+                    pb.pack(b, t.piece_labels().data(), k, t.piece_occ1(), t.piece_edge(), t.piece_depth_dev());
+                }
+                for (int c = 0; c * pb.chunk_frames() < n; c++) SIND_TRY(piece_chunk_flush(pb, rb, c, fr.data() + pb.chunk_first(c)));
+            } else {
+                for (int b = 0; b < n; b++) {
+                    PieceChunkFrame& f = fr[b]; DynaTail& t = *tails[b];
+                    f.rc = t.seg_pieces_batched(nullptr, 0, nullptr, nullptr);
+                    if (f.rc != SIND_OK) { f.err = sind_last_error(); continue; }
+                    if (t.rag_pieces() < 1) continue;
+                    unsigned long long *pc = nullptr, *cn = nullptr;
+                    if (rb.reserve(t.rag_pieces(), &f.rag_slot, &pc, &cn)) { t.rag_pack(pc, cn); rb.set_inputs(f.rag_slot, pre[b].occ2_dev, pre[b].depthN_dev, nullptr); } else { f.rag_slot = -1; f.own = true; }
+                }
+                for (int c = 0; c * rb.chunk_frames() < rb.slots(); c++) { SIND_TRY(rb.enqueue(c)); SIND_TRY(rb.wait(c)); }
+            }
+            std::string cap_err;
+            for (int b = 0; b < n; b++) {
+                PieceChunkFrame& f = fr[b]; DynaTail& t = *tails[b]; int* inf = info + 4 * b;
+                if (f.rc != SIND_OK) {          // more than 254 pieces: the count and the code; the text stays in sind_last_error
+                    if (f.rc != SIND_E_CAPACITY) { sind_set_error("%s", f.err.c_str()); return f.rc; }
+                    inf[0] = t.dbg.nClusters; inf[1] = f.rc; inf[2] = f.fell_back ? 1 : 0; inf[3] = 0; cap_err = f.err; continue;
+                }
+                std::vector<SegPiece> got = t.debug_pieces(); const int C = (int)got.size();
+                inf[0] = C; inf[1] = 0; inf[2] = f.fell_back ? 1 : 0; inf[3] = f.on_device ? 1 : 0;
+                if (C == 0) continue;
+                if (rag_result_ints(C) > (size_t)rag_cap) { sind_set_error("sind_debug_pieces_batch: frame %d has %d pieces, its RAG block does not fit %d ints", b, C, rag_cap); return SIND_E_CAPACITY; }
+                std::vector<unsigned long long> raw;
+                if (f.on_device) {          // the planes as the commit kernels left them in the RAG batch's device slab: [0, C) pieces, [C, 2C) connection areas, rank order
+                    raw.resize((size_t)2 * C * pw);
+                    HIP_TRY(hipMemcpyAsync(raw.data(), rb.slab_dev() + rb.plane_off(f.rag_slot), raw.size() * 8, hipMemcpyDeviceToHost, ts)); HIP_TRY(sind_stream_wait(ts));
+                    for (int r = 0; r < C; r++) { SegPiece& p = got[r]; p.img.create(width, height); std::memcpy(p.img.d.data(), raw.data() + (size_t)r * pw, pw * 8);
+                        p.lianjie.create(width, height); std::memcpy(p.lianjie.d.data(), raw.data() + ((size_t)C + r) * pw, pw * 8); }
+                }
+                std::vector<SegPiece> disc(C); for (int r = 0; r < C; r++) disc[got[r].disc] = got[r];
+                int* rc12 = recs + (size_t)b * cap * 12; uint64_t* cn_b = cn_out + (size_t)b * cap * pw;
+                seg_pieces_export(disc, width, height, cap, rc12, vals + (size_t)b * cap * 2, pl_out + (size_t)b * cap * pw, cn_b, nullptr);
+                for (int r = 0; r < C; r++) if (disc[r].disc != got[r].disc) { sind_set_error("sind_debug_pieces_batch: the export ranked the pieces of frame %d differently", b); return SIND_E_STATE; }
+                if (f.on_device) for (int i = 0; i < std::min(C, cap); i++) std::memcpy(cn_b + (size_t)i * pw, raw.data() + ((size_t)C + rc12[12 * i + 11]) * pw, pw * 8);      // (what the device wrote, zeros of a missing connection area included)
+                std::memcpy(po_out + (size_t)b * N, f.on_device ? pb.piece_of(b) : t.debug_piece_of().data(), N);
+                const int* rag = nullptr;
+                if (f.rag_slot >= 0) rag = rb.result(f.rag_slot); else SIND_TRY(t.rag_own(&rag));
+                std::memcpy(rag_out + (size_t)b * rag_cap, rag, rag_result_ints(C) * sizeof(int));
+            }
+            if (!cap_err.empty()) sind_set_error("%s", cap_err.c_str());
+        }
+        return SIND_OK;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(ts); (void)hipStreamDestroy(ts);
+    return rc;
 }
 
 // parity-test access to k_piece_contours: see include/sind_hip.h

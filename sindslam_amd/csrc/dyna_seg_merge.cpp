@@ -12,28 +12,44 @@ namespace sind {
 
 // ---- DD:653-1018: split every depth cluster on edges into pieces, region-adjacency statistics on the GPU, greedy merge on the host
 // host part up to the pieces in score order and pieceOf; they stay in segAll / segPieceOf (no pieces: segAll is empty and the frame's labels are all 0)
-int DynaTail::seg_pieces(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& labelForSegEdge, const uint16_t* depth_host) {
+int DynaTail::seg_pieces(const std::vector<BitImg>& allLabels, const BitImg& occ1, const BitImg& labelForSegEdge, const uint16_t* depth_host, bool allow_device) {
     typedef SegPiece Piece;
     std::vector<Piece>& all = segAll; all.clear();
     double tf = tick_ms();
-    #define FLAP(i) { const double t_ = tick_ms(); t_fine[i] += t_ - tf; tf = t_; }
     bool on_device = false;
-    if (device_pieces) SIND_TRY(seg_pieces_device(allLabels, occ1, labelForSegEdge, all, &on_device));      // (counts the frame as on the device or as fallen back)
+    if (device_pieces && allow_device) SIND_TRY(seg_pieces_device(allLabels, occ1, labelForSegEdge, all, &on_device));      // (counts the frame as on the device or as fallen back)
     segOnDevice = on_device;
     if (!on_device) seg_pieces_host(allLabels.data(), std::max(0, (int)allLabels.size() - 1), occ1, labelForSegEdge, depth_host, zInvalidFrom, invDepthScale, piece_threads, t_fine, all);      // (host/pieces.hpp)
-    FLAP(6)
+    t_fine[6] += tick_ms() - tf;
+    return seg_pieces_check_and_rank(on_device);
+}
+static int too_many_pieces(int C) { sind_set_error("seg_and_merge: %d pieces exceed the 8-bit label range of the reference", C); return SIND_E_CAPACITY; }
+int DynaTail::seg_pieces_check_and_rank(bool on_device) {
+    std::vector<SegPiece>& all = segAll;
+    const double tf = tick_ms();
     const int C = (int)all.size();
     dbg.nClusters = C;
     if (C == 0) { segOnDevice = false; return SIND_OK; }
-    if (C > 254) { all.clear(); segOnDevice = false; sind_set_error("seg_and_merge: %d pieces exceed the 8-bit label range of the reference", C); return SIND_E_CAPACITY; }
+    if (C > 254) { all.clear(); segOnDevice = false; return too_many_pieces(C); }
     seg_pieces_rank(all);
     if (on_device) SIND_TRY(seg_pieces_commit());      // the planes stay on the device, in rank order in the RAG stage's layout; pieceOf is painted there and comes back with the RAG counters
     else {
         segPieceOf.assign(N, (uint8_t)(C + 1));       // index of the piece that owns a pixel (the reference paints the pieces in score order)
         for (int i = 0; i < C; i++) all[i].img.paint_u8(segPieceOf.data(), W, (uint8_t)i);
     }
-    FLAP(10)
-    #undef FLAP
+    t_fine[10] += tick_ms() - tf;
+    return SIND_OK;
+}
+// the second part of process_begin for a frame of a round's PieceBatch: its records, ranked (the planes are committed on the device, pieceOf comes with process_end),
+// or -- recs = nullptr: the frame exceeded a capacity of the device stage -- the host function, whatever the tail's own switch says
+int DynaTail::seg_pieces_batched(const PieceRecDev* recs, int C, int* order, int* has_conn) {
+    segOnDevice = false;
+    if (!recs) return seg_pieces(segLabels, segOcc1, segEdge, segDepthHost, false);
+    const double tf = tick_ms();
+    const int n = seg_pieces_order(recs, C, segAll, order, has_conn);      // (host/pieces.hpp)
+    t_fine[10] += tick_ms() - tf;
+    dbg.nClusters = C;
+    if (n < 0) return too_many_pieces(C);
     return SIND_OK;
 }
 // the pieces' planes and their connection areas' (zeros for a piece without one), C planes of H * W / 64 words each
@@ -173,7 +189,7 @@ int RagBatch::init(const DynaConfig& c, int max_frames, hipStream_t s) {
     cfg = c; W = c.W; H = c.H; cap = max_frames; stream = s; pw = (size_t)H * (W / 64);
     if (W % 64 != 0 || max_frames < 1) { sind_set_error("RagBatch: width must be a multiple of 64 (got %d), %d frames", W, max_frames); return SIND_E_ARG; }
     SIND_TRY(recs_h.alloc(cap)); SIND_TRY(recs_d.alloc(cap));
-    occ2_ev.assign(cap, nullptr); done.resize(cap, nullptr);
+    occ2_ev.assign(cap, nullptr); done.resize(cap, nullptr); on_dev.assign(cap, 0);
     for (hipEvent_t& e : done) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return SIND_OK;
 }
@@ -188,27 +204,52 @@ int RagBatch::begin_round() {
     n_slots = 0; in_used = 0; res_used = 0;
     return SIND_OK;
 }
-bool RagBatch::reserve(int C, int* slot, unsigned long long** pieces, unsigned long long** conn) {
+bool RagBatch::reserve_locked(int C, bool dev, int* slot, unsigned long long** pieces, unsigned long long** conn) {
     if (C < 1 || C > 254) return false;
     const size_t words = (size_t)2 * C * pw, ints = rag_result_ints(C);
-    std::lock_guard<std::mutex> lk(m);
     if (n_slots >= cap || in_used + words > in_cap || res_used + ints > res_cap) return false;
     RagRec& R = recs_h.p[n_slots];
     R.plane_off = in_used; R.res_off = res_used; R.C = C; R.pad = 0; R.occ2 = nullptr; R.depthN = nullptr;
+    on_dev[n_slots] = dev ? 1 : 0;
     *pieces = in_h.p + in_used; *conn = *pieces + (size_t)C * pw; *slot = n_slots++;
     in_used += words; res_used += ints;
     return true;
 }
+bool RagBatch::reserve(int C, int* slot, unsigned long long** pieces, unsigned long long** conn) {
+    std::lock_guard<std::mutex> lk(m);
+    return reserve_locked(C, false, slot, pieces, conn);
+}
+int RagBatch::reserve_run(int n, const int* C, const uint8_t* on_device, int* slots, unsigned long long** pieces, unsigned long long** conn) {
+    std::lock_guard<std::mutex> lk(m);      // (held over the run: its slots and planes are consecutive)
+    int first = -1;
+    for (int i = 0; i < n; i++) {
+        slots[i] = -1;
+        if (reserve_locked(C[i], on_device[i] != 0, &slots[i], &pieces[i], &conn[i]) && first < 0) first = slots[i];
+    }
+    return first;
+}
 void RagBatch::set_inputs(int slot, const uint8_t* occ2, const uint8_t* depthN, hipEvent_t ev) { recs_h.p[slot].occ2 = occ2; recs_h.p[slot].depthN = depthN; occ2_ev[slot] = ev; }
 int RagBatch::enqueue(int chunk) {
-    HIP_TRY(hipSetDevice(cfg.device));
     int first, n; { std::lock_guard<std::mutex> lk(m); first = chunk_first(chunk); n = chunk_count(chunk); }
     if (chunk < 0 || n < 1) { sind_set_error("RagBatch::enqueue: chunk %d holds no frame", chunk); return SIND_E_ARG; }
+    return enqueue_run(first, n, chunk);
+}
+int RagBatch::enqueue_run(int first, int n, int ev) {
+    HIP_TRY(hipSetDevice(cfg.device));
+    { std::lock_guard<std::mutex> lk(m); if (first < 0 || n < 1 || first + n > n_slots || ev < 0 || ev >= cap) { sind_set_error("RagBatch::enqueue_run: slots [%d, %d) of %d, event %d", first, first + n, n_slots, ev); return SIND_E_ARG; } }
+    const int chunk = ev;
     const RagRec& A = recs_h.p[first]; const RagRec& Z = recs_h.p[first + n - 1];
-    const size_t w0 = A.plane_off, w1 = Z.plane_off + (size_t)2 * Z.C * pw, r0 = A.res_off, r1 = Z.res_off + rag_result_ints(Z.C);
+    const size_t r0 = A.res_off, r1 = Z.res_off + rag_result_ints(Z.C);
     std::lock_guard<std::mutex> lk(enq);      // (two chunks of a round may be enqueued by two pool threads: one chunk's calls stay together on the stream)
     for (int b = first; b < first + n; b++) if (occ2_ev[b]) HIP_TRY(hipStreamWaitEvent(stream, occ2_ev[b], 0));       // occ2 uploaded on the CalOccluded runner's stream without a host wait
-    HIP_TRY(hipMemcpyAsync(in_d.p + w0, in_h.p + w0, (w1 - w0) * 8, hipMemcpyHostToDevice, stream));
+    // the planes of every run of host-packed slots in one copy (all of them, where no slot's planes lie in the device slab already: one copy, as ever)
+    for (int b = first; b < first + n;) {
+        if (on_dev[b]) { b++; continue; }
+        int e = b; while (e + 1 < first + n && !on_dev[e + 1]) e++;
+        const size_t w0 = recs_h.p[b].plane_off, w1 = recs_h.p[e].plane_off + (size_t)2 * recs_h.p[e].C * pw;
+        HIP_TRY(hipMemcpyAsync(in_d.p + w0, in_h.p + w0, (w1 - w0) * 8, hipMemcpyHostToDevice, stream));
+        b = e + 1;
+    }
     HIP_TRY(hipMemcpyAsync(recs_d.p + first, recs_h.p + first, (size_t)n * sizeof(RagRec), hipMemcpyHostToDevice, stream));
     SIND_TRY(launch_rag_frames(stream, recs_d.p + first, recs_h.p + first, n, in_d.p, in_cap, dil_d.p, res_d.p, res_cap, W, H));
     HIP_TRY(hipMemcpyAsync(res_h.p + r0, res_d.p + r0, (r1 - r0) * sizeof(int), hipMemcpyDeviceToHost, stream));

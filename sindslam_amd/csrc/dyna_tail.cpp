@@ -71,14 +71,21 @@ int DynaTail::process(const uint16_t* depth_host, const uint16_t* depth_dev, con
 // the same in two parts around the batched RAG stage (dyna.hpp)
 int DynaTail::process_begin(const uint16_t* depth_host, const uint16_t* depth_dev, const float* U, const float* V, const OccResult* pre, DynaTail* depth_half,
                             const KmFrameResult* km, const FlowMasksReady* fm) {
+    SIND_TRY(process_begin_inputs(depth_host, depth_dev, U, V, pre, depth_half, km, fm));
+    return rag_half()->depth_stage_pieces();
+}
+// ... and that in two parts around a round's batched piece stage (dyna.hpp): up to the inputs of the piece extraction
+int DynaTail::process_begin_inputs(const uint16_t* depth_host, const uint16_t* depth_dev, const float* U, const float* V, const OccResult* pre, DynaTail* depth_half,
+                                   const KmFrameResult* km, const FlowMasksReady* fm) {
     HIP_TRY(hipSetDevice(cfg.device));
     n_frames++; pendHalf = depth_half;
     { const double t0 = tick_ms(); if (fm) flow_masks_ready(*fm, pendLow, pendHigh); else SIND_TRY(flow_masks(U, V, pendLow, pendHigh, pre ? pre->gridFlow : nullptr)); t_stage[0] += tick_ms() - t0; }
     pendD = DepthStageOut();
-    return rag_half()->depth_stage_begin(depth_host, depth_dev, pre, pendD, km);
+    return rag_half()->depth_stage_inputs(depth_host, depth_dev, pre, pendD, km);
 }
-int DynaTail::process_end(const int* rag, uint8_t* dyna_out, uint8_t* label_out) {
+int DynaTail::process_end(const int* rag, uint8_t* dyna_out, uint8_t* label_out, const uint8_t* piece_of) {
     HIP_TRY(hipSetDevice(cfg.device));
+    if (piece_of) { DynaTail* h = rag_half(); h->segPieceOf.assign(piece_of, piece_of + h->N); }
     SIND_TRY(rag_half()->depth_stage_end(pendD, rag));
     return fuse(pendLow, pendHigh, pendD, dyna_out, label_out);
 }
@@ -91,6 +98,16 @@ int DynaTail::depth_stage(const uint16_t* depth_host, const uint16_t* depth_dev,
     return depth_stage_end(out, rag);
 }
 int DynaTail::depth_stage_begin(const uint16_t* depth_host, const uint16_t* depth_dev, const OccResult* pre, DepthStageOut& out, const KmFrameResult* km) {
+    SIND_TRY(depth_stage_inputs(depth_host, depth_dev, pre, out, km));
+    return depth_stage_pieces();
+}
+int DynaTail::depth_stage_pieces() {
+    const double tk = tick_ms();
+    if (!segLabels.empty()) SIND_TRY(seg_pieces(segLabels, segOcc1, segEdge, segDepthHost));
+    t_stage[4] += tick_ms() - tk;
+    return SIND_OK;
+}
+int DynaTail::depth_stage_inputs(const uint16_t* depth_host, const uint16_t* depth_dev, const OccResult* pre, DepthStageOut& out, const KmFrameResult* km) {
     HIP_TRY(hipSetDevice(cfg.device));
     double tk = tick_ms();
     #define LAP(i) { const double t_ = tick_ms(); t_stage[i] += t_ - tk; tk = t_; }
@@ -104,7 +121,7 @@ int DynaTail::depth_stage_begin(const uint16_t* depth_host, const uint16_t* dept
     for (int i = 0; i < KM_K; i++) { depth_vals[i] = centers[i][2]; if (depth_vals[i] < 0.2) depth_vals[i] += 20.0f; order[i] = i; }
     std::stable_sort(order, order + KM_K, [&](int a, int b) { return depth_vals[a] < depth_vals[b]; });
     std::vector<BitImg> labelMask(KM_K); BitImg::split_labels(label8.data(), W, H, W, 0, KM_K, labelMask.data());
-    std::vector<BitImg> allLabels; BitImg labelForSegEdge(W, H);
+    std::vector<BitImg>& allLabels = segLabels; allLabels.clear(); BitImg& labelForSegEdge = segEdge; labelForSegEdge.create(W, H);
     float ratioArea = 0.0f; const float TotalArea = (float)(H * W); int count0 = 0;
     for (int i = 0; i < KM_K; i++) {
         const int idx = order[i]; const int cnt = labelMask[idx].count();
@@ -120,9 +137,7 @@ int DynaTail::depth_stage_begin(const uint16_t* depth_host, const uint16_t* dept
     else SIND_TRY(cal_occluded(depth_host, depth_dev, out.totalArea, occ1, occ2));
     LAP(3)
     out.label3.assign(N, 0);
-    segAll.clear(); segOnDevice = false; segDepthDev = depth_dev; segPre = pre && pre->ready ? pre : nullptr;
-    if (!allLabels.empty()) SIND_TRY(seg_pieces(allLabels, occ1, labelForSegEdge, depth_host));
-    LAP(4)
+    segAll.clear(); segOnDevice = false; segDepthDev = depth_dev; segDepthHost = depth_host; segPre = pre && pre->ready ? pre : nullptr;
     #undef LAP
     return SIND_OK;
 }

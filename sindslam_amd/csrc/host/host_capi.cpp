@@ -59,6 +59,17 @@ int sindh_seg_pieces(const uint64_t* planes, int k, const uint64_t* occ1, const 
     seg_pieces_host(cl.data(), k, img(occ1), img(label_edge), depth, z_invalid_from(depth_scale), 1.0f / depth_scale, 1, nullptr, all);
     return seg_pieces_export(all, w, h, cap, recs, vals, piece_planes, conn_planes, piece_of);
 }
+// The host step between the two device steps of a batched frame (seg_pieces_order, pieces.hpp) on C records in discovery order, recs [C][16] ints in PieceRecDev's
+// layout (cluster, contour, start x y, length, box x0 y0 x1 y1, twice the area low / high, area, band count, has_conn, cz as float bits, pad): order [255] = slot per
+// rank, has_conn [255] = per rank, score [255] = per rank (float).  Returns C, 0 for no pieces, -1 for more than 254 (nothing is written then).
+int sindh_seg_pieces_order(const int* recs, int C, int* order, int* has_conn, float* score) {
+    static_assert(sizeof(PieceRecDev) == 16 * sizeof(int), "PieceRecDev is 16 words");
+    if ((!recs && C > 0) || !order || !has_conn || !score) return -2;
+    std::vector<SegPiece> all;
+    const int n = seg_pieces_order(reinterpret_cast<const PieceRecDev*>(recs), C, all, order, has_conn);
+    for (int r = 0; r < n; r++) score[r] = all[r].score;
+    return n;
+}
 // the device stage's documented capacities (pieces_dev.hpp), so that the tests' scenes can be held against them
 void sindh_piece_capacities(int* out6) { piece_capacities(out6); }
 void sindh_draw(const uint8_t* src, int w, int h, int filled, uint8_t* out) {     // draw every external contour of src, filled or thickness 2

@@ -39,6 +39,31 @@ inline void seg_pieces_rank(std::vector<SegPiece>& all) {
     std::sort(all.begin(), all.end(), [](const SegPiece& a, const SegPiece& b) { return a.score > b.score; });
 }
 
+// what the device stage (pieces_dev.hpp) knows of a piece, in discovery order (cluster, then raster order of the contour's start pixel); PIECE_SLOTS of them per frame
+#define PIECE_SLOTS 255
+struct PieceRecDev { int cluster, contour, sx, sy, clen, x0, y0, x1, y1; unsigned sum2_lo; int sum2_hi; int area, band, has_conn; float cz; int pad; };
+// the first min(C, PIECE_SLOTS) records as the host's pieces (fields only: the planes stay where the device made them); `all` takes C entries
+inline void seg_pieces_from_records(const PieceRecDev* recs, int C, std::vector<SegPiece>& all) {
+    all.clear(); all.resize((size_t)std::max(C, 0));
+    for (int i = 0; i < std::min(C, PIECE_SLOTS); i++) {
+        const PieceRecDev& r = recs[i]; SegPiece& p = all[i];
+        p.cluster = r.cluster; p.clen = r.clen; p.start = PtI{r.sx, r.sy}; p.sum2 = (long long)(((unsigned long long)(unsigned)r.sum2_hi << 32) | (unsigned long long)r.sum2_lo); p.box = Rect{r.x0, r.y0, r.x1, r.y1};
+        p.area = (float)r.area; p.cz = r.cz; p.hasLianjie = r.has_conn != 0;
+    }
+}
+// The host step between the two device steps of a batched frame (PieceBatch, dyna.hpp), stated once: the records of a frame -> its pieces in RANK order (seg_pieces_rank
+// on the discovery sequence: the host function's order, ties included) and the order table the commit kernels read: order[r] = slot (discovery index) of the piece of
+// rank r, has_conn[r] = it has a connection area; both take PIECE_SLOTS ints.  Returns C (0: no pieces, nothing ranked), or -1 when C is above 254 (the 8-bit label
+// range of the reference: `all` is cleared and the caller reports the count) or negative.
+inline int seg_pieces_order(const PieceRecDev* recs, int C, std::vector<SegPiece>& all, int* order, int* has_conn) {
+    if (C < 0 || C > 254) { all.clear(); return -1; }
+    seg_pieces_from_records(recs, C, all);
+    if (C == 0) return 0;
+    seg_pieces_rank(all);
+    for (int r = 0; r < C; r++) { order[r] = all[r].disc; has_conn[r] = all[r].hasLianjie ? 1 : 0; }
+    return C;
+}
+
 // The test entries' view of a frame's pieces (sindh_seg_pieces, sind_debug_seg_pieces): the first min(C, cap) pieces in DISCOVERY order as recs [cap][12] ints = cluster,
 // start x, start y, contour length, twice the contour area (low, high word), hasLianjie, box x0 y0 x1 y1, rank after the sort (-1 when C is 0 or above 254: nothing is
 // ranked then and piece_of is left alone); vals [cap][2] = area, cz; piece / connection planes [cap][h * wpr]; piece_of [h * w] as DynaTail::seg_pieces paints it.

@@ -10,6 +10,7 @@
 #pragma once
 #include "common.hpp"
 #include "depth.hpp"
+#include "host/pieces.hpp"
 
 namespace sind {
 
@@ -46,11 +47,9 @@ struct PieceTracer {
 // Further capacities: PIECE_SLOTS pieces per frame (a frame with more than 254 is an error of the stage anyway); second level (the band planes): PIECE_CONTOUR_CAP2
 // contours and PIECE_CHAIN_CAP2 chain points per piece.  A frame in which a plane exceeds a capacity reports status != 0 and the caller runs the host function for it.
 #define PIECE_KMAX 12
-#define PIECE_SLOTS 255
 #define PIECE_CONTOUR_CAP2 256
 #define PIECE_CHAIN_CAP2 16384
-// what the device knows of a piece, in discovery order (cluster, then raster order of the contour's start pixel)
-struct PieceRecDev { int cluster, contour, sx, sy, clen, x0, y0, x1, y1; unsigned sum2_lo; int sum2_hi; int area, band, has_conn; float cz; int pad; };
+// (PIECE_SLOTS and PieceRecDev, what the device knows of a piece, are stated in host/pieces.hpp, where the host step that reads them lives)
 struct PieceFrameHdr { int pieces, status, pad0, pad1; };
 struct PieceStage {
     int W = 0, H = 0, wpr = 0, cap = 0; size_t pw = 0, N = 0;
@@ -60,13 +59,23 @@ struct PieceStage {
     PieceTracer l1, l2;
     int init(int W, int H, int cap);
     // launches only (13 of them whatever the frames hold): afterwards recs [b][PIECE_SLOTS] / frames [b] hold the records, pb the piece planes and pa the connection planes
-    // of frame b at (b * PIECE_SLOTS + slot) * pw.  nplanes_d must hold the frames' plane counts; depth_dev: nullptr = the stage's own `depth`
-    int enqueue(hipStream_t s, int n, const uint16_t* depth_dev, size_t depth_stride, int z_invalid_from, float inv_depth_scale);
+    // of frame b at (b * PIECE_SLOTS + slot) * pw.  nplanes_d must hold the frames' plane counts; depth_dev: nullptr = the stage's own `depth`.
+    // depth_tab (device, optional): n pointers, frame b's depth plane is depth_tab[b] -- frames that come from arbitrary streams lie at no one stride; without it frame b
+    // lies at depth_dev + b * depth_stride (the table's special case, same bits)
+    int enqueue(hipStream_t s, int n, const uint16_t* depth_dev, size_t depth_stride, int z_invalid_from, float inv_depth_scale, const uint16_t* const* depth_tab = nullptr);
 };
 // k_piece_commit for one frame of a stage (frame b): the host has ranked the C pieces (order_dev[r] = slot of the piece of rank r, has_conn_dev[r] = it has a connection area);
 // the planes go in rank order straight into the RAG stage's layout -- pieces into planes_out [0, C), connection planes (zeros where a piece has none) into [2C, 3C) -- and
 // piece_of_out [H * W] takes the rank of the piece that owns a pixel (the highest rank wins, as painting in rank order does), C + 1 elsewhere.  Two launches.
 int launch_piece_commit(hipStream_t s, const PieceStage& st, int b, int C, const int* order_dev, const int* has_conn_dev, unsigned long long* planes_out, uint8_t* piece_of_out);
+// The same for the frames of a chunk at once (PieceBatch, dyna.hpp), straight into the BATCHED RAG stage's slab (RagRec of depth.hpp): frame i of the list is frame
+// `b` of the stage and has C ranked pieces; its order table (order[r] = slot of rank r at table + tab_off, has_conn[r] at table + tab_off + PIECE_SLOTS) came up with the
+// list.  k_piece_commit_frames writes the pieces into slab [plane_off, + C planes) and the connection planes into the C planes behind them -- the batch's [0, C) / [C, 2C)
+// layout, not the per-frame [0, C) / [2C, 3C) -- zeros for a piece without a connection area; k_piece_paint_frames writes pieceOf [H * W] at piece_of + piece_of_off
+// (highest rank wins, C + 1 where no piece is).  Two launches whatever the list holds; `host` is the list as the device will see it (bounds are checked on it).
+struct PieceCommitRec { unsigned long long plane_off, piece_of_off; int b, C, tab_off, pad; };
+int launch_piece_commit_frames(hipStream_t s, const PieceStage& st, const PieceCommitRec* recs_dev, const PieceCommitRec* host, int n, const int* table_dev, size_t table_ints,
+                               unsigned long long* slab, size_t slab_words, uint8_t* piece_of, size_t piece_of_bytes);
 // the capacities above for a test: contours, chain points (first level), contours, chain points (second level), piece slots, planes per frame
 static inline void piece_capacities(int out[6]) { out[0] = PIECE_CONTOUR_CAP; out[1] = PIECE_CHAIN_CAP; out[2] = PIECE_CONTOUR_CAP2; out[3] = PIECE_CHAIN_CAP2; out[4] = PIECE_SLOTS; out[5] = PIECE_KMAX; }
 

@@ -31,7 +31,8 @@ static int build_round_batches(sind_pipe* p) {
         // the group's flow-mask batch shares the k-means chain's stream: the round thread waits for both before it pushes the tails, and a stream more per group
         // moved the other streams over the hardware queues (measured at 1280 x 720, 48 streams, where this stage stays per frame: 820 - 850 -> 780 - 795 pairs/s)
         SIND_TRY(p->fmb[g].init(p->dc, g == 0 ? p->S : (p->S + 1) / 2, p->km_streams[g]));
-        SIND_TRY(p->ragb[g].init(p->dc, g == 0 ? p->S : (p->S + 1) / 2, p->km_streams[g])); }      // (the same stream again: idle while the round's tails run)
+        SIND_TRY(p->ragb[g].init(p->dc, g == 0 ? p->S : (p->S + 1) / 2, p->km_streams[g]));
+        SIND_TRY(p->pieceb[g].init(p->dc, g == 0 ? p->S : (p->S + 1) / 2, p->km_streams[g])); }      // (the same stream again: idle while the round's tails run)
     return SIND_OK;
 }
 static int build_occ_batch(sind_pipe* p, int B) {

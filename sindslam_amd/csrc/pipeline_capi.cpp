@@ -267,6 +267,16 @@ int sind_pipe_get_rag_batch(sind_pipe* p, int* on, long long* frames_batched, lo
     if (!p || !on || !frames_batched || !frames_fallback) { sind_set_error("sind_pipe_get_rag_batch: null argument"); return SIND_E_ARG; }
     *on = p->rag_batch ? 1 : 0; *frames_batched = p->rag_frames.load(); *frames_fallback = p->rag_fallback.load(); return SIND_OK;
 }
+// ---- the round's batched piece stage (PieceBatch); off by default.  Only the non-split rounds with the batched RAG stage read it
+int sind_pipe_set_pieces_batch(sind_pipe* p, int on) {
+    if (!p) { sind_set_error("sind_pipe_set_pieces_batch: null handle"); return SIND_E_ARG; }
+    SIND_TRY(no_step_pending(p, "sind_pipe_set_pieces_batch"));
+    p->pieces_batch = on != 0; p->pieces_frames = 0; p->pieces_fallback = 0; return SIND_OK;
+}
+int sind_pipe_get_pieces_batch(sind_pipe* p, int* on, long long* frames_batched, long long* frames_fallback) {
+    if (!p || !on || !frames_batched || !frames_fallback) { sind_set_error("sind_pipe_get_pieces_batch: null argument"); return SIND_E_ARG; }
+    *on = p->pieces_batch ? 1 : 0; *frames_batched = p->pieces_frames.load(); *frames_fallback = p->pieces_fallback.load(); return SIND_OK;
+}
 int sind_pipe_set_rag_batch_chunk(sind_pipe* p, int chunk_frames, int slab_planes_per_frame) {
     if (!p) { sind_set_error("sind_pipe_set_rag_batch_chunk: null handle"); return SIND_E_ARG; }
     SIND_TRY(no_step_pending(p, "sind_pipe_set_rag_batch_chunk"));

@@ -101,3 +101,68 @@ void tail_rag_begin(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t, int g, i
     if (slot < 0) { if (!own) p->rag_frames++; tail_rag_end(p, sb, o, s, t, worker, own); }      // (no pieces: nothing to count, the frame did not leave the batched path)
     else if (mine) tail_rag_end(p, sb, o, s, t, worker, rb.result(slot));
 }
+// ---- the same with the round's batched piece stage in front of the join (PieceBatch, dyna.hpp; sind_pipe_set_pieces_batch).  The first task runs the frame up to the INPUTS of
+// the piece extraction, takes a slot of the group's piece batch, packs and joins; chunks and the round's last frame are found as above, on piece slots.  The frame that
+// completes a chunk flushes it (piece_chunk_flush: piece launches, wait, the host step of every frame, the run of RAG slots, commit and paint launches, RAG launches,
+// wait) and queues the other frames' second tasks: two waits per chunk, none per frame.  A frame the stage cannot take (no cluster to cut, inputs not on the device) runs
+// the host function and the per-frame RAG stage in its own task, as it does without the switch.
+static void tail_pieces_end(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t, int worker, const int* rag, const uint8_t* piece_of, bool own) {
+    SindRange range_t("sind tail: SegAndMerge from the counters on, fusion, dilation, ORB mask filter");
+    on_worker(p, s, worker);
+    const size_t np = p->np();
+    static thread_local std::vector<uint8_t> dy, lb;
+    dy.resize(np); lb.resize(np);
+    int r = SIND_OK;
+    if (own) r = p->tails[s]->rag_half()->rag_own(&rag);      // (the slab had no room for the frame: the per-frame stage, from host planes)
+    if (r == SIND_OK) r = p->tails[s]->process_end(rag, dy.data(), lb.data(), piece_of);
+    if (r != SIND_OK) { sb->tail_fail.fail(s, r); return; }
+    tail_finish(p, sb, o, s, t, dy, lb);
+}
+void tail_pieces_begin(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t, int g, int worker, const KmFrameResult* km, const FlowMasksReady* fm) {
+    PieceBatch& pb = p->pieceb[g]; RagBatch& rb = p->ragb[g]; sind_pipe::RagRound& rr = p->ragr[g];
+    int slot = -1; const int* own = nullptr; int r;
+    { SindRange range_t("sind tail: flow masks, SegAndMerge up to the inputs of the piece stage");
+      PhaseAOut& a = sb->a; DynaTail* tl = p->tails[s].get(); DynaTail* dh = on_worker(p, s, worker);
+      const size_t np = p->np(); const int k = s * p->T + t;
+      r = tl->process_begin_inputs(a.depth_h.data() + np * k, a.depth_dev.p + np * k, a.U.p + np * k, a.V.p + np * k, &a.occ[k], dh, km, fm);
+      DynaTail* h = tl->rag_half();
+      if (r == SIND_OK) {
+          if (h->piece_batchable() && (slot = pb.take_slot()) >= 0) {
+              const double tp = now_ms(); pb.pack(slot, h->piece_labels().data(), (int)h->piece_labels().size() - 1, h->piece_occ1(), h->piece_edge(), h->piece_depth_dev()); h->t_fine[10] += now_ms() - tp;
+          } else {          // leaves the piece path: today's (the host function; with pieces, the per-frame RAG stage)
+              slot = -1; r = h->seg_pieces_batched(nullptr, 0, nullptr, nullptr);
+              if (r == SIND_OK && h->rag_pieces() > 0) { p->rag_fallback++; r = h->rag_own(&own); }
+          }
+      }
+      if (r != SIND_OK) sb->tail_fail.fail(s, r); }
+    int flush[2] = {-1, -1}, flush_n[2] = {0, 0}, nf = 0;
+    { std::lock_guard<std::mutex> lk(rr.m);
+      if (slot >= 0) { rr.stream_of_slot[slot] = s; const int c = pb.chunk_of(slot); if (++rr.joined[c] == pb.chunk_frames()) { flush[nf] = c; flush_n[nf++] = pb.chunk_frames(); } }
+      if (++rr.arrived == rr.expected && pb.slots() > 0) {                 // the last frame of the round: the partial chunk at the end, if there is one
+          const int lc = pb.chunk_of(pb.slots() - 1), n = pb.chunk_count(lc);
+          if (n < pb.chunk_frames()) { flush[nf] = lc; flush_n[nf++] = n; }
+      } }
+    PieceChunkFrame mine; bool have_mine = false;
+    for (int f = 0; f < nf; f++) {
+        const double te = now_ms();
+        const int first = pb.chunk_first(flush[f]), n = flush_n[f];
+        std::vector<PieceChunkFrame> fr(n);
+        for (int i = 0; i < n; i++) fr[i].half = p->tails[rr.stream_of_slot[first + i]]->rag_half();
+        const int rc = piece_chunk_flush(pb, rb, flush[f], fr.data());
+        p->tails[s]->t_fine[8] += now_ms() - te;      // (SIND_TAIL_TIMING's "rag": the flushing frame's piece and RAG launches and both waits for its whole chunk)
+        const std::string e = rc == SIND_OK ? std::string() : "batched piece stage: " + std::string(sind_last_error());
+        for (int i = 0; i < n; i++) {
+            const int s2 = rr.stream_of_slot[first + i]; const PieceChunkFrame& q = fr[i];
+            if (rc != SIND_OK) { sb->tail_fail.fail(s2, rc, e); continue; }
+            if (q.fell_back) p->pieces_fallback++; else if (q.on_device) p->pieces_frames++;
+            if (q.rc != SIND_OK) { sb->tail_fail.fail(s2, q.rc, q.err); continue; }
+            if (q.own) p->rag_fallback++; else p->rag_frames++;
+            if (s2 == s) { mine = q; have_mine = true; continue; }
+            const int* res = q.rag_slot >= 0 ? rb.result(q.rag_slot) : nullptr; const uint8_t* po = q.on_device ? pb.piece_of(first + i) : nullptr; const bool ow = q.own;
+            p->workers.push(sb->km_tails[g], [p, sb, o, s2, t, res, po, ow](int w) { tail_pieces_end(p, sb, o, s2, t, w, res, po, ow); });
+        }
+    }
+    if (r != SIND_OK || !sb->tail_fail.ok(s)) return;
+    if (slot < 0) { if (!own) p->rag_frames++; tail_pieces_end(p, sb, o, s, t, worker, own, nullptr, false); }
+    else if (have_mine) tail_pieces_end(p, sb, o, s, t, worker, mine.rag_slot >= 0 ? rb.result(mine.rag_slot) : nullptr, mine.on_device ? pb.piece_of(slot) : nullptr, mine.own);
+}

@@ -79,6 +79,9 @@ struct sind_pipe {
     // stream, which is idle while the round's tails run.  rag_chunk: frames per set of launches (< 1: the whole group); rag_planes: input planes of slab per frame
     struct RagRound { std::mutex m; int expected = 0, arrived = 0; std::vector<int> joined, stream_of_slot; };      // frames of the round / through their first task, packed slots per chunk, whose slot
     RagBatch ragb[KM_GROUPS]; RagRound ragr[KM_GROUPS]; bool rag_batch = true; int rag_chunk = 32, rag_planes = 64; std::atomic<long long> rag_frames{0}, rag_fallback{0};
+    // Piece extraction of SegAndMerge in the same rounds (PieceBatch, dyna.hpp; pipeline_frame.cpp: tail_pieces_begin), opt-in: one device stage per chunk of rag_chunk
+    // (at most 64) frames in front of the RAG batch's join, on the same stream; the round's bookkeeping is the RAG round's (ragr)
+    PieceBatch pieceb[KM_GROUPS]; bool pieces_batch = false; std::atomic<long long> pieces_frames{0}, pieces_fallback{0};
     std::vector<std::thread> round_threads; std::mutex km_stat_mu; double km_round_ms = 0; long km_rounds = 0;
     std::vector<std::unique_ptr<PinnedBuf<uint8_t>>> upload_stage;        // page-locked staging of sind_pipe_process (host-buffer entry point), two 4 MB buffers per uploading worker
     std::vector<std::unique_ptr<DynaTail>> occ_tails;     // CalOccluded workspaces, one per pool worker (state free)
@@ -187,6 +190,7 @@ int phase_a(sind_pipe* p, StepBuf& sb, const uint8_t* bgr_dev, const uint16_t* d
 // (km / fm: the frame's share of a round's batched k-means and flow-mask stage, or null)
 bool tail_one(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t, int worker, const KmFrameResult* km, const FlowMasksReady* fm = nullptr);
 void tail_rag_begin(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t, int g, int worker, const KmFrameResult* km, const FlowMasksReady* fm);
+void tail_pieces_begin(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t, int g, int worker, const KmFrameResult* km, const FlowMasksReady* fm);
 void depth_task(sind_pipe* p, StepBuf* sb, int k, int worker);
 void tail_task(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t, int worker);
 void depth_chain(sind_pipe* p, StepBuf* sb, PipeOut o, int s, int t0, int t1, int worker);

@@ -60,7 +60,8 @@ static int rag_open(Round& r) {
     sind_pipe* p = r.p; sind_pipe::RagRound& rr = p->ragr[r.g]; int n = 0;
     for (int s = r.s0; s < r.s0 + r.ns; s++) n += r.live(s);
     p->ragb[r.g].set_limits(p->rag_chunk, p->rag_planes);
-    const int rc = p->ragb[r.g].begin_round();
+    int rc = p->ragb[r.g].begin_round();
+    if (rc == SIND_OK && p->pieces_batch) { p->pieceb[r.g].set_chunk(p->rag_chunk); rc = p->pieceb[r.g].begin_round(); }      // (the workspaces come with the first round that wants them)
     if (rc != SIND_OK) return rc;
     std::lock_guard<std::mutex> lk(rr.m); rr.expected = n; rr.arrived = 0; rr.joined.assign(r.ns + 1, 0); rr.stream_of_slot.assign(r.ns, -1);
     return SIND_OK;
@@ -71,7 +72,8 @@ static void push_tails(Round& r, bool ragb) {
     for (int s = s0; s < s0 + r.ns; s++) {
         if (!r.live(s)) continue;
         const FlowMasksReady fr = have ? r.fm.ready[s - s0] : FlowMasksReady{nullptr, nullptr, nullptr};
-        if (ragb) p->workers.push(sb->km_tails[g], [p, sb, o, s, t, g, s0, fr, have](int w) { tail_rag_begin(p, sb, o, s, t, g, w, &p->kmb[g].result(s - s0), have ? &fr : nullptr); });
+        if (ragb && p->pieces_batch) p->workers.push(sb->km_tails[g], [p, sb, o, s, t, g, s0, fr, have](int w) { tail_pieces_begin(p, sb, o, s, t, g, w, &p->kmb[g].result(s - s0), have ? &fr : nullptr); });
+        else if (ragb) p->workers.push(sb->km_tails[g], [p, sb, o, s, t, g, s0, fr, have](int w) { tail_rag_begin(p, sb, o, s, t, g, w, &p->kmb[g].result(s - s0), have ? &fr : nullptr); });
         else if (!r.split) p->workers.push(sb->km_tails[g], [p, sb, o, s, t, g, s0, fr, have](int w) { tail_one(p, sb, o, s, t, w, &p->kmb[g].result(s - s0), have ? &fr : nullptr); });
         else p->workers.push(sb->km_tails[g], [p, sb, o, s, t, g, s0, np](int w) {
             const int k = s * p->T + t, t1 = sb->range(s, p->T).t1;

@@ -153,6 +153,17 @@ class Pipeline:
         check(lib().sind_pipe_device_pieces(self._h, C.byref(on), C.byref(a), C.byref(b)), "sind_pipe_device_pieces")
         return bool(on.value), int(a.value), int(b.value)
 
+    def set_pieces_batch(self, on: bool = True):
+        """SegAndMerge's piece extraction batched per chunk of a k-means round's frames on the GPU (non-split rounds with the batched RAG stage only; default off; same
+        results), its planes committed straight into the RAG batch's device slab; resets the counters"""
+        check(lib().sind_pipe_set_pieces_batch(self._h, int(bool(on))), "sind_pipe_set_pieces_batch")
+
+    def pieces_batch(self):
+        """(switch, frames whose pieces were cut and committed by the batched stage, frames that exceeded a capacity of it and ran the host function) since the switch was last set"""
+        on = C.c_int(0); a = C.c_longlong(0); b = C.c_longlong(0)
+        check(lib().sind_pipe_get_pieces_batch(self._h, C.byref(on), C.byref(a), C.byref(b)), "sind_pipe_get_pieces_batch")
+        return bool(on.value), int(a.value), int(b.value)
+
     def set_state_hashing(self, on: bool = True):
         """every tail leaves a 128-bit fingerprint of its rolled inter-frame state per frame (read with state_hashes())"""
         check(lib().sind_pipe_set_state_hashing(self._h, int(bool(on))), "sind_pipe_set_state_hashing")
@@ -302,6 +313,8 @@ class PipelineGroup:
     def kmeans_groups(self): return self.pipes[0].kmeans_groups()
     def set_flow_mask_batch(self, on): [p.set_flow_mask_batch(on) for p in self.pipes]
     def flow_mask_batch(self): r = [p.flow_mask_batch() for p in self.pipes]; return r[0][0], sum(x[1] for x in r)
+    def set_pieces_batch(self, on=True): [p.set_pieces_batch(on) for p in self.pipes]
+    def pieces_batch(self): r = [p.pieces_batch() for p in self.pipes]; return r[0][0], sum(x[1] for x in r), sum(x[2] for x in r)
     def set_rag_batch(self, on): [p.set_rag_batch(on) for p in self.pipes]
     def rag_batch(self): r = [p.rag_batch() for p in self.pipes]; return r[0][0], sum(x[1] for x in r), sum(x[2] for x in r)
     def set_rag_batch_chunk(self, chunk_frames, slab_planes_per_frame=-1): [p.set_rag_batch_chunk(chunk_frames, slab_planes_per_frame) for p in self.pipes]
